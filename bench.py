@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the compress/decompress hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input: W4A16 pack-quantized
 (int4, group 128, symmetric) COMPRESS of one 8192x8192 bf16 weight plus DECOMPRESS of one
@@ -13,10 +13,14 @@ numbers are HBM-cold.  The timed loop issues the step's two independent launches
 roofline figures are single-stream HIP-event timings of back-to-back launches.
 
 Protocol (round 3): 250 ms of the real launches before any timed region (independent of
---warmup: a fresh lease measures ~5 % low for its first milliseconds), then --warmup steps, then 5 blocks of
-EXACTLY --steps steps, each bracketed by barrier + torch.cuda.synchronize() and max-reduced over the ranks;
-`ms_per_step` is the MEDIAN block (all blocks, and one block timed without the device warm-up, are in
-roofline.step).  Every extra leg's kernel row is also appended to roofline.kernels[].
+--warmup: a fresh lease measures ~5 % low for its first milliseconds), then --warmup steps, then ONE timed region of
+EXACTLY --steps steps, bracketed by barrier + torch.cuda.synchronize() and max-reduced over the ranks;
+`ms_per_step` is that region's wall time / --steps (the same region on one stream, and one timed without the device
+warm-up, are in roofline.step).  Every extra leg's kernel row is also appended to roofline.kernels[].
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed (the packed words of its compress and the bf16
+weight of its decompress) is written to DIR as .npy files, a fixed sample of rows (see dump_outputs); the inputs are
+seeded, so two builds given the same arguments can be compared output for output.
 
 value = algorithmic bytes of all ranks / max-over-ranks wall time, in GB/s; algorithmic bytes
 per step = 2 x (2 N^2 + 2 N^2/128 + N^2/2) = 337,641,472 B at N = 8192.
@@ -2271,6 +2275,25 @@ def self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_ROWS = 512  # rows of the 8192-row outputs written by --dump-outputs: 4 MiB of packed words (float64) + 16 MiB of weight (float32)
+
+
+def dump_outputs(path, sets, last, dev, suffix=""):
+    """--dump-outputs: what timed step `last` computed, as a caller of the C ABI would receive it — the int32 words its compress wrote
+    (`compress_weight_packed`, as float64: exact) and the bf16 weight its decompress wrote (`decompress_weight`, as float32: exact) —
+    on DUMP_ROWS rows drawn with a fixed seed (`sample_rows`, the same every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rows = torch.randperm(N, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+    idx = rows.to(dev)
+    arrays = {"compress_weight_packed": sets[last % NSETS]["packed"].index_select(0, idx).double(),
+              "decompress_weight": sets[(last + NSETS // 2) % NSETS]["out"].index_select(0, idx).float(),
+              "sample_rows": rows.double()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -2279,10 +2302,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--one-stream", action="store_true", help="issue the step's two launches on one HIP stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--shard", choices=("tensors", "rows"), default="tensors",
                     help="tensors (default): one 8192^2 weight shard per rank, weak scaling.  rows: additionally force the row-block leg "
                          "(ONE tensor split by rows over the ranks, strong scaling) — it always runs when N > 1")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -2335,9 +2361,9 @@ def main():
             dist.barrier()
 
     def timed_steps(c, d, cold_probe=None):
-        """BLOCKS timed regions of EXACTLY --steps steps each, every one bracketed by barrier + synchronize on both sides and
-        max-reduced over the ranks; returns the per-block wall times.  Before them: every packed buffer is populated, a
-        fixed-duration warm-up of the same launches (WARM_MS, independent of --warmup), then the --warmup untimed steps."""
+        """ONE timed region of EXACTLY --steps steps, bracketed by barrier + synchronize on both sides and max-reduced over the
+        ranks; returns its wall time.  Before it: every packed buffer is populated, a fixed-duration warm-up of the same launches
+        (WARM_MS, independent of --warmup), then the --warmup untimed steps."""
         for i in range(NSETS):  # populate every packed buffer once
             c(i)
         torch.cuda.synchronize()
@@ -2369,17 +2395,17 @@ def main():
         for i in range(a.warmup):
             c(i)
             d(i + NSETS // 2)
-        return [block() for _ in range(BLOCKS)]
+        return block()
 
     cold = []
     local_times = []
-    blocks_one = timed_steps(compress, decompress, cold_probe=cold)
-    if not a.one_stream:
-        local_times.clear()
-    blocks = blocks_one if a.one_stream else timed_steps(compress2, decompress2)
-    # what every rank did on its own (median of its blocks of the reported configuration), gathered for the line: a rank that lags shows
+    elapsed_one = timed_steps(compress, decompress, cold_probe=cold)
+    elapsed = elapsed_one if a.one_stream else timed_steps(compress2, decompress2)
+    if a.dump_outputs:  # before anything else writes the buffers of the last timed step
+        dump_outputs(a.dump_outputs, sets, a.steps - 1, dev, f"_rank{rank}" if distributed else "")
+    # what every rank did on its own (its timed region of the reported configuration), gathered for the line: a rank that lags shows
     step_bytes = 2 * alg_bytes_one_direction()
-    mine = step_bytes * a.steps / median(local_times[-BLOCKS:]) / 1e9
+    mine = step_bytes * a.steps / local_times[-1] / 1e9
     ranks_seen, per_rank = 1, [round(mine, 1)]
     if distributed:
         ranks_seen = dist.get_world_size()
@@ -2387,7 +2413,6 @@ def main():
         t[rank] = mine
         dist.all_reduce(t, op=dist.ReduceOp.SUM)  # reporting only
         per_rank = [round(float(v), 1) for v in t.tolist()]
-    elapsed_one, elapsed = median(blocks_one), median(blocks)
     value = world * step_bytes * a.steps / elapsed / 1e9
 
     result = None
@@ -2454,10 +2479,8 @@ def main():
                          "value_one_stream": round(world * step_bytes * a.steps / elapsed_one / 1e9, 1),
                          "frac_two_streams": round(value / world / HBM_PEAK_GBPS, 4),
                          "frac_one_stream": round(step_bytes * a.steps / elapsed_one / 1e9 / HBM_PEAK_GBPS, 4),
-                         "protocol": f"{WARM_MS:.0f} ms device warm-up of the same launches, then --warmup steps, then {BLOCKS} blocks of --steps steps "
-                                     "(barrier + synchronize on both sides of every block, wall clock, max over ranks); the MEDIAN block is ms_per_step",
-                         "ms_per_step_blocks": [round(x / a.steps * 1e3, 5) for x in blocks],
-                         "ms_per_step_blocks_one_stream": [round(x / a.steps * 1e3, 5) for x in blocks_one],
+                         "protocol": f"{WARM_MS:.0f} ms device warm-up of the same launches, then --warmup steps, then ONE timed region of --steps steps "
+                                     "(barrier + synchronize on both sides, wall clock, max over ranks); region / --steps is ms_per_step",
                          "ms_per_step_without_device_warmup": round(cold[0] / a.steps * 1e3, 5) if cold else None},
                 "kernels": [dict(kernel=k, config=f"W4A16 g128 {N}x{N} bf16", alg_bytes=one, us=v["avg_us"], min_us=v.get("min_us"), max_us=v.get("max_us"),
                                  GBps=v["GBps"], frac=v["frac"], valu_busy_frac=v.get("valu_busy_frac")) for k, v in kernels.items()],

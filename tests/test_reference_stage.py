@@ -3,6 +3,7 @@ reference to the GPU box unpacks and imports, and the reference's own codec test
 (everything is handed to upstream: no launch).  The GPU half is tests/test_gpu_reference_suite.py."""
 import json
 import os
+import shutil
 import subprocess
 import sys
 
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(not ref_import.available(), reason="no reference on this machine")
 
 
-def test_stage_recipe_is_idempotent_and_lists_only_reference_files():
+def test_stage_recipe_is_idempotent_and_lists_only_reference_files(tmp_path):
     if not os.path.isdir("/root/reference/src/compressed_tensors"):
         pytest.skip("the recipe runs where /root/reference exists")
     import tarfile
@@ -29,8 +30,10 @@ def test_stage_recipe_is_idempotent_and_lists_only_reference_files():
     assert "src/compressed_tensors/compressors/pack_quantized/helpers.py" in names
     assert "tests/test_compressors/test_compress_decompress_module.py" in names and "STAGED_FROM" in names
     assert all(n == "STAGED_FROM" or n.startswith(("src/compressed_tensors/", "tests/")) for n in names)
-    # git never sees it
-    r = subprocess.run(["git", "check-ignore", "-q", "oracle/_ref/reference_stage.tar.gz"], cwd=ROOT)
+    # git never sees it: the committed .gitignore, checked in a scratch repository (the checkout itself need not be a git work tree)
+    shutil.copy(os.path.join(ROOT, ".gitignore"), tmp_path / ".gitignore")
+    subprocess.run(["git", "init", "-q", str(tmp_path)], check=True)
+    r = subprocess.run(["git", "-c", "core.excludesFile=", "check-ignore", "-q", "--no-index", "oracle/_ref/reference_stage.tar.gz"], cwd=tmp_path)
     assert r.returncode == 0, "oracle/_ref must stay git-ignored"
     if os.path.exists(os.path.join(ROOT, ".gpurunignore")):
         assert "oracle/_ref" not in open(os.path.join(ROOT, ".gpurunignore")).read()
