@@ -110,6 +110,8 @@ _PROTOTYPES = {
     "ct_bitmask_decompress_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_copy_batch_plan": ([_P, _I], _L),
     "ct_copy_batch": ([_P, _I, _L, _S], _I),
+    "ct_awq_repack_plan": ([_P, _I], _L),
+    "ct_awq_repack_batch": ([_P, _I, _L, _S], _I),
     "ct_bitmask_row_popcount": ([_P, _L, _L, _P, _S], _I),
     "ct_sparse24_compress": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_sparse24_mask": ([_P, _I, _L, _P, _S], _I),
@@ -152,6 +154,13 @@ class BitmaskDItem(ctypes.Structure):
 class CopyItem(ctypes.Structure):
     """struct ct_copy_item of include/ct_hip.h"""
     _fields_ = [("src", _P), ("dst", _P), ("bytes", _L), ("first_block", _L)]
+
+
+class AwqItem(ctypes.Structure):
+    """struct ct_awq_item of include/ct_hip.h (a row of ct_awq_repack_batch's table)"""
+    _fields_ = [("qweight", _P), ("qzeros", _P), ("scales", _P), ("weight_packed", _P), ("zp_packed", _P), ("scale_t", _P),
+                ("K", _L), ("N", _L), ("G", _L), ("scale_shape", _L * 2), ("zp_shape", _L * 2), ("scale_dt", _c.c_int32),
+                ("wide", _c.c_int32), ("first_block", _L), ("weight_blocks", _L), ("zp_blocks", _L)]
 
 
 ITEM_WORDS = ctypes.sizeof(W4Item) // 8  # 13: every host table of ct_w4_item rows is a flat array of this many 64-bit words per item

@@ -461,6 +461,35 @@ typedef struct ct_copy_item {
 int64_t ct_copy_batch_plan(ct_copy_item* items_host, int n);
 int ct_copy_batch(const ct_copy_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream);
 
+/* AutoAWQ GEMM -> pack-quantized (entrypoints/convert/converters/autoawq.py, AutoAWQConverter.process) for a TABLE of modules in ONE
+ * launch.  Per item, with K = in_features, N = out_features, G = number of groups:
+ *   qweight int32 (K, N / 8)          -> weight_packed int32 (N, ceil(K / 8)): nibble i of word (n, w) is the AWQ nibble of element
+ *                                        (k = 8w + i, n); the AWQ nibble of column c of a word sits at position [0,4,1,5,2,6,3,7][c];
+ *                                        nibbles past K are zero
+ *   qzeros  int32 (G, N / 8) or NULL  -> zp_packed int32 (N / 8, G): word (j, g) is qzeros[g, j] with its nibbles in natural order
+ *   scales  16-bit (G, N)             -> scale_t (N, G), the same bits (scale_dt: CT_F16 or CT_BF16)
+ * scale_shape / zp_shape are the shapes the caller found (checked against N and G).  Protocol as the other batches: fill the
+ * non-derived fields, call ct_awq_repack_plan on the HOST copy (derived fields; returns the workgroup count, or -1 with ct_last_error
+ * set for a malformed item or a batch too large for one launch — split it), copy the table to the device, launch. */
+typedef struct ct_awq_item {
+    const int32_t* qweight;
+    const int32_t* qzeros;
+    const void* scales;
+    int32_t* weight_packed;
+    int32_t* zp_packed;        /* NULL exactly when qzeros is */
+    void* scale_t;
+    int64_t K, N, G;
+    int64_t scale_shape[2];
+    int64_t zp_shape[2];       /* ignored without qzeros */
+    int32_t scale_dt;
+    int32_t wide;              /* derived: bit 0 = 16-byte qweight loads, bit 1 = 16-byte weight_packed stores */
+    int64_t first_block;       /* derived */
+    int64_t weight_blocks;     /* derived: the 4-bit transpose; the zero-point and scale tails follow */
+    int64_t zp_blocks;         /* derived */
+} ct_awq_item;                 /* 17 64-bit words */
+int64_t ct_awq_repack_plan(ct_awq_item* items_host, int n);
+int ct_awq_repack_batch(const ct_awq_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream);
+
 /* sparse-bitmask decompress: out = zeros; out[mask] = values.  row_offsets may be NULL only if
  * fixed_row_nnz >= 0 (every row holds exactly that many values: the 2:4 codec).  16-bit payloads with
  * cols % 32 == 0 and 32-bit payloads with cols % 16 == 0 (as pairs of halves) take the LDS-window
