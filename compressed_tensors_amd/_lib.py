@@ -112,6 +112,8 @@ _PROTOTYPES = {
     "ct_copy_batch": ([_P, _I, _L, _S], _I),
     "ct_awq_repack_plan": ([_P, _I], _L),
     "ct_awq_repack_batch": ([_P, _I, _L, _S], _I),
+    "ct_fp8block_dequant_plan": ([_P, _I], _L),
+    "ct_fp8block_dequant_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_bitmask_row_popcount": ([_P, _L, _L, _P, _S], _I),
     "ct_sparse24_compress": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_sparse24_mask": ([_P, _I, _L, _P, _S], _I),
@@ -161,6 +163,13 @@ class AwqItem(ctypes.Structure):
     _fields_ = [("qweight", _P), ("qzeros", _P), ("scales", _P), ("weight_packed", _P), ("zp_packed", _P), ("scale_t", _P),
                 ("K", _L), ("N", _L), ("G", _L), ("scale_shape", _L * 2), ("zp_shape", _L * 2), ("scale_dt", _c.c_int32),
                 ("wide", _c.c_int32), ("first_block", _L), ("weight_blocks", _L), ("zp_blocks", _L)]
+
+
+class Fp8BlockItem(ctypes.Structure):
+    """struct ct_fp8block_item of include/ct_hip.h (a row of ct_fp8block_dequant_batch's table)"""
+    _fields_ = [("w", _P), ("scale", _P), ("out", _P), ("rows", _L), ("cols", _L), ("block_h", _L), ("block_w", _L),
+                ("scale_shape", _L * 2), ("sdt", _c.c_int32), ("fast", _c.c_int32), ("scale_stride", _L * 2), ("units_per_row", _L),
+                ("first_block", _L)]
 
 
 ITEM_WORDS = ctypes.sizeof(W4Item) // 8  # 13: every host table of ct_w4_item rows is a flat array of this many 64-bit words per item

@@ -490,6 +490,30 @@ typedef struct ct_awq_item {
 int64_t ct_awq_repack_plan(ct_awq_item* items_host, int n);
 int ct_awq_repack_batch(const ct_awq_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream);
 
+/* FP8 block dequantize (entrypoints/convert/converters/fp8block_dequantizer.py, FP8BlockDequantizer._create_dequantized_weight) for a
+ * TABLE of modules in ONE launch.  Per item and element:
+ *   out[r, c] = rnd_odt( f32(w[r, c]) * f32(scale[r / block_h, c / block_w]) )
+ * w is float8_e4m3fn (rows, cols) row-major, out (rows, cols) of odt (CT_BF16, CT_F16 or CT_F32: one per launch), the scale
+ * (weight_scale_inv) of sdt CT_F32 / CT_BF16 / CT_F16 with scale_shape (ceil(rows / block_h), ceil(cols / block_w)) or a shape torch
+ * broadcasts the same way (a dimension of 1).  Block sizes are any positive sizes; a ragged last block row or column is handled
+ * without padding.  Protocol as the other batches: fill the non-derived fields, call ct_fp8block_dequant_plan on the HOST copy
+ * (derived fields; returns the workgroup count, or -1 with ct_last_error set for a malformed item or a batch too large for one
+ * launch — split it), copy the table to the device, launch. */
+typedef struct ct_fp8block_item {
+    const uint8_t* w;
+    const void* scale;
+    void* out;
+    int64_t rows, cols, block_h, block_w;
+    int64_t scale_shape[2];    /* as found; the plan checks it */
+    int32_t sdt;
+    int32_t fast;              /* derived: 1 = 16 codes per lane with 16-byte loads, one scale and 16-byte stores; 0 = general path */
+    int64_t scale_stride[2];   /* derived: in elements, 0 along a broadcast dimension */
+    int64_t units_per_row;     /* derived: ceil(cols / 16) */
+    int64_t first_block;       /* derived */
+} ct_fp8block_item;            /* 14 64-bit words */
+int64_t ct_fp8block_dequant_plan(ct_fp8block_item* items_host, int n);
+int ct_fp8block_dequant_batch(const ct_fp8block_item* items_dev, int n, int64_t total_blocks, int odt, ct_stream_t stream);
+
 /* sparse-bitmask decompress: out = zeros; out[mask] = values.  row_offsets may be NULL only if
  * fixed_row_nnz >= 0 (every row holds exactly that many values: the 2:4 codec).  16-bit payloads with
  * cols % 32 == 0 and 32-bit payloads with cols % 16 == 0 (as pairs of halves) take the LDS-window
