@@ -26,6 +26,7 @@ __all__ = [
     "unpack_and_dequantize_many",
     "minmax_qparams",
     "minmax_qparams_float",
+    "dynamic_qdq",
     "generate_gparam",
     "rtn_quantize_and_pack",
     "rtn_mxfp4_quantize_and_pack",
@@ -549,6 +550,35 @@ def minmax_qparams_float(x, *, kind: str, group_size=None, global_scale=None) ->
     gs = _gs_arg(global_scale, dev) if kind == "nvfp4" else None
     call("ct_minmax_qparams_float", ptr(xd), DT[xd.dtype], rows, cols, cdiv, _QP_KIND[kind], ptr(gs), ptr(scale), stream_of(xd))
     return _home(scale, x)
+
+
+DYNAMIC_KINDS = {"int": 0, "fp8": 1, "nvfp4": 2, "mxfp4": 3, "mxfp8": 4}
+_DYNAMIC_WORKSPACE_BYTES = 16384  # CT_DYNAMIC_WORKSPACE_BYTES of include/ct_hip.h
+
+
+def dynamic_qdq(x: torch.Tensor, *, kind: str, segs: int, seg_len: int, num_bits: int = 8, symmetric: bool = True,
+                global_scale: Optional[torch.Tensor] = None, scale_shape=None, scale_dtype=None, zp_dtype=None, want_out: bool = True):
+    """Dynamic min-max observer + calculate_qparams + fake_quantize of a contiguous activation viewed as `segs` segments of
+    `seg_len` elements, one scale each (ct_dynamic_qdq; segs == 1 with seg_len == numel is the two-launch tensor form,
+    ct_dynamic_qdq_tensor).  Returns (out or None, scale or None, zero_point or None): `scale_shape` / `scale_dtype` /
+    `zp_dtype` None means "not requested" (the kernel then keeps them in registers)."""
+    _check_float(x, "activation")
+    if not x.is_cuda or not x.is_contiguous():
+        raise NotImplementedError("the dynamic QDQ kernels take contiguous GPU activations")
+    dev = x.device
+    out = torch.empty_like(x) if want_out else None
+    scale = torch.empty(scale_shape, dtype=scale_dtype, device=dev) if scale_dtype is not None else None
+    zp = torch.empty(scale_shape, dtype=zp_dtype, device=dev) if zp_dtype is not None else None
+    zdt = DT[zp_dtype] if zp_dtype is not None else -1
+    gs = _gs_arg(global_scale, dev)
+    head = (ptr(x), DT[x.dtype])
+    tail = (DYNAMIC_KINDS[kind], int(num_bits), int(bool(symmetric)), ptr(gs))
+    if segs == 1 and seg_len == x.numel() and seg_len > 512:
+        ws = torch.empty(_DYNAMIC_WORKSPACE_BYTES // 4, dtype=torch.int32, device=dev)
+        call("ct_dynamic_qdq_tensor", *head, int(seg_len), *tail, ptr(ws), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
+    else:
+        call("ct_dynamic_qdq", *head, int(segs), int(seg_len), *tail, ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
+    return out, scale, zp
 
 
 def generate_gparam(x: torch.Tensor) -> torch.Tensor:

@@ -409,11 +409,87 @@ def _patch_functions() -> None:
                 _FN_REBOUND.append((mod, attr, hit[0]))
 
 
-def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False):
+_FWD_SWAP = {}  # the same table for install(patch_forward=True): its own, so that either keyword may come first
+
+
+def _patch_forward() -> None:
+    """`install(patch_forward=True)`: `forward_quantize` (quantization/lifecycle/forward.py:304-335) and
+    `compute_dynamic_scales_and_zp` (quantization/utils/helpers.py:140-195) are rebound, in every already-imported
+    `compressed_tensors.*` module that holds them, to wrappers that send contiguous GPU activations of a layout the kernels
+    implement to quantization.dynamic (the fused dynamic QDQ of csrc/ct_dynamic.hip, or the static fake_quantize kernels) and
+    everything else — CPU / meta tensors, other strategies or formats, group activations under an initialised weight_g_idx,
+    a NotImplementedError from the HIP side — to the original.  upstream's `quantized_forward` looks `forward_quantize` up in
+    its module's globals at call time, so modules set up by set_forward_quantized are covered."""
+    import functools
+    import sys
+
+    import compressed_tensors.quantization.lifecycle.forward as up_forward
+    import compressed_tensors.quantization.utils.helpers as up_helpers
+
+    from .quantization import dynamic as amd_dynamic
+
+    floats = (torch.float32, torch.float16, torch.bfloat16)
+
+    def plannable(value, args, global_scale) -> bool:
+        if not (value.is_cuda and value.dtype in floats and value.is_contiguous()):
+            return False
+        if enum_value(args.strategy) not in ("token", "tensor", "group", "tensor_group"):
+            return False  # the reference raises its own ValueError
+        amd_dynamic.plan_dynamic(value.shape, value.dtype, args, global_scale)  # NotImplementedError -> original
+        return True
+
+    def static_ok(value, args, global_scale) -> bool:
+        qt, bits = enum_value(getattr(args, "type", "int")), int(args.num_bits)
+        return (value.is_cuda and value.dtype in floats and global_scale is None and enum_value(args.strategy) in ("tensor", "channel", "token", "group")
+                and ((qt == "int" and 1 <= bits <= 8) or (qt == "float" and bits == 8)))
+
+    def take_forward(module, value, base_name, args) -> bool:
+        gs = getattr(module, f"{base_name}_global_scale", None)
+        if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
+            return plannable(value, args, gs)
+        scale = getattr(module, f"{base_name}_scale", None)
+        return scale is not None and scale.is_cuda and scale.dtype in floats and static_ok(value, args, gs)
+
+    def take_dynamic(value, args, module=None, global_scale=None) -> bool:
+        return plannable(value, args, global_scale)
+
+    def dispatching(orig, ours, take):
+        @functools.wraps(orig)
+        def fn(*args, **kwargs):
+            try:
+                if take(*args, **kwargs):
+                    return ours(*args, **kwargs)
+            except NotImplementedError:
+                pass
+            return orig(*args, **kwargs)
+
+        fn._ct_original = orig
+        return fn
+
+    if not _FWD_SWAP:
+        def orig_of(fn):
+            return getattr(fn, "_ct_original", fn)
+
+        for orig, ours, take in ((orig_of(up_forward.forward_quantize), amd_dynamic.forward_quantize, take_forward),
+                                 (orig_of(up_helpers.compute_dynamic_scales_and_zp), amd_dynamic.compute_dynamic_scales_and_zp, take_dynamic)):
+            _FWD_SWAP[id(orig)] = (orig, dispatching(orig, ours, take))
+    for mod_name, mod in list(sys.modules.items()):
+        if mod is None or not (mod_name == "compressed_tensors" or mod_name.startswith("compressed_tensors.")):
+            continue
+        for attr, val in list(vars(mod).items()):
+            hit = _FWD_SWAP.get(id(val))
+            if hit is not None and callable(val):
+                setattr(mod, attr, hit[1])
+                _FN_REBOUND.append((mod, attr, hit[0]))
+
+
+def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False,
+            patch_forward: bool = False):
     """registry swap + ImplBackend registration
     (+ the by-name bindings of the codec classes inside upstream's own modules unless rebind_names=False;
      + batched launches behind upstream's ModelCompressor.compress_model / decompress_model unless wrap_model_compressor=False;
-     + with patch_functions=True the plain functions pack_to_int32 / unpack_from_int32 / dequantize / fake_quantize)."""
+     + with patch_functions=True the plain functions pack_to_int32 / unpack_from_int32 / dequantize / fake_quantize;
+     + with patch_forward=True the QDQ forward's forward_quantize / compute_dynamic_scales_and_zp)."""
     import compressed_tensors  # the upstream package; ImportError if it is not installed
     from compressed_tensors.compressors import BaseCompressor
     from compressed_tensors.registry import registry as up_registry
@@ -429,6 +505,8 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
         _wrap_model_compressor()
     if patch_functions:
         _patch_functions()
+    if patch_forward:
+        _patch_forward()
     return compressed_tensors
 
 
@@ -456,5 +534,6 @@ def uninstall():
     _REBOUND.clear()
     _FN_REBOUND.clear()
     _FN_SWAP.clear()
+    _FWD_SWAP.clear()
     _unwrap_model_compressor()
     uninstall_from(up_registry._REGISTRY[BaseCompressor], _SAVED)

@@ -1,6 +1,8 @@
+from .dynamic import compute_dynamic_scales_and_zp, forward_quantize
 from .forward import calculate_range, dequantize, fake_quantize, quantize
 from .quant_args import (
     ActivationOrdering,
+    DynamicType,
     QuantizationArgs,
     QuantizationScheme,
     QuantizationStatus,
@@ -14,6 +16,8 @@ __all__ = [
     "dequantize",
     "fake_quantize",
     "calculate_range",
+    "compute_dynamic_scales_and_zp",
+    "forward_quantize",
     "calculate_qparams_from_weight",
     "is_module_quantized",
     "QuantizationArgs",
@@ -22,4 +26,5 @@ __all__ = [
     "QuantizationStrategy",
     "QuantizationType",
     "ActivationOrdering",
+    "DynamicType",
 ]

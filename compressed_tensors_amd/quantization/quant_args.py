@@ -8,7 +8,7 @@ tests).  No arithmetic lives here.
 """
 from dataclasses import dataclass, field
 from enum import Enum
-from typing import List, Optional
+from typing import List, Optional, Union
 
 import torch
 
@@ -16,6 +16,7 @@ __all__ = [
     "QuantizationType",
     "QuantizationStrategy",
     "ActivationOrdering",
+    "DynamicType",
     "QuantizationStatus",
     "QuantizationArgs",
     "QuantizationScheme",
@@ -43,6 +44,12 @@ class ActivationOrdering(str, Enum):
     DYNAMIC = "dynamic"
 
 
+class DynamicType(str, Enum):
+    """`dynamic="local"` (quant_args.py:123-135): the local scales are observed per call, the global scale is static (NVFP4)"""
+
+    LOCAL = "local"
+
+
 class QuantizationStatus(str, Enum):
     """lifecycle stages the compressors set on modules (quant_config.py:56-121)"""
 
@@ -61,7 +68,7 @@ class QuantizationArgs:
     group_size: Optional[int] = None
     strategy: Optional[QuantizationStrategy] = None
     block_structure: Optional[List[int]] = None
-    dynamic: bool = False
+    dynamic: Union[bool, DynamicType] = False  # True, False or "local"
     actorder: Optional[ActivationOrdering] = None
     scale_dtype: Optional[torch.dtype] = None  # quant_args.py:201-202
     zp_dtype: Optional[torch.dtype] = None
@@ -79,6 +86,8 @@ class QuantizationArgs:
             else:
                 self.strategy = QuantizationStrategy.TENSOR
         self.strategy = QuantizationStrategy(getattr(self.strategy, "value", self.strategy))
+        if isinstance(self.dynamic, str):
+            self.dynamic = DynamicType(getattr(self.dynamic, "value", self.dynamic))
         if self.strategy in (QuantizationStrategy.GROUP, QuantizationStrategy.TENSOR_GROUP):
             if self.group_size is None or self.group_size <= 0:
                 raise ValueError(f"strategy {self.strategy} requires group_size to be set to a positive value")

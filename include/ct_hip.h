@@ -279,6 +279,26 @@ int ct_minmax_qparams(const void* x, int xdt, int64_t rows, int64_t cols, int64_
 int ct_minmax_qparams_float(const void* x, int xdt, int64_t rows, int64_t cols, int64_t cdiv, int kind,
                             const float* global_scale, void* scale_out, ct_stream_t stream);
 
+/* Dynamic activation QDQ in one pass: compute_dynamic_scales_and_zp (quantization/utils/helpers.py:140-195, with
+ * calculate_qparams, helpers.py:50-137) followed by fake_quantize (quantization/lifecycle/forward.py:148-181,
+ * forward_helpers.py:180-215) — the dynamic branch of forward_quantize (forward.py:304-335).  x is `segs` contiguous
+ * segments of `seg_len` elements, one scale each: a token row, or a group.  kind: 0 INT (bits, symmetric; zero point int8),
+ * 1 FP8, 2 NVFP4 (global_scale: device float32[1] or NULL), 3 MXFP4, 4 MXFP8, with the scales of ct_minmax_qparams_float.
+ * out (nullable: scales only) has x's dtype.  scale_out (nullable, segs entries) has x's dtype, float32 for NVFP4 under a
+ * global scale.  zp_out (nullable, segs bytes) has zdt: CT_I8 for INT; CT_F8E4M3, CT_U8 or CT_I8 zeros for the FLOAT kinds.
+ * One launch; segments of 8 * 2^k <= 512 elements are reduced inside a wave, longer ones by one workgroup each. */
+int ct_dynamic_qdq(const void* x, int xdt, int64_t segs, int64_t seg_len, int kind, int bits, int symmetric,
+                   const float* global_scale, void* out, void* scale_out, void* zp_out, int zdt, ct_stream_t stream);
+
+/* The same with ONE segment of `numel` elements (tensor strategy; token strategy on a 1-D / 2-D input, whose reduce dims
+ * are empty upstream, helpers.py:187-188) in two launches: min / max partials into `workspace` (device memory of
+ * CT_DYNAMIC_WORKSPACE_BYTES, no initialisation needed), then the QDQ.  scale_out / zp_out: one entry. */
+#define CT_DYNAMIC_PARTS 1024
+#define CT_DYNAMIC_WORKSPACE_BYTES 16384
+int ct_dynamic_qdq_tensor(const void* x, int xdt, int64_t numel, int kind, int bits, int symmetric,
+                          const float* global_scale, void* workspace, void* out, void* scale_out, void* zp_out, int zdt,
+                          ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
