@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the compress/decompress hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: W4A16 pack-quantized
 (int4, group 128, symmetric) COMPRESS of one 8192x8192 bf16 weight plus DECOMPRESS of one
@@ -9,14 +9,20 @@ A "step" is one pass of the hot path over one batch of synthetic input: W4A16 pa
 inputs resident in HBM.  Buffers rotate over 16 disjoint sets (4.8 GiB; even the smallest stream,
 the packed words, is 537 MB across the sets) so the 256 MiB Infinity Cache cannot serve re-reads:
 numbers are HBM-cold.  The timed loop issues the step's two independent launches on two HIP streams
-(`value`); the same loop on one stream is reported as `value_one_stream`, and the per-kernel
+(`value`); with --full the same loop on one stream is reported as `value_one_stream`, and the per-kernel
 roofline figures are single-stream HIP-event timings of back-to-back launches.
 
 Protocol (round 3): 250 ms of the real launches before any timed region (independent of
 --warmup: a fresh lease measures ~5 % low for its first milliseconds), then --warmup steps, then ONE timed region of
 EXACTLY --steps steps, bracketed by barrier + torch.cuda.synchronize() and max-reduced over the ranks;
-`ms_per_step` is that region's wall time / --steps (the same region on one stream, and one timed without the device
-warm-up, are in roofline.step).  Every extra leg's kernel row is also appended to roofline.kernels[].
+`ms_per_step` is that region's wall time / --steps.
+
+A plain run does only that: it sets up, warms up, times the steps, writes --dump-outputs and prints the result line.
+--full runs everything else too.  Before the headline's region: the same region on one stream, and once more without the
+device warm-up (roofline.step).  After it: the per-kernel roofline timings, the parity gate, the extra legs (other sizes,
+dtypes, formats and checkpoints; every leg's kernel row is appended to roofline.kernels[]), the multi-rank legs, the CPU
+baseline and the oracle slice check.  The full result goes to bench_details.json and to stderr.
+--no-extra, --no-cpu-baseline and --shard rows take effect under --full only.
 
 --dump-outputs DIR: after the timed steps, what the last timed step computed (the packed words of its compress and the bf16
 weight of its decompress) is written to DIR as .npy files, a fixed sample of rows (see dump_outputs); the inputs are
@@ -1250,12 +1256,15 @@ def headline_line(result, cap=LINE_CAP):
     """The ONE line the driver parses: the contract keys, `config`, `roofline` (with <= 17 kernel rows) and `cpu_baseline`, serialised
     in at most `cap` characters.  Everything else bench.py measures (per-dtype quantize legs, float formats, W8A8, thread sweeps, the
     restatement / port baselines, per-leg detail) stays in the full result, which main() writes to bench_details.json and to stderr.
+    A plain run's result (no `roofline`; no details file) gives the contract keys and `config` alone.
     tests/test_bench_line.py feeds recorded results through this function and holds it to the cap and to the key list."""
     line = _pick(result, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data"))
     line["vs_baseline"] = result.get("vs_baseline")
     line["config"] = _pick(result.get("config", {}), ("workload", "alg_bytes_per_step_per_gpu", "buffers", "boundary", "streams", "parallelism",
                                                        "value_one_stream", "ranks_seen", "per_rank_GBps"))
-    r = result.get("roofline", {})
+    if "roofline" not in result:
+        return json.dumps(line, separators=(",", ":"))
+    r = result["roofline"]
     roof = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac"))
     roof["traffic"] = r.get("traffic")
     roof.update(_pick(r, ("alg_bytes_per_launch", "traffic_source")))
@@ -2299,13 +2308,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (other configurations, sizes and formats, per-kernel "
+                         "roofline, multi-rank legs, CPU baseline, oracle check) and write the full result to " + DETAILS_FILE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs and the cache-warm kernel timings")
     ap.add_argument("--one-stream", action="store_true", help="issue the step's two launches on one HIP stream")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--shard", choices=("tensors", "rows"), default="tensors",
-                    help="tensors (default): one 8192^2 weight shard per rank, weak scaling.  rows: additionally force the row-block leg "
-                         "(ONE tensor split by rows over the ranks, strong scaling) — it always runs when N > 1")
+                    help="tensors (default): one 8192^2 weight shard per rank, weak scaling.  rows: with --full, additionally force the row-block "
+                         "leg (ONE tensor split by rows over the ranks, strong scaling) — under --full it always runs when N > 1")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -2399,8 +2411,11 @@ def main():
 
     cold = []
     local_times = []
-    elapsed_one = timed_steps(compress, decompress, cold_probe=cold)
-    elapsed = elapsed_one if a.one_stream else timed_steps(compress2, decompress2)
+    if a.full:  # the one-stream region (value_one_stream, and the same region without the device warm-up) goes first
+        elapsed_one = timed_steps(compress, decompress, cold_probe=cold)
+        elapsed = elapsed_one if a.one_stream else timed_steps(compress2, decompress2)
+    else:
+        elapsed = timed_steps(compress, decompress) if a.one_stream else timed_steps(compress2, decompress2)
     if a.dump_outputs:  # before anything else writes the buffers of the last timed step
         dump_outputs(a.dump_outputs, sets, a.steps - 1, dev, f"_rank{rank}" if distributed else "")
     # what every rank did on its own (its timed region of the reported configuration), gathered for the line: a rank that lags shows
@@ -2416,6 +2431,40 @@ def main():
     value = world * step_bytes * a.steps / elapsed / 1e9
 
     result = None
+    if rank == 0:
+        result = {
+            "metric": "GB/s pack+unpack (int4 g128, bitmask) vs HBM peak; bit-exact round-trip",
+            "value": round(value, 1),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(elapsed / a.steps * 1e3, 5),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": "synthetic",
+            "config": {
+                "workload": f"W4A16 pack-quantized (int4, group_size=128, symmetric) compress+decompress, {N}x{N} bf16 per GPU",
+                "alg_bytes_per_step_per_gpu": step_bytes,
+                "buffers": f"{NSETS} rotating sets (HBM-cold)",
+                "boundary": "C ABI (ct_quant_pack + ct_unpack_dequant), inputs resident in HBM",
+                "streams": 1 if a.one_stream else 2,
+                "parallelism": f"{world} independent weight shards, no collectives",
+                "ranks_seen": ranks_seen,
+                "per_rank_GBps": per_rank,
+            },
+            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBPS, 4),
+        }
+    if not a.full:  # a plain run ends with its headline
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(headline_line(result), flush=True)
+        return
+
     if rank == 0:
         one = alg_bytes_one_direction()
         sp_c, sp_d = {}, {}
@@ -2438,31 +2487,8 @@ def main():
                 kernels[kname].update(busy)
         dom = max(kernels, key=lambda k: kernels[k]["avg_us"])
         traffic, traffic_src = committed_traffic(dom)
-        result = {
-            "metric": "GB/s pack+unpack (int4 g128, bitmask) vs HBM peak; bit-exact round-trip",
-            "value": round(value, 1),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic",
-            "config": {
-                "workload": f"W4A16 pack-quantized (int4, group_size=128, symmetric) compress+decompress, {N}x{N} bf16 per GPU",
-                "alg_bytes_per_step_per_gpu": step_bytes,
-                "buffers": f"{NSETS} rotating sets (HBM-cold)",
-                "boundary": "C ABI (ct_quant_pack + ct_unpack_dequant), inputs resident in HBM",
-                "streams": 1 if a.one_stream else 2,
-                "parallelism": f"{world} independent weight shards, no collectives",
-                "value_one_stream": round(world * step_bytes * a.steps / elapsed_one / 1e9, 1),
-                "ranks_seen": ranks_seen,
-                "per_rank_GBps": per_rank,
-            },
-            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBPS, 4),
+        result["config"]["value_one_stream"] = round(world * step_bytes * a.steps / elapsed_one / 1e9, 1)
+        result.update({
             "value_one_stream": round(world * step_bytes * a.steps / elapsed_one / 1e9, 1),
             "roofline": {
                 "bound": "hbm",
@@ -2487,7 +2513,7 @@ def main():
             },
             "kernels": kernels,
             "parity_gate": parity_gate(sets),
-        }
+        })
         if world == 1 and not a.no_extra:
             del sets
             torch.cuda.empty_cache()

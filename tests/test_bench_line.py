@@ -96,3 +96,20 @@ def test_an_oversized_result_sheds_rows_not_contract_keys():
         assert k in line
     with pytest.raises(RuntimeError):
         bench.headline_line(full, cap=500)
+
+
+def test_plain_result_gives_the_contract_keys_alone():
+    """a run without --full measures nothing beyond the timed steps: its line is the contract keys and `config`, with no roofline,
+    no baseline and no pointer to a details file (a plain run writes none)"""
+    full = _load(os.path.join(ROOT, "profiles", "r06_bench_line_driver_command.json"))
+    keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
+    plain = {k: full[k] for k in keys}
+    plain["config"] = {k: v for k, v in full["config"].items() if k != "value_one_stream"}
+    plain["frac_of_hbm_peak"] = 0.7447
+    text = bench.headline_line(plain)
+    line = json.loads(text)
+    assert "\n" not in text and len(text) <= bench.LINE_CAP
+    assert set(line) == set(keys) | {"config"}
+    for k in keys:
+        assert line[k] == full[k], k
+    assert line["config"] == plain["config"]

@@ -3036,7 +3036,7 @@ def test_fp4_quantize_all_inputs(cta, dev, xdt):
 
 
 def test_bench_two_ranks_on_one_gpu(tmp_path):
-    """the N > 1 path of bench.py (launch contract, barrier, max-over-ranks timing, rank-sharded checkpoint leg) with
+    """the N > 1 path of bench.py --full (launch contract, barrier, max-over-ranks timing, rank-sharded checkpoint leg) with
     both ranks on cuda:0 and the timing collectives over gloo (CT_BENCH_SHARE_GPU=1)"""
     import json
     import os
@@ -3050,7 +3050,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, CT_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -3072,7 +3072,7 @@ MAX_PROCESSES_ON_ONE_GPU = 6  # the most processes that may have one GPU open at
 
 @pytest.mark.parametrize("world", [4, 8])
 def test_bench_many_ranks_on_one_gpu(world):
-    """VERDICT r05 next #2c: `CT_BENCH_SHARE_GPU=1 python3 bench.py --gpus 8 --steps 6 --warmup 2` (and --gpus 4) — every line of the
+    """VERDICT r05 next #2c: `CT_BENCH_SHARE_GPU=1 python3 bench.py --gpus 8 --steps 6 --warmup 2 --full` (and --gpus 4) — every line of the
     N = 8 code path executes before the driver's first real 8-GPU run: the self-launch, eight ranks in the process group, the LPT split of
     the 154 TinyLlama modules covering each exactly once, the row-sharded legs on the HBM-cold C-ABI protocol (every shard equal to the
     slice of the single-rank result), the 4096^2 leg at this world size, and a final line inside the driver's window"""
@@ -3090,7 +3090,7 @@ def test_bench_many_ranks_on_one_gpu(world):
     env.update(CT_BENCH_WARM_SCALE="0.2")  # (shorter device warm-ups, same code path)
     if share:
         env.update(CT_BENCH_SHARE_GPU="1")  # the ranks take turns on ONE GPU
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -3112,9 +3112,9 @@ def test_bench_many_ranks_on_one_gpu(world):
 
 
 def test_bench_self_launches_two_ranks_without_a_launcher():
-    """exactly `CT_BENCH_SHARE_GPU=1 python3 bench.py --gpus 2 --steps 6 --warmup 2` — no torchrun in the
+    """`CT_BENCH_SHARE_GPU=1 python3 bench.py --gpus 2 --steps 6 --warmup 2 --full` — no torchrun in the
     command — must start its two ranks itself, exit 0 and print ONE line with n_gpus 2, the process group's size and what every
-    rank did on its own"""
+    rank did on its own (the plain command: test_bench_plain_run_prints_the_headline_alone)"""
     import json
     import os
     import subprocess
@@ -3123,7 +3123,7 @@ def test_bench_self_launches_two_ranks_without_a_launcher():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CT_BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-extra"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extra"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -3133,6 +3133,44 @@ def test_bench_self_launches_two_ranks_without_a_launcher():
     cfg = out["config"]
     assert cfg["ranks_seen"] == 2 and len(cfg["per_rank_GBps"]) == 2 and all(v > 0 for v in cfg["per_rank_GBps"])
     assert cfg["value_one_stream"] > 0
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_prints_the_headline_alone(tmp_path, gpus):
+    """the plain command (`python3 bench.py --gpus N --steps K --warmup W`, no --full; at N = 2 both ranks on cuda:0, started by the
+    script itself): ONE line of the contract keys and `config` only, nothing measured beyond the timed steps, and --dump-outputs
+    written from the last timed step"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CT_BENCH_SHARE_GPU")}
+    if gpus > 1:
+        env.update(CT_BENCH_SHARE_GPU="1")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", str(gpus), "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert set(out) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                        "data", "config"}
+    assert out["metric"] == "GB/s pack+unpack (int4 g128, bitmask) vs HBM peak; bit-exact round-trip" and out["unit"] == "GB/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16" and out["n_gpus"] == gpus and out["steps"] == 6 and out["warmup"] == 2
+    assert out["value"] > 0 and out["ms_per_step"] > 0
+    cfg = out["config"]
+    assert cfg["streams"] == 2 and cfg["ranks_seen"] == gpus and len(cfg["per_rank_GBps"]) == gpus and "value_one_stream" not in cfg
+    suffixes = [f"_rank{i}" for i in range(gpus)] if gpus > 1 else [""]
+    for sfx in suffixes:
+        packed = np.load(tmp_path / f"compress_weight_packed{sfx}.npy")
+        weight = np.load(tmp_path / f"decompress_weight{sfx}.npy")
+        rows = np.load(tmp_path / f"sample_rows{sfx}.npy")
+        assert packed.shape == (512, 1024) and weight.shape == (512, 8192) and rows.shape == (512,)
+        assert np.all(np.isfinite(weight)) and np.any(packed != 0)
 
 
 @pytest.mark.parametrize("n,dtype,sym", [(8192, BF16, True), (2048, BF16, False), (2048, F16, True), (2048, F16, False)])

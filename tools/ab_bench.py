@@ -1,5 +1,5 @@
 """dev helper (run U): bench.py under one perturbation, to find what moves `tinyllama_checkpoint.api` between contexts.
-python tools/ab_bench.py asis|pywait|lateimport|timed|timed_late|cpufirst|nogc|nocpu [bench args]"""
+python tools/ab_bench.py asis|pywait|lateimport|timed|timed_late|cpufirst|nogc|nocpu [bench args]  (always with --full)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 mode = sys.argv.pop(1)
@@ -83,4 +83,6 @@ elif mode == "nogc":
     gc.disable()
 elif mode == "nocpu":
     sys.argv.append("--no-cpu-baseline")
+if "--full" not in sys.argv:
+    sys.argv.append("--full")
 bench.main()

@@ -4,7 +4,7 @@
 # Everything a step writes goes to gpurun_out/<tag>/ (scratch; copy what should be judged into profiles/).  Steps:
 #   smoke      __graft_entry__.smoke()
 #   tests      pytest -m gpu (whole suite)                 tests:<expr>  pytest -m gpu -k <expr>
-#   bench      the driver's command: python bench.py --gpus 1 --steps 20 --warmup 5 (stdout -> bench.json, stderr -> bench.err)
+#   bench      python bench.py --gpus 1 --steps 20 --warmup 5 --full: every leg (stdout -> bench.json, stderr -> bench.err)
 #   bench2     the same once more (-> bench_run2.json)
 #   profile    tools/profile_round.sh <tag> (kernel trace + FETCH / WRITE / SQ counter passes; -> gpurun_out/profile_<tag>/)
 #   exp:<args> python tools/archive/exp_r05.py <args with ',' for spaces>   (-> exp_<args>.jsonl)
@@ -19,7 +19,7 @@ for step in "$@"; do
     tests:*) timeout 1500 python -m pytest tests -m gpu -x -q -k "${step#tests:}" > $O/pytest_k.log 2>&1; echo "pytest -k rc=$?"; tail -8 $O/pytest_k.log;;
     bench|bench2)
       f=$O/bench; [ "$step" = bench2 ] && f=$O/bench_run2
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $f.json 2> $f.err; echo "$step rc=$? final line $(tail -1 $f.json | wc -c) bytes"
+      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $f.json 2> $f.err; echo "$step rc=$? final line $(tail -1 $f.json | wc -c) bytes"
       cp bench_details.json ${f}_details.json 2>/dev/null
       tail -1 $f.json | python -c "
 import json,sys

@@ -12,8 +12,8 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/profile_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-HEAD="python $ROOT/bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-extra --one-stream"
-FULL="python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+HEAD="python $ROOT/bench.py --steps 60 --warmup 10 --full --no-cpu-baseline --no-extra --one-stream"
+FULL="python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline"
 run() {  # name, rocprof args..., -- cmd
     local name=$1; shift
     rocprofv3 --kernel-trace "$@" > "$OUT/$name.stdout" 2> /dev/null
