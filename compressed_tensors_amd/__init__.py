@@ -32,6 +32,14 @@ from .quantization import (
     fake_quantize,
     quantize,
 )
+from .transform import (
+    HadamardTransform,
+    TransformArgs,
+    TransformConfig,
+    TransformLocation,
+    TransformScheme,
+    apply_transform_config,
+)
 
 __all__ = [
     "codec",
@@ -60,4 +68,10 @@ __all__ = [
     "quantize",
     "dequantize",
     "fake_quantize",
+    "TransformLocation",
+    "TransformArgs",
+    "TransformScheme",
+    "TransformConfig",
+    "HadamardTransform",
+    "apply_transform_config",
 ]

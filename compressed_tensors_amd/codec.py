@@ -7,7 +7,7 @@ tensors are staged through the GPU (H2D, kernel, D2H) so the arithmetic is alway
 path; without a GPU the calls raise.
 """
 import math
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -28,6 +28,9 @@ __all__ = [
     "minmax_qparams_float",
     "dynamic_qdq",
     "generate_gparam",
+    "HadamardPlan",
+    "plan_hadamard",
+    "hadamard_transform",
     "rtn_quantize_and_pack",
     "rtn_mxfp4_quantize_and_pack",
     "rtn_quantize_channel8",
@@ -579,6 +582,84 @@ def dynamic_qdq(x: torch.Tensor, *, kind: str, segs: int, seg_len: int, num_bits
     else:
         call("ct_dynamic_qdq", *head, int(segs), int(seg_len), *tail, ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
     return out, scale, zp
+
+
+HADAMARD_MAX_SIZE = {torch.float32: 16384, torch.float64: 16384}  # kHadMaxF32 / kHadMaxF64 of csrc/ct_hadamard.hip
+
+
+class HadamardPlan(NamedTuple):
+    """what `hadamard_transform` launches: form "rows" (ct_hadamard_rows over `numel` elements, the transformed dimension
+    contiguous) or "cols" (ct_hadamard_cols along dim 0 of a rows x cols matrix), `blocks` independent blocks of `size`"""
+    form: str
+    size: int
+    blocks: int
+    acc64: bool
+    rows: int
+    cols: int
+
+
+def plan_hadamard(shape, dtype, size: int, dim: int = -1, precision=torch.float32, *, device_type: str = "cuda", contiguous: bool = True) -> HadamardPlan:
+    """The host-side decision of `hadamard_transform`, from shapes and dtypes alone (no tensor data is touched): the form, the
+    block count and the accumulator — or upstream's ValueError (transform/utils/hadamard.py:37-42, transform/utils/matrix.py:41-45)
+    for a size that is not a positive power of two or does not divide the dimension, or NotImplementedError for what the
+    kernels decline (a caller such as install() hands those to the reference)."""
+    size = int(size)
+    if size <= 0:
+        raise ValueError("Cannot construct deterministic hadamard of size <= 0")
+    if size & (size - 1):
+        raise ValueError("Cannot construct deterministic hadamard of size != 2^n")
+    shape = tuple(int(d) for d in shape)
+    if not shape:
+        raise ValueError("hadamard_transform of a 0-dim tensor")
+    if not -len(shape) <= dim < len(shape):
+        raise IndexError(f"dim {dim} out of range for a {len(shape)}-dim tensor")
+    dim %= len(shape)
+    if shape[dim] % size != 0:
+        raise ValueError(f"{size} must divide {shape[dim]} (dim {dim} of shape {shape})")
+    if precision in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"precision {precision}: upstream would run its GEMM in that dtype, which no kernel here reproduces")
+    if precision not in HADAMARD_MAX_SIZE:
+        raise NotImplementedError(f"precision must be torch.float32 or torch.float64, got {precision}")
+    if dtype not in _FLOATS:
+        raise NotImplementedError(f"the hadamard kernels take bfloat16, float16 and float32 tensors, got {dtype}")
+    if device_type != "cuda":
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {device_type} tensor")
+    if not contiguous:
+        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    if size > HADAMARD_MAX_SIZE[precision]:
+        raise NotImplementedError(f"hadamard size {size} exceeds the supported maximum {HADAMARD_MAX_SIZE[precision]} at precision {precision}")
+    outer, inner = math.prod(shape[:dim]), math.prod(shape[dim + 1:])
+    acc64 = precision is torch.float64
+    if inner == 1 or size == 1:  # the transformed dimension is contiguous (a bias column (n, 1) included)
+        numel = outer * shape[dim] * inner
+        return HadamardPlan("rows", size, numel // size, acc64, numel // max(shape[dim], 1), shape[dim])
+    if outer != 1:
+        raise NotImplementedError(f"the column form takes one matrix: dim {dim} of shape {shape} is neither the first nor the last dimension")
+    return HadamardPlan("cols", size, (shape[dim] // size) * inner, acc64, shape[dim], inner)
+
+
+def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=torch.float32) -> torch.Tensor:
+    """HadamardTransform.forward (transform/factory/hadamard.py:91-108) for the Sylvester matrix of
+    deterministic_hadamard_matrix(size): every run of `size` elements along `dim` is multiplied by H_size / sqrt(size) (the
+    block-diagonal `_multihead_matmul` of transform/utils/matrix.py:124-158 when the dimension is longer), accumulated in
+    `precision` and rounded once to x's dtype.  A fast Walsh-Hadamard butterfly on the GPU: no matrix, no GEMM.  The matrix is
+    symmetric, so `inverse=True` upstream is the same call.  dim == last (or any dimension followed only by 1s): one launch;
+    dim == 0 of a matrix: ct_hadamard_cols."""
+    plan = plan_hadamard(x.shape, x.dtype, size, dim, precision, contiguous=x.is_contiguous())
+    _lib.require_device()
+    if not x.is_cuda:
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
+    if x.data_ptr() % 16:
+        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    if plan.form == "rows":
+        call("ct_hadamard_rows", ptr(x), ptr(out), DT[x.dtype], x.numel(), plan.size, int(plan.acc64), stream_of(x))
+    else:
+        ws = torch.empty_like(x)
+        call("ct_hadamard_cols", ptr(x), ptr(out), ptr(ws), DT[x.dtype], plan.rows, plan.cols, plan.size, int(plan.acc64), stream_of(x))
+    return out
 
 
 def generate_gparam(x: torch.Tensor) -> torch.Tensor:

@@ -483,13 +483,65 @@ def _patch_forward() -> None:
                 _FN_REBOUND.append((mod, attr, hit[0]))
 
 
+_TR_SAVED = {}  # install(patch_transforms=True): the two originals of transform/factory/hadamard.py
+
+
+def _patch_transforms() -> None:
+    """`install(patch_transforms=True)`: upstream's RandomHadamardFactory reuses the HadamardTransform class with another matrix, so
+    the class alone does not identify a Sylvester transform.  `HadamardFactory.create_transform` is wrapped to tag what a factory
+    whose type is EXACTLY HadamardFactory makes, and `HadamardTransform.forward` (transform/factory/hadamard.py:91-108) to send a
+    tagged transform without a permutation, on a GPU value the kernels plan, to codec.hadamard_transform (csrc/ct_hadamard.hip)
+    with the precision of the materialised weight; everything else — randomize=True, random-hadamard, CPU / meta / non-contiguous
+    values, a NotImplementedError from the HIP side — runs the original.  The n x n weight stays where upstream put it."""
+    import functools
+
+    import compressed_tensors.transform.factory.hadamard as up_h
+
+    from .transform.hadamard import transform_dim
+
+    if _TR_SAVED:
+        return
+    orig_create, orig_forward = up_h.HadamardFactory.create_transform, up_h.HadamardTransform.forward
+
+    @functools.wraps(orig_create)
+    def create_transform(self, module, args):
+        transform = orig_create(self, module, args)
+        if type(self) is up_h.HadamardFactory:
+            transform._ct_sylvester = True
+        return transform
+
+    @functools.wraps(orig_forward)
+    def forward(self, value):
+        if getattr(self, "_ct_sylvester", False) and self.perm is None and value.is_cuda:
+            try:
+                out = codec.hadamard_transform(value, self.weight.size(0), dim=transform_dim(self.args.location, self.module_type),
+                                               precision=self.weight.dtype)
+                return out.to(value.dtype)
+            except (NotImplementedError, ValueError):
+                pass  # upstream computes it, or raises its own error
+        return orig_forward(self, value)
+
+    create_transform._ct_original, forward._ct_original = orig_create, orig_forward
+    _TR_SAVED.update(cls_factory=up_h.HadamardFactory, cls_transform=up_h.HadamardTransform, create=orig_create, forward=orig_forward)
+    up_h.HadamardFactory.create_transform = create_transform
+    up_h.HadamardTransform.forward = forward
+
+
+def _unpatch_transforms() -> None:
+    if _TR_SAVED:
+        _TR_SAVED["cls_factory"].create_transform = _TR_SAVED["create"]
+        _TR_SAVED["cls_transform"].forward = _TR_SAVED["forward"]
+        _TR_SAVED.clear()
+
+
 def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False,
-            patch_forward: bool = False):
+            patch_forward: bool = False, patch_transforms: bool = False):
     """registry swap + ImplBackend registration
     (+ the by-name bindings of the codec classes inside upstream's own modules unless rebind_names=False;
      + batched launches behind upstream's ModelCompressor.compress_model / decompress_model unless wrap_model_compressor=False;
      + with patch_functions=True the plain functions pack_to_int32 / unpack_from_int32 / dequantize / fake_quantize;
-     + with patch_forward=True the QDQ forward's forward_quantize / compute_dynamic_scales_and_zp)."""
+     + with patch_forward=True the QDQ forward's forward_quantize / compute_dynamic_scales_and_zp;
+     + with patch_transforms=True the deterministic HadamardTransform.forward)."""
     import compressed_tensors  # the upstream package; ImportError if it is not installed
     from compressed_tensors.compressors import BaseCompressor
     from compressed_tensors.registry import registry as up_registry
@@ -507,6 +559,8 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
         _patch_functions()
     if patch_forward:
         _patch_forward()
+    if patch_transforms:
+        _patch_transforms()
     return compressed_tensors
 
 
@@ -524,6 +578,7 @@ def _broadcast_layout(x, scale):
 
 
 def uninstall():
+    _unpatch_transforms()
     if not _SAVED:
         return
     from compressed_tensors.compressors import BaseCompressor

@@ -299,6 +299,21 @@ int ct_dynamic_qdq_tensor(const void* x, int xdt, int64_t numel, int kind, int b
                           const float* global_scale, void* workspace, void* out, void* scale_out, void* zp_out, int zdt,
                           ct_stream_t stream);
 
+/* The Sylvester Hadamard rotation of HadamardTransform.forward (transform/factory/hadamard.py:91-108; the matrix of
+ * transform/utils/hadamard.py:21-50, block-diagonal as in transform/utils/matrix.py:124-158) as a fast Walsh-Hadamard
+ * butterfly: out = FWHT_n(x) / sqrt(n) over every run of n consecutive elements (n a power of two that divides numel), no
+ * n x n matrix and no GEMM.  dt: CT_BF16, CT_F16 or CT_F32 for x and out alike.  acc64: 0 accumulates in float32 (online
+ * rotations), 1 in float64 (fused rotations: hadamard.py:44); the sum is divided once by sqrt(n) in that type and rounded to
+ * dt as torch's cast does.  One launch.  n up to 16384, beyond that CT_ERR_UNSUPPORTED; x and
+ * out are 16-byte aligned and distinct. */
+int ct_hadamard_rows(const void* x, void* out, int dt, int64_t numel, int64_t n, int acc64, ct_stream_t stream);
+
+/* The same along dim 0 of a row-major rows x cols matrix (n divides rows): Linear `weight_output`, Embedding `weight_input`
+ * (matrix.py:107-114).  Three launches: transpose into `workspace` (device memory of rows * cols elements of dt), the row
+ * form in place, transpose back into out. */
+int ct_hadamard_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64,
+                     ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
