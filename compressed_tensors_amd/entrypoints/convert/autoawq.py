@@ -4,31 +4,16 @@ MI355X design of `AutoAWQConverter.process`: the qweight / qzeros / scales of AL
 GPU through one pinned buffer and one copy, and ONE `ct_awq_repack_batch` launch per shard turns them into weight_packed /
 weight_zero_point / weight_scale (a 4-bit transpose, csrc/ct_awq.hip); the results come back through one pinned buffer.  Nothing
 is unpacked, reordered or re-packed on the host."""
-import array
-import copy
-import ctypes
 import re
-from typing import Any, Dict, Iterable, List, Set
+from typing import Any, Dict, Iterable, Set
 
 import torch
 
-from .converters import _READY_BYTES, _STREAMING, Converter, ReadyDict, _stage_to_device, match_name
+from .converters import Converter, _ConfigDict, match_name
 from .safetensors_io import CONFIG_NAME, get_checkpoint_files
+from .staging import ReadyDict, device_outputs, launch_tables, return_to_host, settle, stage_inputs
 
 __all__ = ["AutoAWQConverter"]
-
-_ALIGN = 256
-
-
-class _ConfigDict:
-    """what `create_config` returns: the reference's QuantizationConfig only as far as `model_dump()` (this package has no pydantic
-    config; `write_checkpoint_quantization_config` needs no more)"""
-
-    def __init__(self, data: Dict[str, Any]):
-        self._data = data
-
-    def model_dump(self) -> Dict[str, Any]:
-        return copy.deepcopy(self._data)
 
 
 class AutoAWQConverter(Converter):
@@ -94,7 +79,6 @@ class AutoAWQConverter(Converter):
         """the converted shard: the AWQ tensors of every targeted module are consumed (popped from `tensors`) and replaced by their
         pack-quantized form, every other tensor passes through"""
         from ... import _lib
-        from ...codec import _upload_table
 
         modules, inputs = [], []
         for name in list(tensors):
@@ -120,11 +104,7 @@ class AutoAWQConverter(Converter):
             dev = self.device or _lib.require_device()
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev)
-                out.keep.append(_stage_to_device(inputs, dev))
-                for sd in inputs:  # tensors handed over on the device already are not staged
-                    for k in sd:
-                        sd[k] = sd[k].contiguous()
-                # every output of the shard in ONE device buffer, laid out in the order the writer stores the tensors (sorted names)
+                stage_inputs(out, inputs, dev)
                 specs = []  # (name, shape, dtype)
                 for m, sd in zip(modules, inputs):
                     K, N, G = sd["qweight"].shape[0], 8 * sd["qweight"].shape[1], sd["scales"].shape[0]
@@ -133,13 +113,7 @@ class AutoAWQConverter(Converter):
                     if self.zero_point:
                         specs.append((f"{m}.weight_zero_point", (N // 8, G), torch.int32))
                     out[f"{m}.weight_shape"] = torch.tensor([N, K], dtype=torch.int64)
-                offs, off = {}, 0
-                for name, shape, dtype in sorted(specs):
-                    offs[name] = off
-                    off += -(-shape[0] * shape[1] * dtype.itemsize // _ALIGN) * _ALIGN
-                dbuf = torch.empty(off, dtype=torch.uint8, device=dev)
-                dev_out = {name: dbuf[offs[name]:offs[name] + shape[0] * shape[1] * dtype.itemsize].view(dtype).view(shape)
-                           for name, shape, dtype in specs}
+                dbuf, dev_out = device_outputs(specs, dev)
 
                 items = []
                 for m, sd in zip(modules, inputs):
@@ -153,32 +127,10 @@ class AutoAWQConverter(Converter):
                     it.K, it.N, it.G = qw.shape[0], 8 * qw.shape[1], sc.shape[0]
                     it.scale_shape[0], it.scale_shape[1] = sc.shape
                     items.append(it)
-                for table in _plan(items):
-                    words = array.array("q", bytes(table[1]))
-                    dtable = _upload_table(words, dev)
-                    _lib.check(_lib.load().ct_awq_repack_batch(dtable.data_ptr(), table[0], table[2], _lib.stream_on(dev)))
-                    dtable.record_stream(stream)
-
-                # back to the host through one pinned buffer, in copies of ~32 MB that end on tensor boundaries, an event behind each:
-                # the writer waits for a tensor's event, not for the whole shard
-                stage = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-                order = sorted(specs)
-                start, pending = 0, []
-                for i, (name, shape, dtype) in enumerate(order):
-                    out[name] = stage[offs[name]:offs[name] + shape[0] * shape[1] * dtype.itemsize].view(dtype).view(shape)
-                    pending.append(name)
-                    end = offs[order[i + 1][0]] if i + 1 < len(order) else off
-                    if end - start >= _READY_BYTES or i + 1 == len(order):
-                        stage[start:end].copy_(dbuf[start:end], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(stream)
-                        out.ready.update(dict.fromkeys(pending, ev))
-                        start, pending = end, []
-                out.keep.append(dbuf)
-                if not (self.stream_results or getattr(_STREAMING, "on", False)):
-                    stream.synchronize()
-                    out.ready.clear()
-                    out.keep.clear()
+                lib = _lib.load()
+                launch_tables(items, modules, _lib.AwqItem, lib.ct_awq_repack_plan, lib.ct_awq_repack_batch, dev)
+                return_to_host(out, specs, dbuf, stream)
+                settle(out, stream, self.stream_results)
         for name, t in tensors.items():
             out[name] = t
         return out
@@ -230,19 +182,3 @@ def _check_module(module_name: str, sd: Dict[str, torch.Tensor]) -> None:
         raise ValueError(f"{module_name}.qzeros: expected a 2-D int32 tensor, got {qz.dtype} {tuple(qz.shape)}")
     if sc.dim() != 2 or sc.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"{module_name}.scales: expected a 2-D float16 or bfloat16 tensor, got {sc.dtype} {tuple(sc.shape)}")
-
-
-def _plan(items: List["ctypes.Structure"]):
-    """[(n, table, workgroups)]: the items in as few tables as `ct_awq_repack_plan` accepts (a refused batch is halved; a refused
-    single item is malformed and raises)"""
-    from ... import _lib
-
-    lib = _lib.load()
-    table = (_lib.AwqItem * len(items))(*items)
-    blocks = int(lib.ct_awq_repack_plan(ctypes.cast(table, ctypes.c_void_p), len(items)))
-    if blocks >= 0:
-        return [(len(items), table, blocks)]
-    if len(items) == 1:
-        raise ValueError(_lib.last_error())
-    half = len(items) // 2
-    return _plan(items[:half]) + _plan(items[half:])

@@ -5,11 +5,10 @@ MI355X design of `CompressedTensorsDequantizer.process`: the compressed tensors 
 of a shard are moved to the GPU, decompressed by ONE batched launch per scheme where the codec allows it
 (`BaseCompressor.decompress_many`, W4A16 -> `ct_unpack_dequant_batch`), cast, and copied back into pinned
 host buffers on the caller's stream; nothing is decompressed on the CPU."""
-import contextlib
+import copy
 import re
-import threading
 from collections import defaultdict
-from typing import Dict, Iterable, List, Optional, Set
+from typing import Any, Dict, Iterable, List, Optional, Set
 
 import torch
 
@@ -18,6 +17,8 @@ from ...compressors.format import infer_module_format
 from ...config import CompressionFormat
 from ...quantization.quant_args import QuantizationArgs, QuantizationScheme
 from .safetensors_io import CONFIG_NAME, find_config_path, get_checkpoint_files, get_quantization_config
+# the shard round trip the converters share lives in staging.py; its names stay reachable here
+from .staging import _READY_BYTES, _STREAMING, ReadyDict, _stage_to_device, settle, streaming_results  # noqa: F401
 
 __all__ = ["Converter", "build_inverse_weight_maps", "CompressedTensorsDequantizer", "match_name", "match_quantizable_tensors"]
 
@@ -38,6 +39,17 @@ class Converter:
 
     def get_dependencies(self, weight_name: str) -> Set[str]:
         raise NotImplementedError()
+
+
+class _ConfigDict:
+    """what `create_config` returns: the reference's QuantizationConfig only as far as `model_dump()` (this package has no pydantic
+    config; `write_checkpoint_quantization_config` needs no more)"""
+
+    def __init__(self, data: Dict[str, Any]):
+        self._data = data
+
+    def model_dump(self) -> Dict[str, Any]:
+        return copy.deepcopy(self._data)
 
 
 def match_name(name: str, target: str) -> bool:
@@ -103,75 +115,6 @@ def _args_from_dict(d: Optional[dict]) -> Optional[QuantizationArgs]:
         if isinstance(v, torch.dtype):
             known[key] = v
     return QuantizationArgs(**known)
-
-
-_H2D_ALIGN = 256
-_READY_BYTES = 32 << 20  # one event per ~32 MB of D2H copies
-
-
-_STREAMING = threading.local()
-
-
-@contextlib.contextmanager
-def streaming_results():
-    """inside this context (per thread) a converter that supports it hands its tensors over while their D2H copies are still in flight"""
-    prev = getattr(_STREAMING, "on", False)
-    _STREAMING.on = True
-    try:
-        yield
-    finally:
-        _STREAMING.on = prev
-
-
-class ReadyDict(dict):
-    """a shard's converted tensors: host tensors whose device-to-host copies may still be in flight.  `ready[name]` is the event
-    recorded behind the copy of `name` (absent: the tensor is complete); `keep` holds what must stay alive until then.  Consumers
-    that do not know about it call `wait()` first."""
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.ready = {}
-        self.keep = []
-
-    def wait(self, name=None) -> None:
-        if name is not None:
-            ev = self.ready.pop(name, None)
-            if ev is not None:
-                ev.synchronize()
-            return
-        for ev in set(self.ready.values()):
-            ev.synchronize()
-        self.ready.clear()
-        self.keep.clear()
-
-
-def _stage_to_device(state_dicts, dev, host_only=()):
-    """Move a shard's compressed tensors to the device through ONE pinned buffer and ONE copy.  The tensors safetensors
-    hands out are lazily mapped file pages: `t.to(device)` per tensor is a pageable copy that faults the file in 4 KB at a
-    time on the calling thread (23.0 ms for the 125 MB of a TinyLlama-shaped shard, half of `process`).  Here the I/O
-    threads copy the mapped pages into the pinned buffer in parallel, one asynchronous H2D moves it (6.7 ms together), and
-    the device tensors are views into the device buffer (256-byte aligned).  Replaces the entries of `state_dicts` in place; returns what must stay alive until
-    the stream is synchronised."""
-    from .safetensors_io import host_bytes, parallel_copy
-
-    plan, off = [], 0
-    for sd in state_dicts:
-        for key, t in sd.items():
-            if key in host_only or t is None or t.device.type != "cpu":
-                continue
-            t = t.contiguous()
-            n = t.numel() * t.element_size()
-            plan.append((sd, key, t, off, n))
-            off += (n + _H2D_ALIGN - 1) // _H2D_ALIGN * _H2D_ALIGN
-    if not plan:
-        return None
-    stage = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-    flat = stage.numpy()
-    parallel_copy([(flat[o:o + n], host_bytes(t)) for _, _, t, o, n in plan if n])
-    dbuf = stage.to(dev, non_blocking=True)
-    for sd, key, t, o, n in plan:
-        sd[key] = dbuf[o:o + n].view(t.dtype).view(t.shape)
-    return stage, dbuf
 
 
 class CompressedTensorsDequantizer(Converter):
@@ -254,10 +197,7 @@ class CompressedTensorsDequantizer(Converter):
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(dev))
                 ready.update(dict.fromkeys(pending, ev))
-        if not (self.stream_results or getattr(_STREAMING, "on", False)):
-            torch.cuda.current_stream(dev).synchronize()
-            ready.clear()
-            keep.clear()  # the list lives on in the returned ReadyDict: empty it, or the pinned H2D staging stays alive for the shard's lifetime
+        settle(out, torch.cuda.current_stream(dev), self.stream_results)
         # remaining (ignored / untargeted) tensors pass through, KV-cache qparams are dropped
         for name, t in tensors.items():
             if name.endswith(KV_CACHE_PARAM_NAMES):

@@ -4,17 +4,15 @@ MI355X design of `FP8BlockDequantizer.process`: the float8_e4m3fn `weight` and t
 shard are staged to the GPU through one pinned buffer and one copy, and ONE `ct_fp8block_dequant_batch` launch per shard writes the
 dequantized weights (csrc/ct_fp8block.hip: w * scale_inv per element, no padding, no transposes); the results come back through
 one pinned buffer.  Nothing is widened, multiplied or cast on the host."""
-import array
-import ctypes
 from typing import Dict, Iterable, List, Set
 
 import torch
 
-from .converters import _READY_BYTES, _STREAMING, Converter, ReadyDict, _stage_to_device, match_name, match_quantizable_tensors
+from .converters import Converter, match_name, match_quantizable_tensors
+from .staging import ReadyDict, device_outputs, launch_tables, return_to_host, settle, stage_inputs
 
 __all__ = ["FP8BlockDequantizer"]
 
-_ALIGN = 256
 _OUT_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 
 
@@ -48,19 +46,11 @@ class FP8BlockDequantizer(Converter):
             if f"{m}.weight_scale_inv" not in tensors:
                 raise ValueError(f"Found weight without corresponding weight_scale_inv {m}.weight")
             _check_module(m, tensors[f"{m}.weight"], tensors[f"{m}.weight_scale_inv"])
-        done = self._dequantize(modules, [(tensors[f"{m}.weight"], tensors[f"{m}.weight_scale_inv"]) for m in modules]) if modules else ReadyDict()
-        targeted, out = set(modules), ReadyDict()
-        for name, t in tensors.items():
-            module_name, _, param_name = name.rpartition(".")
-            if module_name not in targeted:
-                out[name] = t
-            elif param_name == "weight":
-                out[name] = done[module_name]
-            elif param_name != "weight_scale_inv":
-                out[name] = t
-        # the events of `done` are keyed by module; the writer waits by tensor name
-        out.ready = {f"{m}.weight": ev for m, ev in done.ready.items()}
-        out.keep = done.keep
+        targeted = set(modules)
+        out = ReadyDict((name, t) for name, t in tensors.items()
+                        if not (name.endswith(".weight_scale_inv") and name.rpartition(".")[0] in targeted))
+        if modules:  # every targeted `weight` of `out` is replaced in place, so the order stays
+            self._dequantize(out, modules, [(tensors[f"{m}.weight"], tensors[f"{m}.weight_scale_inv"]) for m in modules])
         return out
 
     def validate(self, tensors: Dict[str, torch.Tensor]):
@@ -96,32 +86,23 @@ class FP8BlockDequantizer(Converter):
         _check_module("weight", weight, weight_scale_inv)
         on_device = weight.device.type == "cuda"
         dev = weight.device if on_device else None
-        got = self._dequantize(["weight"], [(weight, weight_scale_inv)], device=dev, to_host=not on_device)
+        got = ReadyDict()
+        self._dequantize(got, ["weight"], [(weight, weight_scale_inv)], device=dev, to_host=not on_device)
         got.wait()
-        return got["weight"]
+        return got["weight.weight"]
 
-    def _dequantize(self, modules: List[str], pairs, device=None, to_host: bool = True) -> ReadyDict:
-        """module name -> dequantized weight for every (weight, weight_scale_inv) pair, through one staging copy and one launch per
-        table the planner accepts"""
+    def _dequantize(self, out: ReadyDict, modules: List[str], pairs, device=None, to_host: bool = True) -> None:
+        """`out[f"{module}.weight"]` = the dequantized weight of every (weight, weight_scale_inv) pair, through one staging copy and
+        one launch per table the planner accepts"""
         from ... import _lib
-        from ...codec import _upload_table
 
-        out = ReadyDict()
         dev = device or self.device or _lib.require_device()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             inputs = [{"w": w, "s": s} for w, s in pairs]
-            out.keep.append(_stage_to_device(inputs, dev))
-            for sd in inputs:  # tensors handed over on the device already are not staged
-                sd["w"], sd["s"] = sd["w"].contiguous(), sd["s"].contiguous()
-            # every output in ONE device buffer, laid out in the order the writer stores the tensors (sorted names)
-            nbytes = {m: sd["w"].numel() * self.dtype.itemsize for m, sd in zip(modules, inputs)}
-            offs, off = {}, 0
-            for m in sorted(modules):
-                offs[m] = off
-                off += -(-nbytes[m] // _ALIGN) * _ALIGN
-            dbuf = torch.empty(max(off, 1), dtype=torch.uint8, device=dev)
-            dev_out = {m: dbuf[offs[m]:offs[m] + nbytes[m]].view(self.dtype).view(sd["w"].shape) for m, sd in zip(modules, inputs)}
+            stage_inputs(out, inputs, dev)
+            specs = [(f"{m}.weight", tuple(sd["w"].shape), self.dtype) for m, sd in zip(modules, inputs)]
+            dbuf, dev_out = device_outputs(specs, dev)
 
             items, names = [], []
             bh, bw = self.weight_block_size
@@ -131,46 +112,24 @@ class FP8BlockDequantizer(Converter):
                     continue
                 s2 = s.reshape((1,) * (2 - s.dim()) + tuple(s.shape))  # torch broadcasting of a 0-D / 1-D scale
                 it = _lib.Fp8BlockItem()
-                it.w, it.scale, it.out = w.data_ptr(), s2.data_ptr(), dev_out[m].data_ptr()
+                it.w, it.scale, it.out = w.data_ptr(), s2.data_ptr(), dev_out[f"{m}.weight"].data_ptr()
                 it.rows, it.cols, it.block_h, it.block_w = w.shape[0], w.shape[1], bh, bw
                 it.scale_shape[0], it.scale_shape[1] = s2.shape
                 it.sdt = _lib.DT[s.dtype]
                 items.append(it)
                 names.append(m)
-            odt = _lib.DT[self.dtype]
-            for n, table, blocks in _plan(items, names):
-                dtable = _upload_table(array.array("q", bytes(table)), dev)
-                _lib.check(_lib.load().ct_fp8block_dequant_batch(dtable.data_ptr(), n, blocks, odt, _lib.stream_on(dev)))
-                dtable.record_stream(stream)
+            lib, odt = _lib.load(), _lib.DT[self.dtype]
+            launch_tables(items, names, _lib.Fp8BlockItem, lib.ct_fp8block_dequant_plan,
+                          lambda table, n, blocks, handle: lib.ct_fp8block_dequant_batch(table, n, blocks, odt, handle), dev)
 
             if not to_host:
                 stream.synchronize()
                 out.keep.clear()
-                for m in modules:
-                    out[m] = dev_out[m].clone()
-                return out
-            # back to the host through one pinned buffer, in copies of ~32 MB that end on tensor boundaries, an event behind each:
-            # the writer waits for a tensor's event, not for the whole shard
-            stage = torch.empty(max(off, 1), dtype=torch.uint8, pin_memory=True)
-            order = sorted(modules)
-            start, pending = 0, []
-            for i, m in enumerate(order):
-                out[m] = stage[offs[m]:offs[m] + nbytes[m]].view(self.dtype).view(dev_out[m].shape)
-                pending.append(m)
-                end = offs[order[i + 1]] if i + 1 < len(order) else off
-                if end - start >= _READY_BYTES or i + 1 == len(order):
-                    if end > start:
-                        stage[start:end].copy_(dbuf[start:end], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(stream)
-                    out.ready.update(dict.fromkeys(pending, ev))
-                    start, pending = end, []
-            out.keep.append(dbuf)
-            if not (self.stream_results or getattr(_STREAMING, "on", False)):
-                stream.synchronize()
-                out.ready.clear()
-                out.keep.clear()
-        return out
+                for name, view in dev_out.items():
+                    out[name] = view.clone()
+                return
+            return_to_host(out, specs, dbuf, stream)
+            settle(out, stream, self.stream_results)
 
 
 def _check_module(module_name: str, w: torch.Tensor, s: torch.Tensor) -> None:
@@ -180,21 +139,3 @@ def _check_module(module_name: str, w: torch.Tensor, s: torch.Tensor) -> None:
     if s.dtype not in (torch.float32, torch.bfloat16, torch.float16) or s.dim() > 2:
         raise ValueError(f"{module_name}.weight_scale_inv: expected a float32, bfloat16 or float16 tensor of at most 2 dimensions, "
                          f"got {s.dtype} {tuple(s.shape)}")
-
-
-def _plan(items: List["ctypes.Structure"], names: List[str]):
-    """[(n, table, workgroups)]: the items in as few tables as `ct_fp8block_dequant_plan` accepts (a refused batch is halved; a
-    refused single item is malformed and raises, naming its module)"""
-    from ... import _lib
-
-    if not items:
-        return []
-    lib = _lib.load()
-    table = (_lib.Fp8BlockItem * len(items))(*items)
-    blocks = int(lib.ct_fp8block_dequant_plan(ctypes.cast(table, ctypes.c_void_p), len(items)))
-    if blocks >= 0:
-        return [(len(items), table, blocks)]
-    if len(items) == 1:
-        raise ValueError(f"{names[0]}: {_lib.last_error()}")
-    half = len(items) // 2
-    return _plan(items[:half], names[:half]) + _plan(items[half:], names[half:])

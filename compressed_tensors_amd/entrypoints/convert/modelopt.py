@@ -7,8 +7,7 @@ from typing import Any, Dict, Iterable, Optional, Set
 import torch
 
 from ...quantization.quant_args import QuantizationArgs
-from .autoawq import _ConfigDict
-from .converters import Converter, match_name, match_quantizable_tensors
+from .converters import Converter, _ConfigDict, match_name, match_quantizable_tensors
 
 __all__ = ["ModelOptNvfp4Converter"]
 

@@ -1,7 +1,7 @@
 """AutoAWQConverter (reference entrypoints/convert/converters/autoawq.py): AutoAWQ GEMM checkpoints to pack-quantized through one
 `ct_awq_repack_batch` launch per shard.  CPU tests: the converter's host logic against the reference tests' cases and the fixture's
 config dicts, and the C planner through ctypes.  GPU tests: `process` against the reference's outputs in tests/golden/awq.safetensors
-(tools/gen_golden_awq.py), an 8B-shaped table against an eager int32 restatement of the format, and convert_checkpoint end to end
+(tools/gen_golden_awq.py), one launch per shard, an 8B-shaped table against an eager int32 restatement of the format, and convert_checkpoint end to end
 followed by the existing dequantizer."""
 import ctypes
 import json
@@ -221,13 +221,16 @@ def test_plan_refuses_malformed_items_and_oversized_batches(lib):
 
 
 def test_python_splits_a_batch_the_plan_refuses(lib):
-    from compressed_tensors_amd.entrypoints.convert import autoawq
+    from compressed_tensors_amd.entrypoints.convert import staging
 
+    plan = lib.load().ct_awq_repack_plan
     big = [_item(1 << 26, 8192, 1, scale_shape=(1, 8192), zp_shape=(1, 1024), base=0x100000 * (i + 1)) for i in range(5)]
-    tables = autoawq._plan(big)
-    assert len(tables) > 1 and sum(n for n, _, _ in tables) == 5 and all(b > 0 for _, _, b in tables)
+    tables = staging.plan_tables(big, [f"m{i}" for i in range(5)], lib.AwqItem, plan)
+    assert len(tables) > 1 and sum(n for n, _, _ in tables) == 5 and all(0 < b < 1 << 24 for _, _, b in tables)
     with pytest.raises(ValueError, match="scales of shape"):
-        autoawq._plan([_item(64, 64, 1), _item(64, 64, 1, scale_shape=(1, 32))])
+        staging.plan_tables([_item(64, 64, 1), _item(64, 64, 1, scale_shape=(1, 32))], ["model.good", "model.bad"], lib.AwqItem, plan)
+    with pytest.raises(ValueError, match="^model.bad: ct_awq_repack_plan: item 0: "):
+        staging.plan_tables([_item(64, 64, 1), _item(64, 64, 1, scale_shape=(1, 32))], ["model.good", "model.bad"], lib.AwqItem, plan)
 
 
 # ------------------------------------------------------------------------------------------------------------------- GPU
@@ -281,6 +284,26 @@ def test_process_matches_the_reference_on_every_fixture_case():
         assert set(got) == set(ref), case["name"]
         for k, v in ref.items():
             assert got[k].device.type == "cpu" and got[k].dtype == v.dtype and got[k].shape == v.shape, (case["name"], k)
+            assert torch.equal(got[k], v), (case["name"], k)
+
+
+@pytest.mark.gpu
+def test_every_fixture_module_of_one_case_in_one_shard_takes_one_launch(monkeypatch):
+    from compressed_tensors_amd import _lib
+
+    lib = _lib.load()
+    calls = []
+    real = lib.ct_awq_repack_batch
+    monkeypatch.setattr(lib, "ct_awq_repack_batch", lambda *a: calls.append(a[1]) or real(*a))
+    for case in _manifest()["cases"]:
+        inp, ref = _case_tensors(case["name"], "in"), _case_tensors(case["name"], "out")
+        modules = [k for k in ref if k.endswith(".weight_packed")]  # one per module the reference converted
+        assert modules, case["name"]
+        del calls[:]
+        got = AutoAWQConverter.from_autoawq_config(case["autoawq_config"], targets=case["targets"]).process(dict(inp))
+        assert calls == [len(modules)], case["name"]
+        assert set(got) == set(ref), case["name"]
+        for k, v in ref.items():
             assert torch.equal(got[k], v), (case["name"], k)
 
 

@@ -275,13 +275,14 @@ def test_launch_refuses_a_bad_output_dtype(lib):
 
 
 def test_python_splits_a_table_the_plan_refuses(lib):
-    from compressed_tensors_amd.entrypoints.convert import fp8block
+    from compressed_tensors_amd.entrypoints.convert import staging
 
+    plan = lib.load().ct_fp8block_dequant_plan
     big = [_item(1 << 20, 1 << 16, scale_shape=(1, 1), base=0x100000 * (i + 1)) for i in range(5)]
-    tables = fp8block._plan(big, [f"m{i}" for i in range(5)])
+    tables = staging.plan_tables(big, [f"m{i}" for i in range(5)], lib.Fp8BlockItem, plan)
     assert len(tables) > 1 and sum(n for n, _, _ in tables) == 5 and all(0 < b < 1 << 24 for _, _, b in tables)
     with pytest.raises(ValueError, match="model.bad: ct_fp8block_dequant_plan: item 0: weight_scale_inv of shape"):
-        fp8block._plan([_item(64, 64), _item(128, 128, scale_shape=(2, 2))], ["model.good", "model.bad"])
+        staging.plan_tables([_item(64, 64), _item(128, 128, scale_shape=(2, 2))], ["model.good", "model.bad"], lib.Fp8BlockItem, plan)
 
 
 def test_restatement_matches_the_reference_fixtures():
