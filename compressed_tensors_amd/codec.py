@@ -27,6 +27,7 @@ __all__ = [
     "minmax_qparams",
     "minmax_qparams_float",
     "dynamic_qdq",
+    "hadamard_dynamic_qdq",
     "generate_gparam",
     "HadamardPlan",
     "plan_hadamard",
@@ -660,6 +661,38 @@ def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=t
         ws = torch.empty_like(x)
         call("ct_hadamard_cols", ptr(x), ptr(out), ptr(ws), DT[x.dtype], plan.rows, plan.cols, plan.size, int(plan.acc64), stream_of(x))
     return out
+
+
+ROTATED_MAX_BLOCK = 8192  # kRotMaxBlock of csrc/ct_rotated.hip: the largest rotation block the fused launch takes (16384 measured slower)
+ROTATED_MAX_ROW = 32768  # kSegMaxThreads * kSegUnits * 8 of csrc/ct_dynamic.h: the longest token row the staged form holds
+
+
+def hadamard_dynamic_qdq(x: torch.Tensor, size: int, *, kind: str, seg_len: int, num_bits: int = 8, symmetric: bool = True,
+                         global_scale: Optional[torch.Tensor] = None, scale_shape=None, scale_dtype=None, zp_dtype=None,
+                         want_out: bool = True, want_rotated: bool = False):
+    """`hadamard_transform(x, size)` (last dimension, float32 accumulation) followed by `dynamic_qdq` over segments of `seg_len`
+    elements of the rotated tensor, in ONE launch (ct_hadamard_dynamic_qdq): the rotated tensor stays in registers unless
+    `want_rotated` asks for it.  Returns (out or None, scale or None, zero_point or None, rotated or None), bit for bit what the two
+    calls return; the library answers CT_ERR_UNSUPPORTED (NotImplementedError) for a combination it does not fuse —
+    quantization.dynamic.plan_rotated_dynamic is the rule."""
+    _check_float(x, "activation")
+    _lib.require_device()
+    if not x.is_cuda:
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
+    if not x.is_contiguous():
+        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    if x.data_ptr() % 16:
+        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
+    dev = x.device
+    out = torch.empty_like(x) if want_out else None
+    rotated = torch.empty_like(x) if want_rotated else None
+    scale = torch.empty(scale_shape, dtype=scale_dtype, device=dev) if scale_dtype is not None else None
+    zp = torch.empty(scale_shape, dtype=zp_dtype, device=dev) if zp_dtype is not None else None
+    zdt = DT[zp_dtype] if zp_dtype is not None else -1
+    gs = _gs_arg(global_scale, dev)
+    call("ct_hadamard_dynamic_qdq", ptr(x), DT[x.dtype], x.numel(), int(size), int(seg_len), DYNAMIC_KINDS[kind], int(num_bits),
+         int(bool(symmetric)), ptr(gs), ptr(rotated), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
+    return out, scale, zp, rotated
 
 
 def generate_gparam(x: torch.Tensor) -> torch.Tensor:

@@ -1,0 +1,157 @@
+// ct_hadamard.h — the device helpers of the Walsh-Hadamard butterfly (csrc/ct_hadamard.hip), shared with the fused
+// rotation + dynamic QDQ launch of csrc/ct_rotated.hip: the lane exchanges, the butterfly stages, the 1 / sqrt(n) quotient.
+#pragma once
+#include "ct_common.h"
+
+namespace ct {
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+
+// the 32-bit value of lane (id ^ M)
+template <int M>
+__device__ __forceinline__ int lane_xor_i(int v) {
+    if constexpr (M == 1) return dpp_i<0xB1>(v);                                // quad_perm [1,0,3,2]
+    else if constexpr (M == 2) return dpp_i<0x4E>(v);                           // quad_perm [2,3,0,1]
+    else if constexpr (M == 4) return __builtin_amdgcn_ds_swizzle(v, 0x101F);   // bit mode: and 0x1f, or 0, xor 4
+    else if constexpr (M == 8) return dpp_i<0x128>(v);                          // row_ror:8 == xor 8 inside a row of 16
+    else if constexpr (M == 16) return __builtin_amdgcn_ds_swizzle(v, 0x401F);  // xor 16
+    else return __shfl_xor(v, 32, 64);
+}
+
+template <int M>
+__device__ __forceinline__ float lane_xor(float v) {
+    return __builtin_bit_cast(float, lane_xor_i<M>(__builtin_bit_cast(int, v)));
+}
+
+template <int M>
+__device__ __forceinline__ double lane_xor(double v) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)lane_xor_i<M>((int)(uint32_t)b), hi = (uint32_t)lane_xor_i<M>((int)(uint32_t)(b >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// one butterfly stage across the lanes whose index differs in bit M: the lower lane keeps a + b, the upper one a - b.  Both are
+// partner + sign * own with sign = +-1 — one fma, exact in the product, rounded once like the addition it replaces
+template <int M, typename A>
+__device__ __forceinline__ void lane_stage(A (&v)[8], bool upper) {
+    const A sign = upper ? (A)-1 : (A)1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = fma_t(v[k], sign, lane_xor<M>(v[k]));
+}
+
+// the stages of the lane bits below `lpb` (lanes per block, a power of two <= 64; uniform over the launch)
+template <typename A>
+__device__ __forceinline__ void lane_stages(A (&v)[8], int lpb, int lane) {
+    if (lpb > 1) lane_stage<1>(v, lane & 1);
+    if (lpb > 2) lane_stage<2>(v, lane & 2);
+    if (lpb > 4) lane_stage<4>(v, lane & 4);
+    if (lpb > 8) lane_stage<8>(v, lane & 8);
+    if (lpb > 16) lane_stage<16>(v, lane & 16);
+    if (lpb > 32) lane_stage<32>(v, lane & 32);
+}
+
+// the stages inside a unit: element bits below n (n >= 8: all three)
+template <typename A>
+__device__ __forceinline__ void unit_stages(A (&v)[8], int n) {
+#pragma unroll
+    for (int h = 1; h < 8; h <<= 1) {
+        if (h < n) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (!(k & h)) {
+                    const A a = v[k], b = v[k | h];
+                    v[k] = a + b;
+                    v[k | h] = a - b;
+                }
+            }
+        }
+    }
+}
+
+template <int XDT, typename A>
+__device__ __forceinline__ void had_load(const void* x, int64_t i0, int64_t numel, A (&v)[8]) {
+    float f[8];
+    if (i0 + 8 <= numel) {
+        load8<XDT>(x, i0, f);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = i0 + k < numel ? load_as_f<XDT>(x, i0 + k) : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (A)f[k];
+}
+
+// v / sqrt(n), correctly rounded, for the divisor every thread shares.  sqrt(n) is 2^k (n a power of 4) or fl(2^k * sqrt 2):
+//   HAD_MUL   2^k: v * 2^-k is the same correctly rounded quotient, one multiplication
+//   HAD_FAST  float, fl(2^k * sqrt 2): q = fl(v * r), e = v - q * sn (exact, one fma), q' = fl(q + e * r) with r = fl(1 / sn) —
+//             Markstein's correction step; checked over all 2^23 significands of v (two binades) against the IEEE quotient on the
+//             CPU and by tests/test_gpu_hadamard.py on the GPU.  Scaling by 2^k commutes with every step while nothing under- or
+//             overflows: a unit (8 values) that holds a zero, |v| < 2^-90, |v| > 2^100, inf or NaN takes the IEEE division (3 instructions against ~11)
+//   HAD_IEEE  the division itself (double, fl(2^k * sqrt 2))
+enum { HAD_MUL = 0, HAD_FAST = 1, HAD_IEEE = 2 };
+
+template <typename A>
+struct HadScale {
+    A sn, rn;  // fl(sqrt n) and fl(1 / sn)
+    int mode;
+};
+
+// the 8 quotients of a unit; the mode is uniform over the launch, the range test of HAD_FAST is per lane (one branch per unit)
+__device__ __forceinline__ void had_div8(const float (&v)[8], const HadScale<float>& s, float (&f)[8]) {
+    if (s.mode == HAD_MUL) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = v[k] * s.rn;
+        return;
+    }
+    float lo = __builtin_inff(), hi = 0.0f;  // a NaN fails `lo >=`: fminf / fmaxf would drop it, so it is counted separately
+    bool nan = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float a = __builtin_fabsf(v[k]);
+        lo = __builtin_fminf(lo, a);
+        hi = __builtin_fmaxf(hi, a);
+        nan |= v[k] != v[k];
+    }
+    if (!nan && lo >= 0x1p-90f && hi <= 0x1p100f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float q = v[k] * s.rn;
+            f[k] = __builtin_fmaf(__builtin_fmaf(-q, s.sn, v[k]), s.rn, q);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = v[k] / s.sn;
+    }
+}
+
+__device__ __forceinline__ void had_div8(const double (&v)[8], const HadScale<double>& s, float (&f)[8]) {
+    if (s.mode == HAD_MUL) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = (float)(v[k] * s.rn);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = (float)(v[k] / s.sn);
+    }
+}
+
+// divide by sqrt(n) in A, round as torch's cast does (through float) and store
+template <int XDT, typename A>
+__device__ __forceinline__ void had_store(void* out, int64_t i0, int64_t numel, const A (&v)[8], const HadScale<A>& sn) {
+    float f[8];
+    had_div8(v, sn, f);
+    if (i0 + 8 <= numel) {
+        store8<XDT>(out, i0, f);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (i0 + k < numel) store1<XDT>(out, i0 + k, f[k]);
+    }
+}
+
+}  // namespace ct

@@ -453,9 +453,16 @@ def _patch_forward() -> None:
     def take_dynamic(value, args, module=None, global_scale=None) -> bool:
         return plannable(value, args, global_scale)
 
-    def dispatching(orig, ours, take):
+    def handed_off(module, value, base_name, args) -> bool:
+        # transform.fuse_input_quantization: the rotation's pre-hook already quantized this very tensor.  Consulted before the
+        # take_forward decision — the original would quantize it a second time, and a dynamic QDQ is not idempotent bit for bit
+        return amd_dynamic.take_prequantized(module, value, base_name)
+
+    def dispatching(orig, ours, take, done=None):
         @functools.wraps(orig)
         def fn(*args, **kwargs):
+            if done is not None and done(*args, **kwargs):
+                return args[1] if len(args) > 1 else kwargs["value"]
             try:
                 if take(*args, **kwargs):
                     return ours(*args, **kwargs)
@@ -470,9 +477,9 @@ def _patch_forward() -> None:
         def orig_of(fn):
             return getattr(fn, "_ct_original", fn)
 
-        for orig, ours, take in ((orig_of(up_forward.forward_quantize), amd_dynamic.forward_quantize, take_forward),
-                                 (orig_of(up_helpers.compute_dynamic_scales_and_zp), amd_dynamic.compute_dynamic_scales_and_zp, take_dynamic)):
-            _FWD_SWAP[id(orig)] = (orig, dispatching(orig, ours, take))
+        for orig, ours, take, done in ((orig_of(up_forward.forward_quantize), amd_dynamic.forward_quantize, take_forward, handed_off),
+                                       (orig_of(up_helpers.compute_dynamic_scales_and_zp), amd_dynamic.compute_dynamic_scales_and_zp, take_dynamic, None)):
+            _FWD_SWAP[id(orig)] = (orig, dispatching(orig, ours, take, done))
     for mod_name, mod in list(sys.modules.items()):
         if mod is None or not (mod_name == "compressed_tensors" or mod_name.startswith("compressed_tensors.")):
             continue

@@ -6,8 +6,13 @@ and the scales and zero points stay in registers unless they are asked for.  `pl
 reference's arguments onto the kernel's segments and kinds, and raises NotImplementedError for every case the kernel does
 not compute exactly as the reference does (`install(patch_forward=True)` hands those to the reference), or the reference's
 own ValueError where it raises one.
+
+`plan_rotated_dynamic` / `rotated_fake_quantize` / `forward_rotate_quantize` are the same forward behind an online Hadamard
+rotation (QuaRot, SpinQuant, a `transform_config` with `location: input`): where the plan fuses, the rotation and the QDQ are
+ONE launch of csrc/ct_rotated.hip; where it does not, they are the two existing calls — the same bits either way.
 """
 import math
+import weakref
 from typing import Optional
 
 import torch
@@ -16,7 +21,8 @@ from .. import codec
 from .forward import fake_quantize
 from .quant_args import enum_value
 
-__all__ = ["compute_dynamic_scales_and_zp", "forward_quantize", "plan_dynamic", "DynamicPlan"]
+__all__ = ["compute_dynamic_scales_and_zp", "forward_quantize", "plan_dynamic", "DynamicPlan", "plan_rotated_dynamic", "RotatedPlan",
+           "rotated_fake_quantize", "forward_rotate_quantize", "MEASURED_FASTER", "ALL_FORMS", "remember_prequantized", "take_prequantized"]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _F8 = torch.float8_e4m3fn
@@ -137,6 +143,8 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
         return value
     if value.numel() == 0:
         return value
+    if take_prequantized(module, value, base_name):
+        return value  # transform.fuse_input_quantization: the rotation's pre-hook quantized this very tensor in its own launch
     g_idx = getattr(module, "weight_g_idx", None)
     global_scale = getattr(module, f"{base_name}_global_scale", None)
     if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
@@ -147,3 +155,131 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
     scale = getattr(module, f"{base_name}_scale")
     zero_point = getattr(module, f"{base_name}_zero_point", None)
     return fake_quantize(x=value, scale=scale, zero_point=zero_point, args=args, g_idx=g_idx, global_scale=global_scale)
+
+
+# ---- the same forward behind an online Hadamard rotation ----------------------------------------------------------------------------
+_PREQUANTIZED = "_ct_prequantized_input"  # module attribute: a weak reference to the tensor the fused pre-hook returned
+
+
+def remember_prequantized(module: torch.nn.Module, value: torch.Tensor) -> None:
+    """the hand-off of transform.fuse_input_quantization: `value` is the module's input, already rotated AND quantized"""
+    module.__dict__[_PREQUANTIZED] = weakref.ref(value)
+
+
+def take_prequantized(module: torch.nn.Module, value: torch.Tensor, base_name: str) -> bool:
+    """True when `value` IS (object identity) the tensor the module's fused pre-hook returned for this call: forward_quantize then
+    returns it untouched (a dynamic QDQ is not idempotent bit for bit).  The reference is cleared either way; any other tensor —
+    another hook replaced the input, or nobody pre-quantized — is quantized as always."""
+    if base_name != "input":
+        return False
+    ref = module.__dict__.pop(_PREQUANTIZED, None)
+    return ref is not None and ref() is value
+
+
+class RotatedPlan:
+    """what `rotated_fake_quantize` launches for one call: `fused` (one launch of ct_hadamard_dynamic_qdq) in `form`
+      "in_wave"    n <= 512, segments of 8 * 2^k <= 512 elements: butterfly, reduction and QDQ inside a wave
+      "block"      n = 1024 .. 8192, one workgroup per rotation block, such segments reduced inside the wave
+      "block_row"  n = 1024 .. 8192 and the block IS the segment (a token row): min / max finished across the waves
+      "head_row"   n <= 512 dividing a longer segment (a token row of head-dim blocks, up to 32768 elements)
+    or not fused (`form` None, `reason` says why — a shape the kernels do not fuse, or a form outside MEASURED_FASTER): the two
+    existing calls.  `hadamard` / `dynamic` are the parents' plans."""
+
+    __slots__ = ("fused", "form", "reason", "hadamard", "dynamic")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def launches(self) -> int:
+        return 1 if self.fused else 1 + self.dynamic.launches()
+
+
+def _measure_key(form: str, n: int) -> str:
+    """what one measurement of tools/rotated_bench.py speaks for: a form, and for the workgroup-block kernel its instantiation"""
+    return form if form in ("in_wave", "head_row") else f"{form}_{n}"
+
+
+ALL_FORMS = frozenset({"in_wave", "head_row"} | {f"{f}_{n}" for f in ("block", "block_row") for n in (1024, 2048, 4096, 8192)})
+# The forms the plan dispatches to the fused launch: those `tools/rotated_bench.py` has MEASURED faster than the two launches by
+# more than the spread between its runs (profiles/rotated_bench.jsonl, DESIGN 5.12).  A form that is not listed — not measured
+# yet, or measured and not faster — is declined: rotated_fake_quantize is then the two existing calls.
+MEASURED_FASTER = frozenset({"head_row", "block_1024", "block_2048", "block_4096", "block_row_1024", "block_row_2048", "block_row_4096", "block_row_8192"})
+
+
+def plan_rotated_dynamic(shape, dtype: torch.dtype, size: int, args, global_scale: Optional[torch.Tensor] = None) -> RotatedPlan:
+    """Host plan of `dynamic_fake_quantize(hadamard_transform(x, size), args, global_scale)` for an activation of `shape` /
+    `dtype`: plan_hadamard (last dimension, float32) and plan_dynamic composed — their ValueErrors and NotImplementedErrors come
+    through unchanged — the rule of csrc/ct_rotated.hip for what one launch computes, and MEASURED_FASTER for which of those forms
+    are dispatched to it.  No tensor is touched."""
+    hp = codec.plan_hadamard(shape, dtype, size, -1, torch.float32)
+    dp = plan_dynamic(shape, dtype, args, global_scale)
+    n, L = hp.size, dp.seg_len
+    units = L // 8
+    in_wave = L % 8 == 0 and units <= 64 and units & (units - 1) == 0  # ct_dynamic_qdq's in-wave segments
+    form = reason = None
+    if dp.launches() == 2:
+        reason = f"one segment of {L} elements is the tensor form: its reduction is global"
+    elif n <= 512 and in_wave:
+        form = "in_wave"
+    elif n <= 512:
+        if L % 8 or L % n:
+            reason = f"segments of {L} elements are not whole 16-byte units of whole blocks of {n}"
+        elif L > codec.ROTATED_MAX_ROW:
+            reason = f"rows of {L} elements exceed the staged form ({codec.ROTATED_MAX_ROW})"
+        else:
+            form = "head_row"
+    elif n > codec.ROTATED_MAX_BLOCK:
+        reason = f"hadamard size {n} was measured slower in one launch than in two (DESIGN 5.12)"
+    elif in_wave:
+        form = "block"
+    elif L == n:
+        form = "block_row"
+    else:
+        reason = f"a segment of {L} elements over workgroup-sized blocks of {n} is not fused"
+    if form is not None and _measure_key(form, n) not in MEASURED_FASTER:
+        form, reason = None, f"the {_measure_key(form, n)} form is not measured faster than the two launches (MEASURED_FASTER)"
+    return RotatedPlan(fused=form is not None, form=form, reason=reason, hadamard=hp, dynamic=dp)
+
+
+def _run_rotated(value, size, plan: RotatedPlan, global_scale, want_qparams: bool, want_rotated: bool):
+    dp = plan.dynamic
+    return codec.hadamard_dynamic_qdq(value, size, kind=dp.kind, seg_len=dp.seg_len, num_bits=dp.num_bits, symmetric=dp.symmetric,
+                                      global_scale=global_scale, scale_shape=dp.scale_shape,
+                                      scale_dtype=dp.scale_dtype if want_qparams else None, zp_dtype=dp.zp_dtype if want_qparams else None,
+                                      want_out=True, want_rotated=want_rotated)
+
+
+def rotated_fake_quantize(value: torch.Tensor, size: int, args, global_scale: Optional[torch.Tensor] = None, *,
+                          return_qparams: bool = False, return_rotated: bool = False):
+    """dynamic_fake_quantize(hadamard_transform(value, size), args, global_scale, ...): one launch where the plan fuses, the two
+    existing calls where it does not — the same bits either way.  Returns out, or (out, scale, zero_point) with return_qparams,
+    with the rotated tensor appended under return_rotated."""
+    plan = plan_rotated_dynamic(value.shape, value.dtype, size, args, global_scale)
+    if plan.fused:
+        out, scale, zp, rotated = _run_rotated(value, size, plan, global_scale, return_qparams, return_rotated)
+    else:
+        rotated = codec.hadamard_transform(value, size)
+        out, scale, zp = _run(rotated, plan.dynamic, global_scale, want_out=True, want_qparams=return_qparams)
+    res = (out, scale, zp) if return_qparams else (out,)
+    if return_rotated:
+        res += (rotated,)
+    return res if len(res) > 1 else out
+
+
+@torch.no_grad()
+def forward_rotate_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: str, args, size: int) -> torch.Tensor:
+    """forward_quantize(module, hadamard_transform(value, size), base_name, args) with the dynamic branch in one launch where
+    the plan fuses.  The early returns hand back the rotated value; a static scheme rotates and calls the static fake_quantize."""
+    status = enum_value(getattr(module, "quantization_status", None))
+    if (base_name == "weight" and _LIFECYCLE.get(status, -1) >= _LIFECYCLE["compressed"]) or value.numel() == 0:
+        return codec.hadamard_transform(value, size)
+    g_idx = getattr(module, "weight_g_idx", None)
+    global_scale = getattr(module, f"{base_name}_global_scale", None)
+    if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
+        if _g_idx_initialised(g_idx) and enum_value(args.strategy) in ("group", "tensor_group"):
+            raise NotImplementedError("group activations under an initialised weight_g_idx are left to the reference")
+        return rotated_fake_quantize(value, size, args, global_scale)
+    scale = getattr(module, f"{base_name}_scale")
+    zero_point = getattr(module, f"{base_name}_zero_point", None)
+    return fake_quantize(x=codec.hadamard_transform(value, size), scale=scale, zero_point=zero_point, args=args, g_idx=g_idx, global_scale=global_scale)

@@ -1,12 +1,13 @@
 """apply_transform_config (transform/apply.py:14-30 with TransformFactory._apply_to_module, transform/factory/base.py:105-190)
-for the deterministic `hadamard` type."""
+for the deterministic `hadamard` type, and the opt-in `fuse_input_quantization`: an `input` rotation in front of a dynamically
+quantized module runs in the QDQ's launch (csrc/ct_rotated.hip)."""
 import torch
 
 from ..entrypoints.convert.converters import match_name
 from .config import TRANSFORM_CONFIG_NAME, TransformConfig, TransformLocation
 from .hadamard import HadamardTransform, get_transform_size
 
-__all__ = ["apply_transform_config", "match_named_modules"]
+__all__ = ["apply_transform_config", "fuse_input_quantization", "match_named_modules"]
 
 
 def _match_class(module: torch.nn.Module, target: str) -> bool:
@@ -40,13 +41,95 @@ def _check_supported(name, scheme) -> None:
             raise NotImplementedError(f"config group {name!r}: location={args.location!r} needs attention / KV-cache hooks, which are not built here")
 
 
+_INPUT_ROTATIONS = "_ct_input_rotations"  # module attribute: the InputRotation pre-hooks apply_transform_config registered
+
+
+class InputRotation:
+    """the forward pre-hook of an `input` transform: inputs[0] rotated.  With `fuse_quantization` set (fuse_input_quantization)
+    and upstream's quantized_forward predicate true for the module, a call whose plan fuses returns the rotated AND dynamically
+    quantized input from one launch and leaves a weak reference to it on the module; dynamic.forward_quantize(module, value,
+    "input", args) hands that very tensor back untouched.  Every other call rotates only, as without the opt-in.
+    Precondition of the opt-in: the module's forward calls forward_quantize(module, x, "input", ...) under that same predicate
+    (upstream's quantized_forward does).  A module that carries a scheme and a status but runs a plain forward would receive a
+    quantized input where it received a rotated one before — do not opt such a model in."""
+
+    def __init__(self, transform: HadamardTransform):
+        self.transform = transform
+        self.fuse_quantization = False
+
+    def __call__(self, module, inputs):
+        value = inputs[0]
+        if self.fuse_quantization:
+            out = self._rotate_and_quantize(module, value)
+            if out is not None:
+                return out
+        return self.transform(value)
+
+    def _rotate_and_quantize(self, module, value):
+        from ..quantization import dynamic
+
+        scheme = getattr(module, "quantization_scheme", None)
+        # quantized_forward's own predicate (quantization/lifecycle/forward.py:265-276)
+        if not getattr(module, "quantization_enabled", True) or scheme is None or getattr(module, "quantization_status", None) is None:
+            return None
+        args = getattr(scheme, "input_activations", None)
+        if args is None or not _dynamic_args(args, module) or self.transform.precision is not torch.float32 or self.transform.dim != -1:
+            return None
+        value = value.contiguous()
+        global_scale = getattr(module, "input_global_scale", None)
+        try:
+            if not dynamic.plan_rotated_dynamic(value.shape, value.dtype, self.transform.size, args, global_scale).fused:
+                return None
+        except (NotImplementedError, ValueError):
+            return None  # the rotation alone raises what it raises
+        if value.data_ptr() % 16:
+            return None
+        out = dynamic.rotated_fake_quantize(value, self.transform.size, args, global_scale)
+        dynamic.remember_prequantized(module, out)
+        return out
+
+
+def _dynamic_args(args, module) -> bool:
+    """a dynamic scheme of a kind plan_dynamic knows, on a module forward_quantize does not decline"""
+    from ..quantization import dynamic
+
+    if dynamic.enum_value(getattr(args, "dynamic", False)) not in (True, "local"):
+        return False
+    try:
+        dynamic._kind(args, getattr(module, "input_global_scale", None))
+    except NotImplementedError:
+        return False
+    if dynamic._g_idx_initialised(getattr(module, "weight_g_idx", None)) and dynamic.enum_value(args.strategy) in ("group", "tensor_group"):
+        return False
+    return True
+
+
+def fuse_input_quantization(model: torch.nn.Module) -> list:
+    """Opt-in, after apply_transform_config and after the quantization schemes are attached: every module whose ONE `input`
+    HadamardTransform stands in front of dynamic `input_activations` of a kind the kernels know gets the fused pre-hook
+    (InputRotation).  Returns the names of the modules it fused.  The model computes the same bits, one launch per fused module
+    input instead of two; modules that do not qualify, and calls whose plan does not fuse, run as before.  Only for models whose
+    quantized modules run a forward that calls forward_quantize on the input (set_forward_quantized): see InputRotation."""
+    fused = []
+    for name, module in model.named_modules():
+        hooks = module.__dict__.get(_INPUT_ROTATIONS, ())
+        args = getattr(getattr(module, "quantization_scheme", None), "input_activations", None)
+        if len(hooks) != 1 or args is None or not _dynamic_args(args, module):
+            continue  # several rotations: only the last one could share the QDQ's launch, and the hooks do not know their order
+        hooks[0].fuse_quantization = True
+        fused.append(name)
+    return fused
+
+
 def _apply_to_module(name, scheme, module, args) -> None:
     location = TransformLocation(args.location)
     transform = HadamardTransform(get_transform_size(module, location, scheme.head_dim), scheme, args, type(module))
     transform_name = f"{name}_{location.value}"
     if location == TransformLocation.INPUT:
         module.register_module(transform_name, transform)
-        module.register_forward_pre_hook(lambda _, inputs: transform(inputs[0]), prepend=True)
+        hook = InputRotation(transform)
+        module.__dict__.setdefault(_INPUT_ROTATIONS, []).append(hook)
+        module.register_forward_pre_hook(hook, prepend=True)
     elif location == TransformLocation.OUTPUT:
         module.register_module(transform_name, transform)
         module.register_forward_hook(lambda _, _inputs, output: transform(output))

@@ -314,6 +314,18 @@ int ct_hadamard_rows(const void* x, void* out, int dt, int64_t numel, int64_t n,
 int ct_hadamard_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64,
                      ct_stream_t stream);
 
+/* HadamardTransform.forward (online, float32 accumulation) followed by the dynamic branch of forward_quantize, one launch:
+ * r = round_to_xdt(FWHT_n(x) / sqrt(n)) over runs of n elements, then ct_dynamic_qdq's observer / calculate_qparams /
+ * fake_quantize over runs of seg_len elements of r.  rotated_out (nullable) receives r.  out / scale_out / zp_out / zdt /
+ * kind / bits / symmetric / global_scale as in ct_dynamic_qdq.  Output, scale and zero point are the bits ct_hadamard_rows
+ * followed by ct_dynamic_qdq produce.  Fused: n <= 512 with seg_len = 8 * 2^k <= 512 (in-wave); n = 1024 .. 8192 with such a
+ * seg_len or seg_len == n (one workgroup per block); n <= 512 dividing a longer seg_len of up to 32768 elements (a token row of
+ * head-dim blocks).  CT_ERR_UNSUPPORTED for a combination it does not fuse: one segment (the tensor form), 1024 <= n < seg_len,
+ * longer rows, n > 8192 (16384 measured slower than the two launches), tensors that are not 16-byte aligned. */
+int ct_hadamard_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, int64_t seg_len, int kind, int bits, int symmetric,
+                            const float* global_scale, void* rotated_out, void* out, void* scale_out, void* zp_out, int zdt,
+                            ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
