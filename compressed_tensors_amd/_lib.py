@@ -99,6 +99,9 @@ _PROTOTYPES = {
     "ct_dynamic_qdq_tensor": ([_P, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_hadamard_rows": ([_P, _P, _I, _L, _L, _I, _S], _I),
     "ct_hadamard_cols": ([_P, _P, _P, _I, _L, _L, _L, _I, _S], _I),
+    "ct_hadamard_k_rows": ([_P, _P, _I, _L, _L, _L, _P, _P, _I, _I, _P, _S], _I),
+    "ct_hadamard_k_cols": ([_P, _P, _I, _L, _L, _L, _L, _P, _P, _I, _I, _P, _S], _I),
+    "ct_hadamard_k_workspace_bytes": ([_I, _L, _L, _L, _I, _I], _L),
     "ct_hadamard_dynamic_qdq": ([_P, _I, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_generate_gparam": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_pack_bitmasks": ([_P, _L, _L, _P, _S], _I),

@@ -32,6 +32,9 @@ __all__ = [
     "HadamardPlan",
     "plan_hadamard",
     "hadamard_transform",
+    "HadamardKPlan",
+    "plan_hadamard_k",
+    "hadamard_k_transform",
     "rtn_quantize_and_pack",
     "rtn_mxfp4_quantize_and_pack",
     "rtn_quantize_channel8",
@@ -660,6 +663,114 @@ def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=t
     else:
         ws = torch.empty_like(x)
         call("ct_hadamard_cols", ptr(x), ptr(out), ptr(ws), DT[x.dtype], plan.rows, plan.cols, plan.size, int(plan.acc64), stream_of(x))
+    return out
+
+
+HADAMARD_K_MAX_K = 256  # kHadKMaxK of csrc/ct_hadamard_k.hip
+HADAMARD_K_MAX_SIZE = 32768  # kHadKMfmaMaxN: the largest n = k * 2^m with k > 1
+HADAMARD_K_MAX_RUN = 4096  # kHadKRunsMaxM: the longest run 2^m of the vector form
+_HADAMARD_K_MAX_LDS = 65536  # kHadKMaxLds: the staged row of the matrix-core form
+
+
+class HadamardKPlan(NamedTuple):
+    """what `hadamard_k_transform` launches: `entry` "rows" (ct_hadamard_k_rows, the transformed dimension contiguous) or "cols"
+    (ct_hadamard_k_cols along dim 0 of a rows x cols matrix) in `form` "butterfly" (k == 1: signs + the Walsh-Hadamard butterfly),
+    "mfma" (one launch, the k x k mix on the matrix cores) or "valu" (two launches through a workspace); `workspace` in bytes"""
+    entry: str
+    form: str
+    size: int
+    k: int
+    m: int
+    blocks: int
+    acc64: bool
+    rows: int
+    cols: int
+    workspace: int
+
+
+def plan_hadamard_k(shape, dtype, size: int, k: int = 1, dim: int = -1, precision=torch.float32, *, device_type: str = "cuda",
+                    contiguous: bool = True) -> HadamardKPlan:
+    """The host-side decision of `hadamard_k_transform`, from shapes and dtypes alone: upstream's ValueErrors first (a size with
+    no k * 2^m factorisation is the one `random_hadamard_matrix` raises, transform/utils/hadamard.py:127-128; a size that does not
+    divide the dimension is transform/utils/matrix.py:41-45), then NotImplementedError for what the kernels of
+    csrc/ct_hadamard_k.hip decline."""
+    size, k = int(size), int(k)
+    if size <= 0 or k <= 0 or size % k or (size // k) & (size // k - 1):
+        raise ValueError(f"Cannot construct random hadamard matrix of size {size}")
+    shape = tuple(int(d) for d in shape)
+    if not shape:
+        raise ValueError("hadamard_k_transform of a 0-dim tensor")
+    if not -len(shape) <= dim < len(shape):
+        raise IndexError(f"dim {dim} out of range for a {len(shape)}-dim tensor")
+    dim %= len(shape)
+    if shape[dim] % size != 0:
+        raise ValueError(f"{size} must divide {shape[dim]} (dim {dim} of shape {shape})")
+    if precision in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"precision {precision}: upstream would run its GEMM in that dtype, which no kernel here reproduces")
+    if precision not in HADAMARD_MAX_SIZE:
+        raise NotImplementedError(f"precision must be torch.float32 or torch.float64, got {precision}")
+    if dtype not in _FLOATS:
+        raise NotImplementedError(f"the hadamard kernels take bfloat16, float16 and float32 tensors, got {dtype}")
+    if device_type != "cuda":
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {device_type} tensor")
+    if not contiguous:
+        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    m, acc64 = size // k, precision is torch.float64
+    if k == 1:
+        form = "butterfly"
+        if size > HADAMARD_MAX_SIZE[precision]:
+            raise NotImplementedError(f"hadamard size {size} exceeds the supported maximum {HADAMARD_MAX_SIZE[precision]} at precision {precision}")
+    else:
+        if k > HADAMARD_K_MAX_K:
+            raise NotImplementedError(f"the hadamard mix takes k <= {HADAMARD_K_MAX_K}, got {k}")
+        if size > HADAMARD_K_MAX_SIZE:
+            raise NotImplementedError(f"hadamard size {size} exceeds the supported maximum {HADAMARD_K_MAX_SIZE} of the mixed forms")
+        lds = max(m, 32) * (-(-k // 16) * 16 + 8) * 2
+        form = "mfma" if dtype is not torch.float32 and not acc64 and 8 <= m <= 128 and lds <= _HADAMARD_K_MAX_LDS else "valu"
+        if form == "valu" and m > HADAMARD_K_MAX_RUN:
+            raise NotImplementedError(f"the vector form of the hadamard mix takes runs of up to {HADAMARD_K_MAX_RUN} elements, got {m}")
+    outer, inner = math.prod(shape[:dim]), math.prod(shape[dim + 1:])
+    numel = outer * shape[dim] * inner
+    acc_bytes = numel * (8 if acc64 else 4) if form == "valu" else 0
+    if inner == 1 or size == 1:
+        return HadamardKPlan("rows", form, size, k, m, numel // size, acc64, numel // max(shape[dim], 1), shape[dim], acc_bytes)
+    if outer != 1:
+        raise NotImplementedError(f"the column form takes one matrix: dim {dim} of shape {shape} is neither the first nor the last dimension")
+    itemsize = 4 if dtype is torch.float32 else 2
+    return HadamardKPlan("cols", form, size, k, m, (shape[dim] // size) * inner, acc64, shape[dim], inner, ((numel * itemsize + 15) & ~15) + acc_bytes)
+
+
+def hadamard_k_transform(x: torch.Tensor, n: int, had_k: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None, *, dim: int = -1,
+                         precision=torch.float32, transposed: bool = False) -> torch.Tensor:
+    """HadamardTransform.forward (transform/factory/hadamard.py:91-108) for the matrix of `random_hadamard_matrix(n)`
+    (transform/utils/hadamard.py:53-151), W = diag(signs) * (had_k (x) H_M)^T with M = n / k a power of two: every run of n
+    elements along `dim` becomes value @ W / sqrt(n) (`transposed=False`: the online locations, Embedding weight_output, Linear
+    weight_output along dim 0) or value @ W.T / sqrt(n) (`transposed=True`), accumulated in `precision`, rounded once to x's
+    dtype.  `had_k`: int8 (k, k) of +-1 on x's device, None for k == 1; `signs`: int8 (n,) of +-1, None for none.  No n x n
+    matrix: signs, a Walsh-Hadamard butterfly over M and a k x k mix, which for 16-bit activations runs on the matrix cores in
+    one launch (csrc/ct_hadamard_k.hip)."""
+    k = 1 if had_k is None else int(had_k.shape[0])
+    plan = plan_hadamard_k(x.shape, x.dtype, n, k, dim, precision, device_type=x.device.type, contiguous=x.is_contiguous())
+    for name, t, shape in (("had_k", had_k, (k, k)), ("signs", signs, (plan.size,))):
+        if t is not None and (t.dtype is not torch.int8 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int8 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device()
+    if not x.is_cuda:
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
+    for name, t in (("had_k", had_k), ("signs", signs)):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{name} is on {t.device}, the value on {x.device}")
+    if x.data_ptr() % 16 or (signs is not None and signs.data_ptr() % 8):
+        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    ws = torch.empty(plan.workspace, dtype=torch.uint8, device=x.device) if plan.workspace else None
+    tail = (plan.size, plan.k, ptr(had_k), ptr(signs), int(bool(transposed)), int(plan.acc64), ptr(ws), stream_of(x))
+    if plan.entry == "rows":
+        call("ct_hadamard_k_rows", ptr(x), ptr(out), DT[x.dtype], x.numel(), *tail)
+    else:
+        call("ct_hadamard_k_cols", ptr(x), ptr(out), DT[x.dtype], plan.rows, plan.cols, *tail)
     return out
 
 

@@ -154,4 +154,8 @@ __device__ __forceinline__ void had_store(void* out, int64_t i0, int64_t numel, 
     }
 }
 
+// host: out[c][r] = in[r][c] for elements of 2 or 4 bytes on stream s (transpose_kernel of csrc/ct_hadamard.hip), for the column
+// forms of csrc/ct_hadamard_k.hip
+void launch_transpose_words(const void* in, void* out, int elem_size, int64_t rows, int64_t cols, hipStream_t s);
+
 }  // namespace ct

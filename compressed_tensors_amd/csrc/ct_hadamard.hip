@@ -206,6 +206,11 @@ static void launch_transpose(const void* in, void* out, int64_t rows, int64_t co
     hipLaunchKernelGGL((transpose_kernel<E>), dim3((unsigned)g), dim3(kBlock), 0, s, static_cast<const E*>(in), static_cast<E*>(out), rows, cols, tc);
 }
 
+void launch_transpose_words(const void* in, void* out, int elem_size, int64_t rows, int64_t cols, hipStream_t s) {
+    if (elem_size == 4) launch_transpose<uint32_t>(in, out, rows, cols, s);
+    else launch_transpose<uint16_t>(in, out, rows, cols, s);
+}
+
 }  // namespace ct
 
 using namespace ct;

@@ -491,6 +491,30 @@ def _patch_forward() -> None:
 
 
 _TR_SAVED = {}  # install(patch_transforms=True): the two originals of transform/factory/hadamard.py
+_TR_RANDOM = [False]  # install(patch_transforms=True, patch_random_hadamard=True)
+
+
+def _random_hadamard_forward(transform, value):
+    """a tagged RandomHadamardFactory transform on a GPU value: the weight is factored once (transform/random_hadamard.py; the
+    factors, or the fact that there are none, are cached on the transform) and the call goes to codec.hadamard_k_transform
+    (csrc/ct_hadamard_k.hip).  None when the call is upstream's to compute."""
+    from .transform.hadamard import transform_dim
+    from .transform.random_hadamard import factor_hadamard_weight, transform_transposed
+
+    weight = transform.weight
+    dim = transform_dim(transform.args.location, transform.module_type)
+    cached = getattr(transform, "_ct_factors", None)
+    if cached is None:
+        cached = transform._ct_factors = (factor_hadamard_weight(weight.data),)
+    factors = cached[0]
+    if factors is None:
+        return None
+    codec.plan_hadamard_k(value.shape, value.dtype, factors.n, factors.k, dim, weight.dtype, contiguous=value.is_contiguous())  # raises what it declines
+    if factors.signs.device != value.device:
+        factors = factors._replace(had_k=None if factors.had_k is None else factors.had_k.to(value.device), signs=factors.signs.to(value.device))
+        transform._ct_factors = (factors,)
+    transposed = transform_transposed(transform.args.location, transform.module_type, transform.args.inverse)
+    return codec.hadamard_k_transform(value, factors.n, factors.had_k, factors.signs, dim=dim, precision=weight.dtype, transposed=transposed)
 
 
 def _patch_transforms() -> None:
@@ -503,6 +527,7 @@ def _patch_transforms() -> None:
     import functools
 
     import compressed_tensors.transform.factory.hadamard as up_h
+    import compressed_tensors.transform.factory.random_hadamard as up_r
 
     from .transform.hadamard import transform_dim
 
@@ -515,6 +540,8 @@ def _patch_transforms() -> None:
         transform = orig_create(self, module, args)
         if type(self) is up_h.HadamardFactory:
             transform._ct_sylvester = True
+        elif type(self) is up_r.RandomHadamardFactory:
+            transform._ct_random = True  # used only under install(patch_random_hadamard=True)
         return transform
 
     @functools.wraps(orig_forward)
@@ -526,6 +553,13 @@ def _patch_transforms() -> None:
                 return out.to(value.dtype)
             except (NotImplementedError, ValueError):
                 pass  # upstream computes it, or raises its own error
+        elif _TR_RANDOM[0] and getattr(self, "_ct_random", False) and self.perm is None and value.is_cuda:
+            try:
+                out = _random_hadamard_forward(self, value)
+                if out is not None:
+                    return out.to(value.dtype)
+            except (NotImplementedError, ValueError):
+                pass
         return orig_forward(self, value)
 
     create_transform._ct_original, forward._ct_original = orig_create, orig_forward
@@ -539,16 +573,21 @@ def _unpatch_transforms() -> None:
         _TR_SAVED["cls_factory"].create_transform = _TR_SAVED["create"]
         _TR_SAVED["cls_transform"].forward = _TR_SAVED["forward"]
         _TR_SAVED.clear()
+    _TR_RANDOM[0] = False
 
 
 def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False,
-            patch_forward: bool = False, patch_transforms: bool = False):
+            patch_forward: bool = False, patch_transforms: bool = False, patch_random_hadamard: bool = False):
     """registry swap + ImplBackend registration
     (+ the by-name bindings of the codec classes inside upstream's own modules unless rebind_names=False;
      + batched launches behind upstream's ModelCompressor.compress_model / decompress_model unless wrap_model_compressor=False;
      + with patch_functions=True the plain functions pack_to_int32 / unpack_from_int32 / dequantize / fake_quantize;
      + with patch_forward=True the QDQ forward's forward_quantize / compute_dynamic_scales_and_zp;
-     + with patch_transforms=True the deterministic HadamardTransform.forward)."""
+     + with patch_transforms=True the deterministic HadamardTransform.forward;
+     + with patch_transforms=True AND patch_random_hadamard=True the forward of what a RandomHadamardFactory makes, without a permutation:
+       the n x n weight is factored once and the call runs on the kernels of csrc/ct_hadamard_k.hip)."""
+    if patch_random_hadamard and not patch_transforms:
+        raise ValueError("patch_random_hadamard=True needs patch_transforms=True")
     import compressed_tensors  # the upstream package; ImportError if it is not installed
     from compressed_tensors.compressors import BaseCompressor
     from compressed_tensors.registry import registry as up_registry
@@ -568,6 +607,7 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
         _patch_forward()
     if patch_transforms:
         _patch_transforms()
+        _TR_RANDOM[0] = _TR_RANDOM[0] or bool(patch_random_hadamard)
     return compressed_tensors
 
 

@@ -1,11 +1,12 @@
 """apply_transform_config (transform/apply.py:14-30 with TransformFactory._apply_to_module, transform/factory/base.py:105-190)
-for the deterministic `hadamard` type, and the opt-in `fuse_input_quantization`: an `input` rotation in front of a dynamically
+for the deterministic `hadamard` type and, given the caller's matrix constructor, the `random-hadamard` type; and the opt-in `fuse_input_quantization`: an `input` rotation in front of a dynamically
 quantized module runs in the QDQ's launch (csrc/ct_rotated.hip)."""
 import torch
 
 from ..entrypoints.convert.converters import match_name
 from .config import TRANSFORM_CONFIG_NAME, TransformConfig, TransformLocation
 from .hadamard import HadamardTransform, get_transform_size
+from .random_hadamard import RandomHadamardTransform, factor_hadamard_weight
 
 __all__ = ["apply_transform_config", "fuse_input_quantization", "match_named_modules"]
 
@@ -23,14 +24,14 @@ def match_named_modules(model: torch.nn.Module, targets, ignore=()):
     """utils/match.py:34-64: (name, module) of every module a target matches and no ignore entry does, in named_modules order"""
     targets, ignore = list(targets or []), list(ignore or [])
     for name, module in model.named_modules():
-        if isinstance(module, HadamardTransform):
+        if isinstance(module, (HadamardTransform, RandomHadamardTransform)):
             continue  # InternalModule upstream
         if _is_match(name, module, targets) and not _is_match(name, module, ignore):
             yield name, module
 
 
-def _check_supported(name, scheme) -> None:
-    if scheme.type != "hadamard":
+def _check_supported(name, scheme, random_hadamard: bool = False) -> None:
+    if scheme.type != "hadamard" and not (random_hadamard and scheme.type == "random-hadamard"):
         raise NotImplementedError(f"config group {name!r}: type={scheme.type!r} is not built here (only the deterministic 'hadamard' type is)")
     if scheme.randomize:
         raise NotImplementedError(f"config group {name!r}: randomize=True needs upstream's permutation, which is not built here")
@@ -121,14 +122,44 @@ def fuse_input_quantization(model: torch.nn.Module) -> list:
     return fused
 
 
-def _apply_to_module(name, scheme, module, args) -> None:
+class _RandomWeights:
+    """the weights of one `random-hadamard` config group, as RandomHadamardFactory keeps them: one generator per group (unseeded,
+    as TransformFactory.__init__ leaves it without a seed), one draw per size in order of first use (ParameterizedDefaultDict keys
+    the cache by size alone), drawn at the precision of that first use — and factored once"""
+
+    def __init__(self, name, hadamard_weights):
+        self.name, self.hadamard_weights = name, hadamard_weights
+        self.generator = torch.Generator()
+        self.factors = {}
+
+    def get(self, size, precision, device):
+        if size not in self.factors:
+            weight = self.hadamard_weights(size, precision, device, self.generator)
+            factors = factor_hadamard_weight(weight)
+            if factors is None:
+                raise ValueError(f"config group {self.name!r}: the weight of size {size} is not signs * kron(hadK, Sylvester).T")
+            self.factors[size] = factors
+        return self.factors[size]
+
+
+def _apply_to_module(name, scheme, module, args, random_weights=None) -> None:
     location = TransformLocation(args.location)
-    transform = HadamardTransform(get_transform_size(module, location, scheme.head_dim), scheme, args, type(module))
+    size = get_transform_size(module, location, scheme.head_dim)
+    if scheme.type == "random-hadamard":
+        device = next((p.device for p in module.parameters()), torch.device("cpu"))
+        factors = random_weights.get(size, scheme.precision if location.is_online() else torch.float64, device)
+        transform = RandomHadamardTransform(factors, scheme, args, type(module))
+    else:
+        transform = HadamardTransform(size, scheme, args, type(module))
     transform_name = f"{name}_{location.value}"
     if location == TransformLocation.INPUT:
         module.register_module(transform_name, transform)
-        hook = InputRotation(transform)
-        module.__dict__.setdefault(_INPUT_ROTATIONS, []).append(hook)
+        if isinstance(transform, HadamardTransform):
+            hook = InputRotation(transform)
+            module.__dict__.setdefault(_INPUT_ROTATIONS, []).append(hook)
+        else:
+            def hook(_, inputs, transform=transform):
+                return transform(inputs[0])
         module.register_forward_pre_hook(hook, prepend=True)
     elif location == TransformLocation.OUTPUT:
         module.register_module(transform_name, transform)
@@ -142,17 +173,23 @@ def _apply_to_module(name, scheme, module, args) -> None:
                 module.bias.copy_(transform(module.bias.unsqueeze(-1)).squeeze(-1))
 
 
-def apply_transform_config(model: torch.nn.Module, config) -> None:
+def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=None) -> None:
     """Weight locations are fused into the weights (and the bias, for weight_output) under no_grad; `input` becomes a prepended
     forward pre-hook and `output` a forward hook on a HadamardTransform submodule.  `config` (ours or upstream's pydantic
     object) is attached to the model as `transform_config`, where ModelCompressor.from_pretrained_model picks it up.  Everything
     is checked before anything is changed: q_attn / k_cache, requires_grad, randomize and every type but "hadamard" raise
-    NotImplementedError naming the field."""
+    NotImplementedError naming the field.
+    `hadamard_weights`: a callable with the signature of upstream's `random_hadamard_matrix(size, dtype, device, gen)`
+    (transform/utils/hadamard.py:53-77).  With it the `random-hadamard` type is accepted: every weight is drawn as
+    RandomHadamardFactory draws it, factored (transform/random_hadamard.py) and applied by the kernels of csrc/ct_hadamard_k.hip;
+    the table of known matrices behind that callable is upstream's and is not part of this package.  Without it the type
+    raises as every other unsupported type does."""
     ours = TransformConfig.coerce(config)
     for name, scheme in ours.config_groups.items():
-        _check_supported(name, scheme)
+        _check_supported(name, scheme, random_hadamard=hadamard_weights is not None)
     for name, scheme in ours.config_groups.items():
+        random_weights = _RandomWeights(name, hadamard_weights) if scheme.type == "random-hadamard" else None
         for args in scheme.apply:
             for _, module in list(match_named_modules(model, args.targets, args.ignore)):
-                _apply_to_module(name, scheme, module, args)
+                _apply_to_module(name, scheme, module, args, random_weights)
     setattr(model, TRANSFORM_CONFIG_NAME, config)

@@ -314,6 +314,28 @@ int ct_hadamard_rows(const void* x, void* out, int dt, int64_t numel, int64_t n,
 int ct_hadamard_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64,
                      ct_stream_t stream);
 
+/* The random-hadamard rotation (transform/factory/random_hadamard.py; the matrix of transform/utils/hadamard.py:53-151) of size
+ * n = k * 2^m over every run of n consecutive elements.  The matrix is W = diag(signs) * (had_k (x) H_M)^T, M = n / k, H_M the
+ * Sylvester matrix; a run is a k x M matrix with M contiguous.  transposed == 0: out = x @ W / sqrt(n) (signs, then the mix and
+ * the butterfly); transposed == 1: out = x @ W^T / sqrt(n) (had_k^T, the signs last).
+ *   had_k   int8, k x k, row-major, entries +-1; NULL exactly when k == 1
+ *   signs   int8, n entries of +-1, 8-byte aligned; NULL for none
+ *   acc64   0: float32 accumulation (online), 1: float64 (fused locations); one division by fl(sqrt n) in that type
+ * Forms: k == 1 the butterfly of ct_hadamard_rows with signs (n <= 16384); k > 1 with 16-bit x, acc64 == 0 and 8 <= M <= 128:
+ * ONE launch, the mix on the matrix cores (exact: +-1 times a 16-bit float, float32 accumulation); every other k > 1 case two
+ * launches on the vector ALU through `workspace` (ct_hadamard_k_workspace_bytes; may be NULL when that returns 0).
+ * CT_ERR_UNSUPPORTED: k > 256, n > 32768 with k > 1, n > 16384 with k == 1, M > 4096 in the vector form, misaligned tensors. */
+int ct_hadamard_k_rows(const void* x, void* out, int dt, int64_t numel, int64_t n, int64_t k, const int8_t* had_k,
+                       const int8_t* signs, int transposed, int acc64, void* workspace, ct_stream_t stream);
+
+/* The same along dim 0 of a row-major rows x cols matrix (n divides rows), on the transposes of ct_hadamard_cols: transpose
+ * into `workspace`, the row form in place, transpose back.  workspace: ct_hadamard_k_workspace_bytes(..., cols_form = 1). */
+int ct_hadamard_k_cols(const void* x, void* out, int dt, int64_t rows, int64_t cols, int64_t n, int64_t k, const int8_t* had_k,
+                       const int8_t* signs, int transposed, int acc64, void* workspace, ct_stream_t stream);
+
+/* bytes of device workspace the two entries above need for `numel` elements (host arithmetic only); -1 for bad arguments */
+int64_t ct_hadamard_k_workspace_bytes(int dt, int64_t numel, int64_t n, int64_t k, int acc64, int cols_form);
+
 /* HadamardTransform.forward (online, float32 accumulation) followed by the dynamic branch of forward_quantize, one launch:
  * r = round_to_xdt(FWHT_n(x) / sqrt(n)) over runs of n elements, then ct_dynamic_qdq's observer / calculate_qparams /
  * fake_quantize over runs of seg_len elements of r.  rotated_out (nullable) receives r.  out / scale_out / zp_out / zdt /
