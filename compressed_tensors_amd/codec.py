@@ -6,13 +6,14 @@ Every function mirrors a reference function (cited per function; paths relative 
 tensors are staged through the GPU (H2D, kernel, D2H) so the arithmetic is always the HIP
 path; without a GPU the calls raise.
 """
+import functools
 import math
 from typing import NamedTuple, Optional, Sequence
 
 import torch
 
 from . import _lib
-from ._lib import DT, call, ptr, stream_of
+from ._lib import DT, call, ptr, stream_of, stream_on
 
 __all__ = [
     "pack_to_int32",
@@ -72,6 +73,12 @@ __all__ = [
     "selftest_f16_div",
     "selftest_fp4_div",
     "QuantLayout",
+    "AttnPlan",
+    "plan_attn_qdq",
+    "attn_fake_quantize",
+    "attn_quantize",
+    "attn_dequantize",
+    "attn_fake_quantize_pair",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -186,7 +193,7 @@ class QuantLayout:
     idx(r, c) = (r // rdiv) * scale_cols + (col_group[c] if col_group is not None else c // cdiv)
     (see include/ct_hip.h).  Built from the reference's strategy vocabulary."""
 
-    __slots__ = ("rows", "cols", "rdiv", "cdiv", "scale_cols", "col_group", "is_group", "scale_zero_dim")
+    __slots__ = ("rows", "cols", "rdiv", "cdiv", "scale_cols", "col_group", "is_group", "scale_zero_dim", "heads")
 
     def __init__(self, x_shape, scale: torch.Tensor, strategy, group_size=None, block_structure=None,
                  g_idx: Optional[torch.Tensor] = None):
@@ -195,6 +202,7 @@ class QuantLayout:
         rows = math.prod(x_shape[:-1]) if len(x_shape) > 1 else 1
         self.rows, self.cols = rows, cols
         self.col_group = None
+        self.heads = None
         self.is_group = st in ("group", "tensor_group")
         self.scale_zero_dim = scale.ndim == 0 and not self.is_group
         if self.is_group:
@@ -237,10 +245,26 @@ class QuantLayout:
             if scale.numel() != 1:
                 raise ValueError(f"per-tensor quantization expects a single scale, got shape {tuple(scale.shape)}")
             self.rdiv, self.cdiv, self.scale_cols = max(rows, 1), max(cols, 1), 1
+        elif st == "attn_head":
+            # (..., H, S, D) against a scale of (H, 1, 1): idx = (row // S) % H.  quantize_tensor / fake_quantize_tensor /
+            # dequantize_tensor hand this strategy to the strided entry (plan_attn_qdq, attn_*); rdiv / cdiv express it for one batch
+            if len(x_shape) < 3:
+                raise ValueError("Attention quant requires at least 3 observed dimensions")  # lifecycle/initialize.py:242-247
+            self.heads = int(x_shape[-3])
+            if scale.numel() == 1:
+                self.rdiv, self.cdiv, self.scale_cols = max(rows, 1), max(cols, 1), 1
+            elif scale.numel() != self.heads:
+                raise ValueError(f"scale of shape {tuple(scale.shape)} does not match {self.heads} heads")
+            elif rows == self.heads * int(x_shape[-2]):
+                self.rdiv, self.cdiv, self.scale_cols = max(int(x_shape[-2]), 1), max(cols, 1), 1
+            else:
+                self.rdiv = self.cdiv = self.scale_cols = None  # several batches: not a (row // rdiv) layout
         else:
             raise NotImplementedError(f"quantization strategy {st!r} is not supported by the MI355X path")
 
     def args(self, dev):
+        if self.rdiv is None:
+            raise NotImplementedError("attn_head over several batches has no rdiv / cdiv layout: use codec.attn_fake_quantize / attn_quantize / attn_dequantize")
         cg = _dev(self.col_group, dev) if self.col_group is not None else None
         return (self.rows, self.cols, self.rdiv, self.cdiv, self.scale_cols, ptr(cg)), cg
 
@@ -315,6 +339,8 @@ def quantize_tensor(x, scale, zero_point, *, num_bits, strategy, group_size=None
     type) or, when dtype is None, x.dtype for group strategies and the promoted type otherwise.  qtype "float": 8 bits
     clamp to +-448 and round to float8_e4m3fn, 4 bits clamp to +-6 and cast_to_fp4 (values stay in a float dtype), instead
     of rint.  global_scale (FLOAT 4-bit tensor_group): the effective scale is scale / global_scale in float32."""
+    if _strategy_name(strategy) == "attn_head":
+        return attn_quantize(x, scale, zero_point, num_bits=num_bits, strategy=strategy, qtype=qtype, dtype=dtype, global_scale=global_scale)
     qtype = _check_qtype(qtype, num_bits)
     if global_scale is not None and not (qtype == "float" and int(num_bits) == 4):
         raise NotImplementedError("global_scale is implemented for FLOAT 4-bit quantization")
@@ -349,6 +375,8 @@ def quantize_tensor(x, scale, zero_point, *, num_bits, strategy, group_size=None
 def fake_quantize_tensor(x, scale, zero_point, *, num_bits, strategy, group_size=None, block_structure=None,
                          g_idx=None, qtype="int", global_scale=None) -> torch.Tensor:
     """quantization/lifecycle/forward.py:148-181 (forward_helpers.py:180-215); qtype / global_scale as in quantize_tensor."""
+    if _strategy_name(strategy) == "attn_head":
+        return attn_fake_quantize(x, scale, zero_point, num_bits=num_bits, strategy=strategy, qtype=qtype, global_scale=global_scale)
     qtype = _check_qtype(qtype, num_bits)
     if global_scale is not None and not (qtype == "float" and int(num_bits) == 4):
         raise NotImplementedError("global_scale is implemented for FLOAT 4-bit quantization")
@@ -384,6 +412,8 @@ def dequantize_tensor(x_q, scale, zero_point=None, *, strategy=None, group_size=
         raise NotImplementedError(f"dequantize from {x_q.dtype} is not supported by the MI355X path")
     if strategy is None:
         strategy, group_size, block_structure = infer_dequant_layout(x_q.shape, scale)
+    if _strategy_name(strategy) == "attn_head":
+        return attn_dequantize(x_q, scale, zero_point, strategy=strategy, dtype=dtype, global_scale=global_scale)
     layout = QuantLayout(x_q.shape, scale, strategy, group_size, block_structure, g_idx)
     _check_sz(layout, scale, zero_point)
     out_dtype = dtype if dtype is not None else scale.dtype
@@ -402,6 +432,270 @@ def dequantize_tensor(x_q, scale, zero_point=None, *, strategy=None, group_size=
         call("ct_dequantize", ptr(qd), DT[qd.dtype], ptr(sd), DT[sd.dtype], ptr(zd), zdt, *largs, ptr(out), DT[out_dtype],
              stream_of(qd))
     return _home(out, x_q)
+
+
+# --------------------------------------------------------------------------- attention: q / k / v states, strided
+class AttnPlan(NamedTuple):
+    """what the attn_* functions do with one tensor: `in_place` (ct_attn_qdq reads it through its strides; False: `.contiguous()`
+    first, `reason` says why), the (B, H, S, D) view the kernel gets with the b / h / s element strides it reads, `per_head`
+    (H scale entries, index h; False: one entry), and `vector` (rows of whole 8-element units, units aligned on both sides —
+    16-byte units of a 16-bit dtype; False: the element form of the same entry)"""
+    in_place: bool
+    vector: bool
+    B: int
+    H: int
+    S: int
+    D: int
+    strides: tuple
+    per_head: bool
+    reason: Optional[str]
+
+
+def _attn_is_dense(shape, strides) -> bool:
+    dims = sorted((st, sz) for sz, st in zip(shape, strides) if sz > 1)
+    run = 1
+    for st, sz in dims:
+        if st != run:
+            return False
+        run *= sz
+    return True
+
+
+def _attn_overlaps(shape, strides) -> bool:
+    """conservative: dimensions sorted by stride must each step past everything the smaller ones span (expanded dimensions, stride
+    0, are not storage)"""
+    span = 0
+    for st, sz in sorted((st, sz) for sz, st in zip(shape, strides) if sz > 1 and st != 0):
+        if st <= span:
+            return True
+        span += (sz - 1) * st
+    return False
+
+
+def _attn_fold(shape, strides):
+    """(B, H, S, D), (b, h, s strides) of a tensor with a unit last stride, or None when its leading dimensions do not fold into B"""
+    shape, strides = tuple(shape), tuple(strides)
+    if len(shape) < 4:
+        pad = 4 - len(shape)
+        return (1,) * pad + shape, ((0,) * pad + strides)[:3]
+    lead_shape, lead_strides = shape[:-3], strides[:-3]
+    B, sb = 1, 0
+    for sz, st in zip(reversed(lead_shape), reversed(lead_strides)):
+        if sz == 1:
+            continue
+        if B == 1:
+            B, sb = sz, st
+        elif st == sb * B:
+            B *= sz
+        else:
+            return None
+    return (B,) + shape[-3:], (sb,) + strides[-3:-1]
+
+
+def _attn_unit_aligned(offset_bytes, sizes, strides, itemsize, D) -> bool:
+    a = min(16, 8 * itemsize)
+    return D % 8 == 0 and offset_bytes % a == 0 and all((st * itemsize) % a == 0 for sz, st in zip(sizes, strides) if sz > 1)
+
+
+def plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, *, out_dtype=None, offset_bytes: int = 0) -> AttnPlan:
+    """The host plan of the attn_* functions for a tensor of `shape` / `strides` (elements) / `dtype` whose first element sits
+    `offset_bytes` past a 16-byte boundary, with a scale of `scale_shape`: no tensor is touched.  Raises what the reference raises
+    — ValueError for an attn_head tensor of fewer than 3 dimensions (lifecycle/initialize.py:242-247), RuntimeError for a scale that
+    does not broadcast against the heads (torch's own, from forward_helpers.py:199) — and NotImplementedError for a strategy this
+    entry does not serve."""
+    st = _strategy_name(strategy)
+    shape, strides, scale_shape = tuple(int(d) for d in shape), tuple(int(s) for s in strides), tuple(int(d) for d in scale_shape)
+    if st not in ("attn_head", "tensor"):
+        raise NotImplementedError(f"ct_attn_qdq serves the tensor and attn_head strategies, not {st!r}")
+    scale_numel = math.prod(scale_shape)
+    if st == "attn_head":
+        if len(shape) < 3:
+            raise ValueError("Attention quant requires at least 3 observed dimensions")
+        H = shape[-3]
+        if scale_numel != 1 and not (scale_numel == H and len(scale_shape) >= 3 and scale_shape[-3:] == (H, 1, 1)):
+            if len(scale_shape) >= 3 and scale_shape[-2:] == (1, 1) and scale_numel == scale_shape[-3]:
+                raise RuntimeError(f"The size of tensor a ({H}) must match the size of tensor b ({scale_shape[-3]}) at non-singleton dimension {len(shape) - 3}")
+            raise NotImplementedError(f"an attn_head scale has shape (H, 1, 1) or one element, got {scale_shape} for {H} heads")
+    elif scale_numel != 1:
+        raise ValueError(f"per-tensor quantization expects a single scale, got shape {scale_shape}")
+    if len(scale_shape) > max(len(shape), 1) and scale_numel == 1:
+        raise NotImplementedError(f"a scale of {len(scale_shape)} dimensions would add dimensions to a tensor of {len(shape)}")
+    if len(shape) == 0:
+        shape, strides = (1,), (1,)
+    out_dtype = dtype if out_dtype is None else out_dtype
+    isz, osz = dtype.itemsize, out_dtype.itemsize
+    reason = None
+    if any(s < 0 for s in strides):
+        reason = "negative strides"
+    elif shape[-1] > 1 and strides[-1] != 1:
+        reason = f"the last dimension has stride {strides[-1]}"
+    elif _attn_overlaps(shape, strides):
+        reason = "the tensor overlaps itself in storage"
+    folded = None if reason else _attn_fold(shape, tuple(strides[:-1]) + (1,))
+    if reason is None and folded is None:
+        reason = "the leading dimensions do not fold into one batch dimension"
+    per_head = st == "attn_head" and scale_numel != 1
+    if reason is not None:
+        dense = []
+        run = 1
+        for sz in reversed(shape):
+            dense.append(run)
+            run *= max(sz, 1)
+        (B, H, S, D), xs = _attn_fold(shape, tuple(reversed(dense)))
+        return AttnPlan(False, D % 8 == 0, B, H, S, D, xs, per_head, reason)
+    (B, H, S, D), xs = folded
+    vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, isz, D)
+    if vec and _attn_is_dense(shape, strides):  # the output keeps these strides; otherwise it is dense in the same order: multiples of D
+        vec = _attn_unit_aligned(0, (B, H, S), xs, osz, D)
+    return AttnPlan(True, vec, B, H, S, D, xs, per_head, None)
+
+
+_ATTN_MODES = {"fake": 0, "quantize": 1, "dequantize": 2}
+
+
+@functools.lru_cache(maxsize=1024)
+def _attn_out_strides(shape, strides, dtype, scale_shape, scale_strides, scale_dtype, mode: str, rounds: bool):
+    """the strides the reference's result has: those torch's elementwise ops leave behind — x's own for a dense permuted x, dense
+    in x's order for a slice or an expanded x, and torch's placement of size-1 dimensions, which the same-shape torch.round of the
+    INT types rewrites (`rounds`) and the float8 cast does not.  Asked of torch itself, on meta tensors (no memory, no launch),
+    once per layout: the op sequence of forward_helpers.py:180-215, 525-572 and quant_args.py:460-496."""
+    x = torch.empty_strided(shape, strides, dtype=dtype, device="meta")
+    scale = torch.empty_strided(scale_shape, scale_strides, dtype=scale_dtype, device="meta")
+    if mode == "dequantize":
+        return tuple((x.to(scale_dtype) * scale).stride())
+    bound = torch.empty((), dtype=torch.float32, device="meta")
+    t = torch.clamp(x / scale, bound, bound)
+    if rounds and t.is_contiguous():
+        t = torch.empty(shape, dtype=t.dtype, device="meta")  # torch.round of a contiguous tensor allocates the plain contiguous strides
+    if mode == "fake":
+        t = t.to(scale_dtype) * scale
+    return tuple(t.stride())
+
+
+@functools.lru_cache(maxsize=4096)
+def _attn_layout(shape, strides, dtype, scale_shape, scale_strides, scale_dtype, strategy, out_dtype, offset_bytes, mode, rounds):
+    """everything one call decides from shapes alone, once per layout: (plan, the output's strides, its b / h / s strides) — or
+    (plan, None, None) for a tensor that is copied first (the caller asks again for the copy)"""
+    plan = plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, out_dtype=out_dtype, offset_bytes=offset_bytes)
+    if not plan.in_place:
+        return plan, None, None
+    if _attn_is_dense(shape, strides) and 1 not in shape:
+        out_strides = tuple(strides)  # what torch.empty_like gives: a dense permuted x keeps its strides, as in the reference
+    else:
+        out_strides = _attn_out_strides(shape, strides, dtype, scale_shape, scale_strides, scale_dtype, mode, rounds)
+    view = _attn_fold(shape or (1,), out_strides or (1,)) if (not shape or shape[-1] <= 1 or out_strides[-1] == 1) else None
+    if view is None or view[0] != (plan.B, plan.H, plan.S, plan.D):  # an order the kernel does not write: the dense form
+        out_strides = tuple(torch.empty(shape, device="meta").stride())
+        view = _attn_fold(shape or (1,), out_strides or (1,))
+    return plan, out_strides, view[1]
+
+
+def _attn_one(x, scale, zero_point, mode, strategy, out_dtype, dev, rounds):
+    """one descriptor of ct_attn_qdq: (AttnTensor fields, out, zero-point dtype code, tensors to keep alive)"""
+    if zero_point is not None and zero_point.numel() != scale.numel():
+        raise ValueError(f"zero_point shape {tuple(zero_point.shape)} does not match scale shape {tuple(scale.shape)}")
+    tail = (scale.shape, scale.stride(), scale.dtype, strategy, out_dtype)
+    plan, out_strides, out_bhs = _attn_layout(x.shape, x.stride(), x.dtype, *tail, x.data_ptr() % 16, mode, rounds)
+    xr = x
+    if not plan.in_place:
+        xr = x.contiguous()
+        plan, out_strides, out_bhs = _attn_layout(xr.shape, xr.stride(), xr.dtype, *tail, xr.data_ptr() % 16, mode, rounds)
+    out = torch.empty_strided(xr.shape, out_strides, dtype=out_dtype, device=xr.device)
+    sd = scale if (scale.device == dev and scale.is_contiguous()) else _dev(scale, dev)  # read element by element: no alignment needed
+    if zero_point is None:
+        zd, zdt = None, -1
+    elif zero_point.device == dev and zero_point.is_contiguous() and zero_point.dtype in DT and zero_point.dtype is not torch.bool:
+        zd, zdt = zero_point, DT[zero_point.dtype]
+    else:
+        zd, zdt = _zp_arg(zero_point, dev)
+    item = (ptr(xr), ptr(out), ptr(sd), ptr(zd), plan.B, plan.H, plan.S, plan.D, plan.strides, out_bhs, int(plan.per_head))
+    return item, out, zdt, (xr, sd, zd)
+
+
+@functools.lru_cache(maxsize=None)
+def _attn_result_dtype(x_dtype, x_zero_dim: bool, scale_dtype, scale_zero_dim: bool):
+    """_result_dtype on stand-ins of the same dtypes and dimensionality (once per combination)"""
+    x = torch.empty(() if x_zero_dim else (1,), dtype=x_dtype, device="meta")
+    scale = torch.empty(() if scale_zero_dim else (1,), dtype=scale_dtype, device="meta")
+    return _result_dtype(x, scale, scale_zero_dim)
+
+
+def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None, global_scale=None):
+    """tensors: [(x, scale, zero_point)] of one or two q / k / v states sharing dtypes and arguments -> [out]; ONE ct_attn_qdq"""
+    st = _strategy_name(strategy)
+    if global_scale is not None:
+        raise NotImplementedError("a global scale on attention states is not implemented by the MI355X path")
+    if mode != "dequantize":
+        qtype = _check_qtype(qtype, num_bits)
+        if qtype == "float" and int(num_bits) == 4:
+            raise NotImplementedError("FLOAT 4-bit attention states are not implemented by the MI355X path")
+    x0, s0, z0 = tensors[0]
+    for x, s, z in tensors:
+        if mode == "dequantize":
+            if x.dtype not in (torch.int8, torch.int32, _F8, *_FLOATS):
+                raise NotImplementedError(f"dequantize from {x.dtype} is not supported by the MI355X path")
+        else:
+            _check_float(x, "x")
+        _check_float(s, "scale")
+        if x.dtype != x0.dtype or s.dtype != s0.dtype or (z is None) != (z0 is None) or (z is not None and z.dtype != z0.dtype) or s.ndim != s0.ndim:
+            raise NotImplementedError("the two tensors of one launch share their dtypes")
+    if mode == "dequantize":
+        T = s0.dtype
+        out_dtype = dtype if dtype is not None else s0.dtype
+        if out_dtype not in _FLOATS:
+            raise NotImplementedError(f"dequantize to {out_dtype} is not supported by the MI355X path")
+    else:
+        T = _attn_result_dtype(x0.dtype, x0.ndim == 0, s0.dtype, s0.ndim == 0)
+        if mode == "fake":
+            out_dtype = s0.dtype
+        else:
+            out_dtype = dtype if dtype is not None else T
+            allowed = (_F8, *_FLOATS) if qtype == "float" else (torch.int8, torch.int32, *_FLOATS)
+            if out_dtype not in allowed:
+                raise NotImplementedError(f"quantize ({qtype}, {num_bits} bits) to {out_dtype} is not supported by the MI355X path")
+    dev = _compute_device(x0, s0)
+    descs = (_lib.AttnTensor * len(tensors))()
+    outs, keep, zdt = [], [], -1
+    for i, (x, s, z) in enumerate(tensors):
+        xd = x if x.device == dev else x.to(dev)
+        item, out, zdt, alive = _attn_one(xd, s, z, mode, st, out_dtype, dev, mode != "dequantize" and qtype == "int")
+        d = descs[i]
+        d.x, d.out, d.scale, d.zp, d.B, d.H, d.S, d.D = item[:8]
+        d.x_stride[:], d.out_stride[:], d.per_head = item[8], item[9], item[10]
+        outs.append(_home(out, x))
+        keep.append(alive)
+    kind = 1 if (mode != "dequantize" and qtype == "float") else 0
+    call("ct_attn_qdq", descs, len(tensors), _ATTN_MODES[mode], kind, int(num_bits) if mode != "dequantize" else 8, DT[x0.dtype], DT[s0.dtype], zdt, DT[T],
+         DT[out_dtype], stream_on(dev))
+    return outs
+
+
+def attn_fake_quantize(x, scale, zero_point=None, *, num_bits, strategy="attn_head", qtype="int", global_scale=None) -> torch.Tensor:
+    """fake_quantize (lifecycle/forward.py:148-181) of a query / key / value state (..., H, S, D) under the `attn_head` strategy
+    (scale (H, 1, 1), or one element) or the `tensor` strategy, read through its strides: no `.contiguous()` copy of the
+    transposed views attention modules pass.  The result is allocated like torch.empty_like(x) — the strides of a dense permuted
+    input are kept, as the reference's elementwise ops keep them — in the scale's dtype."""
+    return _attn_qdq([(x, scale, zero_point)], "fake", num_bits=num_bits, strategy=strategy, qtype=qtype, global_scale=global_scale)[0]
+
+
+def attn_quantize(x, scale, zero_point=None, *, num_bits, strategy="attn_head", qtype="int", dtype=None, global_scale=None) -> torch.Tensor:
+    """quantize (lifecycle/forward.py:36-73) of such a state: to `dtype` (float8_e4m3fn for FLOAT args — what an FP8 KV cache
+    stores —, int8 / int32, or a float dtype), or the promoted dtype of x / scale"""
+    return _attn_qdq([(x, scale, zero_point)], "quantize", num_bits=num_bits, strategy=strategy, qtype=qtype, dtype=dtype, global_scale=global_scale)[0]
+
+
+def attn_dequantize(x_q, scale, zero_point=None, *, strategy="attn_head", dtype=None, global_scale=None) -> torch.Tensor:
+    """dequantize (lifecycle/forward.py:76-145) of such codes, in the scale's dtype (or `dtype`)"""
+    return _attn_qdq([(x_q, scale, zero_point)], "dequantize", num_bits=8, strategy=strategy, dtype=dtype, global_scale=global_scale)[0]
+
+
+def attn_fake_quantize_pair(k, v, k_scale, v_scale, k_zero_point=None, v_zero_point=None, *, num_bits, strategy="attn_head", qtype="int",
+                            global_scale=None):
+    """(attn_fake_quantize(k, ...), attn_fake_quantize(v, ...)) in ONE launch: what QuantizedKVCache.forward does back to back with
+    the same arguments.  K and V keep their own shapes, strides and scales (MLA: different head dims); they share dtypes."""
+    out = _attn_qdq([(k, k_scale, k_zero_point), (v, v_scale, v_zero_point)], "fake", num_bits=num_bits, strategy=strategy, qtype=qtype,
+                    global_scale=global_scale)
+    return out[0], out[1]
 
 
 def quantize_and_pack(x, scale, zero_point, *, num_bits, strategy, group_size=None, block_structure=None,

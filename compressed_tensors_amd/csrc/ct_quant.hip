@@ -57,9 +57,7 @@ __global__ __launch_bounds__(kBlock) void quant_units_kernel(QParams p) {
                     if constexpr (MODE == MODE_FQ) {
                         // dequantize in S = scale dtype (forward_helpers.py:207-215)
                         float zs = has_zp ? round_to_rt(p.sdt_arith, load_rt(p.zp, p.zdt, srow + col_group_of(p.L, c0 + k))) : 0.0f;
-                        float d = round_to_rt(p.sdt_arith, t);
-                        if (has_zp) d = round_to_rt(p.sdt_arith, d - zs);
-                        t = mul_round_to_rt(p.sdt_arith, d, sz.s);
+                        t = fake_dequant_rt(p.sdt_arith, t, has_zp, zs, sz.s);
                     }
                     v[k] = t;
                 }

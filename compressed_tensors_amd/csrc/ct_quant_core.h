@@ -100,6 +100,14 @@ __device__ __forceinline__ float dequant_core(float q, bool has_zp, float zf, fl
     return mul_round_to<SDT>(d, s);
 }
 
+// the dequantize half of fake_quantize (forward_helpers.py:207-215) on a value quant_core returned: S = scale dtype at run time,
+// zs = the zero point already rounded to S
+__device__ __forceinline__ float fake_dequant_rt(int sdt, float q, bool has_zp, float zs, float s) {
+    float d = round_to_rt(sdt, q);
+    if (has_zp) d = round_to_rt(sdt, d - zs);
+    return mul_round_to_rt(sdt, d, s);
+}
+
 // int8 zero point and an int8 code: |q - z| <= 255 is an integer every supported float dtype holds exactly,
 // so the reference's rounding of the difference is the identity and is not issued
 template <int SDT>

@@ -416,7 +416,8 @@ def _patch_forward() -> None:
     """`install(patch_forward=True)`: `forward_quantize` (quantization/lifecycle/forward.py:304-335) and
     `compute_dynamic_scales_and_zp` (quantization/utils/helpers.py:140-195) are rebound, in every already-imported
     `compressed_tensors.*` module that holds them, to wrappers that send contiguous GPU activations of a layout the kernels
-    implement to quantization.dynamic (the fused dynamic QDQ of csrc/ct_dynamic.hip, or the static fake_quantize kernels) and
+    implement to quantization.dynamic (the fused dynamic QDQ of csrc/ct_dynamic.hip, or the static fake_quantize kernels; the q / k / v
+    states of upstream's attention hooks, strided as they come, under the tensor and attn_head strategies: csrc/ct_attn.hip) and
     everything else — CPU / meta tensors, other strategies or formats, group activations under an initialised weight_g_idx,
     a NotImplementedError from the HIP side — to the original.  upstream's `quantized_forward` looks `forward_quantize` up in
     its module's globals at call time, so modules set up by set_forward_quantized are covered."""
@@ -438,9 +439,10 @@ def _patch_forward() -> None:
         amd_dynamic.plan_dynamic(value.shape, value.dtype, args, global_scale)  # NotImplementedError -> original
         return True
 
-    def static_ok(value, args, global_scale) -> bool:
+    def static_ok(value, args, global_scale, base_name) -> bool:
         qt, bits = enum_value(getattr(args, "type", "int")), int(args.num_bits)
-        return (value.is_cuda and value.dtype in floats and global_scale is None and enum_value(args.strategy) in ("tensor", "channel", "token", "group")
+        strategies = ("tensor", "channel", "token", "group") + (("attn_head",) if base_name in ("q", "k", "v") else ())
+        return (value.is_cuda and value.dtype in floats and global_scale is None and enum_value(args.strategy) in strategies
                 and ((qt == "int" and 1 <= bits <= 8) or (qt == "float" and bits == 8)))
 
     def take_forward(module, value, base_name, args) -> bool:
@@ -448,7 +450,7 @@ def _patch_forward() -> None:
         if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
             return plannable(value, args, gs)
         scale = getattr(module, f"{base_name}_scale", None)
-        return scale is not None and scale.is_cuda and scale.dtype in floats and static_ok(value, args, gs)
+        return scale is not None and scale.is_cuda and scale.dtype in floats and static_ok(value, args, gs, base_name)
 
     def take_dynamic(value, args, module=None, global_scale=None) -> bool:
         return plannable(value, args, global_scale)
@@ -576,8 +578,59 @@ def _unpatch_transforms() -> None:
     _TR_RANDOM[0] = False
 
 
+_KV_SAVED = {}  # install(patch_modeling=True): upstream's QuantizedKVCache class and its own forward
+
+
+def _patch_modeling() -> None:
+    """`install(patch_modeling=True)`: upstream's `QuantizedKVCache.forward` (modeling/kvcache.py:52-77) calls forward_quantize for K
+    and then for V with the same arguments.  It is rebound to a forward that hands static tensor / attn_head GPU states to
+    modeling.quantize_key_value — ONE launch of csrc/ct_attn.hip for both where the pair form is dispatched, the two strided calls
+    where it is not — and then delegates to the wrapped cache exactly as the original does.  Dynamic schemes, CPU states, other
+    strategies and a NotImplementedError from the HIP side run the original forward."""
+    import functools
+
+    import compressed_tensors.modeling.kvcache as up_kv
+
+    from .modeling import kvcache as amd_kv
+    from .quantization import dynamic as amd_dynamic
+
+    if _KV_SAVED:
+        return
+    cls = up_kv.QuantizedKVCache
+    orig = cls.forward
+
+    @functools.wraps(orig)
+    def forward(self, key_states, value_states, *args, **kwargs):
+        module = self.attn_module()
+        quant_args = getattr(getattr(module, "quantization_scheme", None), "input_activations", None)
+        if quant_args is None or not getattr(module, "quantization_enabled", True):
+            return orig(self, key_states, value_states, *args, **kwargs)
+        floats = (torch.float32, torch.float16, torch.bfloat16)
+        if not (amd_kv._static_pair_args(module, key_states, value_states, quant_args) and key_states.dtype in floats and value_states.dtype in floats):
+            return orig(self, key_states, value_states, *args, **kwargs)
+        try:
+            key_states, value_states = amd_kv.quantize_key_value(module, key_states, value_states, quant_args, single=amd_dynamic.forward_quantize)
+        except NotImplementedError:
+            return orig(self, key_states, value_states, *args, **kwargs)
+        wrapped = self.past_key_values() if self.past_key_values is not None else None
+        self.past_key_values = None
+        if wrapped is None:
+            return key_states, value_states
+        return wrapped.update(key_states, value_states, *args, **kwargs)
+
+    forward._ct_original = orig
+    _KV_SAVED.update(cls=cls, forward=orig)
+    cls.forward = forward
+
+
+def _unpatch_modeling() -> None:
+    if _KV_SAVED:
+        _KV_SAVED["cls"].forward = _KV_SAVED["forward"]
+        _KV_SAVED.clear()
+
+
 def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False,
-            patch_forward: bool = False, patch_transforms: bool = False, patch_random_hadamard: bool = False):
+            patch_forward: bool = False, patch_transforms: bool = False, patch_random_hadamard: bool = False, patch_modeling: bool = False):
     """registry swap + ImplBackend registration
     (+ the by-name bindings of the codec classes inside upstream's own modules unless rebind_names=False;
      + batched launches behind upstream's ModelCompressor.compress_model / decompress_model unless wrap_model_compressor=False;
@@ -585,7 +638,8 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
      + with patch_forward=True the QDQ forward's forward_quantize / compute_dynamic_scales_and_zp;
      + with patch_transforms=True the deterministic HadamardTransform.forward;
      + with patch_transforms=True AND patch_random_hadamard=True the forward of what a RandomHadamardFactory makes, without a permutation:
-       the n x n weight is factored once and the call runs on the kernels of csrc/ct_hadamard_k.hip)."""
+       the n x n weight is factored once and the call runs on the kernels of csrc/ct_hadamard_k.hip;
+     + with patch_modeling=True the forward of upstream's QuantizedKVCache: K and V through modeling.quantize_key_value)."""
     if patch_random_hadamard and not patch_transforms:
         raise ValueError("patch_random_hadamard=True needs patch_transforms=True")
     import compressed_tensors  # the upstream package; ImportError if it is not installed
@@ -608,6 +662,8 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
     if patch_transforms:
         _patch_transforms()
         _TR_RANDOM[0] = _TR_RANDOM[0] or bool(patch_random_hadamard)
+    if patch_modeling:
+        _patch_modeling()
     return compressed_tensors
 
 
@@ -626,6 +682,7 @@ def _broadcast_layout(x, scale):
 
 def uninstall():
     _unpatch_transforms()
+    _unpatch_modeling()
     if not _SAVED:
         return
     from compressed_tensors.compressors import BaseCompressor

@@ -27,6 +27,7 @@ __all__ = ["compute_dynamic_scales_and_zp", "forward_quantize", "plan_dynamic", 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _F8 = torch.float8_e4m3fn
 _STRATEGIES = ("token", "tensor", "tensor_group", "group")
+_ATTENTION_STATES = ("q", "k", "v")  # base names of modeling/attention.py and modeling/kvcache.py
 _LIFECYCLE = {"initialized": 0, "calibration": 1, "frozen": 2, "compressed": 3, "decompressed": 4}  # quant_config.py:115-121
 
 
@@ -154,6 +155,10 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
         return dynamic_fake_quantize(value, args, global_scale)
     scale = getattr(module, f"{base_name}_scale")
     zero_point = getattr(module, f"{base_name}_zero_point", None)
+    if base_name in _ATTENTION_STATES and global_scale is None and enum_value(args.strategy) in ("tensor", "attn_head"):
+        # query / key / value states are transposed views: read through their strides (csrc/ct_attn.hip), not copied first
+        return codec.attn_fake_quantize(value, scale, zero_point, num_bits=int(args.num_bits), strategy=enum_value(args.strategy),
+                                        qtype=enum_value(getattr(args, "type", "int")))
     return fake_quantize(x=value, scale=scale, zero_point=zero_point, args=args, g_idx=g_idx, global_scale=global_scale)
 
 

@@ -3,7 +3,8 @@
 
 Scope: INT quantization (num_bits 1..8), FLOAT 8-bit (float8_e4m3fn) and FLOAT 4-bit (E2M1, optionally under a
 `global_scale`: the tensor_group strategy), strategies tensor / channel / token / group / tensor_group / block,
-optional activation ordering (g_idx).
+optional activation ordering (g_idx); and attn_head — a (H, 1, 1) scale against (..., H, S, D) query / key / value states —, which
+codec hands to the strided entry of csrc/ct_attn.hip (codec.attn_fake_quantize / attn_quantize / attn_dequantize).
 """
 from typing import Optional
 

@@ -1,9 +1,12 @@
 """apply_transform_config (transform/apply.py:14-30 with TransformFactory._apply_to_module, transform/factory/base.py:105-190)
 for the deterministic `hadamard` type and, given the caller's matrix constructor, the `random-hadamard` type; and the opt-in `fuse_input_quantization`: an `input` rotation in front of a dynamically
-quantized module runs in the QDQ's launch (csrc/ct_rotated.hip)."""
+quantized module runs in the QDQ's launch (csrc/ct_rotated.hip).  The `q_attn` / `k_cache` locations of a transformers model become
+query / key hooks of modeling/ (base.py:167-189)."""
 import torch
 
 from ..entrypoints.convert.converters import match_name
+from ..modeling import (QuantizedAttentionImpl, QuantizedKVCache, initialize_hooked_attention, initialize_hooked_kv_cache, register_key_hook,
+                        register_query_hook)
 from .config import TRANSFORM_CONFIG_NAME, TransformConfig, TransformLocation
 from .hadamard import HadamardTransform, get_transform_size
 from .random_hadamard import RandomHadamardTransform, factor_hadamard_weight
@@ -24,13 +27,30 @@ def match_named_modules(model: torch.nn.Module, targets, ignore=()):
     """utils/match.py:34-64: (name, module) of every module a target matches and no ignore entry does, in named_modules order"""
     targets, ignore = list(targets or []), list(ignore or [])
     for name, module in model.named_modules():
-        if isinstance(module, (HadamardTransform, RandomHadamardTransform)):
+        if isinstance(module, (HadamardTransform, RandomHadamardTransform, QuantizedAttentionImpl, QuantizedKVCache)):
             continue  # InternalModule upstream
         if _is_match(name, module, targets) and not _is_match(name, module, ignore):
             yield name, module
 
 
-def _check_supported(name, scheme, random_hadamard: bool = False) -> None:
+_ATTENTION_LOCATIONS = (TransformLocation.Q_ATTN, TransformLocation.K_CACHE)
+
+
+class AttentionHookError(ValueError, NotImplementedError):
+    """upstream's `ValueError("Cannot hook attention of model: ...")` (base.py:169-170,180-181) for a q_attn / k_cache location on
+    something that is not a transformers PreTrainedModel.  Also a NotImplementedError: that is what these locations raised before
+    the hooks existed, and what callers that hand undone work to upstream catch."""
+
+
+def _is_pretrained_model(model) -> bool:
+    try:
+        from transformers import PreTrainedModel
+    except ImportError:
+        return False
+    return isinstance(model, PreTrainedModel)
+
+
+def _check_supported(name, scheme, random_hadamard: bool = False, model=None) -> None:
     if scheme.type != "hadamard" and not (random_hadamard and scheme.type == "random-hadamard"):
         raise NotImplementedError(f"config group {name!r}: type={scheme.type!r} is not built here (only the deterministic 'hadamard' type is)")
     if scheme.randomize:
@@ -38,8 +58,8 @@ def _check_supported(name, scheme, random_hadamard: bool = False) -> None:
     if scheme.requires_grad:
         raise NotImplementedError(f"config group {name!r}: requires_grad=True (training, parametrization) is not built here")
     for args in scheme.apply:
-        if TransformLocation(args.location) in (TransformLocation.Q_ATTN, TransformLocation.K_CACHE):
-            raise NotImplementedError(f"config group {name!r}: location={args.location!r} needs attention / KV-cache hooks, which are not built here")
+        if TransformLocation(args.location) in _ATTENTION_LOCATIONS and not _is_pretrained_model(model):
+            raise AttentionHookError(f"config group {name!r}: location={args.location!r}: Cannot hook attention of model: {model}")
 
 
 _INPUT_ROTATIONS = "_ct_input_rotations"  # module attribute: the InputRotation pre-hooks apply_transform_config registered
@@ -142,7 +162,7 @@ class _RandomWeights:
         return self.factors[size]
 
 
-def _apply_to_module(name, scheme, module, args, random_weights=None) -> None:
+def _apply_to_module(name, scheme, module, args, random_weights=None, model=None) -> None:
     location = TransformLocation(args.location)
     size = get_transform_size(module, location, scheme.head_dim)
     if scheme.type == "random-hadamard":
@@ -164,6 +184,15 @@ def _apply_to_module(name, scheme, module, args, random_weights=None) -> None:
     elif location == TransformLocation.OUTPUT:
         module.register_module(transform_name, transform)
         module.register_forward_hook(lambda _, _inputs, output: transform(output))
+    elif location == TransformLocation.Q_ATTN:
+        # the post-rope query states, rotated over the head dimension before they are quantized (base.py:167-176)
+        module.register_module(transform_name, transform)
+        initialize_hooked_attention(model, module)
+        register_query_hook(module, lambda _, query_states: transform(query_states))
+    elif location == TransformLocation.K_CACHE:
+        module.register_module(transform_name, transform)
+        initialize_hooked_kv_cache(model, module)
+        register_key_hook(module, lambda _, key_states: transform(key_states))
     else:
         assert hasattr(module, "weight")
         with torch.no_grad():
@@ -177,8 +206,10 @@ def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=N
     """Weight locations are fused into the weights (and the bias, for weight_output) under no_grad; `input` becomes a prepended
     forward pre-hook and `output` a forward hook on a HadamardTransform submodule.  `config` (ours or upstream's pydantic
     object) is attached to the model as `transform_config`, where ModelCompressor.from_pretrained_model picks it up.  Everything
-    is checked before anything is changed: q_attn / k_cache, requires_grad, randomize and every type but "hadamard" raise
-    NotImplementedError naming the field.
+    is checked before anything is changed: requires_grad, randomize and every type but "hadamard" raise NotImplementedError naming
+    the field.  `q_attn` / `k_cache` (on attention modules, with the scheme's `head_dim`) need a transformers PreTrainedModel — anything
+    else raises upstream's ValueError (AttentionHookError) — and become a query hook on modeling.QuantizedAttentionImpl / a key hook on
+    modeling.QuantizedKVCache that rotates the states over their last dimension, ahead of their quantization.
     `hadamard_weights`: a callable with the signature of upstream's `random_hadamard_matrix(size, dtype, device, gen)`
     (transform/utils/hadamard.py:53-77).  With it the `random-hadamard` type is accepted: every weight is drawn as
     RandomHadamardFactory draws it, factored (transform/random_hadamard.py) and applied by the kernels of csrc/ct_hadamard_k.hip;
@@ -186,10 +217,10 @@ def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=N
     raises as every other unsupported type does."""
     ours = TransformConfig.coerce(config)
     for name, scheme in ours.config_groups.items():
-        _check_supported(name, scheme, random_hadamard=hadamard_weights is not None)
+        _check_supported(name, scheme, random_hadamard=hadamard_weights is not None, model=model)
     for name, scheme in ours.config_groups.items():
         random_weights = _RandomWeights(name, hadamard_weights) if scheme.type == "random-hadamard" else None
         for args in scheme.apply:
             for _, module in list(match_named_modules(model, args.targets, args.ignore)):
-                _apply_to_module(name, scheme, module, args, random_weights)
+                _apply_to_module(name, scheme, module, args, random_weights, model)
     setattr(model, TRANSFORM_CONFIG_NAME, config)

@@ -348,6 +348,33 @@ int ct_hadamard_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, in
                             const float* global_scale, void* rotated_out, void* out, void* scale_out, void* zp_out, int zdt,
                             ct_stream_t stream);
 
+/* Static quantize / dequantize / fake_quantize of the query, key and value states of an attention module
+ * (modeling/attention.py, modeling/kvcache.py -> forward_quantize -> forward_helpers.py:180-215, 525-572): one or two 4-D
+ * tensors (B, H, S, D) read and written IN PLACE through their strides.  The last dimension has stride 1; the b / h / s
+ * strides of input and output are non-negative element counts (0: an expanded dimension).  scale / zp hold one entry
+ * (`per_head` 0, the tensor strategy) or H entries (`per_head` 1, the attn_head strategy: entry h).  A row of D elements is one
+ * scale and one contiguous run; rows of whole 8-element units whose bases and strides keep the units aligned (16 bytes of a
+ * 16-bit dtype) move as vectors, everything else element by element.  B * H * S < 2^31 per tensor. */
+typedef struct ct_attn_tensor {
+    const void* x;
+    void* out;
+    const void* scale;
+    const void* zp;                /* NULL: symmetric */
+    int64_t B, H, S, D;
+    int64_t x_stride[3];           /* b, h, s: elements */
+    int64_t out_stride[3];
+    int64_t per_head;
+} ct_attn_tensor;                  /* 15 64-bit words */
+
+/* mode 0 fake_quantize, 1 quantize, 2 dequantize; kind 0 INT (bits 1..8), 1 FLOAT 8-bit (float8_e4m3fn; bits ignored).
+ * xdt: a float dtype (modes 0, 1), or CT_I8 / CT_I32 / CT_F8E4M3 / a float dtype (mode 2).  tdt: the torch result dtype of
+ * x / scale (modes 0, 1).  odt: a float dtype (modes 0, 2); CT_I8 / CT_I32 / CT_F8E4M3 / a float dtype (mode 1).  n = 2: both
+ * tensors (K and V) share every dtype, the kind, bits and mode, and are served by ONE launch.  The descriptors travel as
+ * kernel arguments: `tensors` is host memory, nothing is uploaded and the library keeps no device state.  The results are the
+ * bits ct_fake_quantize{,_fp8} / ct_quantize{,_fp8} / ct_dequantize give on the same values. */
+int ct_attn_qdq(const ct_attn_tensor* tensors, int n, int mode, int kind, int bits, int xdt, int sdt, int zdt, int tdt, int odt,
+                ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
