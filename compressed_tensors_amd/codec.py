@@ -79,6 +79,13 @@ __all__ = [
     "attn_quantize",
     "attn_dequantize",
     "attn_fake_quantize_pair",
+    "AttnRotPlan",
+    "plan_attn_rot_qdq",
+    "attn_rotated_fake_quantize",
+    "attn_rotated_quantize",
+    "attn_rotated_fake_quantize_pair",
+    "ATTN_ROTATED_MEASURED_FASTER",
+    "ATTN_ROTATED_MAX_SIZE",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -590,14 +597,21 @@ def _attn_layout(shape, strides, dtype, scale_shape, scale_strides, scale_dtype,
     return plan, out_strides, view[1]
 
 
-def _attn_one(x, scale, zero_point, mode, strategy, out_dtype, dev, rounds):
-    """one descriptor of ct_attn_qdq: (AttnTensor fields, out, zero-point dtype code, tensors to keep alive)"""
+def _attn_one(x, scale, zero_point, mode, strategy, out_dtype, dev, rounds, rotated=False):
+    """one descriptor of ct_attn_qdq: (AttnTensor fields, out, zero-point dtype code, tensors to keep alive).  `rotated`
+    (ct_attn_rot_qdq, a tensor plan_attn_rot_qdq fuses): x is read through its own strides, the output is laid out as the
+    composition lays it out — what the QDQ gives for the contiguous rotated tensor of the same shape"""
     if zero_point is not None and zero_point.numel() != scale.numel():
         raise ValueError(f"zero_point shape {tuple(zero_point.shape)} does not match scale shape {tuple(scale.shape)}")
     tail = (scale.shape, scale.stride(), scale.dtype, strategy, out_dtype)
     plan, out_strides, out_bhs = _attn_layout(x.shape, x.stride(), x.dtype, *tail, x.data_ptr() % 16, mode, rounds)
     xr = x
-    if not plan.in_place:
+    if rotated:
+        # hadamard_transform(x.contiguous()) is torch.empty_like of a tensor torch calls contiguous: dense strides — or x's own
+        # where x already counts as contiguous (a decode step's S = 1 view keeps its stride in the size-1 dimension)
+        rot_strides = x.stride() if x.is_contiguous() else _dense_strides(x.shape)
+        _, out_strides, out_bhs = _attn_layout(x.shape, rot_strides, x.dtype, *tail, 0, mode, rounds)
+    elif not plan.in_place:
         xr = x.contiguous()
         plan, out_strides, out_bhs = _attn_layout(xr.shape, xr.stride(), xr.dtype, *tail, xr.data_ptr() % 16, mode, rounds)
     out = torch.empty_strided(xr.shape, out_strides, dtype=out_dtype, device=xr.device)
@@ -620,8 +634,14 @@ def _attn_result_dtype(x_dtype, x_zero_dim: bool, scale_dtype, scale_zero_dim: b
     return _result_dtype(x, scale, scale_zero_dim)
 
 
-def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None, global_scale=None):
-    """tensors: [(x, scale, zero_point)] of one or two q / k / v states sharing dtypes and arguments -> [out]; ONE ct_attn_qdq"""
+@functools.lru_cache(maxsize=1024)
+def _dense_strides(shape) -> tuple:
+    return tuple(torch.empty(tuple(shape), device="meta").stride())
+
+
+def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None, global_scale=None, rot_size=0, rot_mask=0):
+    """tensors: [(x, scale, zero_point)] of one or two q / k / v states sharing dtypes and arguments -> [out]; ONE ct_attn_qdq —
+    or, with `rot_mask` (bit i: tensor i is rotated over runs of `rot_size` elements first), ONE ct_attn_rot_qdq"""
     st = _strategy_name(strategy)
     if global_scale is not None:
         raise NotImplementedError("a global scale on attention states is not implemented by the MI355X path")
@@ -658,15 +678,18 @@ def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None
     outs, keep, zdt = [], [], -1
     for i, (x, s, z) in enumerate(tensors):
         xd = x if x.device == dev else x.to(dev)
-        item, out, zdt, alive = _attn_one(xd, s, z, mode, st, out_dtype, dev, mode != "dequantize" and qtype == "int")
+        item, out, zdt, alive = _attn_one(xd, s, z, mode, st, out_dtype, dev, mode != "dequantize" and qtype == "int", bool((rot_mask >> i) & 1))
         d = descs[i]
         d.x, d.out, d.scale, d.zp, d.B, d.H, d.S, d.D = item[:8]
         d.x_stride[:], d.out_stride[:], d.per_head = item[8], item[9], item[10]
         outs.append(_home(out, x))
         keep.append(alive)
     kind = 1 if (mode != "dequantize" and qtype == "float") else 0
-    call("ct_attn_qdq", descs, len(tensors), _ATTN_MODES[mode], kind, int(num_bits) if mode != "dequantize" else 8, DT[x0.dtype], DT[s0.dtype], zdt, DT[T],
-         DT[out_dtype], stream_on(dev))
+    tail = (_ATTN_MODES[mode], kind, int(num_bits) if mode != "dequantize" else 8, DT[x0.dtype], DT[s0.dtype], zdt, DT[T], DT[out_dtype], stream_on(dev))
+    if rot_mask:
+        call("ct_attn_rot_qdq", descs, len(tensors), int(rot_size), int(rot_mask), *tail)
+    else:
+        call("ct_attn_qdq", descs, len(tensors), *tail)
     return outs
 
 
@@ -696,6 +719,119 @@ def attn_fake_quantize_pair(k, v, k_scale, v_scale, k_zero_point=None, v_zero_po
     out = _attn_qdq([(k, k_scale, k_zero_point), (v, v_scale, v_zero_point)], "fake", num_bits=num_bits, strategy=strategy, qtype=qtype,
                     global_scale=global_scale)
     return out[0], out[1]
+
+
+# --------------------------------------------------------------------------- attention: the head-dim rotation in the QDQ's launch
+ATTN_ROTATED_MAX_SIZE = 512  # the rotation blocks csrc/ct_attn_rot.hip serves: n / 8 lanes of one wave
+ATTN_ROTATED_MAX_UNITS = 256  # D / 8: a row is one pass of a workgroup's lanes
+
+# Which calls `fused=None` dispatches to the one launch (ct_attn_rot_qdq): "single" — one rotated tensor (the query states) —
+# and "pair" — K rotated and V not, one cache update.  True only where tools/attn_bench.py measured the fused launch faster than
+# `.contiguous()` + hadamard_transform + attn_fake_quantize{,_pair} on the same buffers by more than the spread between its runs,
+# in every row that speaks for the key (profiles/attn_rot_bench.jsonl): q (1, 32, 8192, 128) 55.6-55.8 us against
+# 128.3-128.5, k+v (1, 8, 8192, 128) 26.9-28.3 against 54.0-56.1, decode k+v (64, 8, 1, 128) 18.8-20.2 against 26.3-28.0, run spreads
+# 0.2, 2.1 and 1.7 us.  False would mean: the composition.
+ATTN_ROTATED_MEASURED_FASTER = {"single": True, "pair": True}
+
+
+class AttnRotPlan(NamedTuple):
+    """what the attn_rotated_* functions do with one tensor: `fused` (ct_attn_rot_qdq rotates and quantizes it in one launch,
+    reading it `in_place` through its strides) or not (`reason` says why: `.contiguous()`, hadamard_transform, then the attn_*
+    call).  `out_strides`: the result's strides for a rotated tensor with dense strides (the reference's: its GEMM allocates one).
+    The result follows the composition: where torch already counts x as contiguous (S = 1 views) the size-1 dimension may keep
+    x's stride, which no index ever multiplies.  `hadamard` / `attn` are the parents' plans (attn: of the tensor as given)."""
+    fused: bool
+    in_place: bool
+    reason: Optional[str]
+    out_strides: tuple
+    hadamard: "HadamardPlan"
+    attn: AttnPlan
+
+
+def plan_attn_rot_qdq(shape, strides, dtype, size: int, scale_shape, strategy, *, out_dtype=None, offset_bytes: int = 0,
+                      precision=torch.float32) -> AttnRotPlan:
+    """The host plan of the attn_rotated_* functions, from shapes, strides and dtypes alone.  Raises what plan_hadamard raises
+    (upstream's ValueError for a size that is not a positive power of two or does not divide D) first, then what plan_attn_qdq
+    raises; everything the one launch does not serve is declined with a reason, and the composition serves it."""
+    hp = plan_hadamard(shape, dtype, size, -1, precision)
+    ap = plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, out_dtype=out_dtype, offset_bytes=offset_bytes)
+    n, D = hp.size, ap.D
+    reason = None
+    if precision is not torch.float32:
+        reason = f"the fused launch accumulates in float32, not {precision}"
+    elif not 2 <= n <= ATTN_ROTATED_MAX_SIZE:
+        reason = f"hadamard size {n} is outside 2 .. {ATTN_ROTATED_MAX_SIZE}"
+    elif D % 8:
+        reason = f"rows of {D} elements are not whole 8-element units"
+    elif D // 8 > ATTN_ROTATED_MAX_UNITS:
+        reason = f"rows of {D} elements exceed one pass of {ATTN_ROTATED_MAX_UNITS} units"
+    elif not ap.in_place:
+        reason = ap.reason
+    elif not _attn_unit_aligned(offset_bytes, (ap.B, ap.H, ap.S), ap.strides, dtype.itemsize, D):
+        reason = "the storage offset or a stride breaks the alignment of the 8-element units"
+    return AttnRotPlan(reason is None, ap.in_place, reason, _dense_strides(tuple(int(d) for d in shape)), hp, ap)
+
+
+@functools.lru_cache(maxsize=4096)
+def _attn_rot_plan_fused(shape, strides, dtype, size, scale_shape, strategy, out_dtype, offset_bytes) -> bool:
+    """plan_attn_rot_qdq(...).fused, once per layout (what it raises is raised on every call)"""
+    return plan_attn_rot_qdq(shape, strides, dtype, size, scale_shape, strategy, out_dtype=out_dtype, offset_bytes=offset_bytes).fused
+
+
+@functools.lru_cache(maxsize=4096)
+def _attn_rot_plain_ok(shape, strides, dtype, scale_shape, strategy, out_dtype, offset_bytes) -> bool:
+    """the unrotated tensor of a pair: read in place, in the vector form, one pass per row"""
+    p = plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, out_dtype=out_dtype, offset_bytes=offset_bytes)
+    return p.in_place and p.vector and p.D // 8 <= ATTN_ROTATED_MAX_UNITS
+
+
+def _attn_rot_fusable(x, size, scale, strategy, out_dtype) -> bool:
+    """one launch serves the rotated x: GPU tensors and a plan that fuses"""
+    if not (x.is_cuda and scale.is_cuda and x.numel()):
+        return False
+    return _attn_rot_plan_fused(x.shape, x.stride(), x.dtype, int(size), scale.shape, _strategy_name(strategy), out_dtype, x.data_ptr() % 16)
+
+
+def _attn_rot_pair_fusable(k, v, size, k_scale, v_scale, strategy) -> bool:
+    """one launch serves the rotated k and the unrotated v"""
+    if not (_attn_rot_fusable(k, size, k_scale, strategy, k_scale.dtype) and v.is_cuda and v_scale.is_cuda and v.numel()):
+        return False
+    return _attn_rot_plain_ok(v.shape, v.stride(), v.dtype, v_scale.shape, _strategy_name(strategy), v_scale.dtype, v.data_ptr() % 16)
+
+
+def attn_rotated_fake_quantize(x, size: int, scale, zero_point=None, *, num_bits, strategy="attn_head", qtype="int", fused: Optional[bool] = None) -> torch.Tensor:
+    """attn_fake_quantize(hadamard_transform(x.contiguous(), size), scale, zero_point, ...): a query or key state rotated over
+    runs of `size` elements of its head dimension (HadamardTransform at q_attn / k_cache, float32) and quantized.  `fused`: True —
+    ONE launch (ct_attn_rot_qdq) wherever plan_attn_rot_qdq allows it: the strided view is read once, neither the contiguous copy
+    nor the rotated tensor exist; False — the composition; None — the fused launch where ATTN_ROTATED_MEASURED_FASTER["single"]
+    says it was measured faster.  The same bits, dtype, shape and strides either way."""
+    want = ATTN_ROTATED_MEASURED_FASTER["single"] if fused is None else fused
+    if want and _attn_rot_fusable(x, size, scale, strategy, scale.dtype):
+        return _attn_qdq([(x, scale, zero_point)], "fake", num_bits=num_bits, strategy=strategy, qtype=qtype, rot_size=size, rot_mask=1)[0]
+    return attn_fake_quantize(hadamard_transform(x.contiguous(), size), scale, zero_point, num_bits=num_bits, strategy=strategy, qtype=qtype)
+
+
+def attn_rotated_quantize(x, size: int, scale, zero_point=None, *, num_bits, strategy="attn_head", qtype="int", dtype=None,
+                          fused: Optional[bool] = None) -> torch.Tensor:
+    """attn_quantize(hadamard_transform(x.contiguous(), size), ...) — what an FP8 KV cache stores of rotated keys —, in one launch
+    under the rule of attn_rotated_fake_quantize"""
+    want = ATTN_ROTATED_MEASURED_FASTER["single"] if fused is None else fused
+    if want and _attn_rot_fusable(x, size, scale, strategy, dtype):
+        return _attn_qdq([(x, scale, zero_point)], "quantize", num_bits=num_bits, strategy=strategy, qtype=qtype, dtype=dtype, rot_size=size, rot_mask=1)[0]
+    return attn_quantize(hadamard_transform(x.contiguous(), size), scale, zero_point, num_bits=num_bits, strategy=strategy, qtype=qtype, dtype=dtype)
+
+
+def attn_rotated_fake_quantize_pair(k, v, size: int, k_scale, v_scale, k_zero_point=None, v_zero_point=None, *, num_bits, strategy="attn_head",
+                                    qtype="int", fused: Optional[bool] = None):
+    """attn_fake_quantize_pair(hadamard_transform(k.contiguous(), size), v, ...): one cache update under a k_cache rotation — K
+    rotated, V not — in ONE launch where both tensors suit it (`fused` as in attn_rotated_fake_quantize, key "pair")."""
+    want = ATTN_ROTATED_MEASURED_FASTER["pair"] if fused is None else fused
+    if want and _attn_rot_pair_fusable(k, v, size, k_scale, v_scale, strategy):
+        out = _attn_qdq([(k, k_scale, k_zero_point), (v, v_scale, v_zero_point)], "fake", num_bits=num_bits, strategy=strategy, qtype=qtype,
+                        rot_size=size, rot_mask=1)
+        return out[0], out[1]
+    return attn_fake_quantize_pair(hadamard_transform(k.contiguous(), size), v, k_scale, v_scale, k_zero_point, v_zero_point, num_bits=num_bits,
+                                   strategy=strategy, qtype=qtype)
 
 
 def quantize_and_pack(x, scale, zero_point, *, num_bits, strategy, group_size=None, block_structure=None,

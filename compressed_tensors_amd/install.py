@@ -456,7 +456,8 @@ def _patch_forward() -> None:
         return plannable(value, args, global_scale)
 
     def handed_off(module, value, base_name, args) -> bool:
-        # transform.fuse_input_quantization: the rotation's pre-hook already quantized this very tensor.  Consulted before the
+        # transform.fuse_input_quantization / fuse_attention_quantization ("input"; "q", "k", "v"): the rotation's pre-hook already
+        # quantized this very tensor.  Consulted before the
         # take_forward decision — the original would quantize it a second time, and a dynamic QDQ is not idempotent bit for bit
         return amd_dynamic.take_prequantized(module, value, base_name)
 

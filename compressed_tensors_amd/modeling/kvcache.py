@@ -12,11 +12,11 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from .. import codec
-from ..quantization.dynamic import forward_quantize
+from ..quantization.dynamic import forward_quantize, take_prequantized
 from ..quantization.quant_args import enum_value
 
-__all__ = ["QuantizedKVCache", "initialize_hooked_kv_cache", "register_key_hook", "register_value_hook", "KV_CACHE_ATTR", "PAIR_MEASURED_FASTER",
-           "quantize_key_value"]
+__all__ = ["QuantizedKVCache", "initialize_hooked_kv_cache", "register_key_hook", "register_value_hook", "register_key_value_hook", "KV_CACHE_ATTR",
+           "PAIR_MEASURED_FASTER", "ROTATED_MEASURED_FASTER", "quantize_key_value"]
 
 KV_CACHE_ATTR = "kv_cache"
 
@@ -25,6 +25,10 @@ KV_CACHE_ATTR = "kv_cache"
 # prefill AND the decode shape.  profiles/attn_bench.jsonl: k+v (1, 8, 8192, 128) 32.1-32.3 us against 36.5-37.4, k+v
 # (64, 8, 1, 128) 16.1-16.2 against 22.7-23.1, run spreads 0.9 and 0.3 us.  False would mean: two launches.
 PAIR_MEASURED_FASTER = True
+
+# the head-dim rotation of q / k in the QDQ's launch (csrc/ct_attn_rot.hip): {"single": bool, "pair": bool}, the very dict
+# codec.attn_rotated_* dispatch by — held to profiles/attn_rot_bench.jsonl by tests/test_attn_rotated.py
+ROTATED_MEASURED_FASTER = codec.ATTN_ROTATED_MEASURED_FASTER
 
 
 def _static_pair_args(module, key_states, value_states, quant_args) -> bool:
@@ -42,7 +46,12 @@ def _static_pair_args(module, key_states, value_states, quant_args) -> bool:
 
 def quantize_key_value(module, key_states, value_states, quant_args, single=forward_quantize, pair: Optional[bool] = None):
     """forward_quantize(module, key_states, "k", args), forward_quantize(module, value_states, "v", args): as one launch where the
-    pair form is dispatched (`pair`; None: PAIR_MEASURED_FASTER) and the plan takes both, through `single` twice otherwise"""
+    pair form is dispatched (`pair`; None: PAIR_MEASURED_FASTER) and the plan takes both, through `single` twice otherwise.  A state
+    that IS the tensor a fused rotation hook handed off (object identity) comes back untouched."""
+    done_k, done_v = take_prequantized(module, key_states, "k"), take_prequantized(module, value_states, "v")
+    if done_k or done_v:  # transform.fuse_attention_quantization: the rotation's pre-hook quantized these very tensors in its launch
+        return (key_states if done_k else single(module, key_states, "k", quant_args),
+                value_states if done_v else single(module, value_states, "v", quant_args))
     if (PAIR_MEASURED_FASTER if pair is None else pair) and _static_pair_args(module, key_states, value_states, quant_args):
         try:
             return codec.attn_fake_quantize_pair(
@@ -122,3 +131,19 @@ def register_key_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, 
 def register_value_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, torch.Tensor], Optional[torch.Tensor]]):
     """the same for the value states"""
     return _register_state_hook(module, "value_states", hook)
+
+
+def register_key_value_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, torch.Tensor, torch.Tensor], Optional[Tuple[torch.Tensor, torch.Tensor]]]):
+    """`hook(module, key_states, value_states)` sees both states of one cache update; a (key_states, value_states) pair it
+    returns replaces them.  Returns the removable handle."""
+    cache: QuantizedKVCache = getattr(module, KV_CACHE_ATTR)
+    signature = inspect.signature(cache.forward)
+
+    def pre_hook(_cache, args, kwargs):
+        bound = signature.bind(*args, **kwargs)
+        replaced = hook(module, bound.arguments["key_states"], bound.arguments["value_states"])
+        if replaced is not None:
+            bound.arguments["key_states"], bound.arguments["value_states"] = replaced
+        return bound.args, bound.kwargs
+
+    return cache.register_forward_pre_hook(pre_hook, with_kwargs=True)

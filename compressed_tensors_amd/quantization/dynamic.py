@@ -145,7 +145,7 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
     if value.numel() == 0:
         return value
     if take_prequantized(module, value, base_name):
-        return value  # transform.fuse_input_quantization: the rotation's pre-hook quantized this very tensor in its own launch
+        return value  # transform.fuse_{input,attention}_quantization: the rotation's pre-hook quantized this very tensor in its own launch
     g_idx = getattr(module, "weight_g_idx", None)
     global_scale = getattr(module, f"{base_name}_global_scale", None)
     if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
@@ -164,20 +164,25 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
 
 # ---- the same forward behind an online Hadamard rotation ----------------------------------------------------------------------------
 _PREQUANTIZED = "_ct_prequantized_input"  # module attribute: a weak reference to the tensor the fused pre-hook returned
+# one weak reference per base name: the module input (transform.fuse_input_quantization) and the query / key / value states of an
+# attention module (transform.fuse_attention_quantization)
+_PREQUANTIZED_ATTRS = {"input": _PREQUANTIZED, "q": "_ct_prequantized_q", "k": "_ct_prequantized_k", "v": "_ct_prequantized_v"}
 
 
-def remember_prequantized(module: torch.nn.Module, value: torch.Tensor) -> None:
-    """the hand-off of transform.fuse_input_quantization: `value` is the module's input, already rotated AND quantized"""
-    module.__dict__[_PREQUANTIZED] = weakref.ref(value)
+def remember_prequantized(module: torch.nn.Module, value: torch.Tensor, base_name: str = "input") -> None:
+    """the hand-off of transform.fuse_input_quantization (`value` is the module's input, already rotated AND quantized) and of
+    transform.fuse_attention_quantization (base names "q", "k", "v": the attention module's states, already quantized)"""
+    module.__dict__[_PREQUANTIZED_ATTRS[base_name]] = weakref.ref(value)
 
 
 def take_prequantized(module: torch.nn.Module, value: torch.Tensor, base_name: str) -> bool:
-    """True when `value` IS (object identity) the tensor the module's fused pre-hook returned for this call: forward_quantize then
-    returns it untouched (a dynamic QDQ is not idempotent bit for bit).  The reference is cleared either way; any other tensor —
-    another hook replaced the input, or nobody pre-quantized — is quantized as always."""
-    if base_name != "input":
+    """True when `value` IS (object identity) the tensor the module's fused pre-hook returned for this call under `base_name`:
+    forward_quantize then returns it untouched (a QDQ is not idempotent bit for bit).  The reference of that base name is cleared
+    either way; any other tensor — another hook replaced it, or nobody pre-quantized — is quantized as always."""
+    attr = _PREQUANTIZED_ATTRS.get(base_name)
+    if attr is None:
         return False
-    ref = module.__dict__.pop(_PREQUANTIZED, None)
+    ref = module.__dict__.pop(attr, None)
     return ref is not None and ref() is value
 
 

@@ -1,17 +1,18 @@
 """apply_transform_config (transform/apply.py:14-30 with TransformFactory._apply_to_module, transform/factory/base.py:105-190)
 for the deterministic `hadamard` type and, given the caller's matrix constructor, the `random-hadamard` type; and the opt-in `fuse_input_quantization`: an `input` rotation in front of a dynamically
 quantized module runs in the QDQ's launch (csrc/ct_rotated.hip).  The `q_attn` / `k_cache` locations of a transformers model become
-query / key hooks of modeling/ (base.py:167-189)."""
+query / key hooks of modeling/ (base.py:167-189); the opt-in `fuse_attention_quantization` runs them in the launch of the static
+q / k / v QDQ that follows (csrc/ct_attn_rot.hip)."""
 import torch
 
 from ..entrypoints.convert.converters import match_name
-from ..modeling import (QuantizedAttentionImpl, QuantizedKVCache, initialize_hooked_attention, initialize_hooked_kv_cache, register_key_hook,
-                        register_query_hook)
+from ..modeling import (IMPL_ATTR, KV_CACHE_ATTR, QuantizedAttentionImpl, QuantizedKVCache, initialize_hooked_attention, initialize_hooked_kv_cache,
+                        register_key_value_hook, register_query_hook)
 from .config import TRANSFORM_CONFIG_NAME, TransformConfig, TransformLocation
 from .hadamard import HadamardTransform, get_transform_size
 from .random_hadamard import RandomHadamardTransform, factor_hadamard_weight
 
-__all__ = ["apply_transform_config", "fuse_input_quantization", "match_named_modules"]
+__all__ = ["apply_transform_config", "fuse_input_quantization", "fuse_attention_quantization", "match_named_modules"]
 
 
 def _match_class(module: torch.nn.Module, target: str) -> bool:
@@ -142,6 +143,136 @@ def fuse_input_quantization(model: torch.nn.Module) -> list:
     return fused
 
 
+_ATTN_ROTATIONS = "_ct_attn_rotations"  # attention-module attribute: {"q": QueryRotation, "k": KeyRotation} of apply_transform_config
+
+
+def _static_attn_args(module, base_names):
+    """the predicate of the consumer (QuantizedAttentionImpl / QuantizedKVCache.forward, then forward_quantize's strided branch):
+    the module's static tensor / attn_head input_activations with every state's scale on the module and no global scale, or None"""
+    from ..quantization import dynamic
+
+    args = getattr(getattr(module, "quantization_scheme", None), "input_activations", None)
+    if args is None or not getattr(module, "quantization_enabled", True):
+        return None
+    if dynamic.enum_value(getattr(args, "dynamic", False)) in (True, "local") or dynamic.enum_value(args.strategy) not in ("tensor", "attn_head"):
+        return None
+    for b in base_names:
+        if getattr(module, f"{b}_scale", None) is None or getattr(module, f"{b}_global_scale", None) is not None:
+            return None
+    return args
+
+
+class _AttentionRotation:
+    """a `q_attn` / `k_cache` transform as a named hook.  `handle` is its forward pre-hook on the module's impl / kv_cache.  With
+    `fuse_quantization` set (fuse_attention_quantization), a call for which the consumer's own predicate holds — static tensor /
+    attn_head `input_activations`, quantization enabled, scales on the module, no global scales, GPU states — and whose plan fuses
+    returns the rotated AND quantized states from one launch (csrc/ct_attn_rot.hip) and leaves weak references to them on the
+    attention module; forward_quantize / quantize_key_value hand those very tensors back untouched.  Every other call rotates
+    only, as without the opt-in.
+    Precondition of the opt-in: this hook is the last pre-hook of the impl / cache, and stays the last.  A hook registered on
+    the impl or the cache AFTER opting in would see quantized states where it saw rotated ones before (a hook that REPLACES a
+    state is safe: the replacement is another tensor, and is quantized as always)."""
+
+    def __init__(self, transform):
+        self.transform = transform
+        self.fuse_quantization = False
+        self.handle = None
+
+    def fusable(self) -> bool:
+        return isinstance(self.transform, HadamardTransform) and self.transform.precision is torch.float32 and self.transform.dim == -1
+
+    def _kw(self, args):
+        from ..quantization import dynamic
+
+        return dict(num_bits=int(args.num_bits), strategy=dynamic.enum_value(args.strategy), qtype=dynamic.enum_value(getattr(args, "type", "int")))
+
+
+class QueryRotation(_AttentionRotation):
+    """the query hook of a `q_attn` transform (see _AttentionRotation): hand-off under base name "q" """
+
+    def __call__(self, module, query_states):
+        if self.fuse_quantization:
+            out = self._rotate_and_quantize(module, query_states)
+            if out is not None:
+                return out
+        return self.transform(query_states)
+
+    def _rotate_and_quantize(self, module, value):
+        from .. import codec
+        from ..quantization import dynamic
+
+        args = _static_attn_args(module, ("q",))
+        if args is None or not codec.ATTN_ROTATED_MEASURED_FASTER["single"]:
+            return None
+        scale = module.q_scale
+        try:
+            if not codec._attn_rot_fusable(value, self.transform.size, scale, args.strategy, scale.dtype):
+                return None
+            out = codec.attn_rotated_fake_quantize(value, self.transform.size, scale, getattr(module, "q_zero_point", None), fused=True, **self._kw(args))
+        except (NotImplementedError, ValueError):
+            return None  # the rotation alone raises what it raises
+        dynamic.remember_prequantized(module, out, "q")
+        return out
+
+
+class KeyRotation(_AttentionRotation):
+    """the key hook of a `k_cache` transform (see _AttentionRotation): it sees both states of a cache update; fused, K is rotated
+    and quantized and V quantized in ONE launch, handed off under "k" and "v" """
+
+    def __call__(self, module, key_states, value_states):
+        if self.fuse_quantization:
+            out = self._rotate_and_quantize(module, key_states, value_states)
+            if out is not None:
+                return out
+        return self.transform(key_states), value_states
+
+    def _rotate_and_quantize(self, module, key_states, value_states):
+        from .. import codec
+        from ..modeling.kvcache import _static_pair_args
+        from ..quantization import dynamic
+
+        args = _static_attn_args(module, ("k", "v"))
+        if args is None or not codec.ATTN_ROTATED_MEASURED_FASTER["pair"] or not _static_pair_args(module, key_states, value_states, args):
+            return None
+        ks, vs = module.k_scale, module.v_scale
+        try:
+            if not codec._attn_rot_pair_fusable(key_states, value_states, self.transform.size, ks, vs, args.strategy):
+                return None
+            k, v = codec.attn_rotated_fake_quantize_pair(key_states, value_states, self.transform.size, ks, vs, getattr(module, "k_zero_point", None),
+                                                         getattr(module, "v_zero_point", None), fused=True, **self._kw(args))
+        except (NotImplementedError, ValueError):
+            return None
+        dynamic.remember_prequantized(module, k, "k")
+        dynamic.remember_prequantized(module, v, "v")
+        return k, v
+
+
+def fuse_attention_quantization(model: torch.nn.Module) -> list:
+    """Opt-in, after apply_transform_config and after the quantization schemes are attached, the sibling of
+    fuse_input_quantization: every attention module with a deterministic float32 HadamardTransform at `q_attn` and / or `k_cache`
+    whose rotation hook is the LAST forward pre-hook of its impl / kv_cache gets the fused hooks (QueryRotation, KeyRotation).
+    Returns the names of the modules it fused (one entry per module, whichever of its rotations qualified).  The model computes
+    the same bits: one launch for the query states and one for K + V where there were three and four — for the calls
+    modeling.ROTATED_MEASURED_FASTER dispatches; every other call rotates only, as before.  `random-hadamard` rotations are left
+    alone.  Hooks registered on the impl or the cache after opting in would see quantized states: see _AttentionRotation."""
+    fused = []
+    for name, module in model.named_modules():
+        hit = False
+        for key, owner_attr in (("q", IMPL_ATTR), ("k", KV_CACHE_ATTR)):
+            hook = module.__dict__.get(_ATTN_ROTATIONS, {}).get(key)
+            owner = getattr(module, owner_attr, None)
+            if hook is None or owner is None or not hook.fusable() or hook.handle is None:
+                continue
+            order = list(owner._forward_pre_hooks)
+            if not order or order[-1] != hook.handle.id:
+                continue  # a later hook would see quantized states where it saw rotated ones
+            hook.fuse_quantization = True
+            hit = True
+        if hit:
+            fused.append(name)
+    return fused
+
+
 class _RandomWeights:
     """the weights of one `random-hadamard` config group, as RandomHadamardFactory keeps them: one generator per group (unseeded,
     as TransformFactory.__init__ leaves it without a seed), one draw per size in order of first use (ParameterizedDefaultDict keys
@@ -188,11 +319,15 @@ def _apply_to_module(name, scheme, module, args, random_weights=None, model=None
         # the post-rope query states, rotated over the head dimension before they are quantized (base.py:167-176)
         module.register_module(transform_name, transform)
         initialize_hooked_attention(model, module)
-        register_query_hook(module, lambda _, query_states: transform(query_states))
+        hook = QueryRotation(transform)
+        hook.handle = register_query_hook(module, hook)
+        module.__dict__.setdefault(_ATTN_ROTATIONS, {})["q"] = hook  # the last one registered: the one that can share the QDQ's launch
     elif location == TransformLocation.K_CACHE:
         module.register_module(transform_name, transform)
         initialize_hooked_kv_cache(model, module)
-        register_key_hook(module, lambda _, key_states: transform(key_states))
+        hook = KeyRotation(transform)
+        hook.handle = register_key_value_hook(module, hook)
+        module.__dict__.setdefault(_ATTN_ROTATIONS, {})["k"] = hook
     else:
         assert hasattr(module, "weight")
         with torch.no_grad():

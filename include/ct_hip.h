@@ -375,6 +375,17 @@ typedef struct ct_attn_tensor {
 int ct_attn_qdq(const ct_attn_tensor* tensors, int n, int mode, int kind, int bits, int xdt, int sdt, int zdt, int tdt, int odt,
                 ct_stream_t stream);
 
+/* ct_hadamard_rows over runs of `rot_size` elements of the last dimension (float32 accumulation) followed by ct_attn_qdq, in ONE
+ * launch: the strided input is read once, rotated in registers and quantized; the output holds the bits of the two launches.
+ * `tensors` / `n` / kind / bits / the dtype codes are ct_attn_qdq's; mode is 0 (fake_quantize) or 1 (quantize) — dequantize is
+ * CT_ERR_INVALID_ARG.  rot_mask: bit i set = tensor i is rotated (K and V of one cache update: 1 — K rotated, V quantized only).
+ * rot_size: a power of two (anything else: CT_ERR_INVALID_ARG, the reference's ValueError).  CT_ERR_UNSUPPORTED outside
+ * 2 <= rot_size <= 512, for a rotated tensor whose D is not a multiple of rot_size, for D % 8 != 0 or D / 8 > 256 (a row is one
+ * pass of one 8-element unit per lane) and for tensors outside ct_attn_qdq's vector form (bases and strides that keep the units
+ * aligned on both sides).  Allocates nothing, never synchronises, keeps no device state. */
+int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_size, int rot_mask, int mode, int kind, int bits, int xdt, int sdt,
+                    int zdt, int tdt, int odt, ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the

@@ -1,6 +1,6 @@
 """developer script: the strided q / k / v QDQ (csrc/ct_attn.hip) against what it replaces, and its pair form against two launches.
 
-    python tools/attn_bench.py [--iters 20] [--repeats 5] [--runs 2] [--out DIR]   (writes DIR/attn_bench.jsonl; DIR defaults to profiles/)
+    python tools/attn_bench.py [--rotated] [--iters 20] [--repeats 5] [--runs 2] [--out DIR]   (writes DIR/attn_bench.jsonl; DIR defaults to profiles/)
 
 Rows, all bfloat16, FP8, static scales:
   * prefill q   (1, 32, 8192, 128) as the (B, S, H, D).transpose(1, 2) view a Llama passes: one tensor;
@@ -18,7 +18,15 @@ Protocol (as tools/rotated_bench.py): HBM-cold — the inputs rotat
 path warmed up, device events around --iters calls, --repeats regions, median and min; the whole table --runs times.  Rates are over the
 algorithmic bytes (one read plus one write of every tensor) as fractions of the 8 TB/s peak.  One JSON line per row and run, then one
 "verdict" line per k+v row: the pair form is faster when its worst median is below the two launches' best by more than the spread
-between the runs.  The last line says what modeling.kvcache.PAIR_MEASURED_FASTER may hold: True only if every k+v row says so."""
+between the runs.  The last line says what modeling.kvcache.PAIR_MEASURED_FASTER may hold: True only if every k+v row says so.
+With --rotated: the head-dim Hadamard rotation in the QDQ's launch (csrc/ct_attn_rot.hip, codec.attn_rotated_*) against the path it
+replaces.  Rows, all bfloat16, FP8, attn_head, n = 128, `(B, S, H, D).transpose(1, 2)` views: q (1, 32, 8192, 128) — one tensor, key
+"single" —, k+v (1, 8, 8192, 128) and decode k+v (64, 8, 1, 128) — K rotated, V not, key "pair".  Paths, alternated on the same buffers:
+  "fused"     codec.attn_rotated_fake_quantize{,_pair}(fused=True): one launch;
+  "composed"  the three steps it replaces: `.contiguous()`, codec.hadamard_transform, codec.attn_fake_quantize{,_pair}.
+The same protocol; results are APPENDED to DIR/attn_rot_bench.jsonl: one line per row and run, one "verdict" line per row — "faster"
+only if the worst fused median plus the spread between the runs is below the best composed median — and a last line that says what
+modeling.ROTATED_MEASURED_FASTER may hold: a key may be True only if every row that speaks for it says "faster"."""
 import argparse
 import json
 import math
@@ -77,13 +85,77 @@ def reference_fake_quantize():
     return lambda x, scale: fake_quantize(x=x, scale=scale, zero_point=None, args=args)
 
 
+ROTATED_ROWS = [  # (name, logical (B, H, S, D), tensors per call, the key of modeling.ROTATED_MEASURED_FASTER it speaks for)
+    ("rot_prefill_q", (1, 32, 8192, 128), 1, "single"),
+    ("rot_prefill_kv", (1, 8, 8192, 128), 2, "pair"),
+    ("rot_decode_kv", (64, 8, 1, 128), 2, "pair"),
+]
+ROTATED_SIZE = 128
+
+
+def rotated_main(a):
+    dev = torch.device("cuda:0")
+    kw = dict(num_bits=8, qtype="float", strategy="attn_head")
+    n = ROTATED_SIZE
+    lines = []
+    for run in range(a.runs):
+        for name, shape, count, key in ROTATED_ROWS:
+            H = shape[1]
+            nbytes = math.prod(shape) * 2 * count
+            sets = [tuple(make(shape, True, dev) for _ in range(count)) for _ in range(max(2, -(-COLD_BYTES // nbytes)))]
+            head = ((torch.arange(H, dtype=torch.float32, device=dev) + 3.0) / 448.0).to(torch.bfloat16).reshape(H, 1, 1)
+            if count == 1:
+                fns = {"fused": lambda ts: codec.attn_rotated_fake_quantize(ts[0], n, head, None, fused=True, **kw),
+                       "composed": lambda ts: codec.attn_fake_quantize(codec.hadamard_transform(ts[0].contiguous(), n), head, None, **kw)}
+            else:
+                fns = {"fused": lambda ts: codec.attn_rotated_fake_quantize_pair(ts[0], ts[1], n, head, head, fused=True, **kw),
+                       "composed": lambda ts: codec.attn_fake_quantize_pair(codec.hadamard_transform(ts[0].contiguous(), n), ts[1], head, head, **kw)}
+            for fn in fns.values():
+                fn(sets[0])
+            torch.cuda.synchronize()
+            samples = {k: [] for k in fns}
+            for rep in range(a.repeats):  # alternated
+                for k, fn in fns.items():
+                    samples[k].append(region(fn, sets, a.iters, start_at=rep))
+            row = {"run": run, "row": name, "key": key, "shape": list(shape), "rotation": n, "transposed_view": True, "tensors": count,
+                   "MB": round(nbytes / 1e6, 2), "buffer_sets": len(sets)}
+            for k, s in samples.items():
+                med = statistics.median(s)
+                row[f"{k}_median_us"], row[f"{k}_min_us"] = round(med * 1e3, 2), round(min(s) * 1e3, 2)
+                row[f"{k}_of_peak"] = round(2 * nbytes / (med * 1e-3) / HBM_PEAK, 4)
+            del sets, fns
+            torch.cuda.empty_cache()
+            print(json.dumps(row), flush=True)
+            lines.append(row)
+    may = {}
+    for name, _, _, key in ROTATED_ROWS:
+        rs = [r for r in lines if r.get("row") == name]
+        p, b = [r["fused_median_us"] for r in rs], [r["composed_median_us"] for r in rs]
+        spread = max(max(p) - min(p), max(b) - min(b)) if len(rs) > 1 else float("nan")
+        v = {"verdict": name, "key": key, "path": "fused", "baseline": "composed", "path_worst_us": max(p), "baseline_best_us": min(b),
+             "run_spread_us": round(spread, 2), "faster": len(rs) > 1 and max(p) + spread < min(b)}
+        print(json.dumps(v), flush=True)
+        lines.append(v)
+        may[key] = may.get(key, True) and v["faster"]
+    lines.append({"ROTATED_MEASURED_FASTER_may_be": may})
+    print(json.dumps(lines[-1]), flush=True)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "attn_rot_bench.jsonl"), "a") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"), help="directory of attn_bench.jsonl")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"), help="directory of attn_bench.jsonl / attn_rot_bench.jsonl")
+    ap.add_argument("--rotated", action="store_true", help="the rotated rows (fused rotation + QDQ against the three steps it replaces)")
     a = ap.parse_args()
+    if a.rotated:
+        return rotated_main(a)
     dev = torch.device("cuda:0")
     ref_fq = reference_fake_quantize()
     kw = dict(num_bits=8, qtype="float")
