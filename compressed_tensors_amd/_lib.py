@@ -64,6 +64,8 @@ _PROTOTYPES = {
     "ct_quant_pack": (_Q + [_I, _I, _P, _S], _I),
     "ct_rtn_quant_channel8": ([_P, _I, _L, _L, _I, _I, _P, _P, _P, _S], _I),
     "ct_rtn_quant_pack_w4": ([_P, _I, _L, _L, _L, _I, _P, _P, _P, _S], _I),
+    "ct_rtn_w4_batch_plan": ([_P, _I], _L),
+    "ct_rtn_quant_pack_w4_batch": ([_P, _I, _L, _I, _I, _S], _I),
     "ct_unpack_dequant": ([_P, _L, _L, _L, _I, _P, _I, _P, _I, _L, _L, _L, _P, _P, _I, _S], _I),
     "ct_quant_pack_w4_zp": ([_P, _I, _P, _P, _L, _L, _L, _P, _P, _S], _I),
     "ct_unpack_dequant_w4_zp": ([_P, _P, _I, _P, _L, _L, _L, _P, _P, _S], _I),
@@ -88,6 +90,8 @@ _PROTOTYPES = {
     "ct_mx_scale_batch": ([_P, _I, _L, _I, _I, _P, _S], _I),
     "ct_mx_scale_decompress": ([_P, _L, _P, _S], _I),
     "ct_rtn_mxfp4_quant_pack": ([_P, _I, _L, _L, _P, _P, _P, _S], _I),
+    "ct_rtn_mxfp4_batch_plan": ([_P, _I], _L),
+    "ct_rtn_mxfp4_quant_pack_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_rtn_nvfp4_quant_pack": ([_P, _I, _L, _L, _P, _P, _P, _P, _S], _I),
     "ct_fp4_cast": ([_P, _I, _P, _L, _S], _I),
     "ct_fp4_pack": ([_P, _I, _P, _L, _S], _I),

@@ -40,6 +40,10 @@ __all__ = [
     "rtn_mxfp4_quantize_and_pack",
     "rtn_quantize_channel8",
     "rtn_nvfp4_quantize_and_pack",
+    "rtn_quantize_and_pack_many",
+    "rtn_mxfp4_quantize_and_pack_many",
+    "launch_rtn_w4_words",
+    "launch_rtn_mxfp4_words",
     "pack_bitmasks",
     "unpack_bitmasks",
     "W4Batch",
@@ -1587,6 +1591,124 @@ def unpack_and_dequantize_many(items, *, num_bits, strategy, group_size=None):
         batch.table.record_stream(torch.cuda.current_stream(batch.device))
         for i, e in zip(where, entries):
             out[i] = e[3]
+    return out
+
+
+def launch_rtn_w4_words(words, n: int, dtype: torch.dtype, device: torch.device, symmetric: bool) -> torch.Tensor:
+    """`launch_w4_words` for a table of the one-pass round-to-nearest W4 compress (`ct_rtn_quant_pack_w4_batch`): src = weights, dst = packed words,
+    scale / zp = OUTPUTS, zp_packed = 0.  `words`: a flat CPU int64 tensor or an `array.array("q")` of `struct ct_w4_item` words, planned in place.
+    Returns the device table (the caller owes it a `record_stream` when its stream is not the allocator's) or None for an empty table."""
+    if not n:
+        return None
+    addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
+    blocks = int(_lib.load().ct_rtn_w4_batch_plan(addr, n))
+    if blocks < 0:
+        raise ValueError(_lib.last_error())
+    table = _upload_table(words, device)
+    call("ct_rtn_quant_pack_w4_batch", table.data_ptr(), n, blocks, DT[dtype], int(bool(symmetric)), _lib.stream_on(device))
+    return table
+
+
+def launch_rtn_mxfp4_words(words, n: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass MXFP4 compress (`ct_rtn_mxfp4_quant_pack_batch`): src = weights, dst = packed bytes,
+    zp_packed = the E8M0 code output, scale = the float-scale output or 0, group = 32"""
+    if not n:
+        return None
+    addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
+    blocks = int(_lib.load().ct_rtn_mxfp4_batch_plan(addr, n))
+    if blocks < 0:
+        raise ValueError(_lib.last_error())
+    table = _upload_table(words, device)
+    call("ct_rtn_mxfp4_quant_pack_batch", table.data_ptr(), n, blocks, DT[dtype], _lib.stream_on(device))
+    return table
+
+
+def rtn_w4_group(shape, group_size) -> int:
+    """the group (elements per scale) when `ct_rtn_quant_pack_w4` and its table form take a weight of this shape — 2-D, rows > 0, a group of
+    32 * 2^k <= 2048 columns that divides the row (group_size None / 0: the whole row) — else 0"""
+    if len(shape) != 2 or int(shape[0]) <= 0 or int(shape[1]) <= 0:
+        return 0
+    cols = int(shape[1])
+    g = int(group_size) if group_size else cols
+    if g <= 0 or cols % g or g % 32 or g > 2048 or (g // 32) & (g // 32 - 1):
+        return 0
+    return g
+
+
+def _rtn_table_tensor(x) -> bool:
+    return x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and x.data_ptr() % 16 == 0
+
+
+def _rtn_w4_one(x, group_size, symmetric):
+    """one tensor outside the table: the one-pass kernel where it applies, the observer + compress composition otherwise"""
+    if x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and rtn_w4_group((1, x.shape[1]), group_size):
+        return rtn_quantize_and_pack(x, group_size=group_size, symmetric=symmetric)
+    scale, zp = minmax_qparams(x, num_bits=4, group_size=group_size, symmetric=symmetric)
+    packed = quantize_and_pack(x, scale, zp, num_bits=4, strategy="group" if group_size else "channel", group_size=group_size)
+    return packed, scale, zp
+
+
+def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True):
+    """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (on one GPU, 2-D, contiguous, 16-byte aligned, 16-bit, of the first
+    such tensor's device and dtype, with a group the one-pass kernel takes) leave in ONE `ct_rtn_quant_pack_w4_batch` launch — a checkpoint is a few hundred
+    launch-bound tensors — and the others one by one (the one-pass kernel, or `minmax_qparams` + `quantize_and_pack` where that does not apply).
+    `group_size`: one value for all, or one per weight (None = one group per row).  Returns [(packed, scale, zero_point)] in input order,
+    bit-identical to the single-tensor call per item (quantization/utils/helpers.py:50-137 + compressors/pack_quantized/base.py:96-104)."""
+    import array
+
+    weights = list(weights)
+    groups = list(group_size) if isinstance(group_size, (list, tuple)) else [group_size] * len(weights)
+    if len(groups) != len(weights):
+        raise ValueError(f"{len(groups)} group sizes for {len(weights)} weights")
+    out = [None] * len(weights)
+    entries, where, flat = [], [], []
+    for i, (x, gs) in enumerate(zip(weights, groups)):
+        g = rtn_w4_group(x.shape, gs) if _rtn_table_tensor(x) else 0
+        if g and (not entries or (x.device == entries[0][0].device and x.dtype == entries[0][0].dtype)):
+            rows, cols = int(x.shape[0]), int(x.shape[1])
+            packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=x.device)
+            scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
+            zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device)
+            entries.append((x, packed, scale, zp))  # the table holds raw pointers: this list keeps the tensors alive
+            flat += (x.data_ptr(), scale.data_ptr(), zp.data_ptr(), packed.data_ptr(), rows, cols, g, 0, 0, 0, 0, *_ITEM_TAIL)
+            where.append(i)
+        else:
+            out[i] = _rtn_w4_one(x, gs, symmetric)
+    if entries:
+        dev = entries[0][0].device
+        table = launch_rtn_w4_words(array.array("q", flat), len(entries), entries[0][0].dtype, dev, symmetric)
+        table.record_stream(torch.cuda.current_stream(dev))
+        for i, e in zip(where, entries):
+            out[i] = e[1:]
+    return out
+
+
+def rtn_mxfp4_quantize_and_pack_many(weights):
+    """`rtn_mxfp4_quantize_and_pack` for a LIST of weights: the tensors the table takes (on one GPU, 2-D, contiguous, 16-byte aligned, 16-bit, of the
+    first such tensor's device and dtype, cols % 32 == 0) leave in ONE `ct_rtn_mxfp4_quant_pack_batch` launch, the others one by one.  Returns
+    [(packed uint8 (R, C / 2), E8M0 codes uint8 (R, C / 32))] in input order, bit-identical to the single-tensor call per item."""
+    import array
+
+    weights = list(weights)
+    out = [None] * len(weights)
+    entries, where, flat = [], [], []
+    for i, x in enumerate(weights):
+        if (_rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0
+                and (not entries or (x.device == entries[0][0].device and x.dtype == entries[0][0].dtype))):
+            rows, cols = int(x.shape[0]), int(x.shape[1])
+            packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+            code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+            entries.append((x, packed, code))
+            flat += (x.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, 0, 0, 0, code.data_ptr(), *_ITEM_TAIL)
+            where.append(i)
+        else:
+            out[i] = rtn_mxfp4_quantize_and_pack(x)
+    if entries:
+        dev = entries[0][0].device
+        table = launch_rtn_mxfp4_words(array.array("q", flat), len(entries), entries[0][0].dtype, dev)
+        table.record_stream(torch.cuda.current_stream(dev))
+        for i, e in zip(where, entries):
+            out[i] = e[1:]
     return out
 
 

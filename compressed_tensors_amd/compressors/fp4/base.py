@@ -13,7 +13,7 @@ from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
 from ...quantization.quant_args import QuantizationStatus
 from ...utils.module import direct_entry, swap_direct_entries
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, symmetric_zp_keys
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, symmetric_zp_keys
 
 __all__ = ["NVFP4PackedCompressor", "MXFP4PackedCompressor"]
 
@@ -242,6 +242,40 @@ class MXFP4PackedCompressor(NVFP4PackedCompressor):
             return {"weight_packed": packed, "weight_scale": code.to(getattr(scheme.weights, "scale_dtype", None) or torch.uint8)}
         scale = codec.minmax_qparams_float(weight, kind="mxfp4", group_size=32)
         return cls.compress({"weight": weight, "weight_scale": scale}, scheme)
+
+    @classmethod
+    def compress_rtn_modules(cls, modules) -> None:
+        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`): the ones with a 16-bit weight on a GPU (cols % 32 ==
+        0, E8M0 codes stored as uint8) leave in ONE table launch per (device, dtype) (codec.launch_rtn_mxfp4_words) and the parameter dictionaries are
+        rewritten under the kernel.  Every module ends in exactly the state `compress_rtn_module` leaves it in; the others go through that, from
+        this call."""
+        import array
+
+        tail = (0,) * (codec._ITEM_WORDS - 11)
+        for window in rtn_windows(modules):
+            tables, rest = {}, []
+            for m in window:
+                w = direct_entry(m, "weight")
+                ok = (w is not None and codec._rtn_table_tensor(w) and w.shape[0] > 0 and w.shape[1] > 0 and w.shape[1] % 32 == 0
+                      and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.uint8) is torch.uint8)
+                if not ok:
+                    rest.append(m)
+                    continue
+                rows, cols = int(w.shape[0]), int(w.shape[1])
+                packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=w.device)
+                code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=w.device)
+                flat, jobs = tables.setdefault((w.device, w.dtype), ([], []))
+                flat += (w.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, 0, 0, 0, code.data_ptr(), *tail)
+                jobs.append((m, w, packed, code))  # the table holds raw pointers: the jobs keep the tensors alive
+            for (device, dtype), (flat, jobs) in tables.items():
+                table = codec.launch_rtn_mxfp4_words(array.array("q", flat), len(jobs), dtype, device)
+                table.record_stream(torch.cuda.current_stream(device))
+            for flat, jobs in tables.values():  # from here on the host works under the kernel
+                for m, w, packed, code in jobs:
+                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
+                    swap_direct_entries(m, remove, {"weight_packed": packed, "weight_scale": code}, status=QuantizationStatus.COMPRESSED)
+            for m in rest:
+                cls.compress_rtn_module(m)
 
     @classmethod
     def _compress_scale(cls, scale: torch.Tensor, weights) -> torch.Tensor:

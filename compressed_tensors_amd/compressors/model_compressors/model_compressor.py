@@ -125,13 +125,15 @@ class ModelCompressor:
         self._finish_compress(model, recouple)
         return mine
 
-    def compress_model_rtn(self, model: torch.nn.Module, recouple: bool = True):
+    def compress_model_rtn(self, model: torch.nn.Module, recouple: bool = True, batched: bool = True):
         """Data-free (round-to-nearest) compression of a model whose modules carry a `quantization_scheme` but no scales yet:
         for every quantized module the min-max observer, calculate_qparams and the codec run fused — one pass over each
         weight where the scheme allows it (int4 group / channel, MXFP4, NVFP4, channel-wise int8 / float8; see the codecs'
         `compress_rtn`).  Bias and other parameters are kept.  Under torch.distributed the modules are sharded over the
         ranks exactly like `compress_model`.  No upstream counterpart: upstream separates calibration (observers,
-        llm-compressor) from `compress_model`; the result equals that two-step flow with min-max observers."""
+        llm-compressor) from `compress_model`; the result equals that two-step flow with min-max observers.
+        `batched` (default): the modules are grouped by codec, and a codec with a `compress_rtn_modules` (pack-quantized, MXFP4) turns its group into
+        one table launch per window of 32 modules; the others (NVFP4, the 8-bit codecs) run per module.  `batched=False`: one launch per module throughout — same result."""
         from ...utils.module import direct_entry, swap_direct_entries
         from ..base import BaseCompressor
         from ..format import infer_module_format
@@ -140,7 +142,7 @@ class ModelCompressor:
             # the format resolution and its write-back to the scheme happen once per (scheme object, module type), and the parameter dictionary is
             # rewritten as a delta (every `weight*` entry goes, the codec's entries come) — what get_direct_state_dict / replace_direct_state_dict did
             # per module at 28-45 us of host time beside one 2-30 us kernel (round 6)
-            resolved = {}
+            resolved, groups = {}, {}
             for module in modules:
                 scheme = module.quantization_scheme
                 key = (id(scheme), type(module))
@@ -156,10 +158,20 @@ class ModelCompressor:
                     except Exception:
                         scheme.format = fmt.value
                     resolved[key] = comp
+                if batched:
+                    groups.setdefault(comp, []).append(module)
+                    continue
                 weight = direct_entry(module, "weight")
                 new = comp.compress_rtn(weight.data, scheme)
                 remove = [k for k in (*module._parameters, *module._buffers) if k.startswith("weight")]
                 swap_direct_entries(module, remove, new, status=QuantizationStatus.COMPRESSED)
+            for comp, group in groups.items():  # in module order within a codec
+                many = getattr(comp, "compress_rtn_modules", None)
+                if many is not None:
+                    many(group)
+                else:
+                    for module in group:
+                        comp.compress_rtn_module(module)
 
         mine = self._parallel(model, apply, recouple, skip_compressed=True)
         self._finish_compress(model, recouple)

@@ -276,6 +276,61 @@ class PackedQuantizationCompressor(BaseCompressor):
             out["weight_zero_point"] = codec.pack_to_int32(zp, weights.num_bits, packed_dim=0)
         return out
 
+    @classmethod
+    def compress_rtn_modules(cls, modules) -> None:
+        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`): the int4 group / channel modules of a window with a
+        16-bit weight on a GPU leave in ONE table launch per (device, dtype, symmetric) (codec.launch_rtn_w4_words), the stored zero points of the
+        asymmetric ones in one `zp4_batch(..., "pack")` behind it, and the parameter dictionaries are rewritten under the kernels.  Every module ends
+        in exactly the state `compress_rtn_module` leaves it in; the modules the table does not take go through that, from this call."""
+        import array
+
+        from ...quantization.quant_args import QuantizationStatus
+        from ...utils.module import direct_entry, swap_direct_entries
+        from ..base import rtn_windows
+
+        schemes = {}
+        tail = (0,) * (codec._ITEM_WORDS - 11)
+        for window in rtn_windows(modules):
+            tables, rest = {}, []
+            for m in window:
+                scheme = m.quantization_scheme
+                info = schemes.get(id(scheme), 0)
+                if info == 0:  # (group or None for channel, symmetric) | None: what only depends on the scheme
+                    wa = scheme.weights
+                    st = enum_value(wa.strategy)
+                    info = None
+                    if int(wa.num_bits) == 4 and enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel"):
+                        info = (getattr(wa, "group_size", None) if st == "group" else None, bool(wa.symmetric))
+                    schemes[id(scheme)] = info
+                w = direct_entry(m, "weight")
+                g = codec.rtn_w4_group(w.shape, info[0]) if info is not None and w is not None and codec._rtn_table_tensor(w) else 0
+                if not g:
+                    rest.append(m)
+                    continue
+                rows, cols = int(w.shape[0]), int(w.shape[1])
+                packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=w.device)
+                scale = torch.empty((rows, cols // g), dtype=w.dtype, device=w.device)
+                # (a symmetric table needs no zero-point output: the kernel skips the store)
+                zp = None if info[1] else torch.empty((rows, cols // g), dtype=torch.int8, device=w.device)
+                zpp = None if info[1] else torch.empty((math.ceil(rows * 4 / 32), cols // g), dtype=torch.int32, device=w.device)
+                flat, jobs = tables.setdefault((w.device, w.dtype, info[1]), ([], []))
+                flat += (w.data_ptr(), scale.data_ptr(), 0 if zp is None else zp.data_ptr(), packed.data_ptr(), rows, cols, g, 0, 0, 0, 0, *tail)
+                jobs.append((m, w, packed, scale, zp, zpp))  # the table holds raw pointers: the jobs keep the tensors alive
+            for (device, dtype, symmetric), (flat, jobs) in tables.items():
+                table = codec.launch_rtn_w4_words(array.array("q", flat), len(jobs), dtype, device, symmetric)
+                table.record_stream(torch.cuda.current_stream(device))
+                if not symmetric:  # pack_to_int32(zp, 4, packed_dim=0) of every module, behind the launch that computes the zero points
+                    codec.zp4_batch([(j[4], j[5]) for j in jobs], "pack")
+            for flat, jobs in tables.values():  # from here on the host works under the kernels
+                for m, w, packed, scale, zp, zpp in jobs:
+                    add = {"weight_packed": packed, "weight_scale": scale, "weight_shape": torch.tensor(w.shape)}
+                    if zpp is not None:
+                        add["weight_zero_point"] = zpp
+                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
+                    swap_direct_entries(m, remove, add, status=QuantizationStatus.COMPRESSED)
+            for m in rest:
+                cls.compress_rtn_module(m)
+
     # ------------------------------------------------------------------ batched module paths
     @classmethod
     def compress_modules(cls, modules) -> None:

@@ -275,10 +275,8 @@ __global__ __launch_bounds__(kBlock) void fp4_quant_pack_batch_kernel(const ct_w
 // exponent byte.  2 + 0.5 + 1/32 B per element instead of (2 + 2/32) + (2 + 0.5 + 2/32); bit-identical to
 // ct_minmax_qparams_float(kind 3) + ct_fp4_quant_pack + compress_mx_scale by construction (same helpers).
 template <int XDT>
-__global__ __launch_bounds__(kBlock) void rtn_mxfp4_kernel(const u32x4* __restrict__ in, int64_t lanes, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0,
-                                                           void* __restrict__ scale_out) {
-    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (l >= lanes) return;
+__device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0, void* __restrict__ scale_out,
+                                               int64_t l) {
     u32x4 r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = in[l * 4 + i];
@@ -298,6 +296,24 @@ __global__ __launch_bounds__(kBlock) void rtn_mxfp4_kernel(const u32x4* __restri
         w[i] = fp4_quant_unit<XDT, false>(ws, s, 1.0f, true);
     }
     stream_store16(out + l, u32x4{w[0], w[1], w[2], w[3]});
+}
+
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void rtn_mxfp4_kernel(const u32x4* __restrict__ in, int64_t lanes, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0,
+                                                           void* __restrict__ scale_out) {
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (l >= lanes) return;
+    rtn_mxfp4_lane<XDT>(in, out, e8m0, scale_out, l);
+}
+
+// the same lane over a table (ct_rtn_mxfp4_quant_pack_batch): dst = the packed bytes, zp_packed = the E8M0 codes (the role the field plays in
+// fp4_quant_pack_batch_kernel), scale = the optional float-scale output.  A lane owns its group: nothing crosses lanes, a dead lane just leaves.
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void rtn_mxfp4_batch_kernel(const ct_w4_item* __restrict__ items, int n) {
+    const ct_w4_item& it = fp4_batch_find(items, n, blockIdx.x);
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    if (l >= (it.units >> 2)) return;
+    rtn_mxfp4_lane<XDT>(static_cast<const u32x4*>(it.src), static_cast<u32x4*>(it.dst), static_cast<uint8_t*>(it.zp_packed), const_cast<void*>(it.scale), l);
 }
 
 // The NVFP4 counterpart: a lane owns two groups of 16; the global scale (generate_gparam: a tensor-wide amax, i.e. one
@@ -908,6 +924,48 @@ int ct_rtn_mxfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, 
     else hipLaunchKernelGGL((rtn_mxfp4_kernel<CT_F16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes,
                             reinterpret_cast<u32x4*>(packed), scale_e8m0, scale_out);
     CT_LAUNCH_CHECK("ct_rtn_mxfp4_quant_pack");
+}
+
+int64_t ct_rtn_mxfp4_batch_plan(ct_w4_item* items, int n) {
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_mxfp4_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        ct_w4_item& it = items[i];
+        // the conditions of ct_rtn_mxfp4_quant_pack, per item
+        const bool ok = it.rows > 0 && it.cols > 0 && it.group == 32 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && aligned16(it.src) && aligned16(it.dst) &&
+                        (reinterpret_cast<uintptr_t>(it.scale) & 1u) == 0;
+        if (!ok) {
+            set_error("ct_rtn_mxfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass MXFP4 compress "
+                      "(needs group 32, cols %% 32 == 0, 16-byte aligned src / dst, the E8M0 output in zp_packed)", i, (long long)it.rows, (long long)it.cols,
+                      (long long)it.group);
+            return -1;
+        }
+        it.units = it.rows * (it.cols / 8);
+        it.upg = 4;
+        it.upg_shift = 2;
+        it.first_block = blocks;
+        it.main_blocks = cdiv64(it.units / 4, kBlock);
+        it.g_magic = 0;
+        it.g_shift = 0;
+        blocks += it.main_blocks;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_mxfp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_mxfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass MXFP4 compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    else hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_LAUNCH_CHECK("ct_rtn_mxfp4_quant_pack_batch");
 }
 
 int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, const float* global_scale, uint8_t* packed, uint8_t* scale_f8,

@@ -671,12 +671,15 @@ __global__ __launch_bounds__(kBlock) void w4_quant_pack_lean_kernel(const u32x4*
 // traffic for 8192^2 g128, one launch instead of two.  Results are bit-identical to ct_minmax_qparams followed by
 // ct_quant_pack by construction (same helpers), and tested against that composition.
 // ------------------------------------------------------------------------------------------
+// the body on lane `l` of ONE tensor: shared by the single-tensor kernel and the table kernel (rtn_w4_batch_kernel), whose workgroups start
+// at their item's own first block — so `threadIdx.x & (lpg - 1)` is the lane's position in its group in both.  Every lane of the workgroup
+// enters (the DPP reduction reads its neighbours): `live` guards the memory accesses, and the return comes after the reduction.
+// zp_out == NULL (a symmetric table may leave it out): the zero-point store is skipped.
 template <int DT, bool SYM>
-__global__ __launch_bounds__(kBlock) void rtn_w4_kernel(const u32x4* __restrict__ in, int64_t lanes, int lpg, u32x4* __restrict__ out,
-                                                        void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
+__device__ __forceinline__ void rtn_w4_lane(const u32x4* __restrict__ in, int64_t lanes, int lpg, u32x4* __restrict__ out,
+                                            void* __restrict__ scale_out, int8_t* __restrict__ zp_out, int64_t l) {
     constexpr int symmetric = SYM ? 1 : 0;
-    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // lanes is a multiple of lpg, kBlock too: groups never straddle blocks
-    const bool live = l < lanes;
+    const bool live = l < lanes;  // lanes is a multiple of lpg, kBlock too: groups never straddle blocks
     u32x4 r[4];
     MinMax m;
     m.mn = __builtin_inff(); m.mx = -__builtin_inff(); m.nan = 0;
@@ -707,7 +710,7 @@ __global__ __launch_bounds__(kBlock) void rtn_w4_kernel(const u32x4* __restrict_
     compute_qparams<DT>(m, 4, symmetric, s, z);
     if ((threadIdx.x & (lpg - 1)) == 0) {
         store1<DT>(scale_out, l / lpg, s);
-        zp_out[l / lpg] = (int8_t)(int)z;
+        if (zp_out) zp_out[l / lpg] = (int8_t)(int)z;
     }
     const bool fast = fast_scale_ok<DT>(s) && fast_data_ok<DT, 4>(r);
     const float rs = 1.0f / s;
@@ -731,6 +734,12 @@ __global__ __launch_bounds__(kBlock) void rtn_w4_kernel(const u32x4* __restrict_
         }
     }
     stream_store16(out + l, u32x4{w[0], w[1], w[2], w[3]});
+}
+
+template <int DT, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_w4_kernel(const u32x4* __restrict__ in, int64_t lanes, int lpg, u32x4* __restrict__ out,
+                                                        void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
+    rtn_w4_lane<DT, SYM>(in, lanes, lpg, out, scale_out, zp_out, (int64_t)blockIdx.x * kBlock + threadIdx.x);
 }
 
 // value of lane 0 of each 16-lane row in every lane of the row (DPP row_newbcast:0)
@@ -866,6 +875,18 @@ __device__ __forceinline__ const ct_w4_item& batch_find(const ct_w4_item* __rest
         if (items[mid].first_block <= block) lo = mid; else hi = mid - 1;
     }
     return items[lo];
+}
+
+// the one-pass round-to-nearest compress (rtn_w4_lane) over a table: `scale` and `zp` of the item are OUTPUTS here, `dst` the packed words.
+// ct_rtn_w4_batch_plan admits groups of 32 * 2^k <= 2048 elements only, so lanes per group = 1 << (upg_shift - 2) is a power of two <= 64 that
+// divides kBlock, and gives every item whole workgroups from its own `first_block`: a group never straddles a workgroup, and the lanes behind
+// an item's last one (a partial last workgroup in front of the next item) stay in the reduction as dead lanes.
+template <int DT, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_w4_batch_kernel(const ct_w4_item* __restrict__ items, int n) {
+    const ct_w4_item& it = batch_find(items, n, blockIdx.x);
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    rtn_w4_lane<DT, SYM>(static_cast<const u32x4*>(it.src), it.units >> 2, 1 << (it.upg_shift - 2), static_cast<u32x4*>(it.dst), const_cast<void*>(it.scale),
+                         static_cast<int8_t*>(const_cast<void*>(it.zp)), l);
 }
 
 // groups per row of an item (a shift for the power-of-two group sizes; the division runs for the others only)
@@ -2312,6 +2333,55 @@ int ct_unpack_dequant_batch(const ct_w4_item* items_dev, int n, int64_t total_bl
     if (dt == CT_BF16) hipLaunchKernelGGL((w4_unpack_dequant_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, stride);
     else hipLaunchKernelGGL((w4_unpack_dequant_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, stride);
     CT_LAUNCH_CHECK("ct_unpack_dequant_batch");
+}
+
+int64_t ct_rtn_w4_batch_plan(ct_w4_item* items, int n) {
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_w4_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        ct_w4_item& it = items[i];
+        const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
+        // the conditions of ct_rtn_quant_pack_w4, per item
+        const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
+                        aligned16(it.src) && aligned16(it.dst);
+        if (!ok) {
+            set_error("ct_rtn_w4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W4 compress "
+                      "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, 16-byte aligned src / dst, the scale output)", i, (long long)it.rows,
+                      (long long)it.cols, (long long)it.group);
+            return -1;
+        }
+        if (it.zp_packed) {
+            set_error("ct_rtn_w4_batch_plan: item %d gives zp_packed; the stored zero points come from ct_zp4_pack_dim0_batch behind this launch", i);
+            return -1;
+        }
+        it.units = it.rows * (it.cols / 8);
+        it.upg = (int32_t)(g / 8);
+        it.upg_shift = log2_exact(it.upg);
+        it.first_block = blocks;
+        it.main_blocks = cdiv64(it.units / 4, kBlock);
+        it.g_magic = 0;
+        it.g_shift = 0;
+        blocks += it.main_blocks;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_w4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_quant_pack_w4_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int symmetric, ct_stream_t stream) {
+    CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched one-pass W4 compress: 16-bit weights only, got dtype %d", dt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+#define CT_RTN4B(DT, SY) hipLaunchKernelGGL((rtn_w4_batch_kernel<DT, SY>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n)
+    if (dt == CT_BF16) { if (symmetric) CT_RTN4B(CT_BF16, true); else CT_RTN4B(CT_BF16, false); }
+    else { if (symmetric) CT_RTN4B(CT_F16, true); else CT_RTN4B(CT_F16, false); }
+#undef CT_RTN4B
+    CT_LAUNCH_CHECK("ct_rtn_quant_pack_w4_batch");
 }
 
 int64_t ct_q8_batch_plan(ct_w4_item* items, int n, int direction) {

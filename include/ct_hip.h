@@ -246,6 +246,19 @@ int ct_unpack_dequant_w4_zp(const int32_t* packed, const void* scale, int sdt, c
 int64_t ct_zp4_batch_plan(ct_w4_item* items_host, int n);
 int ct_zp4_pack_dim0_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int direction, ct_stream_t stream);
 
+/* Batched round-to-nearest W4 compress in one pass: ct_rtn_quant_pack_w4 — the min-max observer + calculate_qparams
+ * (quantization/utils/helpers.py:50-137) and PackedQuantizationCompressor's weight path (compressors/pack_quantized/base.py:96-110) fused —
+ * for a whole table of tensors in one launch: the data-free counterpart of ct_quant_pack_batch.  The table is `struct ct_w4_item` read this way:
+ * src = the weights, dst = packed int32 (rows, cols / 8), scale = OUTPUT (rows, cols / group) in the weights' dtype, zp = OUTPUT int8 of the same
+ * shape (NULL only in a table launched with symmetric != 0: the store is then skipped), group <= 0 or >= cols = one group per row, zp_packed =
+ * NULL.  ct_rtn_w4_batch_plan (host only) admits what ct_rtn_quant_pack_w4 admits, per item — 16-byte aligned src / dst, cols % group == 0,
+ * group = 32 * 2^k <= 2048, the scale output — fills the derived fields and returns the workgroup count, or -1 with the error text set (also
+ * for 2^31 workgroups or more).  The stored zero points of an asymmetric scheme (pack_to_int32(zp, 4, packed_dim=0), base.py:107-110) depend on
+ * zero points that other workgroups of the launch compute: issue ct_zp4_pack_dim0_batch over the asymmetric items behind it on the same stream.
+ * Bit-identical to ct_rtn_quant_pack_w4 per item. */
+int64_t ct_rtn_w4_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_quant_pack_w4_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int symmetric, ct_stream_t stream);
+
 /* Batched 8-bit codecs (Naive / Int / FloatQuantizationCompressor.compress / decompress, compressors/naive_quantized/
  * base.py:48-126, looped per module by model_compressor.py:167-169,196-198): quantize to int8 (num_bits <= 8, clamped to the
  * num_bits range) or float8_e4m3fn, and the inverse, for a whole table of 16-bit tensors in one launch.  Same table type and
@@ -454,6 +467,13 @@ int ct_mx_scale_decompress(const uint8_t* codes, int64_t n, void* scale_bf16_out
  * Bit-identical to ct_minmax_qparams_float(kind 3) + ct_fp4_quant_pack + the E8M0 encoding. */
 int ct_rtn_mxfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, uint8_t* packed,
                             uint8_t* scale_e8m0, void* scale_out, ct_stream_t stream);
+/* The same for a whole table of tensors in one launch (the per-module loop over MXFP4PackedCompressor, compressors/mxfp4/base.py, without a
+ * launch per module).  The table is `struct ct_w4_item` read this way: src = the weights, dst = the packed bytes (rows, cols / 2), zp_packed =
+ * the E8M0 code OUTPUT uint8 (rows, cols / 32) (the role the field plays in ct_fp4_quant_pack_batch), scale = the optional float-scale output
+ * (the weights' dtype) or NULL, group = 32.  ct_rtn_mxfp4_batch_plan (host only) admits what ct_rtn_mxfp4_quant_pack admits, per item, fills the
+ * derived fields and returns the workgroup count, or -1 with the error text set.  Bit-identical to ct_rtn_mxfp4_quant_pack per item. */
+int64_t ct_rtn_mxfp4_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_mxfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
 /* The NVFP4 counterpart (groups of 16 under `global_scale`, device float32[1], e.g. generate_gparam of the weight):
  * scale_f8: float8_e4m3fn bytes (rows, cols/16), the stored form; scale_out (nullable): the float32 scales. cols % 32 == 0. */
 int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, const float* global_scale,

@@ -1,0 +1,127 @@
+"""ModelCompressor.compress_model_rtn wall time, table launches (batched=True) against one launch per module (batched=False, the path before the
+tables existed), alternated in one process on the same trees: a Llama-3-8B-shaped tree (32 layers, 224 modules) and a TinyLlama-shaped one (22
+layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4.  A compress consumes the model, so the dense weights are kept and re-attached
+between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
+their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
+
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import compressed_tensors_amd as cta  # noqa: E402
+
+HBM_PEAK = 8e12  # bytes / s, the figure every table of DESIGN.md is relative to
+TINY = ((2048, 2048), (256, 2048), (256, 2048), (2048, 2048), (5632, 2048), (5632, 2048), (2048, 5632))
+L8B = ((4096, 4096), (1024, 4096), (1024, 4096), (4096, 4096), (14336, 4096), (14336, 4096), (4096, 14336))
+TREES = {"8b": ("llama-8B-shaped", L8B, 32), "tiny": ("tinyllama-shaped", TINY, 22)}
+
+
+def scheme_of(name):
+    if name == "w4":
+        args = cta.QuantizationArgs(num_bits=4, group_size=128, symmetric=True, strategy="group")
+    elif name == "w4asym":
+        args = cta.QuantizationArgs(num_bits=4, group_size=128, symmetric=False, strategy="group")
+    elif name == "mxfp4":
+        args = cta.QuantizationArgs(num_bits=4, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8)
+    else:
+        raise SystemExit(f"unknown scheme {name}")
+    return cta.QuantizationScheme(targets=["Linear"], weights=args)
+
+
+def algorithmic_bytes(name, rows, cols):
+    """what one compress has to move: the weight in, the codes and the scales (and stored zero points) out"""
+    n = rows * cols
+    if name == "mxfp4":
+        return 2 * n + n // 2 + n // 32
+    out = 2 * n + n // 2 + 2 * (n // 128)
+    if name == "w4asym":
+        out += -(-rows // 8) * (cols // 128) * 4  # weight_zero_point, packed along the rows
+    return out
+
+
+def build(shapes, nlayers, dev):
+    """the tree on the meta device plus the pool of dense weights that is re-attached before every compress"""
+    root = torch.nn.Module()
+    root.layers = torch.nn.ModuleList()
+    g = torch.Generator(device=dev).manual_seed(1)
+    pool = []
+    for _ in range(nlayers):
+        blk = torch.nn.Module()
+        root.layers.append(blk)
+        for k, (r, c) in enumerate(shapes):
+            lin = torch.nn.Linear(c, r, bias=False, device="meta")
+            setattr(blk, f"proj{k}", lin)
+            w = torch.randn(r, c, dtype=torch.bfloat16, device=dev, generator=g)
+            pool.append((lin, torch.nn.Parameter(w, requires_grad=False)))
+    return root, pool
+
+
+def attach(model, pool, scheme, mc):
+    mc.remove_decompression_hook(model)
+    for lin, w in pool:
+        lin._parameters.clear()
+        lin._parameters["weight"] = w
+        lin.__dict__.pop("quantization_status", None)
+        lin.quantization_scheme = scheme
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=7, help="alternations of the two paths (the median is reported; at least 5)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--trees", default="8b,tiny")
+    ap.add_argument("--schemes", default="w4,w4asym,mxfp4")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    a = ap.parse_args()
+    if a.reps < 5:
+        raise SystemExit("--reps must be at least 5")
+    if not torch.cuda.is_available():
+        raise SystemExit("rtn_bench.py measures on the GPU: no device is visible")
+    dev = torch.device("cuda:0")
+    for tree in a.trees.split(","):
+        label, shapes, nlayers = TREES[tree]
+        model, pool = build(shapes, nlayers, dev)
+        for name in a.schemes.split(","):
+            scheme = scheme_of(name)
+            mc = cta.ModelCompressor()
+            alg = sum(algorithmic_bytes(name, *w.shape) for _, w in pool)
+            wall, host = {True: [], False: []}, {True: [], False: []}
+            for rep in range(a.warmup + a.reps):
+                for batched in (True, False) if rep % 2 == 0 else (False, True):
+                    attach(model, pool, scheme, mc)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    mc.compress_model_rtn(model, batched=batched)
+                    t1 = time.perf_counter()
+                    torch.cuda.synchronize()
+                    t2 = time.perf_counter()
+                    if rep >= a.warmup:
+                        wall[batched].append(t2 - t0)
+                        host[batched].append(t1 - t0)
+            line = {"tree": label, "modules": len(pool), "scheme": name, "reps": a.reps, "algorithmic_bytes": alg}
+            for batched, key in ((True, "table"), (False, "per_module")):
+                med = statistics.median(wall[batched])
+                line[key] = {"wall_ms_median": round(med * 1e3, 4), "wall_ms_min": round(min(wall[batched]) * 1e3, 4),
+                             "wall_ms_max": round(max(wall[batched]) * 1e3, 4), "host_ms_median": round(statistics.median(host[batched]) * 1e3, 4),
+                             "host_us_per_module": round(statistics.median(host[batched]) * 1e6 / len(pool), 2),
+                             "hbm_peak_fraction": round(alg / med / HBM_PEAK, 4)}
+            line["speedup"] = round(line["per_module"]["wall_ms_median"] / line["table"]["wall_ms_median"], 3)
+            text = json.dumps(line)
+            print(text, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(text + "\n")
+        del model, pool
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
