@@ -6,8 +6,10 @@ Every function mirrors a reference function (cited per function; paths relative 
 tensors are staged through the GPU (H2D, kernel, D2H) so the arithmetic is always the HIP
 path; without a GPU the calls raise.
 """
+import array
 import functools
 import math
+import operator
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -90,6 +92,9 @@ __all__ = [
     "attn_rotated_fake_quantize_pair",
     "ATTN_ROTATED_MEASURED_FASTER",
     "ATTN_ROTATED_MAX_SIZE",
+    "item_row",
+    "rtn_w4_table_item",
+    "rtn_mxfp4_table_item",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -1398,35 +1403,91 @@ def _upload_table(words, dev) -> torch.Tensor:
     return host.to(dev, non_blocking=True)
 
 
-def launch_w4_words(words: torch.Tensor, n: int, direction: str, dtype: torch.dtype, device: torch.device) -> None:
-    """plan, upload and launch a W4 table that already exists as a flat CPU int64 tensor of `struct ct_w4_item` words (built by the
-    C++ host loop, csrc/host/ct_hostpath.cpp) on `device`'s current stream.  The caller keeps the tensors the table points at alive."""
-    if not n:
-        return
-    d = 0 if direction == "compress" else 1
-    blocks = int(_lib.load().ct_w4_batch_plan(words.data_ptr(), n, d))
+# --------------------------------------------------------------------------- table launches
+_ITEM_WORDS = _lib.ITEM_WORDS  # struct ct_w4_item of include/ct_hip.h in 64-bit words: 4 pointers, rows, cols, group, first_block, units,
+#                                {upg_shift, upg}, zp_packed, main_blocks, {g_magic, g_shift}
+# a row is its eight settable fields and a zero, picked into word order; the order comes from the struct itself, so the next field added to
+# ct_w4_item moves words here and nowhere else
+_ITEM_FIELDS = ("src", "scale", "zp", "dst", "rows", "cols", "group", "zp_packed")
+_ITEM_AT = {getattr(_lib.W4Item, name).offset // 8: i for i, name in enumerate(_ITEM_FIELDS)}
+_pick_row = operator.itemgetter(*(_ITEM_AT.get(word, len(_ITEM_FIELDS)) for word in range(_ITEM_WORDS)))
+
+
+def _word(v) -> int:
+    return 0 if v is None else v.data_ptr() if isinstance(v, torch.Tensor) else int(v)
+
+
+def item_row(src=0, scale=0, zp=0, dst=0, rows=0, cols=0, group=0, zp_packed=0) -> tuple:
+    """one row of a host table of `struct ct_w4_item`, as `_ITEM_WORDS` ints.  The pointer arguments are ints, tensors (their `data_ptr()`) or
+    None (0); the derived words (first_block, units, {upg_shift, upg}, main_blocks, {g_magic, g_shift}) are zero: the library's plan fills them.
+    (The module loops build a row per module beside ~10 us of other host work: with ints given by position this is one test and one C call.)"""
+    if not (type(src) is int and type(scale) is int and type(zp) is int and type(dst) is int and type(zp_packed) is int):
+        src, scale, zp, dst, zp_packed = map(_word, (src, scale, zp, dst, zp_packed))
+    return _pick_row((src, scale, zp, dst, rows, cols, group, zp_packed, 0))
+
+
+# table kind -> (plan symbol, the plan takes the direction, launch symbol | (compress, decompress) launch symbols): every table of ct_w4_item rows
+_TABLES = {
+    "w4": ("ct_w4_batch_plan", True, ("ct_quant_pack_batch", "ct_unpack_dequant_batch")),
+    "q8": ("ct_q8_batch_plan", True, ("ct_q8_quant_batch", "ct_q8_dequant_batch")),
+    "fp4": ("ct_fp4_batch_plan", True, ("ct_fp4_quant_pack_batch", "ct_fp4_unpack_dequant_batch")),
+    "mx_scale": ("ct_mx_scale_batch_plan", False, "ct_mx_scale_batch"),
+    "zp4": ("ct_zp4_batch_plan", False, "ct_zp4_pack_dim0_batch"),
+    "rtn_w4": ("ct_rtn_w4_batch_plan", False, "ct_rtn_quant_pack_w4_batch"),
+    "rtn_mxfp4": ("ct_rtn_mxfp4_batch_plan", False, "ct_rtn_mxfp4_quant_pack_batch"),
+}
+_Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
+
+
+def _plan_table(kind: str, words, n: int, device, d: int = 0):
+    """the first half of `_launch_table`: plan `words` in place and upload them -> (device table, workgroups)"""
+    plan, directed, _ = _TABLES[kind]
+    if isinstance(words, list):
+        words = array.array("q", words)
+    addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
+    fn = getattr(_lib.load(), plan)
+    blocks = int(fn(addr, n, d) if directed else fn(addr, n))
     if blocks < 0:
         raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    call("ct_quant_pack_batch" if d == 0 else "ct_unpack_dequant_batch", table.data_ptr(), n, blocks, DT[dtype], _lib.stream_on(device))
+    return _upload_table(words, device), blocks
 
 
-_Q8_KINDS = ("int8", "fp8", "fp8z")
+def _run_table(kind: str, table, n: int, blocks: int, device, d: int, scalars, stream=None) -> None:
+    """the second half: ONE launch of a planned, uploaded table"""
+    symbol = _TABLES[kind][2]
+    call(symbol if isinstance(symbol, str) else symbol[d], table.data_ptr(), n, blocks, *scalars, _lib.stream_on(device, stream))
+
+
+def _launch_table(kind: str, words, n: int, device, d: int = 0, scalars=(), stream=None):
+    """plan, upload and launch one table of `struct ct_w4_item` rows: `words` is `n` rows (`item_row`) as a flat CPU int64 tensor or an
+    `array.array("q")`, planned in place, or as a flat list of ints, copied into one; `d`: 0 compress / pack, 1 decompress / unpack (handed to the
+    plans that take it, and picking the launch of the kinds that have two); `scalars`: the launch's arguments between the workgroup count and the stream; `stream`: a raw hipStream_t of `device` (default:
+    the caller's current stream there).  Returns the device table, or None for an empty one, before touching the library.
+
+    Lifetime, for every entry point built on this: the caller keeps the tensors the rows point at alive.  The device table is allocated and
+    uploaded on the current stream, whatever `stream` is: a caller that launches on another stream orders that stream behind the current one first
+    (`wait_stream`).  One that stays on the current stream may drop the table at once — the `launch_*_words` of the C++ host loops do, and
+    return nothing.  `launch_rtn_w4_words` / `launch_rtn_mxfp4_words` hand the table back and the caller owes it a `record_stream` when its stream
+    is not the allocator's; `zp4_batch` records it itself; `W4Batch` keeps it for as long as the batch lives."""
+    if not n:
+        return None
+    table, blocks = _plan_table(kind, words, n, device, d)
+    _run_table(kind, table, n, blocks, device, d, scalars, stream)
+    return table
+
+
+def launch_w4_words(words: torch.Tensor, n: int, direction: str, dtype: torch.dtype, device: torch.device) -> None:
+    """a W4 table that already exists as a flat CPU int64 tensor of `struct ct_w4_item` words (built by the C++ host loop,
+    csrc/host/ct_hostpath.cpp) in ONE launch (`ct_quant_pack_batch` / `ct_unpack_dequant_batch`) on `device`'s current stream"""
+    if n:
+        _launch_table("w4", words, n, device, 0 if direction == "compress" else 1, (DT[dtype],))
 
 
 def launch_q8_words(words: torch.Tensor, n: int, direction: str, dtype: torch.dtype, device: torch.device, kind: int, bits: int = 8) -> None:
     """`launch_w4_words` for a table of the 8-bit codecs (`ct_q8_quant_batch` / `ct_q8_dequant_batch`); kind 0 int8, 1 fp8, 2 fp8 with float8 zero points"""
-    if not n:
-        return
     d = 0 if direction == "compress" else 1
-    blocks = int(_lib.load().ct_q8_batch_plan(words.data_ptr(), n, d))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    if d == 0:
-        call("ct_q8_quant_batch", table.data_ptr(), n, blocks, DT[dtype], kind, bits, _lib.stream_on(device))
-    else:
-        call("ct_q8_dequant_batch", table.data_ptr(), n, blocks, DT[dtype], kind, _lib.stream_on(device))
+    if n:
+        _launch_table("q8", words, n, device, d, (DT[dtype], kind, bits) if d == 0 else (DT[dtype], kind))
 
 
 def launch_fp4_words(words: torch.Tensor, n: int, direction: str, device: torch.device, group: int, x_dtype=None, scale_dtype=None) -> None:
@@ -1434,47 +1495,28 @@ def launch_fp4_words(words: torch.Tensor, n: int, direction: str, device: torch.
     scale), 32 = MXFP4; compress: the weights' and the float scales' dtype (one per table); decompress writes bfloat16"""
     if not n:
         return
-    d = 0 if direction == "compress" else 1
-    blocks = int(_lib.load().ct_fp4_batch_plan(words.data_ptr(), n, d))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    if d == 0:
+    if direction == "compress":
         lut = _mx_code_table(scale_dtype, device) if group == 32 else None
-        call("ct_fp4_quant_pack_batch", table.data_ptr(), n, blocks, DT[x_dtype], DT[scale_dtype], int(group), ptr(lut), _lib.stream_on(device))
+        _launch_table("fp4", words, n, device, 0, (DT[x_dtype], DT[scale_dtype], int(group), ptr(lut)))
     else:
-        call("ct_fp4_unpack_dequant_batch", table.data_ptr(), n, blocks, int(group), DT[torch.bfloat16], _lib.stream_on(device))
+        _launch_table("fp4", words, n, device, 1, (int(group), DT[torch.bfloat16]))
 
 
 def launch_mx_scale_words(words: torch.Tensor, n: int, direction: str, device: torch.device, scale_dtype=None) -> None:
     """a table of MX scale tensors in ONE launch (`ct_mx_scale_batch`): "compress" 16-bit scales -> E8M0 codes, "decompress" codes -> bfloat16"""
     if not n:
         return
-    blocks = int(_lib.load().ct_mx_scale_batch_plan(words.data_ptr(), n))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
     if direction == "compress":
-        call("ct_mx_scale_batch", table.data_ptr(), n, blocks, 0, DT[scale_dtype], ptr(_mx_code_table(scale_dtype, device)), _lib.stream_on(device))
+        _launch_table("mx_scale", words, n, device, 0, (0, DT[scale_dtype], ptr(_mx_code_table(scale_dtype, device))))
     else:
-        call("ct_mx_scale_batch", table.data_ptr(), n, blocks, 1, -1, None, _lib.stream_on(device))
+        _launch_table("mx_scale", words, n, device, 1, (1, -1, None))
 
 
 def launch_zp4_words(words: torch.Tensor, n: int, direction: str, device: torch.device) -> None:
-    """`zp4_batch` for a table that already exists as a flat CPU int64 tensor (src, 0, 0, dst, unpacked rows, cols, 0 ... per item;
-    built by the C++ host loop): plan, upload, ONE `ct_zp4_pack_dim0_batch` launch on `device`'s current stream"""
-    if not n:
-        return
-    blocks = int(_lib.load().ct_zp4_batch_plan(words.data_ptr(), n))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    call("ct_zp4_pack_dim0_batch", table.data_ptr(), n, blocks, 0 if direction == "pack" else 1, _lib.stream_on(device))
-
-
-_ITEM_WORDS = _lib.ITEM_WORDS  # struct ct_w4_item of include/ct_hip.h in 64-bit words: 4 pointers, rows, cols, group, first_block, units,
-#                                {upg_shift, upg}, zp_packed, main_blocks, {g_magic, g_shift}
-_ITEM_TAIL = (0,) * (_ITEM_WORDS - 11)  # the derived words behind zp_packed
+    """`zp4_batch` for a table that already exists as a flat CPU int64 tensor (src, dst, unpacked rows, cols per item; built by the C++ host
+    loop): ONE `ct_zp4_pack_dim0_batch` launch on `device`'s current stream"""
+    d = 0 if direction == "pack" else 1
+    _launch_table("zp4", words, n, device, d, (d,))
 
 
 def w4_packed_zp_readable(cols: int, group: int) -> bool:
@@ -1494,48 +1536,34 @@ class W4Batch:
     dst / src = packed int32 words); kind "int8" / "fp8": the 8-bit codecs (`ct_q8_quant_batch` / `ct_q8_dequant_batch`, one
     byte per element, `bits` = the INT scheme's num_bits; group may be rows * cols for a per-tensor scale).
 
-    The host table is one flat array of 64-bit words (13 per item, the layout of `struct ct_w4_item`) planned in place by the
-    library and uploaded asynchronously from pinned memory."""
+    The host table is one flat array of 64-bit words (`item_row` per entry, the layout of `struct ct_w4_item`) planned in place by the
+    library and uploaded asynchronously from pinned memory when the batch is built; `launch` may then be called any number of times."""
 
     def __init__(self, entries, direction: str, dtype: torch.dtype, kind: str = "w4", bits: int = 8):
-        assert direction in ("compress", "decompress") and kind in ("w4", "int8", "fp8", "fp8z")  # fp8z: float8 codes with float8 zero points
-        import array
-
+        assert direction in ("compress", "decompress") and (kind == "w4" or kind in _Q8_KINDS)
         self.direction = 0 if direction == "compress" else 1
         self.kind, self.bits = kind, int(bits)
         self.dt = DT[dtype]
         self.keep = entries if isinstance(entries, list) else list(entries)  # the table holds raw pointers: keep the tensors alive
         n = self.n = len(self.keep)
-        flat = []
-        dev = None
-        for e in self.keep:
-            src, scale, zp, dst, rows, cols, group = e[:7]
-            zpp = e[7] if len(e) > 7 else None
-            flat += (src.data_ptr(), scale.data_ptr(), 0 if zp is None else zp.data_ptr(), dst.data_ptr(), rows, cols, group, 0, 0, 0,
-                     0 if zpp is None else zpp.data_ptr(), *_ITEM_TAIL)
         self.blocks, self.table, self.device = 0, None, None
         if n:
-            dev = self.keep[0][0].device
-            words = array.array("q", flat)
-            lib = _lib.load()
-            plan = lib.ct_w4_batch_plan if kind == "w4" else lib.ct_q8_batch_plan
-            self.blocks = int(plan(words.buffer_info()[0], n, self.direction))
-            if self.blocks < 0:
-                raise ValueError(_lib.last_error())
-            self.device = dev
-            self.table = _upload_table(words, dev)
+            flat = []
+            for e in self.keep:
+                flat += item_row(*e)  # an entry is item_row's arguments, in order
+            self.device = self.keep[0][0].device
+            self.table, self.blocks = _plan_table("w4" if kind == "w4" else "q8", flat, n, self.device, self.direction)
 
     def launch(self, stream=None):
         """`stream`: a raw hipStream_t of self.device (default: the caller's current stream there)"""
         if not self.n:
             return
-        s = _lib.stream_on(self.device, stream)
         if self.kind == "w4":
-            call("ct_quant_pack_batch" if self.direction == 0 else "ct_unpack_dequant_batch", self.table.data_ptr(), self.n, self.blocks, self.dt, s)
-        elif self.direction == 0:
-            call("ct_q8_quant_batch", self.table.data_ptr(), self.n, self.blocks, self.dt, {"int8": 0, "fp8": 1, "fp8z": 2}[self.kind], self.bits, s)
+            _run_table("w4", self.table, self.n, self.blocks, self.device, self.direction, (self.dt,), stream)
         else:
-            call("ct_q8_dequant_batch", self.table.data_ptr(), self.n, self.blocks, self.dt, {"int8": 0, "fp8": 1, "fp8z": 2}[self.kind], s)
+            kind = _Q8_KINDS[self.kind]
+            _run_table("q8", self.table, self.n, self.blocks, self.device, self.direction,
+                       (self.dt, kind, self.bits) if self.direction == 0 else (self.dt, kind), stream)
 
 
 def quantize_and_pack_many(items, *, num_bits, strategy, group_size=None):
@@ -1596,31 +1624,15 @@ def unpack_and_dequantize_many(items, *, num_bits, strategy, group_size=None):
 
 def launch_rtn_w4_words(words, n: int, dtype: torch.dtype, device: torch.device, symmetric: bool) -> torch.Tensor:
     """`launch_w4_words` for a table of the one-pass round-to-nearest W4 compress (`ct_rtn_quant_pack_w4_batch`): src = weights, dst = packed words,
-    scale / zp = OUTPUTS, zp_packed = 0.  `words`: a flat CPU int64 tensor or an `array.array("q")` of `struct ct_w4_item` words, planned in place.
-    Returns the device table (the caller owes it a `record_stream` when its stream is not the allocator's) or None for an empty table."""
-    if not n:
-        return None
-    addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
-    blocks = int(_lib.load().ct_rtn_w4_batch_plan(addr, n))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    call("ct_rtn_quant_pack_w4_batch", table.data_ptr(), n, blocks, DT[dtype], int(bool(symmetric)), _lib.stream_on(device))
-    return table
+    scale / zp = OUTPUTS, zp_packed = 0.  Returns the device table (the caller owes it a `record_stream` when its stream is not the allocator's) or
+    None for an empty table."""
+    return _launch_table("rtn_w4", words, n, device, 0, (DT[dtype], int(bool(symmetric)))) if n else None
 
 
 def launch_rtn_mxfp4_words(words, n: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
     """`launch_rtn_w4_words` for a table of the one-pass MXFP4 compress (`ct_rtn_mxfp4_quant_pack_batch`): src = weights, dst = packed bytes,
     zp_packed = the E8M0 code output, scale = the float-scale output or 0, group = 32"""
-    if not n:
-        return None
-    addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
-    blocks = int(_lib.load().ct_rtn_mxfp4_batch_plan(addr, n))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
-    table = _upload_table(words, device)
-    call("ct_rtn_mxfp4_quant_pack_batch", table.data_ptr(), n, blocks, DT[dtype], _lib.stream_on(device))
-    return table
+    return _launch_table("rtn_mxfp4", words, n, device, 0, (DT[dtype],)) if n else None
 
 
 def rtn_w4_group(shape, group_size) -> int:
@@ -1639,6 +1651,31 @@ def _rtn_table_tensor(x) -> bool:
     return x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and x.data_ptr() % 16 == 0
 
 
+def rtn_w4_table_item(x, group_size, with_zp: bool = True):
+    """does the one-pass W4 table (`launch_rtn_w4_words`) take this weight — on a GPU, 2-D, contiguous, 16-byte aligned, 16-bit, with a group
+    `rtn_w4_group` accepts?  Then its freshly allocated outputs and its row: (packed int32 (R, C / 8), scale (R, C / g), int8 zero point (R, C / g)
+    or None without `with_zp` — a symmetric table needs no zero-point output, the kernel skips the store —, row); else None"""
+    g = rtn_w4_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
+    if not g:
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=x.device)
+    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
+    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
+    return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
+
+
+def rtn_mxfp4_table_item(x):
+    """`rtn_w4_table_item` for the one-pass MXFP4 table (`launch_rtn_mxfp4_words`; cols % 32 == 0): (packed uint8 (R, C / 2), E8M0 codes uint8
+    (R, C / 32), row) or None"""
+    if not (_rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0):
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+    code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+    return packed, code, item_row(x.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, code.data_ptr())
+
+
 def _rtn_w4_one(x, group_size, symmetric):
     """one tensor outside the table: the one-pass kernel where it applies, the observer + compress composition otherwise"""
     if x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and rtn_w4_group((1, x.shape[1]), group_size):
@@ -1649,66 +1686,51 @@ def _rtn_w4_one(x, group_size, symmetric):
 
 
 def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True):
-    """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (on one GPU, 2-D, contiguous, 16-byte aligned, 16-bit, of the first
-    such tensor's device and dtype, with a group the one-pass kernel takes) leave in ONE `ct_rtn_quant_pack_w4_batch` launch — a checkpoint is a few hundred
+    """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_w4_table_item`, of the first such tensor's device and
+    dtype) leave in ONE `ct_rtn_quant_pack_w4_batch` launch — a checkpoint is a few hundred
     launch-bound tensors — and the others one by one (the one-pass kernel, or `minmax_qparams` + `quantize_and_pack` where that does not apply).
     `group_size`: one value for all, or one per weight (None = one group per row).  Returns [(packed, scale, zero_point)] in input order,
     bit-identical to the single-tensor call per item (quantization/utils/helpers.py:50-137 + compressors/pack_quantized/base.py:96-104)."""
-    import array
-
     weights = list(weights)
     groups = list(group_size) if isinstance(group_size, (list, tuple)) else [group_size] * len(weights)
     if len(groups) != len(weights):
         raise ValueError(f"{len(groups)} group sizes for {len(weights)} weights")
     out = [None] * len(weights)
-    entries, where, flat = [], [], []
+    first, where, flat = None, [], []  # (`out` keeps the tensors the table's raw pointers name alive, `weights` the inputs)
     for i, (x, gs) in enumerate(zip(weights, groups)):
-        g = rtn_w4_group(x.shape, gs) if _rtn_table_tensor(x) else 0
-        if g and (not entries or (x.device == entries[0][0].device and x.dtype == entries[0][0].dtype)):
-            rows, cols = int(x.shape[0]), int(x.shape[1])
-            packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=x.device)
-            scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
-            zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device)
-            entries.append((x, packed, scale, zp))  # the table holds raw pointers: this list keeps the tensors alive
-            flat += (x.data_ptr(), scale.data_ptr(), zp.data_ptr(), packed.data_ptr(), rows, cols, g, 0, 0, 0, 0, *_ITEM_TAIL)
-            where.append(i)
-        else:
+        item = rtn_w4_table_item(x, gs) if first is None or (x.device == first.device and x.dtype == first.dtype) else None
+        if item is None:
             out[i] = _rtn_w4_one(x, gs, symmetric)
-    if entries:
-        dev = entries[0][0].device
-        table = launch_rtn_w4_words(array.array("q", flat), len(entries), entries[0][0].dtype, dev, symmetric)
-        table.record_stream(torch.cuda.current_stream(dev))
-        for i, e in zip(where, entries):
-            out[i] = e[1:]
+            continue
+        first = x if first is None else first
+        out[i] = item[:3]
+        flat += item[3]
+        where.append(i)
+    if where:
+        table = launch_rtn_w4_words(flat, len(where), first.dtype, first.device, symmetric)
+        table.record_stream(torch.cuda.current_stream(first.device))
     return out
 
 
 def rtn_mxfp4_quantize_and_pack_many(weights):
-    """`rtn_mxfp4_quantize_and_pack` for a LIST of weights: the tensors the table takes (on one GPU, 2-D, contiguous, 16-byte aligned, 16-bit, of the
-    first such tensor's device and dtype, cols % 32 == 0) leave in ONE `ct_rtn_mxfp4_quant_pack_batch` launch, the others one by one.  Returns
+    """`rtn_mxfp4_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_mxfp4_table_item`, of the first such tensor's device
+    and dtype) leave in ONE `ct_rtn_mxfp4_quant_pack_batch` launch, the others one by one.  Returns
     [(packed uint8 (R, C / 2), E8M0 codes uint8 (R, C / 32))] in input order, bit-identical to the single-tensor call per item."""
-    import array
-
     weights = list(weights)
     out = [None] * len(weights)
-    entries, where, flat = [], [], []
+    first, n, flat = None, 0, []
     for i, x in enumerate(weights):
-        if (_rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0
-                and (not entries or (x.device == entries[0][0].device and x.dtype == entries[0][0].dtype))):
-            rows, cols = int(x.shape[0]), int(x.shape[1])
-            packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
-            code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
-            entries.append((x, packed, code))
-            flat += (x.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, 0, 0, 0, code.data_ptr(), *_ITEM_TAIL)
-            where.append(i)
-        else:
+        item = rtn_mxfp4_table_item(x) if first is None or (x.device == first.device and x.dtype == first.dtype) else None
+        if item is None:
             out[i] = rtn_mxfp4_quantize_and_pack(x)
-    if entries:
-        dev = entries[0][0].device
-        table = launch_rtn_mxfp4_words(array.array("q", flat), len(entries), entries[0][0].dtype, dev)
-        table.record_stream(torch.cuda.current_stream(dev))
-        for i, e in zip(where, entries):
-            out[i] = e[1:]
+            continue
+        first = x if first is None else first
+        out[i] = item[:2]
+        flat += item[2]
+        n += 1
+    if n:
+        table = launch_rtn_mxfp4_words(flat, n, first.dtype, first.device)
+        table.record_stream(torch.cuda.current_stream(first.device))
     return out
 
 
@@ -1719,19 +1741,13 @@ def zp4_batch(pairs, direction: str) -> None:
     pairs = list(pairs)
     if not pairs:
         return
-    import array
-
     flat = []
     for src, dst in pairs:
         unpacked = src if direction == "pack" else dst
-        flat += (src.data_ptr(), 0, 0, dst.data_ptr(), int(unpacked.shape[0]), int(unpacked.shape[1]), 0, 0, 0, 0, 0, *_ITEM_TAIL)
-    words = array.array("q", flat)
-    blocks = int(_lib.load().ct_zp4_batch_plan(words.buffer_info()[0], len(pairs)))
-    if blocks < 0:
-        raise ValueError(_lib.last_error())
+        flat += item_row(src.data_ptr(), 0, 0, dst.data_ptr(), int(unpacked.shape[0]), int(unpacked.shape[1]))
+    d = 0 if direction == "pack" else 1
     dev = pairs[0][0].device
-    table = _upload_table(words, dev)
-    call("ct_zp4_pack_dim0_batch", table.data_ptr(), len(pairs), blocks, 0 if direction == "pack" else 1, _lib.stream_on(dev))
+    table = _launch_table("zp4", flat, len(pairs), dev, d, (d,))
     table.record_stream(torch.cuda.current_stream(dev))
 
 

@@ -15,7 +15,7 @@ from ..quantization.quant_args import QuantizationStatus, is_scheme
 from ..registry import RegistryMixin
 from ..utils.module import get_direct_state_dict, replace_direct_state_dict
 
-__all__ = ["BaseCompressor", "symmetric_zp_keys", "rtn_windows", "compress_module", "decompress_module", "compress_modules", "decompress_modules", "COMPRESSIBLE_MODULE_TYPES"]
+__all__ = ["BaseCompressor", "symmetric_zp_keys", "zp_drop_mask", "rtn_windows", "launch_chunks", "run_planned", "compress_module", "decompress_module", "compress_modules", "decompress_modules", "COMPRESSIBLE_MODULE_TYPES"]
 
 # reference compressors/base.py:31
 COMPRESSIBLE_MODULE_TYPES = (torch.nn.Linear, torch.nn.Embedding)
@@ -34,6 +34,14 @@ def symmetric_zp_keys(scheme) -> list:
     return keys
 
 
+def zp_drop_mask(scheme) -> int:
+    """`symmetric_zp_keys` as the bit mask the C++ host loops take (csrc/host/ct_hostpath.cpp): 1 weight, 2 input, 4 output zero point"""
+    drop = 0
+    for key in symmetric_zp_keys(scheme):
+        drop |= {"weight_zero_point": 1, "input_zero_point": 2, "output_zero_point": 4}[key]
+    return drop
+
+
 # modules per table of the data-free (round-to-nearest) module paths, `compress_rtn_modules`: building a table costs the host ~10 us per module, during
 # which the GPU would idle, so a long list leaves as windows — the host builds window k + 1 and rewrites the parameter dictionaries of window k under
 # window k's kernel.  tools/rtn_bench.py, W4 g128, windows of 16 / 32 / 64 / one table: 3.60 / 3.63 / 3.74 / 4.66 ms on an 8B-shaped tree (the per-module
@@ -44,6 +52,33 @@ RTN_WINDOW = 32
 def rtn_windows(modules):
     modules = list(modules)
     return [modules[lo:lo + RTN_WINDOW] for lo in range(0, len(modules), RTN_WINDOW)]
+
+
+def launch_chunks(n: int):
+    """[lo, hi) slices of a module list for the batched launches: planning a 154-module table takes the host ~0.17 ms during which the
+    GPU would idle, so a large list goes out as a short first table (the GPU starts after ~40 us) and two longer ones; a small list
+    as one (every extra launch costs the host ~15 us and the device a ramp / tail of ~3 us)"""
+    if n <= 64:
+        return [(0, n)]
+    a = 32
+    b = a + (n - a) // 2
+    return [(0, a), (a, b), (b, n)]
+
+
+def run_planned(modules, plan, launch, finish) -> list:
+    """the driver of every C++ host loop (csrc/host/ct_hostpath.cpp): per chunk of `modules` (`launch_chunks`), `plan(chunk)` -> ({(device index, code):
+    (table words, n, jobs, second table's words, its n)}, the modules it does not take); `launch(device, code, words, n, aux_words, aux_n)` issues each
+    group's table or tables; then `finish(jobs)` rewrites the parameter dictionaries of every group, under the kernels.  Returns the modules no plan took."""
+    rest, pending = [], []
+    for lo, hi in launch_chunks(len(modules)):  # the first launch leaves after a fifth of the planning, not after all of it
+        planned, back = plan(modules[lo:hi])
+        rest += back
+        for (dev_index, code), (words, n, jobs, aux_words, aux_n) in planned.items():
+            launch(torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu"), code, words, n, aux_words, aux_n)
+            pending.append(jobs)
+    for jobs in pending:
+        finish(jobs)
+    return rest
 
 
 class BaseCompressor(RegistryMixin, ABC):

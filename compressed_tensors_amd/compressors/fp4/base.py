@@ -13,7 +13,7 @@ from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
 from ...quantization.quant_args import QuantizationStatus
 from ...utils.module import direct_entry, swap_direct_entries
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, symmetric_zp_keys
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, run_planned, symmetric_zp_keys, zp_drop_mask
 
 __all__ = ["NVFP4PackedCompressor", "MXFP4PackedCompressor"]
 
@@ -81,7 +81,6 @@ class NVFP4PackedCompressor(BaseCompressor):
         window (`ct_fp4_quant_pack_batch` / `ct_fp4_unpack_dequant_batch`) — the same results and the same dictionary delta as the loop below at ~3 instead of
         14 us of host work per module and without a launch per module; returns the modules it left for that loop"""
         from ... import _lib
-        from ..pack_quantized.base import _launch_chunks
 
         modules = list(modules)
         hp = _lib.hostpath()
@@ -93,25 +92,19 @@ class NVFP4PackedCompressor(BaseCompressor):
             wa = getattr(scheme, "weights", None)
             if wa is None or (getattr(wa, "scale_dtype", None) or want) is not want:
                 return 0
-            drop = 0
-            for key in symmetric_zp_keys(scheme):
-                drop |= {"weight_zero_point": 1, "input_zero_point": 2, "output_zero_point": 4}[key]
-            return 1 | (drop << 1)
+            return 1 | (zp_drop_mask(scheme) << 1)
 
         compress = direction == "compress"
         status = QuantizationStatus.COMPRESSED if compress else QuantizationStatus.DECOMPRESSED
         codes = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}
-        rest, pending = [], []
-        for lo, hi in _launch_chunks(len(modules)):
-            planned, back = hp.fp4_plan_compress(modules[lo:hi], info, cls.GROUP) if compress else hp.fp4_plan_decompress(modules[lo:hi], cls.GROUP)
-            rest += back
-            for (dev_index, code), (words, n, jobs, _zw, _zn) in planned.items():
-                device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-                codec.launch_fp4_words(words, n, direction, device, cls.GROUP, codes[code & 15], codes[code >> 4])
-                pending.append(jobs)
-        for jobs in pending:
-            hp.fp4_finish(jobs, status, compress)
-        return rest
+
+        def plan(ms):
+            return hp.fp4_plan_compress(ms, info, cls.GROUP) if compress else hp.fp4_plan_decompress(ms, cls.GROUP)
+
+        def launch(device, code, words, n, _zw, _zn):
+            codec.launch_fp4_words(words, n, direction, device, cls.GROUP, codes[code & 15], codes[code >> 4])
+
+        return run_planned(modules, plan, launch, lambda jobs: hp.fp4_finish(jobs, status, compress))
 
     @classmethod
     def _native_group(cls):
@@ -157,7 +150,6 @@ class NVFP4PackedCompressor(BaseCompressor):
         want = torch.float8_e4m3fn if cls.GROUP == 16 else torch.uint8
         out, words, keep, where = [None] * len(state_dicts), [], [], []
         device = None
-        tail = (0,) * (codec._ITEM_WORDS - 11)
         for i, sd in enumerate(state_dicts):
             packed, sc, gs = sd.get("weight_packed"), sd.get("weight_scale"), sd.get("weight_global_scale")
             ok = (packed is not None and sc is not None and packed.is_cuda and packed.dtype is torch.uint8 and packed.dim() == 2 and packed.is_contiguous()
@@ -174,7 +166,7 @@ class NVFP4PackedCompressor(BaseCompressor):
             device = packed.device
             weight = torch.empty((rows, cols), dtype=torch.bfloat16, device=device)  # unpack_fp4_from_uint8's default dtype (nvfp4/base.py:118-131)
             scale = torch.empty((rows, cols // cls.GROUP), dtype=torch.bfloat16, device=device)
-            words += (packed.data_ptr(), sc.data_ptr(), 0 if gs is None else gs.data_ptr(), weight.data_ptr(), rows, cols, cls.GROUP, 0, 0, 0, scale.data_ptr(), *tail)
+            words += codec.item_row(packed, sc, gs, weight, rows, cols, cls.GROUP, scale)
             keep.append((packed, sc, gs))
             new = dict(sd)
             del new["weight_packed"]
@@ -249,26 +241,22 @@ class MXFP4PackedCompressor(NVFP4PackedCompressor):
         0, E8M0 codes stored as uint8) leave in ONE table launch per (device, dtype) (codec.launch_rtn_mxfp4_words) and the parameter dictionaries are
         rewritten under the kernel.  Every module ends in exactly the state `compress_rtn_module` leaves it in; the others go through that, from
         this call."""
-        import array
-
-        tail = (0,) * (codec._ITEM_WORDS - 11)
         for window in rtn_windows(modules):
             tables, rest = {}, []
             for m in window:
                 w = direct_entry(m, "weight")
-                ok = (w is not None and codec._rtn_table_tensor(w) and w.shape[0] > 0 and w.shape[1] > 0 and w.shape[1] % 32 == 0
-                      and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.uint8) is torch.uint8)
-                if not ok:
+                item = None
+                if w is not None and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.uint8) is torch.uint8:
+                    item = codec.rtn_mxfp4_table_item(w)
+                if item is None:
                     rest.append(m)
                     continue
-                rows, cols = int(w.shape[0]), int(w.shape[1])
-                packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=w.device)
-                code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=w.device)
+                packed, code, row = item
                 flat, jobs = tables.setdefault((w.device, w.dtype), ([], []))
-                flat += (w.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, 0, 0, 0, code.data_ptr(), *tail)
+                flat += row
                 jobs.append((m, w, packed, code))  # the table holds raw pointers: the jobs keep the tensors alive
             for (device, dtype), (flat, jobs) in tables.items():
-                table = codec.launch_rtn_mxfp4_words(array.array("q", flat), len(jobs), dtype, device)
+                table = codec.launch_rtn_mxfp4_words(flat, len(jobs), dtype, device)
                 table.record_stream(torch.cuda.current_stream(device))
             for flat, jobs in tables.values():  # from here on the host works under the kernel
                 for m, w, packed, code in jobs:

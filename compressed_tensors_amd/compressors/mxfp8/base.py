@@ -47,8 +47,7 @@ class MXFP8QuantizationCompressor(NaiveQuantizationCompressor):
     def _native(cls, modules, direction: str):
         from ... import _lib
         from ...quantization.quant_args import QuantizationStatus
-        from ..base import symmetric_zp_keys
-        from ..pack_quantized.base import _launch_chunks
+        from ..base import run_planned, zp_drop_mask
 
         modules = list(modules)
         hp = _lib.hostpath()
@@ -60,31 +59,23 @@ class MXFP8QuantizationCompressor(NaiveQuantizationCompressor):
         def info(scheme) -> int:
             if not cls.can_compress(torch.nn.Linear, scheme):
                 return 0
-            drop = 0
-            for key in symmetric_zp_keys(scheme):
-                drop |= {"weight_zero_point": 1, "input_zero_point": 2, "output_zero_point": 4}[key]
-            return 1 | (drop << 1)
+            return 1 | (zp_drop_mask(scheme) << 1)
 
         compress = direction == "compress"
         codes = {1: torch.float16, 2: torch.bfloat16}
-        rest, pending = [], []
-        for lo, hi in _launch_chunks(len(modules)):
-            planned, back = hp.mx8_plan_compress(modules[lo:hi], info) if compress else hp.mx8_plan_decompress(modules[lo:hi])
-            rest += back
-            for (dev_index, code), (words, n, jobs, scale_words, scale_n) in planned.items():
-                device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-                dtype = codes[code & 15]
-                if compress:
-                    codec.launch_q8_words(words, n, "compress", dtype, device, (code >> 4) & 15, 8)
-                    codec.launch_mx_scale_words(scale_words, scale_n, "compress", device, dtype)
-                else:  # the scales first: the weights' table reads their bfloat16 form
-                    codec.launch_mx_scale_words(scale_words, scale_n, "decompress", device)
-                    codec.launch_q8_words(words, n, "decompress", dtype, device, (code >> 4) & 15, 8)
-                pending.append(jobs)
         status = QuantizationStatus.COMPRESSED if compress else QuantizationStatus.DECOMPRESSED
-        for jobs in pending:
-            hp.mx8_finish(jobs, status)
-        return rest
+
+        def launch(device, code, words, n, scale_words, scale_n):
+            dtype = codes[code & 15]
+            if compress:
+                codec.launch_q8_words(words, n, "compress", dtype, device, (code >> 4) & 15, 8)
+                codec.launch_mx_scale_words(scale_words, scale_n, "compress", device, dtype)
+            else:  # the scales first: the weights' table reads their bfloat16 form
+                codec.launch_mx_scale_words(scale_words, scale_n, "decompress", device)
+                codec.launch_q8_words(words, n, "decompress", dtype, device, (code >> 4) & 15, 8)
+
+        return run_planned(modules, (lambda ms: hp.mx8_plan_compress(ms, info)) if compress else hp.mx8_plan_decompress, launch,
+                           lambda jobs: hp.mx8_finish(jobs, status))
 
     @classmethod
     def compress_modules(cls, modules) -> None:
@@ -103,7 +94,6 @@ class MXFP8QuantizationCompressor(NaiveQuantizationCompressor):
             return [cls.decompress(sd, scheme) for sd in state_dicts]
         out, words, swords, where = [None] * len(state_dicts), [], [], []
         device = None
-        tail = (0,) * (codec._ITEM_WORDS - 7)
         for i, sd in enumerate(state_dicts):
             q, sc = sd.get("weight"), sd.get("weight_scale")
             ok = (q is not None and sc is not None and sd.get("weight_zero_point") is None and sd.get("weight_g_idx") is None and q.is_cuda and q.dim() == 2
@@ -118,8 +108,8 @@ class MXFP8QuantizationCompressor(NaiveQuantizationCompressor):
             device = q.device
             scale = torch.empty(sc.shape, dtype=torch.bfloat16, device=device)  # decompress_mx_scale: bfloat16, and so is the weight (mxfp8/base.py:74-101)
             weight = torch.empty((rows, cols), dtype=torch.bfloat16, device=device)
-            words += (q.data_ptr(), scale.data_ptr(), 0, weight.data_ptr(), rows, cols, 32, *tail)
-            swords += (sc.data_ptr(), 0, 0, scale.data_ptr(), sc.numel(), 1, 0, *tail)
+            words += codec.item_row(q, scale, None, weight, rows, cols, 32)
+            swords += codec.item_row(sc, dst=scale, rows=sc.numel(), cols=1)
             new = dict(sd, weight_scale=scale)
             del new["weight"]
             new["weight"] = weight  # the entries in the order `decompress` leaves them

@@ -13,7 +13,7 @@ from ... import codec
 from ...config import CompressionFormat
 from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, zp_drop_mask
 
 __all__ = ["NaiveQuantizationCompressor", "IntQuantizationCompressor", "FloatQuantizationCompressor"]
 
@@ -24,8 +24,6 @@ _STRATEGY_CODE = {"tensor": 0, "channel": 1, "group": 2, "block": 3}
 def _q8_compress_info(scheme) -> int:
     """what the C++ host loop needs to know of a scheme (csrc/host/ct_hostpath.cpp, q8_plan_compress): group size, num_bits, FLOAT, strategy and the
     zero points a symmetric scheme does not store — or -1 for a scheme whose modules stay with the Python loop"""
-    from ..base import symmetric_zp_keys
-
     wa = getattr(scheme, "weights", None)
     if wa is None:
         return -1
@@ -44,10 +42,7 @@ def _q8_compress_info(scheme) -> int:
         bh, gs = int(bs[0]), int(bs[1])
     if not 0 <= gs < (1 << 20) or not 0 <= bh < (1 << 20):
         return -1
-    drop = 0
-    for key in symmetric_zp_keys(scheme):
-        drop |= {"weight_zero_point": 1, "input_zero_point": 2, "output_zero_point": 4}[key]
-    return gs | (bits << 20) | ((qtype == "float") << 24) | (_STRATEGY_CODE[st] << 25) | (drop << 27) | (bh << 30)
+    return gs | (bits << 20) | ((qtype == "float") << 24) | (_STRATEGY_CODE[st] << 25) | (zp_drop_mask(scheme) << 27) | (bh << 30)
 
 
 def _q8_decompress_info(scheme) -> int:
@@ -58,23 +53,16 @@ def _native_q8(modules, direction: str, status):
     """the plain modules of `modules` through the C++ host loop (table rows, output allocations, launches in windows, the parameter dictionaries under the
     kernels); returns the modules it did not take.  None of it when the extension is not built or a global parameter-registration hook is installed."""
     from ... import _lib
-    from ..pack_quantized.base import _launch_chunks
 
     hp = _lib.hostpath()
     if hp is None or not hasattr(hp, "q8_plan_compress") or torch.nn.modules.module._global_parameter_registration_hooks:
         return modules
     plan, info = (hp.q8_plan_compress, _q8_compress_info) if direction == "compress" else (hp.q8_plan_decompress, _q8_decompress_info)
-    rest, pending = [], []
-    for lo, hi in _launch_chunks(len(modules)):
-        planned, back = plan(modules[lo:hi], info)
-        rest += back
-        for (dev_index, code), (words, n, jobs, _zw, _zn) in planned.items():
-            device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-            codec.launch_q8_words(words, n, direction, _DTYPE_OF_CODE[code & 15], device, (code >> 4) & 15, code >> 8)
-            pending.append(jobs)
-    for jobs in pending:
-        hp.q8_finish(jobs, status)
-    return rest
+
+    def launch(device, code, words, n, _zw, _zn):
+        codec.launch_q8_words(words, n, direction, _DTYPE_OF_CODE[code & 15], device, (code >> 4) & 15, code >> 8)
+
+    return run_planned(modules, lambda ms: plan(ms, info), launch, lambda jobs: hp.q8_finish(jobs, status))
 
 
 @BaseCompressor.register(name=CompressionFormat.naive_quantized.value)

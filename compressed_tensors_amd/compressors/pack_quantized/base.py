@@ -14,7 +14,7 @@ from ... import _lib, codec
 from ...config import CompressionFormat
 from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, symmetric_zp_keys
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, run_planned, symmetric_zp_keys
 
 __all__ = ["PackedQuantizationCompressor"]
 
@@ -27,17 +27,6 @@ def _hostpath():
 
 
 _DTYPE_OF_CODE = {1: torch.float16, 2: torch.bfloat16}
-
-
-def _launch_chunks(n: int):
-    """[lo, hi) slices of a module list for the batched launches: planning a 154-module table takes the host ~0.17 ms during which the
-    GPU would idle, so a large list goes out as a short first table (the GPU starts after ~40 us) and two longer ones; a small list
-    as one (every extra launch costs the host ~15 us and the device a ramp / tail of ~3 us)"""
-    if n <= 64:
-        return [(0, n)]
-    a = 32
-    b = a + (n - a) // 2
-    return [(0, a), (a, b), (b, n)]
 
 
 def _plain_w4_scheme(scheme):
@@ -78,17 +67,11 @@ def _native_w8(hp, modules, direction: str, status):
     if not hasattr(hp, "w8_plan_compress") or not any(int(getattr(getattr(m.quantization_scheme, "weights", None), "num_bits", 0) or 0) == 8 for m in modules):
         return modules
     plan, finish = (hp.w8_plan_compress, hp.w4_finish_compress) if direction == "compress" else (hp.w8_plan_decompress, hp.w4_finish_decompress)
-    rest, pending = [], []
-    for lo, hi in _launch_chunks(len(modules)):
-        planned, back = plan(modules[lo:hi], _w8_info)
-        rest += back
-        for (dev_index, code), (words, n, jobs, _zw, _zn) in planned.items():
-            device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-            codec.launch_q8_words(words, n, direction, _DTYPE_OF_CODE[code & 15], device, (code >> 4) & 15, code >> 8)
-            pending.append(jobs)
-    for jobs in pending:
-        finish(jobs, status)
-    return rest
+
+    def launch(device, code, words, n, _zw, _zn):
+        codec.launch_q8_words(words, n, direction, _DTYPE_OF_CODE[code & 15], device, (code >> 4) & 15, code >> 8)
+
+    return run_planned(modules, lambda ms: plan(ms, _w8_info), launch, lambda jobs: finish(jobs, status))
 
 
 def _wb_info(scheme) -> int:
@@ -263,10 +246,7 @@ class PackedQuantizationCompressor(BaseCompressor):
         strategy = enum_value(weights.strategy)
         group = getattr(weights, "group_size", None) if strategy == "group" else None
         one_pass = (int(weights.num_bits) == 4 and enum_value(getattr(weights, "type", "int")) == "int" and strategy in ("group", "channel")
-                    and weight.dim() == 2 and weight.dtype in (torch.bfloat16, torch.float16))
-        cols = weight.shape[-1]
-        g = int(group) if group else cols
-        one_pass = one_pass and g > 0 and cols % g == 0 and g % 32 == 0 and g <= 2048 and ((g // 32) & (g // 32 - 1)) == 0
+                    and weight.dim() == 2 and weight.dtype in (torch.bfloat16, torch.float16) and codec.rtn_w4_group((1, weight.shape[-1]), group))
         if not one_pass:
             scale, zp = codec.minmax_qparams(weight, num_bits=int(weights.num_bits), group_size=group, symmetric=bool(weights.symmetric))
             return cls.compress({"weight": weight, "weight_scale": scale, "weight_zero_point": zp}, scheme)
@@ -282,14 +262,10 @@ class PackedQuantizationCompressor(BaseCompressor):
         16-bit weight on a GPU leave in ONE table launch per (device, dtype, symmetric) (codec.launch_rtn_w4_words), the stored zero points of the
         asymmetric ones in one `zp4_batch(..., "pack")` behind it, and the parameter dictionaries are rewritten under the kernels.  Every module ends
         in exactly the state `compress_rtn_module` leaves it in; the modules the table does not take go through that, from this call."""
-        import array
-
         from ...quantization.quant_args import QuantizationStatus
         from ...utils.module import direct_entry, swap_direct_entries
-        from ..base import rtn_windows
 
         schemes = {}
-        tail = (0,) * (codec._ITEM_WORDS - 11)
         for window in rtn_windows(modules):
             tables, rest = {}, []
             for m in window:
@@ -303,21 +279,20 @@ class PackedQuantizationCompressor(BaseCompressor):
                         info = (getattr(wa, "group_size", None) if st == "group" else None, bool(wa.symmetric))
                     schemes[id(scheme)] = info
                 w = direct_entry(m, "weight")
-                g = codec.rtn_w4_group(w.shape, info[0]) if info is not None and w is not None and codec._rtn_table_tensor(w) else 0
-                if not g:
+                item = codec.rtn_w4_table_item(w, info[0], not info[1]) if info is not None and w is not None else None
+                if item is None:
                     rest.append(m)
                     continue
-                rows, cols = int(w.shape[0]), int(w.shape[1])
-                packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=w.device)
-                scale = torch.empty((rows, cols // g), dtype=w.dtype, device=w.device)
-                # (a symmetric table needs no zero-point output: the kernel skips the store)
-                zp = None if info[1] else torch.empty((rows, cols // g), dtype=torch.int8, device=w.device)
-                zpp = None if info[1] else torch.empty((math.ceil(rows * 4 / 32), cols // g), dtype=torch.int32, device=w.device)
+                packed, scale, zp, row = item
+                zpp = None
+                if zp is not None:
+                    rows, groups = zp.shape
+                    zpp = torch.empty((math.ceil(rows * 4 / 32), groups), dtype=torch.int32, device=w.device)
                 flat, jobs = tables.setdefault((w.device, w.dtype, info[1]), ([], []))
-                flat += (w.data_ptr(), scale.data_ptr(), 0 if zp is None else zp.data_ptr(), packed.data_ptr(), rows, cols, g, 0, 0, 0, 0, *tail)
+                flat += row
                 jobs.append((m, w, packed, scale, zp, zpp))  # the table holds raw pointers: the jobs keep the tensors alive
             for (device, dtype, symmetric), (flat, jobs) in tables.items():
-                table = codec.launch_rtn_w4_words(array.array("q", flat), len(jobs), dtype, device, symmetric)
+                table = codec.launch_rtn_w4_words(flat, len(jobs), dtype, device, symmetric)
                 table.record_stream(torch.cuda.current_stream(device))
                 if not symmetric:  # pack_to_int32(zp, 4, packed_dim=0) of every module, behind the launch that computes the zero points
                     codec.zp4_batch([(j[4], j[5]) for j in jobs], "pack")
@@ -349,20 +324,15 @@ class PackedQuantizationCompressor(BaseCompressor):
             # and, after the launch, the parameter dictionaries; whatever it does not take comes back in `modules`
             modules = _native_w8(hp, list(modules), "compress", QuantizationStatus.COMPRESSED)
             modules = _native_wb(hp, modules, "compress", QuantizationStatus.COMPRESSED)
-            rest, pending = [], []
-            for lo, hi in _launch_chunks(len(modules)):  # the first launch leaves after a fifth of the planning, not after all of it
-                planned, back = hp.w4_plan_compress(modules[lo:hi], _compress_info)  # (asked once per distinct scheme object and chunk)
-                rest += back
-                for (dev_index, code), (words, n, jobs, zp_words, zp_n) in planned.items():
-                    device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-                    codec.launch_w4_words(words, n, "compress", _DTYPE_OF_CODE[code], device)
-                    # (the asymmetric modules' zero points — pack_to_int32(zp, 4, packed_dim=0) — are written by tail workgroups of that launch;
-                    # zp_n is 0 since round 6 and the call below a no-op, kept for a host extension built from an older source)
-                    codec.launch_zp4_words(zp_words, zp_n, "pack", device)
-                    pending.append(jobs)
-            for jobs in pending:  # the parameter dictionaries, under the kernels
-                hp.w4_finish_compress(jobs, QuantizationStatus.COMPRESSED)
-            modules = rest
+
+            def launch(device, code, words, n, zp_words, zp_n):
+                codec.launch_w4_words(words, n, "compress", _DTYPE_OF_CODE[code], device)
+                # (the asymmetric modules' zero points — pack_to_int32(zp, 4, packed_dim=0) — are written by tail workgroups of that launch;
+                # zp_n is 0 since round 6 and the call below a no-op, kept for a host extension built from an older source)
+                codec.launch_zp4_words(zp_words, zp_n, "pack", device)
+
+            modules = run_planned(modules, lambda ms: hp.w4_plan_compress(ms, _compress_info),  # (asked once per distinct scheme object and chunk)
+                                  launch, lambda jobs: hp.w4_finish_compress(jobs, QuantizationStatus.COMPRESSED))
 
         batches = {}  # (device, dtype) -> (entries, jobs): one table and one launch per GPU and weight dtype
         rest = []
@@ -502,18 +472,13 @@ class PackedQuantizationCompressor(BaseCompressor):
         if hp is not None and not torch.nn.modules.module._global_parameter_registration_hooks:
             modules = _native_w8(hp, modules, "decompress", QuantizationStatus.DECOMPRESSED)
             modules = _native_wb(hp, modules, "decompress", QuantizationStatus.DECOMPRESSED)
-            rest, pending = [], []
-            for lo, hi in _launch_chunks(len(modules)):
-                planned, back = hp.w4_plan_decompress(modules[lo:hi], _decompress_info)
-                rest += back
-                for (dev_index, code), (words, n, jobs, zp_words, zp_n) in planned.items():
-                    device = torch.device("cuda", dev_index) if dev_index >= 0 else torch.device("cpu")
-                    codec.launch_zp4_words(zp_words, zp_n, "unpack", device)  # first: the weights' table points at the unpacked zero points
-                    codec.launch_w4_words(words, n, "decompress", _DTYPE_OF_CODE[code], device)
-                    pending.append(jobs)
-            for jobs in pending:
-                hp.w4_finish_decompress(jobs, QuantizationStatus.DECOMPRESSED)
-            modules = rest
+
+            def launch(device, code, words, n, zp_words, zp_n):
+                codec.launch_zp4_words(zp_words, zp_n, "unpack", device)  # first: the weights' table points at the unpacked zero points
+                codec.launch_w4_words(words, n, "decompress", _DTYPE_OF_CODE[code], device)
+
+            modules = run_planned(modules, lambda ms: hp.w4_plan_decompress(ms, _decompress_info),
+                                  launch, lambda jobs: hp.w4_finish_decompress(jobs, QuantizationStatus.DECOMPRESSED))
         names = ("weight_packed", "weight_scale", "weight_shape", "weight_zero_point", "weight_g_idx")
         sds = [{k: t for k in names if (t := direct_entry(m, k)) is not None} for m in modules]
         pre = PackedQuantizationCompressor._batch_decompress(sds, [m.quantization_scheme for m in modules])  # (`cls` may be install()'s subclass of the UPSTREAM codec)

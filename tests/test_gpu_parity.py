@@ -2404,6 +2404,60 @@ def test_w4_batch_vs_oracle(cta, dev):
             assert eq(e[3].cpu(), O.dequantize(q, scale, zp))
 
 
+def test_w4_batch_on_a_side_stream_vs_oracle(cta, dev, monkeypatch):
+    """`W4Batch.launch(stream=...)` on a stream that is not the current one, both directions, for an asymmetric g128 table whose zero points ride in the
+    launch: 20 rows make the stored zero points round up to 3 rows (tail workgroups), (32, 512) is the shape whose stored form the decompress reads
+    itself, (64, 256) / (20, 256) are one group per row pair; bit for bit against the oracle's pack_quantized_compress / pack_quantized_decompress, and
+    against its fake_quantize up to the sign of zero: where a group's zero point is 0, fake_quantize keeps the -0.0 of round(x / scale) that no integer
+    code can store, so the oracle's own decompress(compress(W)) differs from its fake_quantize(W) there (419 / 366 / 193 elements of these weights) and
+    nowhere else.  The stream each of the two launches is handed to the library with is recorded on the way: it is the side stream, not the current one"""
+    issued = []
+    through = cta.codec.call
+
+    def recording_call(name, *args):
+        issued.append((name, int(args[-1]), args[-1].device_index))
+        through(name, *args)
+
+    monkeypatch.setattr(cta.codec, "call", recording_call)
+    g = torch.Generator().manual_seed(21)
+    kw = dict(num_bits=4, strategy="group", group_size=128)
+    side = torch.cuda.Stream(dev)
+    assert side.cuda_stream != torch.cuda.current_stream(dev).cuda_stream
+    refs, centries = [], []
+    for rows, cols in ((64, 256), (32, 512), (20, 256)):
+        w = torch.randn(rows, cols, generator=g).to(BF16)
+        scale, zp = O.calculate_qparams_minmax(w, num_bits=4, group_size=128, symmetric=False)
+        ref = O.pack_quantized_compress({"weight": w, "weight_scale": scale, "weight_zero_point": zp}, symmetric=False, **kw)
+        refs.append((w, scale, zp, ref))
+        packed = torch.empty(rows, cols // 8, dtype=torch.int32, device=dev)
+        zpp = torch.empty((rows + 7) // 8, cols // 128, dtype=torch.int32, device=dev)
+        centries.append((w.to(dev), scale.to(dev), zp.to(dev), packed, rows, cols, 128, zpp))
+    batch = cta.codec.W4Batch(centries, "compress", BF16)
+    side.wait_stream(torch.cuda.current_stream(dev))  # the inputs and the table were written on the current stream
+    batch.launch(stream=side.cuda_stream)
+    side.synchronize()
+    dentries = []
+    for (w, scale, zp, ref), e in zip(refs, centries):
+        assert torch.equal(e[3].cpu(), ref["weight_packed"].contiguous())
+        assert tuple(e[7].shape) == tuple(ref["weight_zero_point"].shape) and torch.equal(e[7].cpu(), ref["weight_zero_point"])
+        out = torch.empty_like(e[0])
+        if cta.codec.w4_packed_zp_readable(e[5], 128):  # stored form in, unpacked form written back
+            dentries.append((e[3], e[1], torch.full_like(e[2], 55), out, e[4], e[5], 128, e[7]))
+        else:
+            dentries.append((e[3], e[1], e[2], out, e[4], e[5], 128))
+    assert [len(e) for e in dentries] == [7, 8, 7]
+    batch = cta.codec.W4Batch(dentries, "decompress", BF16)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    batch.launch(stream=side.cuda_stream)
+    side.synchronize()
+    for (w, scale, zp, ref), e in zip(refs, dentries):
+        assert eq(e[3].cpu(), O.pack_quantized_decompress(ref, symmetric=False, num_bits=4, strategy="group")["weight"])
+        assert eq(e[3].cpu(), O.fake_quantize(w, scale, zp, **kw) + 0.0)  # (-0.0 + 0.0 == +0.0; every other bit pattern is kept)
+        assert torch.equal(e[2].cpu(), zp)
+    index = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
+    assert issued == [("ct_quant_pack_batch", side.cuda_stream, index), ("ct_unpack_dequant_batch", side.cuda_stream, index)]
+
+
 # ----------------------------------------------------------------------------- FP4 codecs (SURVEY §8f N4)
 def _fp4_scheme(cta, fmt):
     from compressed_tensors_amd.quantization import QuantizationArgs, QuantizationScheme

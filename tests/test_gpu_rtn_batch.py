@@ -217,20 +217,18 @@ def test_table_entries_are_hip_graph_capturable(cta, dev):
     zpp = [torch.empty(r // 8, c // 128, dtype=torch.int32, device=dev) for r, c in shapes]
     mxp = [torch.empty(r, c // 2, dtype=torch.uint8, device=dev) for r, c in shapes]
     code = [torch.empty(r, c // 32, dtype=torch.uint8, device=dev) for r, c in shapes]
-    tail = (0,) * (cta.codec._ITEM_WORDS - 11)
+    row = cta.codec.item_row
 
     def planned(rows, plan):
-        words = array.array("q", [v for row in rows for v in (*row, *tail)])
+        words = array.array("q", [v for r in rows for v in r])
         blocks = int(getattr(lib, plan)(words.buffer_info()[0], len(rows)))
         assert blocks > 0, _lib.last_error()
         return torch.tensor(list(words), dtype=torch.int64).to(dev), blocks
 
     n = len(shapes)
-    t_w4, b_w4 = planned([(w.data_ptr(), s.data_ptr(), z.data_ptr(), p.data_ptr(), r, c, 128, 0, 0, 0, 0)
-                          for w, s, z, p, (r, c) in zip(ws, scale, zp, packed, shapes)], "ct_rtn_w4_batch_plan")
-    t_zp, b_zp = planned([(z.data_ptr(), 0, 0, q.data_ptr(), r, c // 128, 0, 0, 0, 0, 0) for z, q, (r, c) in zip(zp, zpp, shapes)], "ct_zp4_batch_plan")
-    t_mx, b_mx = planned([(w.data_ptr(), 0, 0, p.data_ptr(), r, c, 32, 0, 0, 0, k.data_ptr()) for w, p, k, (r, c) in zip(ws, mxp, code, shapes)],
-                         "ct_rtn_mxfp4_batch_plan")
+    t_w4, b_w4 = planned([row(w, s, z, p, r, c, 128) for w, s, z, p, (r, c) in zip(ws, scale, zp, packed, shapes)], "ct_rtn_w4_batch_plan")
+    t_zp, b_zp = planned([row(z, dst=q, rows=r, cols=c // 128) for z, q, (r, c) in zip(zp, zpp, shapes)], "ct_zp4_batch_plan")
+    t_mx, b_mx = planned([row(w, dst=p, rows=r, cols=c, group=32, zp_packed=k) for w, p, k, (r, c) in zip(ws, mxp, code, shapes)], "ct_rtn_mxfp4_batch_plan")
     torch.cuda.synchronize()
 
     def launches(stream):

@@ -744,6 +744,52 @@ def test_batch_table_words_match_the_struct(cta):
     assert lib.ct_w4_batch_plan(ctypes.cast(bad, ctypes.c_void_p), 1, 0) > 0  # compress: any batch item may ask for it
     bad[0].zp = None
     assert lib.ct_w4_batch_plan(ctypes.cast(bad, ctypes.c_void_p), 1, 0) == -1 and "without giving" in _lib.last_error()
+    # codec.item_row is the struct filled by field name, whatever the positions of its fields
+    one = _lib.W4Item()
+    one.src, one.scale, one.zp, one.dst, one.rows, one.cols, one.group, one.zp_packed = 0x11, 0x22, 0x33, 0x44, 55, 66, 77, 0x88
+    row = codec.item_row(src=0x11, scale=0x22, zp=0x33, dst=0x44, rows=55, cols=66, group=77, zp_packed=0x88)
+    assert isinstance(row, tuple) and len(row) == codec._ITEM_WORDS and all(type(v) is int for v in row)
+    assert bytes(one) == array.array("q", row).tobytes()
+    assert row == codec.item_row(0x11, 0x22, 0x33, 0x44, 55, 66, 77, 0x88)
+    some = _lib.W4Item()
+    some.src, some.dst, some.rows, some.cols = 0x11, 0x44, 55, 66
+    row = codec.item_row(0x11, dst=0x44, rows=55, cols=66)
+    assert bytes(some) == array.array("q", row).tobytes() and sorted(v for v in row if v) == [0x11, 55, 66, 0x44] and row.count(0) == codec._ITEM_WORDS - 4
+    t = torch.zeros(4)
+    assert codec.item_row(t, None, zp_packed=t) == codec.item_row(t.data_ptr(), 0, zp_packed=t.data_ptr())  # a tensor: its address; None: 0
+
+
+def test_the_launcher_table_names_every_item_table_once(cta):
+    """codec._TABLES drives every launch of a `ct_w4_item` table: each kind names a plan and a launch (or one per direction) that the library exports,
+    every `*_batch_plan` of such a table belongs to exactly one kind, an empty table returns None before the library is touched, and a row the plan refuses
+    raises ValueError with the library's own text"""
+    from compressed_tensors_amd import _lib, codec
+
+    item_plans = {"ct_w4_batch_plan", "ct_q8_batch_plan", "ct_fp4_batch_plan", "ct_mx_scale_batch_plan", "ct_zp4_batch_plan", "ct_rtn_w4_batch_plan",
+                  "ct_rtn_mxfp4_batch_plan"}
+    assert item_plans <= set(_lib.EXPORTED_SYMBOLS)
+    plans = [plan for plan, _, _ in codec._TABLES.values()]
+    assert sorted(plans) == sorted(item_plans)  # each of the seven in exactly one kind
+    cpu = torch.device("cpu")
+    for kind, (plan, directed, launch) in codec._TABLES.items():
+        symbols = (launch,) if isinstance(launch, str) else launch
+        assert len(symbols) in (1, 2) and {plan, *symbols} <= set(_lib.EXPORTED_SYMBOLS), kind
+        assert directed == (len(_lib._PROTOTYPES[plan][0]) == 3), kind  # (items, n[, direction])
+        assert codec._launch_table(kind, None, 0, cpu) is None  # (words None: nothing reads them)
+    # an empty table returns before anything about it is looked at, a dtype the library does not know included
+    assert codec.launch_rtn_w4_words(None, 0, None, cpu, True) is None and codec.launch_rtn_mxfp4_words(None, 0, None, cpu) is None
+    assert codec.launch_w4_words(None, 0, "compress", None, cpu) is None and codec.launch_q8_words(None, 0, "decompress", None, cpu, 0) is None
+    assert codec.launch_fp4_words(None, 0, "compress", cpu, 32) is None and codec.launch_mx_scale_words(None, 0, "compress", cpu) is None
+    assert codec.launch_zp4_words(None, 0, "pack", cpu) is None and codec.zp4_batch([], "pack") is None
+    assert sorted(codec._Q8_KINDS.items()) == [("fp8", 1), ("fp8z", 2), ("int8", 0)]
+
+    import array
+
+    refused = codec.item_row(0x10000, 0x20000, 0, 0x40000, rows=4, cols=100, group=128)
+    for words in (array.array("q", refused), torch.tensor(refused, dtype=torch.int64), list(refused)):  # every form of a host table
+        with pytest.raises(ValueError) as err:
+            codec.launch_w4_words(words, 1, "compress", torch.bfloat16, cpu)
+        assert "ct_w4_batch_plan" in str(err.value) and "item 0" in str(err.value), str(err.value)
 
 
 def _tree(cta, scheme, shapes, *, trainable_scale=False, buffer_zp=False, odd_class=False, g_idx=False):
