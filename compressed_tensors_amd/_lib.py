@@ -109,6 +109,7 @@ _PROTOTYPES = {
     "ct_hadamard_dynamic_qdq": ([_P, _I, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_attn_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_rot_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
+    "ct_attn_observe": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_generate_gparam": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_pack_bitmasks": ([_P, _L, _L, _P, _S], _I),
     "ct_unpack_bitmasks": ([_P, _L, _L, _P, _S], _I),
@@ -190,6 +191,12 @@ class AttnTensor(ctypes.Structure):
     """struct ct_attn_tensor of include/ct_hip.h (one descriptor of ct_attn_qdq: host memory, passed on as kernel arguments)"""
     _fields_ = [("x", _P), ("out", _P), ("scale", _P), ("zp", _P), ("B", _L), ("H", _L), ("S", _L), ("D", _L),
                 ("x_stride", _L * 3), ("out_stride", _L * 3), ("per_head", _L)]
+
+
+class AttnObserveTensor(ctypes.Structure):
+    """struct ct_attn_observe_tensor of include/ct_hip.h (one descriptor of ct_attn_observe: host memory, passed on as kernel arguments)"""
+    _fields_ = [("x", _P), ("state", _P), ("scale", _P), ("zp", _P), ("min_vals", _P), ("max_vals", _P), ("B", _L), ("H", _L), ("S", _L), ("D", _L),
+                ("x_stride", _L * 3), ("per_head", _L)]
 
 
 ITEM_WORDS = ctypes.sizeof(W4Item) // 8 # 13: every host table of ct_w4_item rows is a flat array of this many 64-bit words per item

@@ -730,6 +730,185 @@ def attn_fake_quantize_pair(k, v, k_scale, v_scale, k_zero_point=None, v_zero_po
     return out[0], out[1]
 
 
+# --------------------------------------------------------------------------- attention: the min-max observer of the same states
+ATTN_OBSERVE_MAX_ENTRIES = 1024  # kObsMaxEntries of csrc/ct_attn_observe.hip: the LDS table of a workgroup
+_OBSERVE_EMPTY = (0x7FFFFFFF, -0x80000000)  # the armed keys: the identities of integer min and max (include/ct_hip.h)
+
+# what flatten_attention_for_quantization refuses (the reference tests' observer), in its words
+_ATTN_OBSERVE_REFUSED = {
+    "token": "Token quantization cannot be applied to attention",
+    "channel": "Channel quantization cannot be applied to attention",
+    "group": "Group quantization cannot be applied to attention",
+    "tensor_group": "Group quantization cannot be applied to attention",
+    "block": "Block quantization cannot be applied to attention",
+}
+
+
+class AttnObservePlan(NamedTuple):
+    """what attn_observe does with one tensor: `in_place` (ct_attn_observe reads it through its strides; False: `.contiguous()`
+    first, `reason` says why), the (B, H, S, D) view and the b / h / s element strides the kernel gets, `per_head` and `entries`
+    (H scale entries, or one), and `vector` (rows of whole 8-element units whose bases and strides keep the units aligned)"""
+    in_place: bool
+    vector: bool
+    B: int
+    H: int
+    S: int
+    D: int
+    strides: tuple
+    per_head: bool
+    entries: int
+    reason: Optional[str]
+
+
+@functools.lru_cache(maxsize=4096)
+def _plan_attn_observe(shape, strides, dtype, st, offset_bytes, device_type):
+    return plan_attn_observe(shape, strides, dtype, st, offset_bytes=offset_bytes, device_type=device_type)  # once per layout
+
+
+def plan_attn_observe(shape, strides, dtype, strategy, *, offset_bytes: int = 0, device_type: str = "cuda") -> AttnObservePlan:
+    """The host plan of attn_observe for a tensor of `shape` / `strides` (elements) / `dtype` whose first element sits
+    `offset_bytes` past a 16-byte boundary: no tensor is touched.  A read-only kernel takes expanded (stride 0) dimensions and views
+    that overlap themselves as they are; only what it cannot index — a negative stride, a last dimension that is not contiguous,
+    leading dimensions that do not fold into one batch — is copied first.  Raises what the reference raises (the ValueError of
+    flatten_attention_for_quantization for the strategies attention states do not take, of initialize_qparams for an attn_head
+    tensor of fewer than 3 dimensions), ValueError for an empty tensor, and NotImplementedError for float64, CPU tensors and more
+    heads than the kernel's table holds."""
+    st = _strategy_name(strategy)
+    shape, strides = tuple(int(d) for d in shape), tuple(int(s) for s in strides)
+    if st in _ATTN_OBSERVE_REFUSED:
+        raise ValueError(_ATTN_OBSERVE_REFUSED[st])
+    if st not in ("attn_head", "tensor"):
+        raise NotImplementedError(f"ct_attn_observe serves the tensor and attn_head strategies, not {st!r}")
+    if dtype not in _FLOATS:
+        raise NotImplementedError(f"observing {dtype} is not supported by the MI355X path (float32, float16 and bfloat16 are)")
+    if device_type != "cuda":
+        raise NotImplementedError(f"ct_attn_observe runs on the MI355X; the tensor is on {device_type!r} (there is no CPU fallback)")
+    if st == "attn_head" and len(shape) < 3:
+        raise ValueError("Attention quant requires at least 3 observed dimensions")
+    if math.prod(shape) == 0:
+        raise ValueError(f"cannot observe an empty tensor of shape {shape}: the minimum of no elements is undefined")
+    if len(shape) == 0:
+        shape, strides = (1,), (1,)
+    per_head = st == "attn_head"
+    if per_head and shape[-3] > ATTN_OBSERVE_MAX_ENTRIES:
+        raise NotImplementedError(f"{shape[-3]} heads: ct_attn_observe's table holds {ATTN_OBSERVE_MAX_ENTRIES} entries")
+    reason = None
+    if any(s < 0 for s in strides):
+        reason = "negative strides"
+    elif shape[-1] > 1 and strides[-1] != 1:
+        reason = f"the last dimension has stride {strides[-1]}"
+    folded = None if reason else _attn_fold(shape, tuple(strides[:-1]) + (1,))
+    if reason is None and folded is None:
+        reason = "the leading dimensions do not fold into one batch dimension"
+    if reason is not None:
+        (B, H, S, D), xs = _attn_fold(shape, _dense_strides(shape))
+        return AttnObservePlan(False, D % 8 == 0, B, H, S, D, xs, per_head, H if per_head else 1, reason)
+    (B, H, S, D), xs = folded
+    vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, dtype.itemsize, D)
+    return AttnObservePlan(True, vec, B, H, S, D, xs, per_head, H if per_head else 1, None)
+
+
+def attn_observe_state(entries: int, device) -> torch.Tensor:
+    """the armed running state of `entries` scale entries: int32 (2, entries) order keys, row 0 the minima, row 1 the maxima"""
+    return attn_observe_arm(torch.empty((2, int(entries)), dtype=torch.int32, device=device))
+
+
+def attn_observe_arm(state: torch.Tensor) -> torch.Tensor:
+    """arm `state` in place: every entry forgets what it has seen (two fills, nothing waits)"""
+    state[0].fill_(_OBSERVE_EMPTY[0])
+    state[1].fill_(_OBSERVE_EMPTY[1])
+    return state
+
+
+def _observe_kind(num_bits, symmetric, qtype):
+    qtype = _check_qtype(qtype, num_bits)
+    if qtype == "float":
+        if int(num_bits) == 4:
+            raise NotImplementedError("FLOAT 4-bit attention states are not implemented by the MI355X path")
+        if not symmetric:
+            raise NotImplementedError("asymmetric FLOAT 8-bit observation is not implemented by the MI355X path")
+        return 1
+    if not 1 <= int(num_bits) <= 8:
+        raise NotImplementedError(f"INT {num_bits}-bit observation is not implemented by the MI355X path (1 to 8 bits are)")
+    return 0
+
+
+def _observe_out(given, shape, dtype, dev, what):
+    if given is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    t = given.data if isinstance(given, torch.nn.Parameter) else given
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return given
+
+
+def _attn_observe(items, *, num_bits, symmetric, qtype, strategy, zp_dtype, keep, want_minmax, global_scale=None):
+    """items: [(x, state, scale or None, zero_point or None)] of one or two states sharing dtype and arguments; ONE ct_attn_observe"""
+    if global_scale is not None:
+        raise NotImplementedError("a global scale on observed attention states is not implemented by the MI355X path")
+    kind = _observe_kind(num_bits, symmetric, qtype)
+    st = _strategy_name(strategy)
+    zp_dtype = zp_dtype if zp_dtype is not None else (_F8 if kind else torch.int8)
+    if zp_dtype not in (torch.int8, torch.int32, _F8, *_FLOATS):
+        raise NotImplementedError(f"a zero point of {zp_dtype} is not supported by the MI355X path")
+    x0 = items[0][0]
+    descs = (_lib.AttnObserveTensor * len(items))()
+    results, alive = [], []
+    for i, (x, state, scale, zero_point) in enumerate(items):
+        if x.dtype != x0.dtype or x.device != x0.device:
+            raise NotImplementedError("the two tensors of one launch share their dtype and device")
+        plan = _plan_attn_observe(x.shape, x.stride(), x.dtype, st, x.data_ptr() % 16, x.device.type)
+        xr = x
+        if not plan.in_place:
+            xr = x.contiguous()
+            plan = _plan_attn_observe(xr.shape, xr.stride(), xr.dtype, st, xr.data_ptr() % 16, xr.device.type)
+        dev = x.device
+        if state.dtype != torch.int32 or tuple(state.shape) != (2, plan.entries) or state.device != dev or not state.is_contiguous():
+            raise ValueError(f"the observer state of {plan.entries} entries is a contiguous int32 (2, {plan.entries}) tensor on {dev} "
+                             f"(attn_observe_state), got {state.dtype} {tuple(state.shape)} on {state.device}")
+        out_shape = (plan.H, 1, 1) if plan.per_head else (1,)
+        scale_dtype = x.dtype if scale is None else scale.dtype  # a module's parameter may be wider than the state it scales
+        if scale_dtype not in _FLOATS or (results and scale_dtype != results[0][0].dtype):
+            raise NotImplementedError(f"a scale of {scale_dtype} is not supported by the MI355X path (the two tensors of one launch share it)")
+        scale_out = _observe_out(scale, out_shape, scale_dtype, dev, "scale")
+        zp_out = _observe_out(zero_point, out_shape, zp_dtype, dev, "zero_point")
+        mn = torch.empty(out_shape, dtype=x.dtype, device=dev) if want_minmax else None
+        mx = torch.empty(out_shape, dtype=x.dtype, device=dev) if want_minmax else None
+        d = descs[i]
+        d.x, d.state, d.scale, d.zp, d.min_vals, d.max_vals = ptr(xr), ptr(state), ptr(scale_out), ptr(zp_out), ptr(mn), ptr(mx)
+        d.B, d.H, d.S, d.D = plan.B, plan.H, plan.S, plan.D
+        d.x_stride[:], d.per_head = plan.strides, int(plan.per_head)
+        results.append((scale_out, zp_out, mn, mx) if want_minmax else (scale_out, zp_out))
+        alive.append(xr)
+    sdt = results[0][0].dtype
+    call("ct_attn_observe", descs, len(items), kind, int(num_bits), int(bool(symmetric)), DT[x0.dtype], DT[sdt], DT[zp_dtype], int(bool(keep)),
+         stream_on(x0.device))
+    return results
+
+
+def attn_observe(x, state, *, num_bits, symmetric=True, qtype="int", strategy="attn_head", zp_dtype=None, keep=False, scale=None, zero_point=None,
+                 want_minmax=False, global_scale=None):
+    """A min-max observer's forward on a query / key / value state (..., H, S, D) — or, under the `tensor` strategy, any activation
+    (..., hidden) — read through its strides: torch.amin / amax per head (`attn_head`) or over the tensor, folded into `state`
+    (attn_observe_state), then calculate_qparams (quantization/utils/helpers.py:50-137) of the running extremes, evaluated in
+    x's dtype.  Returns (scale, zero_point) — scale in x's dtype of shape (H, 1, 1) or (1,), zero_point in `zp_dtype` (int8, or
+    zeros of float8_e4m3fn for FLOAT 8-bit) — and with `want_minmax` also (min_vals, max_vals) in x's dtype.  `scale` /
+    `zero_point` given (module parameters of that shape): the kernel writes them in place and they are what is returned.
+    keep=False: `state` is armed again behind the call (each call stands alone); keep=True: the next call folds into it.
+    Two launches, no copy of a strided view, no host synchronisation."""
+    return _attn_observe([(x, state, scale, zero_point)], num_bits=num_bits, symmetric=symmetric, qtype=qtype, strategy=strategy, zp_dtype=zp_dtype,
+                         keep=keep, want_minmax=want_minmax, global_scale=global_scale)[0]
+
+
+def attn_observe_pair(k, v, k_state, v_state, *, num_bits, symmetric=True, qtype="int", strategy="attn_head", zp_dtype=None, keep=False,
+                      k_scale=None, v_scale=None, k_zero_point=None, v_zero_point=None, want_minmax=False, global_scale=None):
+    """(attn_observe(k, k_state, ...), attn_observe(v, v_state, ...)) in the SAME two launches: K and V of one cache update keep
+    their own shapes, strides, states and outputs (MLA: different head dims) and share dtype and arguments"""
+    out = _attn_observe([(k, k_state, k_scale, k_zero_point), (v, v_state, v_scale, v_zero_point)], num_bits=num_bits, symmetric=symmetric, qtype=qtype,
+                        strategy=strategy, zp_dtype=zp_dtype, keep=keep, want_minmax=want_minmax, global_scale=global_scale)
+    return out[0], out[1]
+
+
 # --------------------------------------------------------------------------- attention: the head-dim rotation in the QDQ's launch
 ATTN_ROTATED_MAX_SIZE = 512  # the rotation blocks csrc/ct_attn_rot.hip serves: n / 8 lanes of one wave
 ATTN_ROTATED_MAX_UNITS = 256  # D / 8: a row is one pass of a workgroup's lanes

@@ -165,6 +165,48 @@ __device__ __forceinline__ MinMax mmk_finish(MinMaxKey a) {
     return m;
 }
 
+// ---- the 32-bit form of the same map: the running state of the strided observer (csrc/ct_attn_observe.hip) ---------------------
+// key = b ^ ((b >> 31, arithmetic) & 0x7fffffff) on the float32 bits of an element (bf16 / fp16 widen exactly).  Integer min / max on
+// the keys are exact and order-free, in registers, in LDS and as global atomics alike.  The empty keys are the identities of min and
+// max; the map is an involution.
+struct MinMaxKey32 {
+    int32_t mn, mx;
+};
+constexpr int32_t kKey32EmptyMin = 0x7fffffff, kKey32EmptyMax = (int32_t)0x80000000u;
+__device__ __forceinline__ int32_t mm_key32(uint32_t bits) { return (int32_t)(bits ^ ((uint32_t)((int32_t)bits >> 31) & 0x7fffffffu)); }
+__device__ __forceinline__ MinMaxKey32 mmk32_init() { return MinMaxKey32{kKey32EmptyMin, kKey32EmptyMax}; }
+__device__ __forceinline__ MinMaxKey32 mmk32_merge(MinMaxKey32 a, int32_t kmn, int32_t kmx) {
+    a.mn = a.mn < kmn ? a.mn : kmn;
+    a.mx = a.mx > kmx ? a.mx : kmx;
+    return a;
+}
+__device__ __forceinline__ MinMaxKey32 mmk32_acc(MinMaxKey32 a, float v) {
+    const int32_t k = mm_key32(f_bits(v));
+    return mmk32_merge(a, k, k);
+}
+template <int CTRL>
+__device__ __forceinline__ MinMaxKey32 mmk32_dpp(MinMaxKey32 a) {
+    return mmk32_merge(a, __builtin_amdgcn_update_dpp(0, a.mn, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, a.mx, CTRL, 0xf, 0xf, false));
+}
+// group_reduce on keys: every lane of the wave executes it; lpg <= 64
+__device__ __forceinline__ MinMaxKey32 mmk32_group_reduce(MinMaxKey32 a, int lpg) {
+    if (lpg >= 2) a = mmk32_dpp<0xB1>(a);
+    if (lpg >= 4) a = mmk32_dpp<0x4E>(a);
+    if (lpg >= 8) a = mmk32_dpp<0x141>(a);
+    if (lpg >= 16) a = mmk32_dpp<0x140>(a);
+    for (int d = 16; d < lpg; d <<= 1) a = mmk32_merge(a, __shfl_xor(a.mn, d, 64), __shfl_xor(a.mx, d, 64));
+    return a;
+}
+// the MinMax the float reduction would have produced (up to the sign of a zero)
+__device__ __forceinline__ MinMax mmk32_finish(MinMaxKey32 a) {
+    const uint32_t bmn = (uint32_t)mm_key32((uint32_t)a.mn), bmx = (uint32_t)mm_key32((uint32_t)a.mx);
+    MinMax m;
+    m.nan = ((bmn & 0x7fffffffu) > 0x7f800000u) | ((bmx & 0x7fffffffu) > 0x7f800000u);
+    m.mn = bits_f(bmn);
+    m.mx = bits_f(bmx);
+    return m;
+}
+
 // the MinMax the float reduction would have produced, as far as a symmetric scheme can tell: {0, amax, nan}
 template <int XDT>
 __device__ __forceinline__ MinMax absmax_finish(uint32_t acc) {

@@ -1,5 +1,6 @@
 from .dynamic import compute_dynamic_scales_and_zp, forward_quantize
 from .forward import calculate_range, dequantize, fake_quantize, quantize
+from .observer import MinMaxObserver
 from .quant_args import (
     ActivationOrdering,
     DynamicType,
@@ -20,6 +21,7 @@ __all__ = [
     "forward_quantize",
     "calculate_qparams_from_weight",
     "is_module_quantized",
+    "MinMaxObserver",
     "QuantizationArgs",
     "QuantizationScheme",
     "QuantizationStatus",

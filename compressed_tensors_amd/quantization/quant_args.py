@@ -72,6 +72,7 @@ class QuantizationArgs:
     actorder: Optional[ActivationOrdering] = None
     scale_dtype: Optional[torch.dtype] = None  # quant_args.py:201-202
     zp_dtype: Optional[torch.dtype] = None
+    observer: Optional[str] = None  # quant_args.py:203-209; None: quantization.observer picks the reference's default for static arguments
 
     def __post_init__(self):
         self.type = QuantizationType(getattr(self.type, "value", self.type))

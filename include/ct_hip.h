@@ -399,6 +399,38 @@ int ct_attn_qdq(const ct_attn_tensor* tensors, int n, int mode, int kind, int bi
 int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_size, int rot_mask, int mode, int kind, int bits, int xdt, int sdt,
                     int zdt, int tdt, int odt, ct_stream_t stream);
 
+/* The min-max calibration observer of the states ct_attn_qdq serves (an observer's forward: torch.amin / amax per head or per
+ * tensor, then quantization/utils/helpers.py:50-137 calculate_qparams): one or two 4-D tensors (B, H, S, D) read IN PLACE through
+ * their strides (as ct_attn_tensor: unit last stride, non-negative b / h / s element strides, 0 = an expanded dimension); rows of
+ * whole aligned 8-element units move as vectors, everything else element by element.  `per_head` 0: one entry (the tensor
+ * strategy); 1: H entries (attn_head), at most 1024 (more: CT_ERR_UNSUPPORTED).
+ * `state`: caller-owned device memory, 2 * entries 32-bit order keys — all minimum keys, then all maximum keys.  A key is the
+ * float32 bit pattern b of an element mapped by b ^ ((b >> 31, arithmetic) & 0x7fffffff): signed integer order == float order, a
+ * positive NaN above +inf, a negative NaN below -inf.  Armed (empty) state: 0x7fffffff in the minimum half, 0x80000000 in the
+ * maximum half.  The call folds the tensor into the state with integer min / max (exact, order-free: bit-deterministic), then
+ * writes `scale` (dtype sdt) and `zp` (dtype zdt; NULL: not written) of the running extremes and, where given, `min_vals` /
+ * `max_vals` (dtype xdt; both NaN where a NaN was seen).  keep 0: the state is re-armed behind the call (a memoryless observer);
+ * 1: it stays, and the next call folds into it. */
+typedef struct ct_attn_observe_tensor {
+    const void* x;
+    int32_t* state;
+    void* scale;
+    void* zp;                      /* NULL: not written */
+    void* min_vals;                /* NULL: not written */
+    void* max_vals;
+    int64_t B, H, S, D;
+    int64_t x_stride[3];           /* b, h, s: elements */
+    int64_t per_head;
+} ct_attn_observe_tensor;          /* 14 64-bit words */
+
+/* kind 0 INT (bits 1..8, symmetric or not), 1 FLOAT 8-bit (float8_e4m3fn, symmetric; bits ignored).  xdt: a float dtype; the
+ * arithmetic of calculate_qparams runs in it, as ct_minmax_qparams{,_float} run it.  n = 2: both tensors (K and V) share every
+ * argument and every launch.  Two launches (fold, finalize), whatever the size; the descriptors travel as kernel arguments.
+ * Allocates nothing, never synchronises, keeps no device state.  CT_ERR_INVALID_ARG for a negative shape or stride, an empty
+ * tensor (the minimum of no elements is undefined: torch.amin raises) and B * H * S >= 2^31. */
+int ct_attn_observe(const ct_attn_observe_tensor* tensors, int n, int kind, int bits, int symmetric, int xdt, int sdt, int zdt, int keep,
+                    ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
