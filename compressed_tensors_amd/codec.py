@@ -513,6 +513,60 @@ def _attn_unit_aligned(offset_bytes, sizes, strides, itemsize, D) -> bool:
     return D % 8 == 0 and offset_bytes % a == 0 and all((st * itemsize) % a == 0 for sz, st in zip(sizes, strides) if sz > 1)
 
 
+@functools.lru_cache(maxsize=1024)
+def _dense_strides(shape) -> tuple:
+    return tuple(torch.empty(tuple(shape), device="meta").stride())
+
+
+def _attn_view(shape, strides, writes: bool):
+    """The rule every strided attention launch plans by: (in_place, (B, H, S, D), the b / h / s strides, reason) of a tensor of at
+    least one dimension.  Read in place through its strides unless a stride is negative, the last dimension is not contiguous, the
+    leading dimensions do not fold into one batch (_attn_fold) or — `writes`: the launch lays out an output like the input —
+    the tensor overlaps itself in storage; otherwise `reason` says why, and the view is the dense copy's."""
+    reason = None
+    if any(s < 0 for s in strides):
+        reason = "negative strides"
+    elif shape[-1] > 1 and strides[-1] != 1:
+        reason = f"the last dimension has stride {strides[-1]}"
+    elif writes and _attn_overlaps(shape, strides):
+        reason = "the tensor overlaps itself in storage"
+    folded = None if reason else _attn_fold(shape, tuple(strides[:-1]) + (1,))
+    if reason is None and folded is None:
+        reason = "the leading dimensions do not fold into one batch dimension"
+    if reason is not None:
+        folded = _attn_fold(shape, _dense_strides(shape))
+    return reason is None, folded[0], folded[1], reason
+
+
+def _attn_refusals(global_scale, qtype, num_bits, quantizes: bool, what: str):
+    """what no strided attention launch serves — a global scale and, where it quantizes, FLOAT 4-bit states; returns the checked qtype"""
+    if global_scale is not None:
+        raise NotImplementedError(f"a global scale on {what} is not implemented by the MI355X path")
+    if not quantizes:
+        return qtype
+    qtype = _check_qtype(qtype, num_bits)
+    if qtype == "float" and int(num_bits) == 4:
+        raise NotImplementedError("FLOAT 4-bit attention states are not implemented by the MI355X path")
+    return qtype
+
+
+def _attn_describe(d, x, layout_of, rest):
+    """One tensor of a strided launch -> (the tensor read, what `layout_of` gave for it).  Plans x —
+    layout_of(shape, strides, dtype, offset_bytes, *rest) -> (plan, ...), one of the two functions cached per layout (_attn_layout,
+    _plan_attn_observe: what depends on x comes first in both, and both return a tuple that starts with the plan) —, and where the
+    plan does not read it in place copies it (`.contiguous()`) and plans the copy; then fills the geometry fields AttnTensor and
+    AttnObserveTensor share.  One function for both and `rest` as a tuple: the decode-shape calls are host-bound, and a frame
+    and a re-packed argument list per tensor showed in them."""
+    got = layout_of(x.shape, x.stride(), x.dtype, x.data_ptr() % 16, *rest)
+    if not got[0].in_place:
+        x = x.contiguous()
+        got = layout_of(x.shape, x.stride(), x.dtype, x.data_ptr() % 16, *rest)
+    plan = got[0]
+    d.x, d.B, d.H, d.S, d.D = ptr(x), plan.B, plan.H, plan.S, plan.D
+    d.x_stride[:], d.per_head = plan.strides, int(plan.per_head)
+    return x, got
+
+
 def plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, *, out_dtype=None, offset_bytes: int = 0) -> AttnPlan:
     """The host plan of the attn_* functions for a tensor of `shape` / `strides` (elements) / `dtype` whose first element sits
     `offset_bytes` past a 16-byte boundary, with a scale of `scale_shape`: no tensor is touched.  Raises what the reference raises
@@ -539,31 +593,13 @@ def plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, *, out_dtype=Non
     if len(shape) == 0:
         shape, strides = (1,), (1,)
     out_dtype = dtype if out_dtype is None else out_dtype
-    isz, osz = dtype.itemsize, out_dtype.itemsize
-    reason = None
-    if any(s < 0 for s in strides):
-        reason = "negative strides"
-    elif shape[-1] > 1 and strides[-1] != 1:
-        reason = f"the last dimension has stride {strides[-1]}"
-    elif _attn_overlaps(shape, strides):
-        reason = "the tensor overlaps itself in storage"
-    folded = None if reason else _attn_fold(shape, tuple(strides[:-1]) + (1,))
-    if reason is None and folded is None:
-        reason = "the leading dimensions do not fold into one batch dimension"
-    per_head = st == "attn_head" and scale_numel != 1
-    if reason is not None:
-        dense = []
-        run = 1
-        for sz in reversed(shape):
-            dense.append(run)
-            run *= max(sz, 1)
-        (B, H, S, D), xs = _attn_fold(shape, tuple(reversed(dense)))
-        return AttnPlan(False, D % 8 == 0, B, H, S, D, xs, per_head, reason)
-    (B, H, S, D), xs = folded
-    vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, isz, D)
-    if vec and _attn_is_dense(shape, strides):  # the output keeps these strides; otherwise it is dense in the same order: multiples of D
-        vec = _attn_unit_aligned(0, (B, H, S), xs, osz, D)
-    return AttnPlan(True, vec, B, H, S, D, xs, per_head, None)
+    in_place, (B, H, S, D), xs, reason = _attn_view(shape, strides, writes=True)
+    vec = D % 8 == 0
+    if in_place:
+        vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, dtype.itemsize, D)
+        if vec and _attn_is_dense(shape, strides):  # the output keeps these strides; otherwise it is dense in the same order: multiples of D
+            vec = _attn_unit_aligned(0, (B, H, S), xs, out_dtype.itemsize, D)
+    return AttnPlan(in_place, vec, B, H, S, D, xs, st == "attn_head" and scale_numel != 1, reason)
 
 
 _ATTN_MODES = {"fake": 0, "quantize": 1, "dequantize": 2}
@@ -589,7 +625,7 @@ def _attn_out_strides(shape, strides, dtype, scale_shape, scale_strides, scale_d
 
 
 @functools.lru_cache(maxsize=4096)
-def _attn_layout(shape, strides, dtype, scale_shape, scale_strides, scale_dtype, strategy, out_dtype, offset_bytes, mode, rounds):
+def _attn_layout(shape, strides, dtype, offset_bytes, scale_shape, scale_strides, scale_dtype, strategy, out_dtype, mode, rounds):  # _attn_describe's order
     """everything one call decides from shapes alone, once per layout: (plan, the output's strides, its b / h / s strides) — or
     (plan, None, None) for a tensor that is copied first (the caller asks again for the copy)"""
     plan = plan_attn_qdq(shape, strides, dtype, scale_shape, strategy, out_dtype=out_dtype, offset_bytes=offset_bytes)
@@ -606,35 +642,6 @@ def _attn_layout(shape, strides, dtype, scale_shape, scale_strides, scale_dtype,
     return plan, out_strides, view[1]
 
 
-def _attn_one(x, scale, zero_point, mode, strategy, out_dtype, dev, rounds, rotated=False):
-    """one descriptor of ct_attn_qdq: (AttnTensor fields, out, zero-point dtype code, tensors to keep alive).  `rotated`
-    (ct_attn_rot_qdq, a tensor plan_attn_rot_qdq fuses): x is read through its own strides, the output is laid out as the
-    composition lays it out — what the QDQ gives for the contiguous rotated tensor of the same shape"""
-    if zero_point is not None and zero_point.numel() != scale.numel():
-        raise ValueError(f"zero_point shape {tuple(zero_point.shape)} does not match scale shape {tuple(scale.shape)}")
-    tail = (scale.shape, scale.stride(), scale.dtype, strategy, out_dtype)
-    plan, out_strides, out_bhs = _attn_layout(x.shape, x.stride(), x.dtype, *tail, x.data_ptr() % 16, mode, rounds)
-    xr = x
-    if rotated:
-        # hadamard_transform(x.contiguous()) is torch.empty_like of a tensor torch calls contiguous: dense strides — or x's own
-        # where x already counts as contiguous (a decode step's S = 1 view keeps its stride in the size-1 dimension)
-        rot_strides = x.stride() if x.is_contiguous() else _dense_strides(x.shape)
-        _, out_strides, out_bhs = _attn_layout(x.shape, rot_strides, x.dtype, *tail, 0, mode, rounds)
-    elif not plan.in_place:
-        xr = x.contiguous()
-        plan, out_strides, out_bhs = _attn_layout(xr.shape, xr.stride(), xr.dtype, *tail, xr.data_ptr() % 16, mode, rounds)
-    out = torch.empty_strided(xr.shape, out_strides, dtype=out_dtype, device=xr.device)
-    sd = scale if (scale.device == dev and scale.is_contiguous()) else _dev(scale, dev)  # read element by element: no alignment needed
-    if zero_point is None:
-        zd, zdt = None, -1
-    elif zero_point.device == dev and zero_point.is_contiguous() and zero_point.dtype in DT and zero_point.dtype is not torch.bool:
-        zd, zdt = zero_point, DT[zero_point.dtype]
-    else:
-        zd, zdt = _zp_arg(zero_point, dev)
-    item = (ptr(xr), ptr(out), ptr(sd), ptr(zd), plan.B, plan.H, plan.S, plan.D, plan.strides, out_bhs, int(plan.per_head))
-    return item, out, zdt, (xr, sd, zd)
-
-
 @functools.lru_cache(maxsize=None)
 def _attn_result_dtype(x_dtype, x_zero_dim: bool, scale_dtype, scale_zero_dim: bool):
     """_result_dtype on stand-ins of the same dtypes and dimensionality (once per combination)"""
@@ -643,21 +650,13 @@ def _attn_result_dtype(x_dtype, x_zero_dim: bool, scale_dtype, scale_zero_dim: b
     return _result_dtype(x, scale, scale_zero_dim)
 
 
-@functools.lru_cache(maxsize=1024)
-def _dense_strides(shape) -> tuple:
-    return tuple(torch.empty(tuple(shape), device="meta").stride())
-
-
 def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None, global_scale=None, rot_size=0, rot_mask=0):
     """tensors: [(x, scale, zero_point)] of one or two q / k / v states sharing dtypes and arguments -> [out]; ONE ct_attn_qdq —
-    or, with `rot_mask` (bit i: tensor i is rotated over runs of `rot_size` elements first), ONE ct_attn_rot_qdq"""
+    or, with `rot_mask` (bit i: tensor i is rotated over runs of `rot_size` elements first), ONE ct_attn_rot_qdq.  A rotated
+    tensor (one plan_attn_rot_qdq fuses) is read through its own strides and its output laid out as the composition lays it
+    out: what the QDQ gives for the contiguous rotated tensor of the same shape"""
     st = _strategy_name(strategy)
-    if global_scale is not None:
-        raise NotImplementedError("a global scale on attention states is not implemented by the MI355X path")
-    if mode != "dequantize":
-        qtype = _check_qtype(qtype, num_bits)
-        if qtype == "float" and int(num_bits) == 4:
-            raise NotImplementedError("FLOAT 4-bit attention states are not implemented by the MI355X path")
+    qtype = _attn_refusals(global_scale, qtype, num_bits, mode != "dequantize", "attention states")
     x0, s0, z0 = tensors[0]
     for x, s, z in tensors:
         if mode == "dequantize":
@@ -685,14 +684,30 @@ def _attn_qdq(tensors, mode: str, *, num_bits, strategy, qtype="int", dtype=None
     dev = _compute_device(x0, s0)
     descs = (_lib.AttnTensor * len(tensors))()
     outs, keep, zdt = [], [], -1
+    rounds = mode != "dequantize" and qtype == "int"
     for i, (x, s, z) in enumerate(tensors):
+        if z is not None and z.numel() != s.numel():
+            raise ValueError(f"zero_point shape {tuple(z.shape)} does not match scale shape {tuple(s.shape)}")
         xd = x if x.device == dev else x.to(dev)
-        item, out, zdt, alive = _attn_one(xd, s, z, mode, st, out_dtype, dev, mode != "dequantize" and qtype == "int", bool((rot_mask >> i) & 1))
         d = descs[i]
-        d.x, d.out, d.scale, d.zp, d.B, d.H, d.S, d.D = item[:8]
-        d.x_stride[:], d.out_stride[:], d.per_head = item[8], item[9], item[10]
+        tail = (s.shape, s.stride(), s.dtype, st, out_dtype, mode, rounds)
+        xr, (_, out_strides, out_bhs) = _attn_describe(d, xd, _attn_layout, tail)
+        if (rot_mask >> i) & 1:
+            # hadamard_transform(x.contiguous()) is torch.empty_like of a tensor torch calls contiguous: dense strides — or x's own
+            # where x already counts as contiguous (a decode step's S = 1 view keeps its stride in the size-1 dimension)
+            rot_strides = xd.stride() if xd.is_contiguous() else _dense_strides(xd.shape)
+            _, out_strides, out_bhs = _attn_layout(xd.shape, rot_strides, xd.dtype, 0, *tail)
+        out = torch.empty_strided(xr.shape, out_strides, dtype=out_dtype, device=xr.device)
+        sd = s if (s.device == dev and s.is_contiguous()) else _dev(s, dev)  # read element by element: no alignment needed
+        if z is None:
+            zd = None
+        elif z.device == dev and z.is_contiguous() and z.dtype in DT and z.dtype is not torch.bool:
+            zd, zdt = z, DT[z.dtype]
+        else:
+            zd, zdt = _zp_arg(z, dev)
+        d.out, d.scale, d.zp, d.out_stride[:] = ptr(out), ptr(sd), ptr(zd), out_bhs
         outs.append(_home(out, x))
-        keep.append(alive)
+        keep.append((xr, sd, zd))
     kind = 1 if (mode != "dequantize" and qtype == "float") else 0
     tail = (_ATTN_MODES[mode], kind, int(num_bits) if mode != "dequantize" else 8, DT[x0.dtype], DT[s0.dtype], zdt, DT[T], DT[out_dtype], stream_on(dev))
     if rot_mask:
@@ -761,8 +776,8 @@ class AttnObservePlan(NamedTuple):
 
 
 @functools.lru_cache(maxsize=4096)
-def _plan_attn_observe(shape, strides, dtype, st, offset_bytes, device_type):
-    return plan_attn_observe(shape, strides, dtype, st, offset_bytes=offset_bytes, device_type=device_type)  # once per layout
+def _plan_attn_observe(shape, strides, dtype, offset_bytes, st, device_type):  # _attn_describe's order, and its 1-tuple
+    return (plan_attn_observe(shape, strides, dtype, st, offset_bytes=offset_bytes, device_type=device_type),)  # once per layout
 
 
 def plan_attn_observe(shape, strides, dtype, strategy, *, offset_bytes: int = 0, device_type: str = "cuda") -> AttnObservePlan:
@@ -792,20 +807,9 @@ def plan_attn_observe(shape, strides, dtype, strategy, *, offset_bytes: int = 0,
     per_head = st == "attn_head"
     if per_head and shape[-3] > ATTN_OBSERVE_MAX_ENTRIES:
         raise NotImplementedError(f"{shape[-3]} heads: ct_attn_observe's table holds {ATTN_OBSERVE_MAX_ENTRIES} entries")
-    reason = None
-    if any(s < 0 for s in strides):
-        reason = "negative strides"
-    elif shape[-1] > 1 and strides[-1] != 1:
-        reason = f"the last dimension has stride {strides[-1]}"
-    folded = None if reason else _attn_fold(shape, tuple(strides[:-1]) + (1,))
-    if reason is None and folded is None:
-        reason = "the leading dimensions do not fold into one batch dimension"
-    if reason is not None:
-        (B, H, S, D), xs = _attn_fold(shape, _dense_strides(shape))
-        return AttnObservePlan(False, D % 8 == 0, B, H, S, D, xs, per_head, H if per_head else 1, reason)
-    (B, H, S, D), xs = folded
-    vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, dtype.itemsize, D)
-    return AttnObservePlan(True, vec, B, H, S, D, xs, per_head, H if per_head else 1, None)
+    in_place, (B, H, S, D), xs, reason = _attn_view(shape, strides, writes=False)
+    vec = _attn_unit_aligned(offset_bytes, (B, H, S), xs, dtype.itemsize, D) if in_place else D % 8 == 0
+    return AttnObservePlan(in_place, vec, B, H, S, D, xs, per_head, H if per_head else 1, reason)
 
 
 def attn_observe_state(entries: int, device) -> torch.Tensor:
@@ -820,23 +824,10 @@ def attn_observe_arm(state: torch.Tensor) -> torch.Tensor:
     return state
 
 
-def _observe_kind(num_bits, symmetric, qtype):
-    qtype = _check_qtype(qtype, num_bits)
-    if qtype == "float":
-        if int(num_bits) == 4:
-            raise NotImplementedError("FLOAT 4-bit attention states are not implemented by the MI355X path")
-        if not symmetric:
-            raise NotImplementedError("asymmetric FLOAT 8-bit observation is not implemented by the MI355X path")
-        return 1
-    if not 1 <= int(num_bits) <= 8:
-        raise NotImplementedError(f"INT {num_bits}-bit observation is not implemented by the MI355X path (1 to 8 bits are)")
-    return 0
-
-
 def _observe_out(given, shape, dtype, dev, what):
     if given is None:
         return torch.empty(shape, dtype=dtype, device=dev)
-    t = given.data if isinstance(given, torch.nn.Parameter) else given
+    t = given  # (a Parameter answers these itself: isinstance(x, Parameter) is a Python-level metaclass check, 0.8 us on a plain tensor)
     if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
         raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
     return given
@@ -844,9 +835,11 @@ def _observe_out(given, shape, dtype, dev, what):
 
 def _attn_observe(items, *, num_bits, symmetric, qtype, strategy, zp_dtype, keep, want_minmax, global_scale=None):
     """items: [(x, state, scale or None, zero_point or None)] of one or two states sharing dtype and arguments; ONE ct_attn_observe"""
-    if global_scale is not None:
-        raise NotImplementedError("a global scale on observed attention states is not implemented by the MI355X path")
-    kind = _observe_kind(num_bits, symmetric, qtype)
+    kind = int(_attn_refusals(global_scale, qtype, num_bits, True, "observed attention states") == "float")
+    if kind and not symmetric:
+        raise NotImplementedError("asymmetric FLOAT 8-bit observation is not implemented by the MI355X path")
+    if not kind and not 1 <= int(num_bits) <= 8:
+        raise NotImplementedError(f"INT {num_bits}-bit observation is not implemented by the MI355X path (1 to 8 bits are)")
     st = _strategy_name(strategy)
     zp_dtype = zp_dtype if zp_dtype is not None else (_F8 if kind else torch.int8)
     if zp_dtype not in (torch.int8, torch.int32, _F8, *_FLOATS):
@@ -857,11 +850,8 @@ def _attn_observe(items, *, num_bits, symmetric, qtype, strategy, zp_dtype, keep
     for i, (x, state, scale, zero_point) in enumerate(items):
         if x.dtype != x0.dtype or x.device != x0.device:
             raise NotImplementedError("the two tensors of one launch share their dtype and device")
-        plan = _plan_attn_observe(x.shape, x.stride(), x.dtype, st, x.data_ptr() % 16, x.device.type)
-        xr = x
-        if not plan.in_place:
-            xr = x.contiguous()
-            plan = _plan_attn_observe(xr.shape, xr.stride(), xr.dtype, st, xr.data_ptr() % 16, xr.device.type)
+        d = descs[i]
+        xr, (plan,) = _attn_describe(d, x, _plan_attn_observe, (st, x.device.type))
         dev = x.device
         if state.dtype != torch.int32 or tuple(state.shape) != (2, plan.entries) or state.device != dev or not state.is_contiguous():
             raise ValueError(f"the observer state of {plan.entries} entries is a contiguous int32 (2, {plan.entries}) tensor on {dev} "
@@ -874,10 +864,7 @@ def _attn_observe(items, *, num_bits, symmetric, qtype, strategy, zp_dtype, keep
         zp_out = _observe_out(zero_point, out_shape, zp_dtype, dev, "zero_point")
         mn = torch.empty(out_shape, dtype=x.dtype, device=dev) if want_minmax else None
         mx = torch.empty(out_shape, dtype=x.dtype, device=dev) if want_minmax else None
-        d = descs[i]
-        d.x, d.state, d.scale, d.zp, d.min_vals, d.max_vals = ptr(xr), ptr(state), ptr(scale_out), ptr(zp_out), ptr(mn), ptr(mx)
-        d.B, d.H, d.S, d.D = plan.B, plan.H, plan.S, plan.D
-        d.x_stride[:], d.per_head = plan.strides, int(plan.per_head)
+        d.state, d.scale, d.zp, d.min_vals, d.max_vals = ptr(state), ptr(scale_out), ptr(zp_out), ptr(mn), ptr(mx)
         results.append((scale_out, zp_out, mn, mx) if want_minmax else (scale_out, zp_out))
         alive.append(xr)
     sdt = results[0][0].dtype
@@ -955,7 +942,7 @@ def plan_attn_rot_qdq(shape, strides, dtype, size: int, scale_shape, strategy, *
         reason = f"rows of {D} elements exceed one pass of {ATTN_ROTATED_MAX_UNITS} units"
     elif not ap.in_place:
         reason = ap.reason
-    elif not _attn_unit_aligned(offset_bytes, (ap.B, ap.H, ap.S), ap.strides, dtype.itemsize, D):
+    elif not ap.vector:  # (the output side never decides: a dense tensor's strides are multiples of D, and D is whole units here)
         reason = "the storage offset or a stride breaks the alignment of the 8-element units"
     return AttnRotPlan(reason is None, ap.in_place, reason, _dense_strides(tuple(int(d) for d in shape)), hp, ap)
 

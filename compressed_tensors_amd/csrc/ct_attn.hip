@@ -4,7 +4,7 @@
 // expanded batches — with one scale per tensor or per head, K and V in one launch.
 //
 // The arithmetic is ct_quant.hip's (quant_core / fake_dequant_rt / dequant_core of ct_quant_core.h, the same reciprocal
-// shortcuts as quant_units_kernel), so the bits are those of ct_fake_quantize / ct_quantize / ct_dequantize on the same values.
+// shortcuts as quant_units_kernel: attn_row_qparams / attn_quant_unit of ct_attn.h, shared with ct_attn_rot.hip), so the bits are those of ct_fake_quantize / ct_quantize / ct_dequantize on the same values.
 //
 // Shape of the work: a row of D elements is one scale and one contiguous run.  The rows are enumerated in the OUTPUT's memory
 // order — the host sorts the b / h / s dimensions by output stride, so that a transposed view's neighbouring rows (b, s, h), not its
@@ -21,18 +21,15 @@ namespace ct {
 // codes' dtype is p.xdt).
 template <int XDT, int TDT, int MODE>
 __global__ __launch_bounds__(kBlock) void attn_qdq_kernel(AttnParams p) {
-    const AttnT& t = p.t[(p.n == 2 && blockIdx.x >= p.t[1].first_block) ? 1 : 0];
-    const uint32_t lpr = 1u << t.lpr_shift, rpb = (uint32_t)kBlock >> t.lpr_shift;
-    const uint32_t lane = threadIdx.x & (lpr - 1u), rl = threadIdx.x >> t.lpr_shift;
-    const uint32_t upr = (t.D + 7u) >> 3;
-    const uint32_t row0 = (blockIdx.x - t.first_block) * (rpb * kAttnRows) + rl;
-    const bool has_zp = t.zp != nullptr;
+    const AttnT& t = p.t[attn_tensor_of(p)];
+    const AttnLanes g = attn_lanes(t);
+    const uint32_t row0 = (blockIdx.x - t.first_block) * (g.rpb * kAttnRows) + g.rl;
     const bool vec = t.vec != 0u;
     AttnRow r[kAttnRows];
 #pragma unroll
-    for (int i = 0; i < kAttnRows; ++i) r[i] = attn_row(t, row0 + (uint32_t)i * rpb);
+    for (int i = 0; i < kAttnRows; ++i) r[i] = attn_row(t, row0 + (uint32_t)i * g.rpb);
 
-    for (uint32_t c = lane; c < upr; c += lpr) {
+    for (uint32_t c = g.lane; c < g.upr; c += g.lpr) {
         const uint32_t c0 = c << 3;
         const int n = (int)((t.D - c0) < 8u ? (t.D - c0) : 8u);
         float v[kAttnRows][8];
@@ -71,28 +68,15 @@ __global__ __launch_bounds__(kBlock) void attn_qdq_kernel(AttnParams p) {
 #pragma unroll
         for (int i = 0; i < kAttnRows; ++i) {
             if (!r[i].valid) continue;
-            const float s = load_rt(t.scale, p.sdt, r[i].si);
-            const float zraw = has_zp ? load_rt(t.zp, p.zdt, r[i].si) : 0.0f;
             if constexpr (MODE == ATTN_DQ) {
-                const float z = round_to<TDT>(zraw);  // zp.to(scale.dtype)
+                const bool has_zp = t.zp != nullptr;
+                const float s = load_rt(t.scale, p.sdt, r[i].si);
+                const float z = round_to<TDT>(has_zp ? load_rt(t.zp, p.zdt, r[i].si) : 0.0f);  // zp.to(scale.dtype)
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
                     if (k < n) v[i][k] = dequant_core<TDT>(v[i][k], has_zp, z, s);
             } else {
-                const float z = round_to<XDT>(zraw);           // zp.to(x.dtype)
-                const float zs = round_to_rt(p.sdt, zraw);     // zp.to(scale.dtype)
-                // one reciprocal per row instead of a divide per element where quant_units_kernel takes it too
-                const bool can_rcp = (XDT == CT_BF16 && TDT == CT_BF16 && p.sdt == CT_BF16) || (XDT == CT_F16 && TDT == CT_F16 && p.sdt == CT_F16) ||
-                                     TDT == CT_F32;
-                const float rs = can_rcp ? (TDT == CT_BF16 ? bf16_fast_rcp(s) : (TDT == CT_F16 ? f16_newton_rcp(s) : f32_fast_rcp(s))) : 0.0f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k < n) {
-                        float q = quant_core<TDT>(v[i][k], s, has_zp, z, p.qmin, p.qmax, rs, p.fkind);
-                        if constexpr (MODE == ATTN_FQ) q = fake_dequant_rt(p.sdt, q, has_zp, zs, s);
-                        v[i][k] = q;
-                    }
-                }
+                attn_quant_unit<TDT, MODE>(p, attn_row_qparams<XDT, TDT>(p, t, r[i].si), v[i], n);
             }
             store_unit(t.out, p.odt, r[i].ooff + c0, v[i], n, vec);
         }
@@ -107,21 +91,11 @@ extern "C" int ct_attn_qdq(const ct_attn_tensor* tensors, int n, int mode, int k
                            ct_stream_t stream) {
     CT_REQUIRE(tensors != nullptr && (n == 1 || n == 2), "ct_attn_qdq takes one or two tensors, got %d", n);
     CT_REQUIRE(mode >= ATTN_FQ && mode <= ATTN_DQ, "mode must be 0 (fake), 1 (quantize) or 2 (dequantize), got %d", mode);
-    CT_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (INT) or 1 (FLOAT 8-bit), got %d", kind);
-    CT_REQUIRE(is_float_dt(sdt), "scale dtype code %d is not a float type", sdt);
-    if (mode == ATTN_DQ) {
-        CT_REQUIRE(xdt == CT_I8 || xdt == CT_I32 || xdt == CT_F8E4M3 || is_float_dt(xdt), "unsupported x_q dtype %d", xdt);
-        CT_REQUIRE(is_float_dt(odt), "unsupported output dtype %d", odt);
-    } else {
-        CT_REQUIRE(kind == 1 || (bits >= 1 && bits <= 8), "num_bits must be in [1, 8], got %d", bits);
-        CT_REQUIRE(xt_ok(xdt, tdt), "unsupported (x dtype, result dtype) = (%d, %d)", xdt, tdt);
-        if (mode == ATTN_FQ) CT_REQUIRE(is_float_dt(odt), "unsupported output dtype %d", odt);
-        else if (kind) CT_REQUIRE(odt == CT_F8E4M3 || is_float_dt(odt), "unsupported output dtype %d", odt);
-        else CT_REQUIRE(odt == CT_I8 || odt == CT_I32 || is_float_dt(odt), "unsupported output dtype %d", odt);
-    }
+    int rc = attn_qdq_check(mode, kind, bits, xdt, sdt, tdt, odt);
+    if (rc) return rc;
     AttnParams p;
     int64_t blocks = 0;
-    const int rc = attn_fill(p, tensors, n, kind, bits, xdt, sdt, zdt, odt, mode != ATTN_DQ || xdt == CT_I8 || xdt == CT_F8E4M3, blocks, "ct_attn_qdq");
+    rc = attn_qdq_fill(p, tensors, n, kind, bits, xdt, sdt, zdt, odt, mode != ATTN_DQ || xdt == CT_I8 || xdt == CT_F8E4M3, false, blocks, "ct_attn_qdq");
     if (rc) return rc;
     if (blocks == 0) return CT_OK;
     const dim3 grid((unsigned)blocks);
@@ -131,10 +105,8 @@ extern "C" int ct_attn_qdq(const ct_attn_tensor* tensors, int n, int mode, int k
             case CT_F16: hipLaunchKernelGGL((attn_qdq_kernel<CT_F16, CT_F16, ATTN_DQ>), grid, dim3(kBlock), 0, as_stream(stream), p); break;
             default: hipLaunchKernelGGL((attn_qdq_kernel<CT_F32, CT_F32, ATTN_DQ>), grid, dim3(kBlock), 0, as_stream(stream), p); break;
         }
-    } else if (mode == ATTN_Q) {
-        CT_DISPATCH_XT(xdt, tdt, hipLaunchKernelGGL((attn_qdq_kernel<X, T, ATTN_Q>), grid, dim3(kBlock), 0, as_stream(stream), p));
     } else {
-        CT_DISPATCH_XT(xdt, tdt, hipLaunchKernelGGL((attn_qdq_kernel<X, T, ATTN_FQ>), grid, dim3(kBlock), 0, as_stream(stream), p));
+        CT_ATTN_DISPATCH_FQ_Q(mode, xdt, tdt, hipLaunchKernelGGL((attn_qdq_kernel<X, T, M>), grid, dim3(kBlock), 0, as_stream(stream), p));
     }
     CT_LAUNCH_CHECK("ct_attn_qdq");
 }

@@ -41,14 +41,9 @@ static inline void obs_magic(uint32_t d, uint32_t& M, uint32_t& sh) {
 }
 
 __device__ __forceinline__ AttnRow obs_row(const AttnT& t, const ObsT& o, uint32_t row) {
-    AttnRow r;
-    r.valid = row < t.rows;
     const uint32_t q = (uint32_t)(((uint64_t)row * o.magic2) >> o.shift2), i2 = row - q * t.n2;
     const uint32_t i0 = (uint32_t)(((uint64_t)q * o.magic1) >> o.shift1), i1 = q - i0 * t.n1;
-    r.xoff = (int64_t)i0 * t.xs[0] + (int64_t)i1 * t.xs[1] + (int64_t)i2 * t.xs[2];
-    r.ooff = 0;
-    r.si = t.head_pos == 0u ? 0u : (t.head_pos == 1u ? i0 : (t.head_pos == 2u ? i1 : i2));
-    return r;
+    return attn_row_at(t, row, i0, i1, i2);  // (the output side of a reader is zeros)
 }
 
 // the extremes of packed 16-bit keys (ct_minmax.h: 2.5 operations per element against 6 on widened values) as 32-bit keys
@@ -71,15 +66,14 @@ struct ObsParams {
 template <int XDT>
 __global__ __launch_bounds__(kBlock) void attn_observe_fold_kernel(ObsParams p) {
     __shared__ int32_t smn[kObsMaxEntries], smx[kObsMaxEntries];
-    const int ti = (p.a.n == 2 && blockIdx.x >= p.a.t[1].first_block) ? 1 : 0;
+    const int ti = attn_tensor_of(p.a);
     const AttnT& t = p.a.t[ti];
     const ObsT& o = p.o[ti];
     for (uint32_t e = threadIdx.x; e < o.entries; e += kBlock) { smn[e] = kKey32EmptyMin; smx[e] = kKey32EmptyMax; }
     __syncthreads();
 
-    const uint32_t lpr = 1u << t.lpr_shift, rpb = (uint32_t)kBlock >> t.lpr_shift;
-    const uint32_t lane = threadIdx.x & (lpr - 1u), rl = threadIdx.x >> t.lpr_shift;
-    const uint32_t upr = (t.D + 7u) >> 3;
+    const AttnLanes g = attn_lanes(t);
+    const uint32_t lpr = g.lpr, rpb = g.rpb, lane = g.lane, upr = g.upr;
     const int lpg = (int)(lpr < 64u ? lpr : 64u);  // a row wider than a wave: each of its waves reduces and posts
     const bool poster = (threadIdx.x & (uint32_t)(lpg - 1)) == 0u;
     const bool vec = t.vec != 0u;
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void attn_observe_fold_kernel(ObsParams p) 
     MinMaxKey32 whole = mmk32_init();  // the tensor strategy: one entry, kept in registers over the whole loop
 
     for (uint32_t step = blockIdx.x - t.first_block; step < o.steps; step += o.blocks) {  // uniform per workgroup
-        const uint32_t row0 = step * (rpb * kObsRows) + rl;
+        const uint32_t row0 = step * (rpb * kObsRows) + g.rl;
         AttnRow r[kObsRows];
 #pragma unroll
         for (int i = 0; i < kObsRows; ++i) r[i] = obs_row(t, o, row0 + (uint32_t)i * rpb);
@@ -199,30 +193,24 @@ extern "C" int ct_attn_observe(const ct_attn_observe_tensor* tensors, int n, int
     CT_REQUIRE(is_float_dt(xdt), "observed dtype code %d is not a float type", xdt);
     CT_REQUIRE(is_float_dt(sdt), "scale dtype code %d is not a float type", sdt);
     CT_REQUIRE(keep == 0 || keep == 1, "keep must be 0 or 1, got %d", keep);
-    ct_attn_tensor view[2];
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) {  // (a negative size passes here and is attn_fill's to refuse)
         const ct_attn_observe_tensor& a = tensors[i];
         CT_REQUIRE(a.x != nullptr && a.state != nullptr && a.scale != nullptr, "tensor %d: x, state and scale must not be NULL", i);
         CT_REQUIRE(a.zp == nullptr || zdt == CT_I8 || zdt == CT_I32 || zdt == CT_F8E4M3 || is_float_dt(zdt), "zero-point dtype code %d unsupported", zdt);
-        CT_REQUIRE(a.B >= 0 && a.H >= 0 && a.S >= 0 && a.D >= 0, "negative shape (%lld, %lld, %lld, %lld)", (long long)a.B, (long long)a.H, (long long)a.S,
-                   (long long)a.D);
-        CT_REQUIRE(a.B > 0 && a.H > 0 && a.S > 0 && a.D > 0, "tensor %d is empty: the minimum of no elements is undefined", i);
+        CT_REQUIRE(a.B != 0 && a.H != 0 && a.S != 0 && a.D != 0, "tensor %d is empty: the minimum of no elements is undefined", i);
         if (a.per_head && a.H > kObsMaxEntries) CT_UNSUPPORTED("%lld heads: the observer's table holds %d entries", (long long)a.H, kObsMaxEntries);
-        ct_attn_tensor& v = view[i];
-        v.x = a.x; v.out = nullptr; v.scale = nullptr; v.zp = nullptr;
-        v.B = a.B; v.H = a.H; v.S = a.S; v.D = a.D;
-        for (int k = 0; k < 3; ++k) { v.x_stride[k] = a.x_stride[k]; v.out_stride[k] = 0; }
-        v.per_head = a.per_head;
     }
     ObsParams p;
-    int64_t unused = 0;
-    const int rc = attn_fill(p.a, view, n, kind, kind ? 8 : bits, xdt, sdt, zdt, xdt, true, unused, "ct_attn_observe", true);
-    if (rc) return rc;
+    attn_params(p.a, n, kind, kind ? 8 : bits, xdt, sdt, zdt, xdt);
     p.bits = bits; p.symmetric = symmetric; p.keep = keep;
+    int64_t unused = 0;
     uint32_t blocks = 0, entries = 0;
     for (int i = 0; i < 2; ++i) {
         const ct_attn_observe_tensor& a = tensors[i < n ? i : 0];
+        const int rc = attn_fill(p.a, i, a.x, a.B, a.H, a.S, a.D, a.x_stride, nullptr, nullptr, (int)a.per_head, true, true, unused, "ct_attn_observe");
+        if (rc) return rc;
         AttnT& t = p.a.t[i];
+        t.scale = nullptr; t.zp = nullptr;
         ObsT& o = p.o[i];
         obs_magic(t.n1, o.magic1, o.shift1);
         obs_magic(t.n2, o.magic2, o.shift2);

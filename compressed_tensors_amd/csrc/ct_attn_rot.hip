@@ -5,9 +5,9 @@
 //
 // The arithmetic is the two parents' own device functions in the parents' order: load8, the butterfly stages in float32
 // (unit_stages, lane_stages), ONE quotient by sqrt(n) (had_div8 with the HadScale ct_hadamard_rows builds), the rounding to x's
-// dtype that had_store's conversion performs — and only those rounded values reach quant_core / fake_dequant_rt, with
-// attn_qdq_kernel's reciprocal rule.  The output is therefore the bits ct_hadamard_rows followed by ct_attn_qdq produce.  The
-// unrotated tensor of a pair (V next to a rotated K) takes attn_qdq_kernel's steps alone.
+// dtype that had_store's conversion performs — and only those rounded values reach the row step attn_qdq_kernel takes too
+// (attn_row_qparams / attn_quant_unit of ct_attn.h).  The output is therefore the bits ct_hadamard_rows followed by ct_attn_qdq
+// produce.  The unrotated tensor of a pair (V next to a rotated K) takes that row step alone.
 //
 // Shape of the work: ct_attn.hip's.  A row of D elements is served by the next power of two >= D / 8 lanes, one 8-element unit
 // per lane, two rows per thread, rows enumerated in the INPUT's memory order (the output of a rotated tensor is a new contiguous
@@ -21,14 +21,12 @@ namespace ct {
 
 template <int XDT, int TDT, int MODE>
 __global__ __launch_bounds__(kBlock) void attn_rot_kernel(AttnParams p, int n, int rot_mask, HadScale<float> sn) {
-    const int ti = (p.n == 2 && blockIdx.x >= p.t[1].first_block) ? 1 : 0;
+    const int ti = attn_tensor_of(p);
     const AttnT& t = p.t[ti];
     const bool rot = (rot_mask >> ti) & 1;  // uniform over the workgroup
-    const uint32_t lpr = 1u << t.lpr_shift, rpb = (uint32_t)kBlock >> t.lpr_shift;
-    const uint32_t lane = threadIdx.x & (lpr - 1u), rl = threadIdx.x >> t.lpr_shift;
-    const uint32_t row0 = (blockIdx.x - t.first_block) * (rpb * kAttnRows) + rl;
-    const uint32_t c0 = lane << 3;
-    const bool has_zp = t.zp != nullptr;
+    const AttnLanes g = attn_lanes(t);
+    const uint32_t row0 = (blockIdx.x - t.first_block) * (g.rpb * kAttnRows) + g.rl;
+    const uint32_t c0 = g.lane << 3;
     AttnRow r[kAttnRows];
     bool live[kAttnRows];
     float v[kAttnRows][8];
@@ -36,7 +34,7 @@ __global__ __launch_bounds__(kBlock) void attn_rot_kernel(AttnParams p, int n, i
     // of a row whose units are no power of two carry zeros through the exchanges (every lane of the wave executes them) and store nothing.
 #pragma unroll
     for (int i = 0; i < kAttnRows; ++i) {
-        r[i] = attn_row(t, row0 + (uint32_t)i * rpb);
+        r[i] = attn_row(t, row0 + (uint32_t)i * g.rpb);
         live[i] = r[i].valid && c0 < t.D;
         if (live[i]) {
             load8<XDT>(t.x, r[i].xoff + c0, v[i]);
@@ -61,18 +59,7 @@ __global__ __launch_bounds__(kBlock) void attn_rot_kernel(AttnParams p, int n, i
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[i][k] = round_to<XDT>(v[i][k]);
         }
-        const float s = load_rt(t.scale, p.sdt, r[i].si);
-        const float zraw = has_zp ? load_rt(t.zp, p.zdt, r[i].si) : 0.0f;
-        const float z = round_to<XDT>(zraw);        // zp.to(x.dtype)
-        const float zs = round_to_rt(p.sdt, zraw);  // zp.to(scale.dtype)
-        const bool can_rcp = (XDT == CT_BF16 && TDT == CT_BF16 && p.sdt == CT_BF16) || (XDT == CT_F16 && TDT == CT_F16 && p.sdt == CT_F16) || TDT == CT_F32;
-        const float rs = can_rcp ? (TDT == CT_BF16 ? bf16_fast_rcp(s) : (TDT == CT_F16 ? f16_newton_rcp(s) : f32_fast_rcp(s))) : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float q = quant_core<TDT>(v[i][k], s, has_zp, z, p.qmin, p.qmax, rs, p.fkind);
-            if constexpr (MODE == ATTN_FQ) q = fake_dequant_rt(p.sdt, q, has_zp, zs, s);
-            v[i][k] = q;
-        }
+        attn_quant_unit<TDT, MODE>(p, attn_row_qparams<XDT, TDT>(p, t, r[i].si), v[i], 8);
         store_unit(t.out, p.odt, r[i].ooff + c0, v[i], 8, true);
     }
 }
@@ -85,13 +72,8 @@ extern "C" int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_siz
                                int tdt, int odt, ct_stream_t stream) {
     CT_REQUIRE(tensors != nullptr && (n == 1 || n == 2), "ct_attn_rot_qdq takes one or two tensors, got %d", n);
     CT_REQUIRE(mode == ATTN_FQ || mode == ATTN_Q, "mode must be 0 (fake) or 1 (quantize), got %d", mode);
-    CT_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (INT) or 1 (FLOAT 8-bit), got %d", kind);
-    CT_REQUIRE(is_float_dt(sdt), "scale dtype code %d is not a float type", sdt);
-    CT_REQUIRE(kind == 1 || (bits >= 1 && bits <= 8), "num_bits must be in [1, 8], got %d", bits);
-    CT_REQUIRE(xt_ok(xdt, tdt), "unsupported (x dtype, result dtype) = (%d, %d)", xdt, tdt);
-    if (mode == ATTN_FQ) CT_REQUIRE(is_float_dt(odt), "unsupported output dtype %d", odt);
-    else if (kind) CT_REQUIRE(odt == CT_F8E4M3 || is_float_dt(odt), "unsupported output dtype %d", odt);
-    else CT_REQUIRE(odt == CT_I8 || odt == CT_I32 || is_float_dt(odt), "unsupported output dtype %d", odt);
+    int rc = attn_qdq_check(mode, kind, bits, xdt, sdt, tdt, odt);
+    if (rc) return rc;
     CT_REQUIRE(rot_size >= 1 && log2_exact(rot_size) >= 0, "Cannot construct deterministic hadamard of size != 2^n");
     CT_REQUIRE(rot_mask >= 0 && rot_mask < (1 << n), "rot_mask %d names a tensor beyond the %d given", rot_mask, n);
     if (rot_size < 2 || rot_size > 512) CT_UNSUPPORTED("the fused attention rotation takes blocks of 2 .. 512 elements, got %d", rot_size);
@@ -99,7 +81,7 @@ extern "C" int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_siz
     int64_t blocks = 0;
     // rows in the INPUT's memory order: the transposed view is read sequentially, the contiguous output takes the strided side
     // (measured against the output's order at q (1, 32, 8192, 128): 54.9 against 56.2-56.4 us; the k+v rows alike: DESIGN 5.15)
-    const int rc = attn_fill(p, tensors, n, kind, bits, xdt, sdt, zdt, odt, true, blocks, "ct_attn_rot_qdq", /*input_order=*/true);
+    rc = attn_qdq_fill(p, tensors, n, kind, bits, xdt, sdt, zdt, odt, true, /*input_order=*/true, blocks, "ct_attn_rot_qdq");
     if (rc) return rc;
     for (int i = 0; i < n; ++i) {
         const AttnT& t = p.t[i];
@@ -114,10 +96,6 @@ extern "C" int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_siz
     sn.rn = 1.0f / sn.sn;
     sn.mode = log2_exact(rot_size) % 2 == 0 ? HAD_MUL : HAD_FAST;
     const dim3 grid((unsigned)blocks);
-    if (mode == ATTN_Q) {
-        CT_DISPATCH_XT(xdt, tdt, hipLaunchKernelGGL((attn_rot_kernel<X, T, ATTN_Q>), grid, dim3(kBlock), 0, as_stream(stream), p, rot_size, rot_mask, sn));
-    } else {
-        CT_DISPATCH_XT(xdt, tdt, hipLaunchKernelGGL((attn_rot_kernel<X, T, ATTN_FQ>), grid, dim3(kBlock), 0, as_stream(stream), p, rot_size, rot_mask, sn));
-    }
+    CT_ATTN_DISPATCH_FQ_Q(mode, xdt, tdt, hipLaunchKernelGGL((attn_rot_kernel<X, T, M>), grid, dim3(kBlock), 0, as_stream(stream), p, rot_size, rot_mask, sn));
     CT_LAUNCH_CHECK("ct_attn_rot_qdq");
 }

@@ -9,8 +9,7 @@ from typing import Optional
 
 import torch
 
-from .. import codec
-from ..quantization.observer import MinMaxObserver
+from ..quantization.observer import MinMaxObserver, observe_key_value
 from ..quantization.quant_args import enum_value
 from .attention import IMPL_ATTR, register_query_hook
 from .kvcache import KV_CACHE_ATTR, register_key_value_hook
@@ -138,12 +137,8 @@ def _key_value_hook(module, key, value):
         _observe_into(module, "k", key)
         _observe_into(module, "v", value)
         return
-    ko, vo = module.k_observer, module.v_observer
-    kw = ko._kwargs()
-    want = kw.pop("want_minmax")
-    (_, _, ko.min_vals, ko.max_vals), (_, _, vo.min_vals, vo.max_vals) = codec.attn_observe_pair(
-        key, value, ko.state_for(key), vo.state_for(value), k_scale=module.k_scale, v_scale=module.v_scale,
-        k_zero_point=getattr(module, "k_zero_point", None), v_zero_point=getattr(module, "v_zero_point", None), want_minmax=want, **kw)
+    observe_key_value(module.k_observer, module.v_observer, key, value, k_scale=module.k_scale, v_scale=module.v_scale,
+                      k_zero_point=getattr(module, "k_zero_point", None), v_zero_point=getattr(module, "v_zero_point", None))
 
 
 @contextlib.contextmanager

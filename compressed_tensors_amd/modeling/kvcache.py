@@ -108,15 +108,17 @@ def initialize_hooked_kv_cache(model, module: torch.nn.Module) -> None:
     module.register_forward_pre_hook(_swap_in_hooked_cache, with_kwargs=True)
 
 
-def _register_state_hook(module: torch.nn.Module, name: str, hook: Callable):
+def _register_states_hook(module: torch.nn.Module, names: Tuple[str, ...], hook: Callable):
+    """a forward pre-hook of the module's cache that hands `hook` the arguments `names` of the cache's forward; what it returns —
+    a tensor for one name, a tuple of as many tensors for several, None for nothing — replaces them"""
     cache: QuantizedKVCache = getattr(module, KV_CACHE_ATTR)
     signature = inspect.signature(cache.forward)
 
     def pre_hook(_cache, args, kwargs):
         bound = signature.bind(*args, **kwargs)
-        replaced = hook(module, bound.arguments[name])
+        replaced = hook(module, *(bound.arguments[name] for name in names))
         if replaced is not None:
-            bound.arguments[name] = replaced
+            bound.arguments.update(zip(names, (replaced,) if len(names) == 1 else replaced, strict=True))
         return bound.args, bound.kwargs
 
     return cache.register_forward_pre_hook(pre_hook, with_kwargs=True)
@@ -125,25 +127,15 @@ def _register_state_hook(module: torch.nn.Module, name: str, hook: Callable):
 def register_key_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, torch.Tensor], Optional[torch.Tensor]]):
     """`hook(module, key_states)` sees the post-rope key states before they are quantized and cached; a tensor it returns
     replaces them.  Returns the removable handle."""
-    return _register_state_hook(module, "key_states", hook)
+    return _register_states_hook(module, ("key_states",), hook)
 
 
 def register_value_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, torch.Tensor], Optional[torch.Tensor]]):
     """the same for the value states"""
-    return _register_state_hook(module, "value_states", hook)
+    return _register_states_hook(module, ("value_states",), hook)
 
 
 def register_key_value_hook(module: torch.nn.Module, hook: Callable[[torch.nn.Module, torch.Tensor, torch.Tensor], Optional[Tuple[torch.Tensor, torch.Tensor]]]):
     """`hook(module, key_states, value_states)` sees both states of one cache update; a (key_states, value_states) pair it
     returns replaces them.  Returns the removable handle."""
-    cache: QuantizedKVCache = getattr(module, KV_CACHE_ATTR)
-    signature = inspect.signature(cache.forward)
-
-    def pre_hook(_cache, args, kwargs):
-        bound = signature.bind(*args, **kwargs)
-        replaced = hook(module, bound.arguments["key_states"], bound.arguments["value_states"])
-        if replaced is not None:
-            bound.arguments["key_states"], bound.arguments["value_states"] = replaced
-        return bound.args, bound.kwargs
-
-    return cache.register_forward_pre_hook(pre_hook, with_kwargs=True)
+    return _register_states_hook(module, ("key_states", "value_states"), hook)

@@ -17,7 +17,7 @@ import torch
 from .. import codec
 from .quant_args import enum_value
 
-__all__ = ["MinMaxObserver", "OBSERVERS"]
+__all__ = ["MinMaxObserver", "OBSERVERS", "observe_key_value"]
 
 # observer name -> keep: "memoryless_minmax" — each call stands alone; "static_minmax" — the extremes of every call since reset()
 OBSERVERS = {"memoryless_minmax": False, "static_minmax": True}
@@ -81,3 +81,16 @@ class MinMaxObserver(torch.nn.Module):
         scale, zero_point, self.min_vals, self.max_vals = codec.attn_observe(
             observed, self.state_for(observed), scale=scale, zero_point=zero_point, global_scale=self._global_scale(), **self._kwargs())
         return scale, zero_point
+
+
+def observe_key_value(k_observer: MinMaxObserver, v_observer: MinMaxObserver, key: torch.Tensor, value: torch.Tensor, *, k_scale=None, v_scale=None,
+                      k_zero_point=None, v_zero_point=None):
+    """the forward of both observers on the K and V of one cache update through ONE ct_attn_observe (codec.attn_observe_pair): the
+    arguments are `k_observer`'s, which the two share; each keeps its own state and `min_vals` / `max_vals`.  Returns
+    ((k_scale, k_zero_point), (v_scale, v_zero_point))."""
+    k_out, v_out = codec.attn_observe_pair(
+        key, value, k_observer.state_for(key), v_observer.state_for(value), k_scale=k_scale, v_scale=v_scale, k_zero_point=k_zero_point,
+        v_zero_point=v_zero_point, **k_observer._kwargs())
+    k_scale, k_zero_point, k_observer.min_vals, k_observer.max_vals = k_out
+    v_scale, v_zero_point, v_observer.min_vals, v_observer.max_vals = v_out
+    return (k_scale, k_zero_point), (v_scale, v_zero_point)

@@ -149,6 +149,36 @@ def make_qparams(r):
     return scale, (None if kind["symmetric"] else zp)
 
 
+def eager_fake_quantize(x, scale, zp, kind):
+    """the reference's arithmetic restated in eager torch (forward_helpers.py:180-215, quant_args.py:460-496), on the same device"""
+    k = KINDS[kind]
+    t = x / scale
+    if zp is not None:
+        t += zp.to(x.dtype)
+    if k["type"] == "float":
+        q = torch.clamp(t, -448.0, 448.0).to(F8).to(t.dtype)
+    else:
+        q = torch.round(torch.clamp(t, -(2.0 ** k["num_bits"]) / 2, 2.0 ** k["num_bits"] / 2 - 1))
+    d = q.to(scale.dtype)
+    if zp is not None:
+        d = d - zp.to(scale.dtype)
+    return d * scale
+
+
+# rows wider than the 256 elements of the fixtures, as (B, H, S, D): a row of two waves; a row that is the workgroup, three rows so that
+# the second workgroup is partial; the unit loop running twice; the element form with 257 units — the loop's second trip has one lane
+# and a 4-element unit
+WIDE_SHAPES = ((1, 2, 3, 1024), (1, 1, 3, 2048), (1, 2, 3, 4096), (1, 2, 3, 2052))
+
+
+def wide_input(shape, dtype, device, seed=0):
+    """finite random values laid out as a Llama's states are: (B, S, H, D).transpose(1, 2)"""
+    B, H, S, D = shape
+    x = torch.randn(B, S, H, D, generator=torch.Generator().manual_seed(seed + D)).to(dtype).to(device).transpose(1, 2)
+    assert torch.isfinite(x).all()
+    return x
+
+
 def strategy_of(r):
     return "attn_head" if r["strategy"] == "attn_head" else "tensor"
 

@@ -11,7 +11,7 @@ import itertools
 import torch
 
 import _attn_cases as C
-from _attn_cases import BF16, DTYPES, F8, F16, F32, canonical_bytes, sha  # noqa: F401
+from _attn_cases import BF16, DTYPES, F8, F16, F32, WIDE_SHAPES, canonical_bytes, sha, wide_input  # noqa: F401
 
 D_VALUES = C.D_VALUES  # 16 = two units .. 256 = 32 lanes per row, 80 = ten units on sixteen lanes, 20 = the element form
 LAYOUTS = ("contiguous", "transposed", "fused_k", "misaligned", "expanded", "3d")

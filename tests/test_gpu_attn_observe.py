@@ -208,8 +208,9 @@ def test_static_equals_memoryless_on_the_union(kind):
 
 # ---- planted extremes: the row loop, the last partial workgroup, both forms ----------------------------------------------------------------
 # (2, 8, 4100, 16): the vector form, 65600 rows of two lanes; (1, 2, 257, 20): the element form, 514 rows of four lanes — a workgroup
-# owns several steps and the last step is partial; (1, 8, 8200, 256): 65600 rows of 32 lanes, enough steps for the grid to stop at its cap
-@pytest.mark.parametrize("shape", [(2, 8, 4100, 16), (1, 2, 257, 20), (1, 8, 8200, 256)])
+# owns several steps and the last step is partial; (1, 8, 8200, 256): 65600 rows of 32 lanes, enough steps for the grid to stop at its cap;
+# C.WIDE_SHAPES: rows of several waves, of a whole workgroup, and of more units than a workgroup has lanes (both forms)
+@pytest.mark.parametrize("shape", [(2, 8, 4100, 16), (1, 2, 257, 20), (1, 8, 8200, 256), *C.WIDE_SHAPES])
 @pytest.mark.parametrize("where", ["first", "last", "middle"])
 def test_planted_extremes_are_found(shape, where):
     from compressed_tensors_amd import codec
@@ -229,6 +230,17 @@ def test_planted_extremes_are_found(shape, where):
     assert torch.equal(mn.cpu().flatten(), lo) and torch.equal(mx.cpu().flatten(), hi), (mn.flatten().tolist(), mx.flatten().tolist())
     _, _, mn, mx = codec.attn_observe(x, _state(x, "tensor"), want_minmax=True, strategy="tensor", **FP8)
     assert torch.equal(mn.cpu(), lo.min().reshape(1)) and torch.equal(mx.cpu(), hi.max().reshape(1))
+
+
+def test_a_wide_float32_row_matches_torch():
+    """(1, 2, 3, 1024) float32: 128 units, a row of two waves, every wave of a row posting its own extremes"""
+    from compressed_tensors_amd import codec
+
+    x = C.wide_input((1, 2, 3, 1024), C.F32, DEV)
+    _, _, mn, mx = codec.attn_observe(x, _state(x), want_minmax=True, **FP8)
+    assert torch.equal(mn, torch.amin(x, dim=(0, 2, 3)).reshape(2, 1, 1)) and torch.equal(mx, torch.amax(x, dim=(0, 2, 3)).reshape(2, 1, 1))
+    _, _, mn, mx = codec.attn_observe(x, _state(x, "tensor"), want_minmax=True, strategy="tensor", **FP8)
+    assert torch.equal(mn, torch.amin(x).reshape(1)) and torch.equal(mx, torch.amax(x).reshape(1))
 
 
 # ---- the key map: every finite bf16 bit pattern -------------------------------------------------------------------------------------------

@@ -75,10 +75,31 @@ def _same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and C.canonical_bytes(a) == C.canonical_bytes(b)
 
 
-@pytest.mark.parametrize("key", sorted(MANIFEST))
-def test_attn_qdq_matches_the_reference(key, counted):
+def _contiguous_kernels(mode, kw, x, scale, zp, shape, qdtype):
+    """today's kernels on the same values, made contiguous: ct_fake_quantize{,_fp8} / ct_quantize{,_fp8} / ct_dequantize"""
     from compressed_tensors_amd import codec
 
+    xc = x.contiguous()
+    if kw["strategy"] == "tensor":
+        layout = dict(strategy="tensor")
+        old_x, old_s, old_z = xc, scale, zp
+    else:  # one batch at a time, a head per row: the channel strategy on (H, S * D)
+        layout = dict(strategy="channel")
+        B, H, S, D = shape
+        old_x, old_s, old_z = xc.reshape(B, H, S * D), scale.reshape(H, 1), (None if zp is None else zp.reshape(H, 1))
+    old_kw = dict(num_bits=kw["num_bits"], qtype=kw["qtype"], **layout)
+
+    def old(xb):
+        if mode == "fake":
+            return codec.fake_quantize_tensor(xb, old_s, old_z, **old_kw)
+        q = codec.quantize_tensor(xb, old_s, old_z, dtype=qdtype, **old_kw)
+        return q if mode == "quantize" else codec.dequantize_tensor(q, old_s, old_z, **layout)
+
+    return old(old_x) if kw["strategy"] == "tensor" else torch.stack([old(old_x[b]) for b in range(old_x.shape[0])])
+
+
+@pytest.mark.parametrize("key", sorted(MANIFEST))
+def test_attn_qdq_matches_the_reference(key, counted):
     entry = MANIFEST[key]
     r = entry["recipe"]
     x = C.make_input(r, DEV)
@@ -98,25 +119,7 @@ def test_attn_qdq_matches_the_reference(key, counted):
         assert C.canonical_bytes(out) == C.canonical_bytes(ref), "the output differs from the stored reference"
     assert dict(counted) == {"ct_attn_qdq": 2 if r["mode"] == "dequantize" else 1}, counted
     assert C.canonical_bytes(x) == C.canonical_bytes(before), "the input was written"
-    # today's kernels on the same values, made contiguous: ct_fake_quantize{,_fp8} / ct_quantize{,_fp8} / ct_dequantize
-    kw = _kw(r)
-    xc = x.contiguous()
-    if kw["strategy"] == "tensor":
-        layout = dict(strategy="tensor")
-        old_x, old_s, old_z = xc, scale, zp
-    else:  # one batch at a time, a head per row: the channel strategy on (H, S * D)
-        layout = dict(strategy="channel")
-        B, H, S, D = C.logical_shape(r)
-        old_x, old_s, old_z = xc.reshape(B, H, S * D), scale.reshape(H, 1), (None if zp is None else zp.reshape(H, 1))
-    old_kw = dict(num_bits=kw["num_bits"], qtype=kw["qtype"], **layout)
-
-    def old(xb):
-        if r["mode"] == "fake":
-            return codec.fake_quantize_tensor(xb, old_s, old_z, **old_kw)
-        q = codec.quantize_tensor(xb, old_s, old_z, dtype=C.quantized_dtype(r), **old_kw)
-        return q if r["mode"] == "quantize" else codec.dequantize_tensor(q, old_s, old_z, **layout)
-
-    ref = old(old_x) if kw["strategy"] == "tensor" else torch.stack([old(old_x[b]) for b in range(old_x.shape[0])])
+    ref = _contiguous_kernels(r["mode"], _kw(r), x, scale, zp, C.logical_shape(r), C.quantized_dtype(r))
     assert _same(out.contiguous().reshape(ref.shape), ref), "the strided entry differs from the contiguous kernels"
 
 
@@ -189,20 +192,7 @@ def test_transposed_view_is_read_in_place():
 
 
 # ---- every bf16 bit pattern ---------------------------------------------------------------------------------------------------------------
-def _eager(x, scale, zp, kind):
-    """the reference's arithmetic restated in eager torch (forward_helpers.py:180-215, quant_args.py:460-496), on the same device"""
-    k = C.KINDS[kind]
-    t = x / scale
-    if zp is not None:
-        t += zp.to(x.dtype)
-    if k["type"] == "float":
-        q = torch.clamp(t, -448.0, 448.0).to(C.F8).to(t.dtype)
-    else:
-        q = torch.round(torch.clamp(t, -(2.0 ** k["num_bits"]) / 2, 2.0 ** k["num_bits"] / 2 - 1))
-    d = q.to(scale.dtype)
-    if zp is not None:
-        d = d - zp.to(scale.dtype)
-    return d * scale
+_eager = C.eager_fake_quantize
 
 
 @pytest.mark.parametrize("kind", ["fp8", "int8", "int8_zp"])
@@ -220,3 +210,38 @@ def test_every_bf16_bit_pattern(kind):
     nan = torch.isnan(ref)
     assert torch.equal(torch.isnan(out), nan)
     assert torch.equal(out[~nan].view(torch.int16), ref[~nan].view(torch.int16))
+
+
+# ---- rows wider than the fixtures' 256 elements: several waves per row, a workgroup per row, the unit loop ----------------------------------
+def _wide(shape, kind):
+    x = C.wide_input(shape, C.BF16, DEV)
+    r = dict(H=shape[1], dtypes="bf16/bf16", kind=kind, strategy="attn_head")
+    scale, zp = C.make_qparams(r)
+    return x, scale.to(DEV), (None if zp is None else zp.to(DEV)), _kw(r)
+
+
+@pytest.mark.parametrize("kind", ["fp8", "int8_zp"])
+@pytest.mark.parametrize("shape", C.WIDE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_wide_rows_fake_quantize_like_eager_torch(shape, kind):
+    from compressed_tensors_amd import codec
+
+    x, scale, zp, kw = _wide(shape, kind)
+    out = codec.attn_fake_quantize(x, scale, zp, **kw)
+    ref = _eager(x, scale, zp, kind)
+    assert torch.isfinite(ref).all()
+    assert out.dtype == ref.dtype == C.BF16 and out.shape == ref.shape
+    # (the stride of a size-1 dimension — H = 1 — is never multiplied by an index; torch's ops place it by rules of their own)
+    assert [st for st, sz in zip(out.stride(), out.shape) if sz > 1] == [st for st, sz in zip(x.stride(), x.shape) if sz > 1]
+    assert torch.equal(out.view(torch.int16), ref.view(torch.int16))
+
+
+@pytest.mark.parametrize("shape", C.WIDE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_wide_rows_quantize_and_dequantize_like_the_contiguous_kernels(shape):
+    from compressed_tensors_amd import codec
+
+    x, scale, zp, kw = _wide(shape, "int8_zp")
+    q = codec.attn_quantize(x, scale, zp, dtype=torch.int8, **kw)
+    back = codec.attn_dequantize(q, scale, zp, strategy=kw["strategy"])
+    for mode, got in (("quantize", q), ("dequantize", back)):
+        ref = _contiguous_kernels(mode, kw, x, scale, zp, shape, torch.int8)
+        assert _same(got.contiguous().reshape(ref.shape), ref), f"{mode}: the strided entry differs from the contiguous kernels"

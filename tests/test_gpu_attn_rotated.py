@@ -127,6 +127,25 @@ def test_special_values_rotate_and_quantize_alike(dn, dtype):
             assert _same(got, want), (kind, mode)
 
 
+@pytest.mark.parametrize("kind", ["fp8", "int8_zp"])
+@pytest.mark.parametrize("shape_n", [((1, 2, 3, 1024), 128), ((1, 1, 3, 2048), 512)], ids=["1x2x3x1024-n128", "1x1x3x2048-n512"])
+def test_wide_rows_equal_the_rotation_kernel_then_eager_torch(shape_n, kind, counted):
+    """rows of two waves and of a whole workgroup: the untouched rotation kernel, then torch's own arithmetic"""
+    from compressed_tensors_amd import codec
+
+    shape, n = shape_n
+    x = A.wide_input(shape, BF16, DEV)
+    scale, zp = _qparams(kind, "attn_head", shape[1], BF16)
+    want = A.eager_fake_quantize(codec.hadamard_transform(x.contiguous(), n), scale, zp, kind)
+    assert torch.isfinite(want).all()
+    counted.clear()
+    got = _call("fake", x, n, scale, zp, kind, "attn_head", fused=True)
+    torch.cuda.synchronize()
+    assert dict(counted) == {"ct_attn_rot_qdq": 1}, counted
+    assert got.dtype == want.dtype == BF16 and got.shape == want.shape
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+
+
 def test_mixed_dtypes_and_a_0_dim_scale():
     x = C.identity_input(dict(dn=(128, 32), layout="fused_k", dtype="bf16", shape="tail", scale=1.0), DEV, 7)
     for sdt in (torch.float32, torch.bfloat16):
