@@ -93,6 +93,9 @@ _PROTOTYPES = {
     "ct_rtn_mxfp4_batch_plan": ([_P, _I], _L),
     "ct_rtn_mxfp4_quant_pack_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_rtn_nvfp4_quant_pack": ([_P, _I, _L, _L, _P, _P, _P, _P, _S], _I),
+    "ct_rtn_nvfp4_batch_plan": ([_P, _I], _L),
+    "ct_rtn_nvfp4_amax_batch": ([_P, _I, _L, _I, _S], _I),
+    "ct_rtn_nvfp4_quant_pack_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_fp4_cast": ([_P, _I, _P, _L, _S], _I),
     "ct_fp4_pack": ([_P, _I, _P, _L, _S], _I),
     "ct_fp4_unpack": ([_P, _L, _P, _I, _S], _I),

@@ -44,8 +44,10 @@ __all__ = [
     "rtn_nvfp4_quantize_and_pack",
     "rtn_quantize_and_pack_many",
     "rtn_mxfp4_quantize_and_pack_many",
+    "rtn_nvfp4_quantize_and_pack_many",
     "launch_rtn_w4_words",
     "launch_rtn_mxfp4_words",
+    "launch_rtn_nvfp4_words",
     "pack_bitmasks",
     "unpack_bitmasks",
     "W4Batch",
@@ -95,6 +97,10 @@ __all__ = [
     "item_row",
     "rtn_w4_table_item",
     "rtn_mxfp4_table_item",
+    "rtn_nvfp4_table_item",
+    "rtn_nvfp4_takes",
+    "rtn_nvfp4_keys",
+    "attn_observe_global_scale",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -896,6 +902,26 @@ def attn_observe_pair(k, v, k_state, v_state, *, num_bits, symmetric=True, qtype
     return out[0], out[1]
 
 
+def attn_observe_global_scale(x, state, *, keep=False, global_scale=None) -> torch.Tensor:
+    """An observer's `get_global_scale` — `generate_gparam` (quantization/utils/helpers.py:308-337) of the extremes of the whole tensor, the
+    reference observer's `reshape((1, 1, -1))` — on any activation, read in place through its strides: folded into `state`
+    (attn_observe_state(1, device)) as one entry, then 448 * 6 / amax of the running extremes evaluated in x's dtype (kind 2 of ct_attn_observe:
+    the arithmetic of ct_generate_gparam).  Returns the float32 (1,) global scale; `global_scale` given (a module's `input_global_scale`): the
+    kernel writes it in place and it is what is returned.  `keep` as in attn_observe.  One ct_attn_observe, no copy of a view the kernel can index,
+    no host synchronisation."""
+    descs = (_lib.AttnObserveTensor * 1)()
+    d = descs[0]
+    xr, (plan,) = _attn_describe(d, x, _plan_attn_observe, ("tensor", x.device.type))
+    dev = x.device
+    if state.dtype != torch.int32 or tuple(state.shape) != (2, 1) or state.device != dev or not state.is_contiguous():
+        raise ValueError(f"the observer state of a global scale is a contiguous int32 (2, 1) tensor on {dev} (attn_observe_state), got {state.dtype} "
+                         f"{tuple(state.shape)} on {state.device}")
+    out = _observe_out(global_scale, (1,), torch.float32, dev, "global_scale")
+    d.state, d.scale, d.zp, d.min_vals, d.max_vals = ptr(state), ptr(out), None, None, None
+    call("ct_attn_observe", descs, 1, 2, 0, 1, DT[x.dtype], DT[torch.float32], DT[torch.int8], int(bool(keep)), stream_on(dev))
+    return out
+
+
 # --------------------------------------------------------------------------- attention: the head-dim rotation in the QDQ's launch
 ATTN_ROTATED_MAX_SIZE = 512  # the rotation blocks csrc/ct_attn_rot.hip serves: n / 8 lanes of one wave
 ATTN_ROTATED_MAX_UNITS = 256  # D / 8: a row is one pass of a workgroup's lanes
@@ -1602,12 +1628,17 @@ _TABLES = {
     "rtn_w4": ("ct_rtn_w4_batch_plan", False, "ct_rtn_quant_pack_w4_batch"),
     "rtn_mxfp4": ("ct_rtn_mxfp4_batch_plan", False, "ct_rtn_mxfp4_quant_pack_batch"),
 }
+# the same triple for a table that ONE plan serves in TWO passes over the same rows — (fold, quantize), both per table, where a kind above has one launch
+# per direction: `d` of `_run_table` picks the pass
+_TWO_PASS_TABLES = {
+    "rtn_nvfp4": ("ct_rtn_nvfp4_batch_plan", False, ("ct_rtn_nvfp4_amax_batch", "ct_rtn_nvfp4_quant_pack_batch")),
+}
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
 def _plan_table(kind: str, words, n: int, device, d: int = 0):
     """the first half of `_launch_table`: plan `words` in place and upload them -> (device table, workgroups)"""
-    plan, directed, _ = _TABLES[kind]
+    plan, directed, _ = _TABLES.get(kind) or _TWO_PASS_TABLES[kind]
     if isinstance(words, list):
         words = array.array("q", words)
     addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
@@ -1620,7 +1651,7 @@ def _plan_table(kind: str, words, n: int, device, d: int = 0):
 
 def _run_table(kind: str, table, n: int, blocks: int, device, d: int, scalars, stream=None) -> None:
     """the second half: ONE launch of a planned, uploaded table"""
-    symbol = _TABLES[kind][2]
+    symbol = (_TABLES.get(kind) or _TWO_PASS_TABLES[kind])[2]
     call(symbol if isinstance(symbol, str) else symbol[d], table.data_ptr(), n, blocks, *scalars, _lib.stream_on(device, stream))
 
 
@@ -1633,7 +1664,7 @@ def _launch_table(kind: str, words, n: int, device, d: int = 0, scalars=(), stre
     Lifetime, for every entry point built on this: the caller keeps the tensors the rows point at alive.  The device table is allocated and
     uploaded on the current stream, whatever `stream` is: a caller that launches on another stream orders that stream behind the current one first
     (`wait_stream`).  One that stays on the current stream may drop the table at once — the `launch_*_words` of the C++ host loops do, and
-    return nothing.  `launch_rtn_w4_words` / `launch_rtn_mxfp4_words` hand the table back and the caller owes it a `record_stream` when its stream
+    return nothing.  `launch_rtn_w4_words` / `launch_rtn_mxfp4_words` / `launch_rtn_nvfp4_words` hand the table back and the caller owes it a `record_stream` when its stream
     is not the allocator's; `zp4_batch` records it itself; `W4Batch` keeps it for as long as the batch lives."""
     if not n:
         return None
@@ -1801,6 +1832,19 @@ def launch_rtn_mxfp4_words(words, n: int, dtype: torch.dtype, device: torch.devi
     return _launch_table("rtn_mxfp4", words, n, device, 0, (DT[dtype],)) if n else None
 
 
+def launch_rtn_nvfp4_words(words, n: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass NVFP4 compress, `generate_gparam` of every weight included: src = weights, dst = packed
+    bytes, zp_packed = the float8 scale output, zp = the item's amax key — its own 32-bit word of a buffer the caller has ZEROED on this stream —,
+    scale = its float32 (1,) global-scale output, group = 16.  One plan, one upload, TWO launches over the same rows: `ct_rtn_nvfp4_amax_batch` folds
+    max |x| into the keys, `ct_rtn_nvfp4_quant_pack_batch` derives each global scale from its key, stores it and quantizes under it."""
+    if not n:
+        return None
+    table, blocks = _plan_table("rtn_nvfp4", words, n, device)
+    for launch in (0, 1):
+        _run_table("rtn_nvfp4", table, n, blocks, device, launch, (DT[dtype],))
+    return table
+
+
 def rtn_w4_group(shape, group_size) -> int:
     """the group (elements per scale) when `ct_rtn_quant_pack_w4` and its table form take a weight of this shape — 2-D, rows > 0, a group of
     32 * 2^k <= 2048 columns that divides the row (group_size None / 0: the whole row) — else 0"""
@@ -1840,6 +1884,29 @@ def rtn_mxfp4_table_item(x):
     packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
     code = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
     return packed, code, item_row(x.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, code.data_ptr())
+
+
+def rtn_nvfp4_takes(x) -> bool:
+    """does the one-pass NVFP4 table take this weight — on a GPU, 2-D, contiguous, 16-byte aligned, 16-bit, cols % 32 == 0?"""
+    return _rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0
+
+
+def rtn_nvfp4_keys(n: int, device) -> torch.Tensor:
+    """the amax keys of a table of up to `n` items, armed: int32 zeros, one word per item (0 is the identity of the fold) — the table's one fill"""
+    return torch.zeros(int(n), dtype=torch.int32, device=device)
+
+
+def rtn_nvfp4_table_item(x, key: int):
+    """`rtn_w4_table_item` for the one-pass NVFP4 table (`launch_rtn_nvfp4_words`; cols % 32 == 0), `key` = the address of the item's word of
+    the table's key buffer (`rtn_nvfp4_keys`): (packed uint8 (R, C / 2), float8_e4m3fn scales (R, C / 16), float32 (1,) global scale, row) or None.  The
+    global scale is a tensor of its own, not a view into a buffer the items share: a saved state dict must not contain aliased tensors."""
+    if not rtn_nvfp4_takes(x):
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+    s8 = torch.empty((rows, cols // 16), dtype=_F8, device=x.device)
+    gs = torch.empty(1, dtype=torch.float32, device=x.device)
+    return packed, s8, gs, item_row(x.data_ptr(), gs.data_ptr(), int(key), packed.data_ptr(), rows, cols, 16, s8.data_ptr())
 
 
 def _rtn_w4_one(x, group_size, symmetric):
@@ -1897,6 +1964,32 @@ def rtn_mxfp4_quantize_and_pack_many(weights):
     if n:
         table = launch_rtn_mxfp4_words(flat, n, first.dtype, first.device)
         table.record_stream(torch.cuda.current_stream(first.device))
+    return out
+
+
+def rtn_nvfp4_quantize_and_pack_many(weights):
+    """`rtn_nvfp4_quantize_and_pack` for a LIST of weights, each under its own `generate_gparam`: the tensors the table takes
+    (`rtn_nvfp4_table_item`, of the first such tensor's device and dtype) leave in one fill of the key buffer and TWO launches
+    (`launch_rtn_nvfp4_words`) instead of three launches each, the others one by one.  Returns [(packed uint8 (R, C / 2), float8_e4m3fn scales
+    (R, C / 16), float32 (1,) global scale)] in input order, bit-identical to the single-tensor call per item; every global scale owns its storage."""
+    weights = list(weights)
+    out = [None] * len(weights)
+    first, n, flat, keys = None, 0, [], None
+    for i, x in enumerate(weights):
+        if not (rtn_nvfp4_takes(x) and (first is None or (x.device == first.device and x.dtype == first.dtype))):
+            out[i] = rtn_nvfp4_quantize_and_pack(x)
+            continue
+        if first is None:
+            first, keys = x, rtn_nvfp4_keys(len(weights) - i, x.device)  # the n-th item's key is word n
+        item = rtn_nvfp4_table_item(x, keys.data_ptr() + 4 * n)
+        out[i] = item[:3]
+        flat += item[3]
+        n += 1
+    if n:
+        table = launch_rtn_nvfp4_words(flat, n, first.dtype, first.device)
+        stream = torch.cuda.current_stream(first.device)
+        table.record_stream(stream)
+        keys.record_stream(stream)
     return out
 
 

@@ -26,6 +26,11 @@ def _is_fp4(scheme, group_size) -> bool:
 @BaseCompressor.register(name=CompressionFormat.nvfp4_pack_quantized.value)
 class NVFP4PackedCompressor(BaseCompressor):
     GROUP = 16
+    # `compress_model_rtn(batched=True)` hands its NVFP4 modules to `compress_rtn_tables` only while this holds: True once tools/rtn_bench.py has
+    # measured the table path faster than the per-module loop on both trees by more than the spread between its two runs (the project's dispatch
+    # rule).  The NVFP4 rows of profiles/rtn_bench.jsonl have not been recorded yet, so it is False: per module, as before; the hook and the codec
+    # entry (codec.rtn_nvfp4_quantize_and_pack_many) stay for a caller that wants them.  DESIGN.md 5.17.
+    RTN_TABLE_MEASURED_FASTER = False
 
     @classmethod
     def compression_param_names(cls, scheme) -> tuple:
@@ -192,6 +197,38 @@ class NVFP4PackedCompressor(BaseCompressor):
         return cls.compress({"weight": weight, "weight_scale": scale, "weight_global_scale": gs}, scheme)
 
     @classmethod
+    def compress_rtn_tables(cls, modules) -> None:
+        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`) — what `MXFP4PackedCompressor.compress_rtn_modules`
+        does, under the name `compress_model_rtn` looks up second: the modules with a 16-bit weight on a GPU (cols % 32 == 0, float8 scales) leave in one
+        fill of the window's amax keys and TWO table launches per (device, dtype) (codec.launch_rtn_nvfp4_words: `generate_gparam` of every weight,
+        then the one-pass compress under it) instead of three launches per module, and the parameter dictionaries are rewritten under the
+        kernels.  Every module ends in exactly the state `compress_rtn_module` leaves it in; the others go through that, from this call."""
+        for window in rtn_windows(modules):
+            tables, rest = {}, []
+            for m in window:
+                w = direct_entry(m, "weight")
+                if not (w is not None and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.float8_e4m3fn) is torch.float8_e4m3fn
+                        and codec.rtn_nvfp4_takes(w)):
+                    rest.append(m)
+                    continue
+                group = tables.get((w.device, w.dtype))
+                if group is None:
+                    group = tables[(w.device, w.dtype)] = ([], [], codec.rtn_nvfp4_keys(len(window), w.device))  # a table's keys: one word per item
+                packed, s8, gs, row = codec.rtn_nvfp4_table_item(w, group[2].data_ptr() + 4 * len(group[1]))
+                group[0].extend(row)
+                group[1].append((m, w, packed, s8, gs))  # the table holds raw pointers: the jobs keep the tensors alive
+            for (device, dtype), (flat, jobs, keys) in tables.items():
+                stream = torch.cuda.current_stream(device)
+                codec.launch_rtn_nvfp4_words(flat, len(jobs), dtype, device).record_stream(stream)
+                keys.record_stream(stream)
+            for flat, jobs, keys in tables.values():  # from here on the host works under the kernels
+                for m, w, packed, s8, gs in jobs:
+                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
+                    swap_direct_entries(m, remove, {"weight_packed": packed, "weight_scale": s8, "weight_global_scale": gs}, status=QuantizationStatus.COMPRESSED)
+            for m in rest:
+                cls.compress_rtn_module(m)
+
+    @classmethod
     def decompress(cls, state_dict: dict, scheme) -> dict:
         """nvfp4/base.py:106-139: the weight comes back as bfloat16 (unpack_fp4_from_uint8's default), the scale as a
         bfloat16 tensor"""
@@ -213,6 +250,7 @@ class NVFP4PackedCompressor(BaseCompressor):
 @BaseCompressor.register(name=CompressionFormat.mxfp4_pack_quantized.value)
 class MXFP4PackedCompressor(NVFP4PackedCompressor):
     GROUP = 32
+    compress_rtn_tables = None  # NVFP4's window hook is not inherited: this class has its own, `compress_rtn_modules`
 
     @classmethod
     def compression_param_names(cls, scheme) -> tuple:

@@ -8,8 +8,8 @@
 // on 32-bit order keys (ct_minmax.h: integer min / max, exact and order-free, a NaN surfaces as an extreme), accumulates per scale entry in LDS over every row the workgroup owns and
 // then folds its table into the caller's state with at most two global integer atomics per entry it touched.  The grid is capped
 // (kObsCap workgroups) and loops over the rows: the atomics on an entry are bounded by the cap, not by the row count.
-// FINALIZE: one thread per entry decodes the keys, runs the weight path's compute_qparams / compute_qparams_float and stores
-// scale, zero point and (optionally) the extremes; unless `keep` it re-arms the state.  Stream order between the two launches is
+// FINALIZE: one thread per entry decodes the keys, runs the weight path's compute_qparams / compute_qparams_float — or, kind 2,
+// generate_gparam's arithmetic (gparam_from_amax) on the same amax — and stores scale, zero point and (optionally) the extremes; unless `keep` it re-arms the state.  Stream order between the two launches is
 // the only synchronisation.
 #include "ct_attn.h"
 #include "ct_minmax.h"
@@ -171,7 +171,8 @@ __global__ __launch_bounds__(kBlock) void attn_observe_finalize_kernel(ObsParams
     int32_t* kmx = o.state + o.entries + e;
     const MinMax m = mmk32_finish(MinMaxKey32{*kmn, *kmx});
     float s, z = 0.0f;
-    if (p.a.fkind) s = compute_qparams_float<XDT>(m, QP_FP8, 0.0f);
+    if (p.a.fkind == 2) s = gparam_from_amax<XDT>(compute_qparams_float<XDT>(m, QP_AMAX, 0.0f));  // generate_gparam(min, max): the NVFP4 global scale
+    else if (p.a.fkind) s = compute_qparams_float<XDT>(m, QP_FP8, 0.0f);
     else compute_qparams<XDT>(m, p.bits, p.symmetric, s, z);
     store_rt(o.scale, p.a.sdt, e, s);
     if (o.zp) store_rt(o.zp, p.a.zdt, e, z);
@@ -188,14 +189,16 @@ using namespace ct;
 extern "C" int ct_attn_observe(const ct_attn_observe_tensor* tensors, int n, int kind, int bits, int symmetric, int xdt, int sdt, int zdt, int keep,
                                ct_stream_t stream) {
     CT_REQUIRE(tensors != nullptr && (n == 1 || n == 2), "ct_attn_observe takes one or two tensors, got %d", n);
-    CT_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (INT) or 1 (FLOAT 8-bit), got %d", kind);
-    CT_REQUIRE(kind == 1 || (bits >= 1 && bits <= 8), "num_bits must be in [1, 8], got %d", bits);
+    CT_REQUIRE(kind >= 0 && kind <= 2, "kind must be 0 (INT), 1 (FLOAT 8-bit) or 2 (the NVFP4 global scale), got %d", kind);
+    CT_REQUIRE(kind != 0 || (bits >= 1 && bits <= 8), "num_bits must be in [1, 8], got %d", bits);
+    CT_REQUIRE(kind != 2 || sdt == CT_F32, "a global scale is float32, got scale dtype code %d", sdt);
     CT_REQUIRE(is_float_dt(xdt), "observed dtype code %d is not a float type", xdt);
     CT_REQUIRE(is_float_dt(sdt), "scale dtype code %d is not a float type", sdt);
     CT_REQUIRE(keep == 0 || keep == 1, "keep must be 0 or 1, got %d", keep);
     for (int i = 0; i < n; ++i) {  // (a negative size passes here and is attn_fill's to refuse)
         const ct_attn_observe_tensor& a = tensors[i];
         CT_REQUIRE(a.x != nullptr && a.state != nullptr && a.scale != nullptr, "tensor %d: x, state and scale must not be NULL", i);
+        CT_REQUIRE(kind != 2 || a.zp == nullptr, "tensor %d: a global scale has no zero point", i);
         CT_REQUIRE(a.zp == nullptr || zdt == CT_I8 || zdt == CT_I32 || zdt == CT_F8E4M3 || is_float_dt(zdt), "zero-point dtype code %d unsupported", zdt);
         CT_REQUIRE(a.B != 0 && a.H != 0 && a.S != 0 && a.D != 0, "tensor %d is empty: the minimum of no elements is undefined", i);
         if (a.per_head && a.H > kObsMaxEntries) CT_UNSUPPORTED("%lld heads: the observer's table holds %d entries", (long long)a.H, kObsMaxEntries);

@@ -320,11 +320,8 @@ __global__ __launch_bounds__(kBlock) void rtn_mxfp4_batch_kernel(const ct_w4_ite
 // read-only pass before this one) is an input.  Writes the nibbles, the float8_e4m3fn group scales (the stored form) and
 // optionally the float32 scales calculate_qparams returns.
 template <int XDT>
-__global__ __launch_bounds__(kBlock) void rtn_nvfp4_kernel(const u32x4* __restrict__ in, int64_t lanes, const float* __restrict__ global_scale,
-                                                           u32x4* __restrict__ out, uint16_t* __restrict__ scale_f8, float* __restrict__ scale_out) {
-    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (l >= lanes) return;
-    const float gs = global_scale[0];
+__device__ __forceinline__ void rtn_nvfp4_lane(const u32x4* __restrict__ in, float gs, u32x4* __restrict__ out, uint16_t* __restrict__ scale_f8, float* __restrict__ scale_out,
+                                               int64_t l) {
     u32x4 r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = in[l * 4 + i];
@@ -346,6 +343,55 @@ __global__ __launch_bounds__(kBlock) void rtn_nvfp4_kernel(const u32x4* __restri
         w[i] = fp4_quant_unit<XDT, true>(ws, s[i >> 1], gs, false);
     }
     stream_store16(out + l, u32x4{w[0], w[1], w[2], w[3]});
+}
+
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void rtn_nvfp4_kernel(const u32x4* __restrict__ in, int64_t lanes, const float* __restrict__ global_scale,
+                                                           u32x4* __restrict__ out, uint16_t* __restrict__ scale_f8, float* __restrict__ scale_out) {
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (l >= lanes) return;
+    rtn_nvfp4_lane<XDT>(in, global_scale[0], out, scale_f8, scale_out, l);
+}
+
+// The same over a table (ct_rtn_nvfp4_amax_batch, then ct_rtn_nvfp4_quant_pack_batch): the tensor-wide amax that generate_gparam needs is a
+// pass of its own, so a table is two launches over the same rows.  Row: src = the weights, dst = the packed bytes, zp_packed = the float8 scale
+// output, zp = the item's amax KEY (one zeroed 32-bit word), scale = its float32 weight_global_scale output.
+// FOLD: a lane takes max |x| of its 32 elements on the raw pairs, the wave reduces, and its first lane folds the wave's 16-bit magnitude into the
+// key with one vector atomic — unsigned integer order is the float order of magnitudes, a NaN above inf, 0 the identity: exact, whatever
+// the schedule.  The key only grows, so a wave that reads a key already at or above its own value has nothing to add and skips the atomic (a
+// large tensor would otherwise queue tens of thousands of them on one address).
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void rtn_nvfp4_amax_batch_kernel(const ct_w4_item* __restrict__ items, int n) {
+    const ct_w4_item& it = fp4_batch_find(items, n, blockIdx.x);
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    uint32_t acc = 0;  // a lane past the end carries the identity through the reduction
+    if (l < (it.units >> 2)) {
+        const u32x4* in = static_cast<const u32x4*>(it.src);
+        u32x4 r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = in[l * 4 + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
+    }
+    acc = absmax_group_reduce(acc, 64);
+    if ((threadIdx.x & 63u) == 0u) {
+        const uint32_t h = (acc & 0xffffu) > (acc >> 16) ? (acc & 0xffffu) : (acc >> 16);
+        uint32_t* key = static_cast<uint32_t*>(const_cast<void*>(it.zp));
+        if (h > __hip_atomic_load(key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(key, h);
+    }
+}
+
+// QUANTIZE: rtn_nvfp4_kernel's lane under the global scale every lane derives from its item's key (gparam_from_amax, ct_minmax.h: what
+// ct_generate_gparam's last workgroup computes); the item's first lane stores it as the weight_global_scale.
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void rtn_nvfp4_batch_kernel(const ct_w4_item* __restrict__ items, int n) {
+    const ct_w4_item& it = fp4_batch_find(items, n, blockIdx.x);
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    if (l >= (it.units >> 2)) return;
+    const MinMax m = absmax_finish<XDT>(static_cast<const uint32_t*>(it.zp)[0]);  // the key is one 16-bit magnitude: the high half is zero
+    const float gs = gparam_from_amax<XDT>(m.nan ? __builtin_nanf("") : m.mx);
+    if (l == 0) static_cast<float*>(const_cast<void*>(it.scale))[0] = gs;
+    rtn_nvfp4_lane<XDT>(static_cast<const u32x4*>(it.src), gs, static_cast<u32x4*>(it.dst), static_cast<uint16_t*>(it.zp_packed), nullptr, l);
 }
 
 // every mantissa of s in [1, 2) against every mantissa of x in [1, 2) (7 bits bf16, 10 bits fp16; `xbits` of them):
@@ -983,6 +1029,58 @@ int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, 
     else hipLaunchKernelGGL((rtn_nvfp4_kernel<CT_F16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, global_scale,
                             reinterpret_cast<u32x4*>(packed), reinterpret_cast<uint16_t*>(scale_f8), scale_out);
     CT_LAUNCH_CHECK("ct_rtn_nvfp4_quant_pack");
+}
+
+int64_t ct_rtn_nvfp4_batch_plan(ct_w4_item* items, int n) {
+    if (n <= 0 || items == nullptr) {
+        set_error("ct_rtn_nvfp4_batch_plan: bad arguments (a table of %d items)", n);
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        ct_w4_item& it = items[i];
+        // the conditions of ct_rtn_nvfp4_quant_pack, per item, and the two words of the table form
+        const bool ok = it.rows > 0 && it.cols > 0 && it.group == 16 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && it.zp && it.scale && aligned16(it.src) &&
+                        aligned16(it.dst) && (reinterpret_cast<uintptr_t>(it.zp_packed) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.zp) & 3u) == 0 &&
+                        (reinterpret_cast<uintptr_t>(it.scale) & 3u) == 0;
+        if (!ok) {
+            set_error("ct_rtn_nvfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass NVFP4 compress "
+                      "(needs group 16, cols %% 32 == 0, 16-byte aligned src / dst, the float8 output in zp_packed, the 4-byte aligned amax key in zp and "
+                      "global-scale output in scale)", i, (long long)it.rows, (long long)it.cols, (long long)it.group);
+            return -1;
+        }
+        it.units = it.rows * (it.cols / 8);
+        it.upg = 2;
+        it.upg_shift = 1;
+        it.first_block = blocks;
+        it.main_blocks = cdiv64(it.units / 4, kBlock);
+        it.g_magic = 0;
+        it.g_shift = 0;
+        blocks += it.main_blocks;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_nvfp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_nvfp4_amax_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass NVFP4 compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_nvfp4_amax_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    else hipLaunchKernelGGL((rtn_nvfp4_amax_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_LAUNCH_CHECK("ct_rtn_nvfp4_amax_batch");
+}
+
+int ct_rtn_nvfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass NVFP4 compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_nvfp4_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    else hipLaunchKernelGGL((rtn_nvfp4_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_LAUNCH_CHECK("ct_rtn_nvfp4_quant_pack_batch");
 }
 
 }  // extern "C"

@@ -269,4 +269,17 @@ __device__ __forceinline__ float compute_qparams_float(MinMax m, int kind, float
     return s == 0.0f ? 1.0f : s;
 }
 
+// generate_gparam's tail (helpers.py:324-337) of a tensor-wide amax (>= 0, or NaN where an element was): clamp(min=finfo(X).tiny) — a NaN passes
+// through —, 448 * 6 / amax in x's dtype as the eager expression evaluates it (`float / tensor` = reciprocal, then product: two roundings), as float32,
+// non-finite -> 1 (nan_to_num).  One thread per tensor runs this: ct_generate_gparam's last workgroup, a lane of the NVFP4 round-to-nearest table
+// (csrc/ct_fp4.hip), the observer's kind-2 finalize (csrc/ct_attn_observe.hip).
+template <int XDT>
+__device__ __forceinline__ float gparam_from_amax(float amax) {
+    const float tiny = XDT == CT_F16 ? 0x1p-14f : 0x1p-126f;  // torch.finfo(dtype).tiny
+    amax = amax < tiny ? tiny : amax;
+    const float recip = round_to<XDT>(1.0f / amax);
+    const float gs = round_to<XDT>(recip * 2688.0f);           // FP8_E4M3_DATA.max * FP4_E2M1_DATA.max
+    return __builtin_isfinite(gs) ? gs : 1.0f;
+}
+
 }  // namespace ct

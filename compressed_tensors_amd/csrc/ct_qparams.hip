@@ -254,12 +254,7 @@ __global__ __launch_bounds__(kBlock) void gparam_finish_kernel(const void* __res
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int w = 1; w < kBlock / 64; ++w) { mx = __builtin_fmaxf(mx, s_mx[w]); nan |= s_nan[w]; }
-        const float tiny = XDT == CT_F16 ? 0x1p-14f : 0x1p-126f;  // torch.finfo(dtype).tiny
-        float amax = nan ? __builtin_nanf("") : mx;
-        amax = amax < tiny ? tiny : amax;                          // clamp(min=tiny): a NaN passes through
-        const float recip = round_to<XDT>(1.0f / amax);
-        const float gs = round_to<XDT>(recip * 2688.0f);           // FP8_E4M3_DATA.max * FP4_E2M1_DATA.max
-        gs_out[0] = __builtin_isfinite(gs) ? gs : 1.0f;            // nan_to_num(nan=1, posinf=1, neginf=1)
+        gs_out[0] = gparam_from_amax<XDT>(nan ? __builtin_nanf("") : mx);  // ct_minmax.h
     }
 }
 

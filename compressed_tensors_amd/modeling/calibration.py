@@ -3,6 +3,9 @@ parameters of an attention module (the behaviour of upstream's lifecycle/initial
 `calibrate_attention` observes the states of every such module while the model runs and writes those parameters in place — the
 launches of csrc/ct_attn_observe.hip, on the views the hooks of this package see, before the QDQ of the same forward reads them.
 
+`calibrate_global_scales` is the same for the NVFP4 preset's activations (`tensor_group`, `dynamic="local"`): it registers `input_global_scale` /
+`output_global_scale` and writes them from the inputs / outputs of every such module while the model runs (kind 2 of the same launch).
+
 Nothing here runs unless it is called: no existing path launches an observer."""
 import contextlib
 from typing import Optional
@@ -14,7 +17,7 @@ from ..quantization.quant_args import enum_value
 from .attention import IMPL_ATTR, register_query_hook
 from .kvcache import KV_CACHE_ATTR, register_key_value_hook
 
-__all__ = ["initialize_attn_qparams", "calibrate_attention", "OBSERVE_PAIR_MEASURED_FASTER", "OBSERVER_ATTR"]
+__all__ = ["initialize_attn_qparams", "calibrate_attention", "calibrate_global_scales", "OBSERVE_PAIR_MEASURED_FASTER", "OBSERVER_ATTR"]
 
 # K and V of one cache update through ONE ct_attn_observe (codec.attn_observe_pair) instead of two: dispatched only where
 # tools/attn_observe_bench.py measured the pair faster than the two single calls by more than the spread between its runs, at the
@@ -162,6 +165,57 @@ def calibrate_attention(model: torch.nn.Module, observer: Optional[str] = None):
                 handles.append(register_query_hook(module, _query_hook))
             if "k" in names and "v" in names and getattr(module, KV_CACHE_ATTR, None) is not None:
                 handles.append(register_key_value_hook(module, _key_value_hook))
+        yield model
+    finally:
+        for handle in handles:
+            handle.remove()
+        for module, attr in registered:
+            if attr in module._modules:
+                del module._modules[attr]
+
+
+def _global_scale_args(module, base_name: str):
+    """the `tensor_group` activation arguments of a module's scheme whose global scale an observer can fill, or None"""
+    args = getattr(getattr(module, "quantization_scheme", None), f"{base_name}_activations", None)
+    if args is None or enum_value(args.strategy) != "tensor_group" or enum_value(getattr(args, "dynamic", False)) != "local":
+        return None
+    return args
+
+
+def _input_global_scale_hook(module, args):
+    if args and isinstance(args[0], torch.Tensor) and args[0].numel():
+        module.input_observer.get_global_scale(args[0], module.input_global_scale)
+
+
+def _output_global_scale_hook(module, args, output):
+    if isinstance(output, torch.Tensor) and output.numel():
+        module.output_observer.get_global_scale(output, module.output_global_scale)
+
+
+@contextlib.contextmanager
+def calibrate_global_scales(model: torch.nn.Module, observer: Optional[str] = None):
+    """While active, every module of `model` whose scheme has `tensor_group`, `dynamic="local"` input (or output) activations — the NVFP4 preset's
+    — has `generate_gparam` of its inputs (outputs) written into its `input_global_scale` (`output_global_scale`) on every forward: a forward
+    pre-hook (a forward hook for outputs) launches the observer on the tensor as it arrives, in place through its strides, in stream order BEFORE the
+    module's own forward_quantize reads the parameter — no host wait, no eager reduction.  A missing parameter is registered as upstream's
+    initialize registers it (float32 (1,), no grad, on the device of the module's parameters); an existing one is kept and written in place.
+    `observer`: "static_minmax" (the extremes of every forward since entry: the preset's) or "memoryless_minmax" (each forward's own); None: the
+    arguments' own.  On exit the hooks and the observers are removed; the parameters keep what the last forward wrote."""
+    handles, registered = [], []
+    try:
+        for module in list(model.modules()):  # the observers registered below are modules too
+            for base_name, register, hook in (("input", "register_forward_pre_hook", _input_global_scale_hook),
+                                              ("output", "register_forward_hook", _output_global_scale_hook)):
+                args = _global_scale_args(module, base_name)
+                if args is None:
+                    continue
+                if getattr(module, f"{base_name}_global_scale", None) is None:
+                    first = next(module.parameters(), None)
+                    device = first.device if first is not None else None
+                    module.register_parameter(f"{base_name}_global_scale", torch.nn.Parameter(torch.empty(1, dtype=torch.float32, device=device), requires_grad=False))
+                module.register_module(OBSERVER_ATTR.format(base_name), MinMaxObserver(base_name, args, module, observer))
+                registered.append((module, OBSERVER_ATTR.format(base_name)))
+                handles.append(getattr(module, register)(hook))
         yield model
     finally:
         for handle in handles:

@@ -5,7 +5,8 @@ strided launch of csrc/ct_attn_observe.hip.
 It serves the states the static QDQ of csrc/ct_attn.hip consumes — `q` / `k` / `v` under the `tensor` and `attn_head`
 strategies, read in place through the strides an attention module passes — and `input` / `output` activations under `tensor`
 (the static W8A8 case: the tensor strategy reduces everything, so a `(..., hidden)` activation is one scale entry whose rows are
-`hidden` long).  Weights stay with `calculate_qparams_from_weight`, which fuses their observer with the scale computation.
+`hidden` long), and the calibrated half of the NVFP4 preset's `tensor_group`, `dynamic="local"` activations: `get_global_scale`, the float32
+global scale under which forward_quantize computes the local scales per call.  Weights stay with `calculate_qparams_from_weight`, which fuses their observer with the scale computation.
 
 No arithmetic lives here: the running extremes are 32-bit order keys in a caller-visible buffer (`state`), folded and turned into
 scale / zero point by the kernel."""
@@ -39,12 +40,17 @@ class MinMaxObserver(torch.nn.Module):
         if base_name == "weight":
             raise NotImplementedError("weights are observed by calculate_qparams_from_weight (quantization/utils.py), which fuses the observer "
                                       "with the scale computation; MinMaxObserver serves q / k / v and input / output")
+        dynamic = enum_value(getattr(args, "dynamic", False))
+        # the NVFP4 preset's activations (tensor_group, dynamic="local"): the local scales are forward_quantize's, per call; the GLOBAL scale is
+        # calibrated — get_global_scale below
+        self.global_only = base_name in _ACTIVATION and strategy == "tensor_group" and dynamic == "local"
         if base_name in _ACTIVATION:
-            if strategy != "tensor":
-                raise NotImplementedError(f"a static {strategy!r} observer of {base_name} activations is not implemented by the MI355X path (tensor is)")
+            if strategy != "tensor" and not self.global_only:
+                raise NotImplementedError(f"a static {strategy!r} observer of {base_name} activations is not implemented by the MI355X path (tensor is, and "
+                                          "tensor_group with dynamic='local' for its global scale)")
         elif base_name not in _ATTENTION:
             raise ValueError(f"Unknown quantization base name: {base_name}")
-        if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
+        if dynamic in (True, "local") and not self.global_only:
             raise NotImplementedError("dynamic arguments are not observed: forward_quantize computes their scales per call")
         self.parent = weakref.ref(module) if module is not None else (lambda: None)
         self.base_name = base_name
@@ -54,6 +60,7 @@ class MinMaxObserver(torch.nn.Module):
         self.min_vals = None
         self.max_vals = None
         self._state = None
+        self._global_state = None
 
     def _kwargs(self):
         a = self.args
@@ -69,15 +76,27 @@ class MinMaxObserver(torch.nn.Module):
 
     def reset(self) -> None:
         """forget every call so far: the state is armed again (in place; nothing waits)"""
-        if self._state is not None:
-            codec.attn_observe_arm(self._state)
+        for state in (self._state, self._global_state):
+            if state is not None:
+                codec.attn_observe_arm(state)
         self.min_vals = self.max_vals = None
 
     def _global_scale(self):
         parent = self.parent()
         return getattr(parent, f"{self.base_name}_global_scale", None) if parent is not None else None
 
+    def get_global_scale(self, observed: torch.Tensor, global_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the reference observer's get_global_scale: generate_gparam of the extremes of the WHOLE tensor (its `reshape((1, 1, -1))`, read in
+        place through the strides), float32 (1,) — of this call alone ("memoryless_minmax") or of every call since reset() ("static_minmax").
+        `global_scale` (a module's `{base_name}_global_scale` parameter): the kernel writes it in place and it is what is returned."""
+        if self._global_state is None or self._global_state.device != observed.device:
+            self._global_state = codec.attn_observe_state(1, observed.device)
+        return codec.attn_observe_global_scale(observed, self._global_state, keep=self.keep, global_scale=global_scale)
+
     def forward(self, observed: torch.Tensor, scale: Optional[torch.Tensor] = None, zero_point: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.global_only:
+            raise NotImplementedError("dynamic arguments are not observed: forward_quantize computes their local scales per call (get_global_scale "
+                                      "calibrates the global one)")
         scale, zero_point, self.min_vals, self.max_vals = codec.attn_observe(
             observed, self.state_for(observed), scale=scale, zero_point=zero_point, global_scale=self._global_scale(), **self._kwargs())
         return scale, zero_point

@@ -423,7 +423,9 @@ typedef struct ct_attn_observe_tensor {
     int64_t per_head;
 } ct_attn_observe_tensor;          /* 14 64-bit words */
 
-/* kind 0 INT (bits 1..8, symmetric or not), 1 FLOAT 8-bit (float8_e4m3fn, symmetric; bits ignored).  xdt: a float dtype; the
+/* kind 0 INT (bits 1..8, symmetric or not), 1 FLOAT 8-bit (float8_e4m3fn, symmetric; bits ignored), 2 the NVFP4 global scale: same fold, same
+ * state, and `scale` (sdt must be float32, zp NULL) receives generate_gparam(min, max) of the running extremes (helpers.py:308-337, the
+ * arithmetic of ct_generate_gparam below, evaluated in xdt) — what an observer's get_global_scale returns.  xdt: a float dtype; the
  * arithmetic of calculate_qparams runs in it, as ct_minmax_qparams{,_float} run it.  n = 2: both tensors (K and V) share every
  * argument and every launch.  Two launches (fold, finalize), whatever the size; the descriptors travel as kernel arguments.
  * Allocates nothing, never synchronises, keeps no device state.  CT_ERR_INVALID_ARG for a negative shape or stride, an empty
@@ -510,6 +512,20 @@ int ct_rtn_mxfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t to
  * scale_f8: float8_e4m3fn bytes (rows, cols/16), the stored form; scale_out (nullable): the float32 scales. cols % 32 == 0. */
 int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, const float* global_scale,
                             uint8_t* packed, uint8_t* scale_f8, float* scale_out, ct_stream_t stream);
+/* ... with generate_gparam of each weight, for a whole table of tensors in TWO launches (the per-module loop over NVFP4PackedCompressor: the two
+ * launches of ct_generate_gparam and ct_rtn_nvfp4_quant_pack per module).  The table is `struct ct_w4_item` read this way: src = the weights, dst =
+ * the packed bytes (rows, cols / 2), zp_packed = the float8 scale OUTPUT (rows, cols / 16), zp = the item's amax KEY — one 32-bit word of device
+ * memory, its own per item, ZERO before the fold (one fill of a per-table buffer) —, scale = the item's weight_global_scale OUTPUT (float32[1]),
+ * group = 16.  ct_rtn_nvfp4_batch_plan (host only) admits what ct_rtn_nvfp4_quant_pack admits, per item (n <= 0: an error), fills the derived
+ * fields and returns the workgroup count, or -1 with the error text set.
+ *   ct_rtn_nvfp4_amax_batch: folds max |x| of every item into its key as the 16-bit magnitude pattern (unsigned integer order == float order, a
+ *     NaN above inf, 0 the identity) with vector atomic maxima: exact, independent of scheduling.
+ *   ct_rtn_nvfp4_quant_pack_batch, behind it on the same stream: every lane derives the item's global scale from the key (the arithmetic of
+ *     ct_generate_gparam), one lane per item stores it, and the weights are quantized under it.  Bit-identical to ct_generate_gparam +
+ *     ct_rtn_nvfp4_quant_pack per item.  The library allocates nothing and never synchronises. */
+int64_t ct_rtn_nvfp4_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_nvfp4_amax_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
+int ct_rtn_nvfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
 
 /* The stand-alone primitives the reference exposes as ImplBackend entry points (utils/impl_backend.py:50-79):
  * cast_to_fp4 (quantization/utils/fp4_utils.py:77-98): n float elements -> the nearest E2M1 value in the same

@@ -1,10 +1,10 @@
 """ModelCompressor.compress_model_rtn wall time, table launches (batched=True) against one launch per module (batched=False, the path before the
 tables existed), alternated in one process on the same trees: a Llama-3-8B-shaped tree (32 layers, 224 modules) and a TinyLlama-shaped one (22
-layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4.  A compress consumes the model, so the dense weights are kept and re-attached
+layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4.  A compress consumes the model, so the dense weights are kept and re-attached
 between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
 their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
 
-    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4] [--out FILE]
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4] [--out FILE]
 """
 import argparse
 import json
@@ -31,6 +31,8 @@ def scheme_of(name):
         args = cta.QuantizationArgs(num_bits=4, group_size=128, symmetric=False, strategy="group")
     elif name == "mxfp4":
         args = cta.QuantizationArgs(num_bits=4, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8)
+    elif name == "nvfp4":
+        args = cta.QuantizationArgs(num_bits=4, type="float", strategy="tensor_group", symmetric=True, group_size=16, scale_dtype=torch.float8_e4m3fn)
     else:
         raise SystemExit(f"unknown scheme {name}")
     return cta.QuantizationScheme(targets=["Linear"], weights=args)
@@ -41,6 +43,8 @@ def algorithmic_bytes(name, rows, cols):
     n = rows * cols
     if name == "mxfp4":
         return 2 * n + n // 2 + n // 32
+    if name == "nvfp4":
+        return 2 * 2 * n + n // 2 + n // 16 + 4  # the weight twice (the tensor-wide amax of generate_gparam is a pass of its own), the float8 scales, the global scale
     out = 2 * n + n // 2 + 2 * (n // 128)
     if name == "w4asym":
         out += -(-rows // 8) * (cols // 128) * 4  # weight_zero_point, packed along the rows
@@ -78,7 +82,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="alternations of the two paths (the median is reported; at least 5)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--trees", default="8b,tiny")
-    ap.add_argument("--schemes", default="w4,w4asym,mxfp4")
+    ap.add_argument("--schemes", default="w4,w4asym,mxfp4,nvfp4")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.reps < 5:
@@ -86,6 +90,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("rtn_bench.py measures on the GPU: no device is visible")
     dev = torch.device("cuda:0")
+    cta.NVFP4PackedCompressor.RTN_TABLE_MEASURED_FASTER = True  # batched=True measures the NVFP4 table whatever the dispatch constant holds: this is its input
     for tree in a.trees.split(","):
         label, shapes, nlayers = TREES[tree]
         model, pool = build(shapes, nlayers, dev)
