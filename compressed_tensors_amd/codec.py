@@ -1618,7 +1618,8 @@ def item_row(src=0, scale=0, zp=0, dst=0, rows=0, cols=0, group=0, zp_packed=0) 
     return _pick_row((src, scale, zp, dst, rows, cols, group, zp_packed, 0))
 
 
-# table kind -> (plan symbol, the plan takes the direction, launch symbol | (compress, decompress) launch symbols): every table of ct_w4_item rows
+# table kind -> (plan symbol, the plan takes the direction, launch symbol | the launch symbols `d` of `_run_table` picks from — (compress, decompress), or
+# the (fold, quantize) passes that ONE plan of "rtn_nvfp4" serves over the same rows): every table of ct_w4_item rows
 _TABLES = {
     "w4": ("ct_w4_batch_plan", True, ("ct_quant_pack_batch", "ct_unpack_dequant_batch")),
     "q8": ("ct_q8_batch_plan", True, ("ct_q8_quant_batch", "ct_q8_dequant_batch")),
@@ -1627,18 +1628,19 @@ _TABLES = {
     "zp4": ("ct_zp4_batch_plan", False, "ct_zp4_pack_dim0_batch"),
     "rtn_w4": ("ct_rtn_w4_batch_plan", False, "ct_rtn_quant_pack_w4_batch"),
     "rtn_mxfp4": ("ct_rtn_mxfp4_batch_plan", False, "ct_rtn_mxfp4_quant_pack_batch"),
-}
-# the same triple for a table that ONE plan serves in TWO passes over the same rows — (fold, quantize), both per table, where a kind above has one launch
-# per direction: `d` of `_run_table` picks the pass
-_TWO_PASS_TABLES = {
     "rtn_nvfp4": ("ct_rtn_nvfp4_batch_plan", False, ("ct_rtn_nvfp4_amax_batch", "ct_rtn_nvfp4_quant_pack_batch")),
 }
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
+def _q8_scalars(dt: int, kind: int, bits: int, d: int) -> tuple:
+    """the scalar arguments of the 8-bit tables' launches: only the compress takes the INT scheme's num_bits"""
+    return (dt, kind, bits) if d == 0 else (dt, kind)
+
+
 def _plan_table(kind: str, words, n: int, device, d: int = 0):
     """the first half of `_launch_table`: plan `words` in place and upload them -> (device table, workgroups)"""
-    plan, directed, _ = _TABLES.get(kind) or _TWO_PASS_TABLES[kind]
+    plan, directed, _ = _TABLES[kind]
     if isinstance(words, list):
         words = array.array("q", words)
     addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
@@ -1651,7 +1653,7 @@ def _plan_table(kind: str, words, n: int, device, d: int = 0):
 
 def _run_table(kind: str, table, n: int, blocks: int, device, d: int, scalars, stream=None) -> None:
     """the second half: ONE launch of a planned, uploaded table"""
-    symbol = (_TABLES.get(kind) or _TWO_PASS_TABLES[kind])[2]
+    symbol = _TABLES[kind][2]
     call(symbol if isinstance(symbol, str) else symbol[d], table.data_ptr(), n, blocks, *scalars, _lib.stream_on(device, stream))
 
 
@@ -1684,7 +1686,7 @@ def launch_q8_words(words: torch.Tensor, n: int, direction: str, dtype: torch.dt
     """`launch_w4_words` for a table of the 8-bit codecs (`ct_q8_quant_batch` / `ct_q8_dequant_batch`); kind 0 int8, 1 fp8, 2 fp8 with float8 zero points"""
     d = 0 if direction == "compress" else 1
     if n:
-        _launch_table("q8", words, n, device, d, (DT[dtype], kind, bits) if d == 0 else (DT[dtype], kind))
+        _launch_table("q8", words, n, device, d, _q8_scalars(DT[dtype], kind, bits, d))
 
 
 def launch_fp4_words(words: torch.Tensor, n: int, direction: str, device: torch.device, group: int, x_dtype=None, scale_dtype=None) -> None:
@@ -1758,9 +1760,7 @@ class W4Batch:
         if self.kind == "w4":
             _run_table("w4", self.table, self.n, self.blocks, self.device, self.direction, (self.dt,), stream)
         else:
-            kind = _Q8_KINDS[self.kind]
-            _run_table("q8", self.table, self.n, self.blocks, self.device, self.direction,
-                       (self.dt, kind, self.bits) if self.direction == 0 else (self.dt, kind), stream)
+            _run_table("q8", self.table, self.n, self.blocks, self.device, self.direction, _q8_scalars(self.dt, _Q8_KINDS[self.kind], self.bits, self.direction), stream)
 
 
 def quantize_and_pack_many(items, *, num_bits, strategy, group_size=None):
@@ -1875,10 +1875,15 @@ def rtn_w4_table_item(x, group_size, with_zp: bool = True):
     return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
 
 
+def _rtn_fp4_takes(x) -> bool:
+    """do the one-pass FP4 tables, MXFP4 and NVFP4, take this weight — on a GPU, 2-D, contiguous, 16-byte aligned, 16-bit, cols % 32 == 0?"""
+    return _rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0
+
+
 def rtn_mxfp4_table_item(x):
     """`rtn_w4_table_item` for the one-pass MXFP4 table (`launch_rtn_mxfp4_words`; cols % 32 == 0): (packed uint8 (R, C / 2), E8M0 codes uint8
     (R, C / 32), row) or None"""
-    if not (_rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0):
+    if not _rtn_fp4_takes(x):
         return None
     rows, cols = int(x.shape[0]), int(x.shape[1])
     packed = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
@@ -1886,9 +1891,7 @@ def rtn_mxfp4_table_item(x):
     return packed, code, item_row(x.data_ptr(), 0, 0, packed.data_ptr(), rows, cols, 32, code.data_ptr())
 
 
-def rtn_nvfp4_takes(x) -> bool:
-    """does the one-pass NVFP4 table take this weight — on a GPU, 2-D, contiguous, 16-byte aligned, 16-bit, cols % 32 == 0?"""
-    return _rtn_table_tensor(x) and x.shape[0] > 0 and x.shape[1] > 0 and x.shape[1] % 32 == 0
+rtn_nvfp4_takes = _rtn_fp4_takes  # public for NVFP4: its callers ask before they open a table's key buffer
 
 
 def rtn_nvfp4_keys(n: int, device) -> torch.Tensor:
@@ -1918,6 +1921,30 @@ def _rtn_w4_one(x, group_size, symmetric):
     return packed, scale, zp
 
 
+def _rtn_many(weights, item, single, launch, held=()) -> list:
+    """the list form of every one-pass round-to-nearest table.  `item(i, x, n)` -> (outputs..., row) when the table takes `weights[i]` as its n-th
+    item, else None; the first tensor taken fixes the table's device and dtype, and every tensor not taken goes to `single(i, x)`.  The rows are
+    gathered flat, ONE `launch(flat, n, dtype, device)` follows, and the device table it returns and then whatever `held` holds by then (a buffer the
+    rows point into) are recorded on the current stream.  Returns the outputs in input order; they keep the tensors the table's raw pointers name
+    alive, `weights` the inputs."""
+    out = [None] * len(weights)
+    first, n, flat = None, 0, []
+    for i, x in enumerate(weights):
+        got = item(i, x, n) if first is None or (x.device == first.device and x.dtype == first.dtype) else None
+        if got is None:
+            out[i] = single(i, x)
+            continue
+        first = x if first is None else first
+        out[i] = got[:-1]
+        flat += got[-1]
+        n += 1
+    if n:
+        stream = torch.cuda.current_stream(first.device)
+        for t in (launch(flat, n, first.dtype, first.device), *held):
+            t.record_stream(stream)
+    return out
+
+
 def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True):
     """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_w4_table_item`, of the first such tensor's device and
     dtype) leave in ONE `ct_rtn_quant_pack_w4_batch` launch — a checkpoint is a few hundred
@@ -1928,43 +1955,15 @@ def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True):
     groups = list(group_size) if isinstance(group_size, (list, tuple)) else [group_size] * len(weights)
     if len(groups) != len(weights):
         raise ValueError(f"{len(groups)} group sizes for {len(weights)} weights")
-    out = [None] * len(weights)
-    first, where, flat = None, [], []  # (`out` keeps the tensors the table's raw pointers name alive, `weights` the inputs)
-    for i, (x, gs) in enumerate(zip(weights, groups)):
-        item = rtn_w4_table_item(x, gs) if first is None or (x.device == first.device and x.dtype == first.dtype) else None
-        if item is None:
-            out[i] = _rtn_w4_one(x, gs, symmetric)
-            continue
-        first = x if first is None else first
-        out[i] = item[:3]
-        flat += item[3]
-        where.append(i)
-    if where:
-        table = launch_rtn_w4_words(flat, len(where), first.dtype, first.device, symmetric)
-        table.record_stream(torch.cuda.current_stream(first.device))
-    return out
+    return _rtn_many(weights, lambda i, x, n: rtn_w4_table_item(x, groups[i]), lambda i, x: _rtn_w4_one(x, groups[i], symmetric),
+                     lambda flat, n, dtype, device: launch_rtn_w4_words(flat, n, dtype, device, symmetric))
 
 
 def rtn_mxfp4_quantize_and_pack_many(weights):
     """`rtn_mxfp4_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_mxfp4_table_item`, of the first such tensor's device
     and dtype) leave in ONE `ct_rtn_mxfp4_quant_pack_batch` launch, the others one by one.  Returns
     [(packed uint8 (R, C / 2), E8M0 codes uint8 (R, C / 32))] in input order, bit-identical to the single-tensor call per item."""
-    weights = list(weights)
-    out = [None] * len(weights)
-    first, n, flat = None, 0, []
-    for i, x in enumerate(weights):
-        item = rtn_mxfp4_table_item(x) if first is None or (x.device == first.device and x.dtype == first.dtype) else None
-        if item is None:
-            out[i] = rtn_mxfp4_quantize_and_pack(x)
-            continue
-        first = x if first is None else first
-        out[i] = item[:2]
-        flat += item[2]
-        n += 1
-    if n:
-        table = launch_rtn_mxfp4_words(flat, n, first.dtype, first.device)
-        table.record_stream(torch.cuda.current_stream(first.device))
-    return out
+    return _rtn_many(list(weights), lambda i, x, n: rtn_mxfp4_table_item(x), lambda i, x: rtn_mxfp4_quantize_and_pack(x), launch_rtn_mxfp4_words)
 
 
 def rtn_nvfp4_quantize_and_pack_many(weights):
@@ -1973,24 +1972,16 @@ def rtn_nvfp4_quantize_and_pack_many(weights):
     (`launch_rtn_nvfp4_words`) instead of three launches each, the others one by one.  Returns [(packed uint8 (R, C / 2), float8_e4m3fn scales
     (R, C / 16), float32 (1,) global scale)] in input order, bit-identical to the single-tensor call per item; every global scale owns its storage."""
     weights = list(weights)
-    out = [None] * len(weights)
-    first, n, flat, keys = None, 0, [], None
-    for i, x in enumerate(weights):
-        if not (rtn_nvfp4_takes(x) and (first is None or (x.device == first.device and x.dtype == first.dtype))):
-            out[i] = rtn_nvfp4_quantize_and_pack(x)
-            continue
-        if first is None:
-            first, keys = x, rtn_nvfp4_keys(len(weights) - i, x.device)  # the n-th item's key is word n
-        item = rtn_nvfp4_table_item(x, keys.data_ptr() + 4 * n)
-        out[i] = item[:3]
-        flat += item[3]
-        n += 1
-    if n:
-        table = launch_rtn_nvfp4_words(flat, n, first.dtype, first.device)
-        stream = torch.cuda.current_stream(first.device)
-        table.record_stream(stream)
-        keys.record_stream(stream)
-    return out
+    keys = []  # the table's key buffer, from its first item on
+
+    def item(i, x, n):
+        if not rtn_nvfp4_takes(x):
+            return None
+        if not keys:
+            keys.append(rtn_nvfp4_keys(len(weights) - i, x.device))  # the n-th item's key is word n
+        return rtn_nvfp4_table_item(x, keys[0].data_ptr() + 4 * n)
+
+    return _rtn_many(weights, item, lambda i, x: rtn_nvfp4_quantize_and_pack(x), launch_rtn_nvfp4_words, keys)
 
 
 def zp4_batch(pairs, direction: str) -> None:

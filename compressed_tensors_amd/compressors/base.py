@@ -13,9 +13,9 @@ import torch
 from ..config import CompressionFormat
 from ..quantization.quant_args import QuantizationStatus, is_scheme
 from ..registry import RegistryMixin
-from ..utils.module import get_direct_state_dict, replace_direct_state_dict
+from ..utils.module import direct_entry, get_direct_state_dict, replace_direct_state_dict, swap_direct_entries
 
-__all__ = ["BaseCompressor", "symmetric_zp_keys", "zp_drop_mask", "rtn_windows", "launch_chunks", "run_planned", "compress_module", "decompress_module", "compress_modules", "decompress_modules", "COMPRESSIBLE_MODULE_TYPES"]
+__all__ = ["BaseCompressor", "symmetric_zp_keys", "zp_drop_mask", "rtn_windows", "run_rtn_windows", "launch_chunks", "run_planned", "compress_module", "decompress_module", "compress_modules", "decompress_modules", "COMPRESSIBLE_MODULE_TYPES"]
 
 # reference compressors/base.py:31
 COMPRESSIBLE_MODULE_TYPES = (torch.nn.Linear, torch.nn.Embedding)
@@ -42,8 +42,8 @@ def zp_drop_mask(scheme) -> int:
     return drop
 
 
-# modules per table of the data-free (round-to-nearest) module paths, `compress_rtn_modules`: building a table costs the host ~10 us per module, during
-# which the GPU would idle, so a long list leaves as windows — the host builds window k + 1 and rewrites the parameter dictionaries of window k under
+# modules per table of the data-free (round-to-nearest) module paths — the codecs' window hook `compress_rtn_modules`, over `run_rtn_windows` below:
+# building a table costs the host ~10 us per module, during which the GPU would idle, so a long list leaves as windows — the host builds window k + 1 and rewrites the parameter dictionaries of window k under
 # window k's kernel.  tools/rtn_bench.py, W4 g128, windows of 16 / 32 / 64 / one table: 3.60 / 3.63 / 3.74 / 4.66 ms on an 8B-shaped tree (the per-module
 # loop: 4.53), 2.20 / 2.06 / 2.00 / 2.09 ms on a TinyLlama-shaped one (3.14)
 RTN_WINDOW = 32
@@ -52,6 +52,53 @@ RTN_WINDOW = 32
 def rtn_windows(modules):
     modules = list(modules)
     return [modules[lo:lo + RTN_WINDOW] for lo in range(0, len(modules), RTN_WINDOW)]
+
+
+def run_rtn_windows(cls, modules, item, launch, entries, state=None) -> None:
+    """the driver of every data-free window hook (`compress_rtn_modules` of the codecs that have a one-pass table): `compress_rtn` + the parameter
+    swap for a list of modules, in windows (`rtn_windows`).  Per window it fetches each module's `weight`, groups the modules the codec takes into
+    tables, issues EVERY table's launch before any module is touched, rewrites the parameter dictionaries under the kernels — every `weight*`
+    entry goes, the codec's entries come — and then runs the modules no table took through `cls.compress_rtn_module`, in module order.  Every
+    module ends in exactly the state `compress_rtn_module` leaves it in.  The codec supplies what differs:
+
+    `item(m, w, table)` -> None, or `(key, row, outs)` once it takes module `m` with weight `w`: `key` = (device, dtype, ...) names the launch the
+        module joins, `row` is its `codec.item_row` and `outs` its freshly allocated outputs.  A table opens at its first item — (flat rows, jobs,
+        `state(len(window), device)` or None); a codec whose rows point into that state (NVFP4: the amax keys, item n owns word n = `len(jobs)`)
+        asks for it with `table(key)` before it builds the row;
+    `launch(key, flat, jobs)` -> the device table: the table's launch and whatever has to follow directly behind it (W4: the stored zero
+        points); the driver records the device table, then the state, on the device's current stream;
+    `entries(w, outs)` -> the parameters a job adds.
+
+    (Host-bound at 10-19 us per module: per module this adds no allocation beyond the job tuple and the returned triple.)"""
+    def table(key):  # closes over `tables` and `window`, which the loop below rebinds: it always opens a table of the CURRENT window
+        t = tables.get(key)
+        if t is None:  # opened by its first item, its state sized by the window
+            t = tables[key] = ([], [], None if state is None else state(len(window), key[0]))
+        return t
+
+    for window in rtn_windows(modules):
+        tables, rest = {}, []
+        for m in window:
+            w = direct_entry(m, "weight")
+            got = item(m, w, table) if w is not None else None
+            if got is None:
+                rest.append(m)
+                continue
+            key, row, outs = got
+            t = tables.get(key) or table(key)
+            t[0].extend(row)
+            t[1].append((m, w, outs))  # the table holds raw pointers: the jobs keep the tensors alive
+        for key, (flat, jobs, held) in tables.items():
+            stream = torch.cuda.current_stream(key[0])
+            launch(key, flat, jobs).record_stream(stream)
+            if held is not None:
+                held.record_stream(stream)
+        for _, jobs, _ in tables.values():  # from here on the host works under the kernels
+            for m, w, outs in jobs:
+                remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
+                swap_direct_entries(m, remove, entries(w, outs), status=QuantizationStatus.COMPRESSED)
+        for m in rest:
+            cls.compress_rtn_module(m)
 
 
 def launch_chunks(n: int):
@@ -132,8 +179,6 @@ class BaseCompressor(RegistryMixin, ABC):
     def compress_rtn_module(cls, module: torch.nn.Module) -> None:
         """data-free compression of one module from its dense weight (`compress_rtn` of the codecs that have one): every `weight*` entry goes,
         the codec's entries come, bias and the rest stay"""
-        from ..utils.module import direct_entry, swap_direct_entries
-
         new = cls.compress_rtn(direct_entry(module, "weight").data, module.quantization_scheme)
         remove = [k for k in (*module._parameters, *module._buffers) if k.startswith("weight")]
         swap_direct_entries(module, remove, new, status=QuantizationStatus.COMPRESSED)

@@ -13,7 +13,7 @@ from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
 from ...quantization.quant_args import QuantizationStatus
 from ...utils.module import direct_entry, swap_direct_entries
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, run_planned, symmetric_zp_keys, zp_drop_mask
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, run_rtn_windows, symmetric_zp_keys, zp_drop_mask
 
 __all__ = ["NVFP4PackedCompressor", "MXFP4PackedCompressor"]
 
@@ -26,10 +26,11 @@ def _is_fp4(scheme, group_size) -> bool:
 @BaseCompressor.register(name=CompressionFormat.nvfp4_pack_quantized.value)
 class NVFP4PackedCompressor(BaseCompressor):
     GROUP = 16
-    # `compress_model_rtn(batched=True)` hands its NVFP4 modules to `compress_rtn_tables` only while this holds: True once tools/rtn_bench.py has
-    # measured the table path faster than the per-module loop on both trees by more than the spread between its two runs (the project's dispatch
-    # rule).  The NVFP4 rows of profiles/rtn_bench.jsonl have not been recorded yet, so it is False: per module, as before; the hook and the codec
-    # entry (codec.rtn_nvfp4_quantize_and_pack_many) stay for a caller that wants them.  DESIGN.md 5.17.
+    # the gate of the window hook: `compress_model_rtn(batched=True)` hands a codec's modules to its `compress_rtn_modules` only while this holds —
+    # True once tools/rtn_bench.py has measured the table path faster than the per-module loop on both trees by more than the spread between its
+    # two runs (the project's dispatch rule).  NVFP4 stays per module (profiles/rtn_bench.jsonl, scheme nvfp4: the table is 1.28x / 1.34x faster on the
+    # TinyLlama-shaped tree and 0.80x / 0.82x slower on the 8B-shaped one); the hook and the codec entry (codec.rtn_nvfp4_quantize_and_pack_many) stay
+    # for a caller that wants them.  DESIGN.md 5.17.
     RTN_TABLE_MEASURED_FASTER = False
 
     @classmethod
@@ -197,36 +198,20 @@ class NVFP4PackedCompressor(BaseCompressor):
         return cls.compress({"weight": weight, "weight_scale": scale, "weight_global_scale": gs}, scheme)
 
     @classmethod
-    def compress_rtn_tables(cls, modules) -> None:
-        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`) — what `MXFP4PackedCompressor.compress_rtn_modules`
-        does, under the name `compress_model_rtn` looks up second: the modules with a 16-bit weight on a GPU (cols % 32 == 0, float8 scales) leave in one
-        fill of the window's amax keys and TWO table launches per (device, dtype) (codec.launch_rtn_nvfp4_words: `generate_gparam` of every weight,
-        then the one-pass compress under it) instead of three launches per module, and the parameter dictionaries are rewritten under the
-        kernels.  Every module ends in exactly the state `compress_rtn_module` leaves it in; the others go through that, from this call."""
-        for window in rtn_windows(modules):
-            tables, rest = {}, []
-            for m in window:
-                w = direct_entry(m, "weight")
-                if not (w is not None and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.float8_e4m3fn) is torch.float8_e4m3fn
-                        and codec.rtn_nvfp4_takes(w)):
-                    rest.append(m)
-                    continue
-                group = tables.get((w.device, w.dtype))
-                if group is None:
-                    group = tables[(w.device, w.dtype)] = ([], [], codec.rtn_nvfp4_keys(len(window), w.device))  # a table's keys: one word per item
-                packed, s8, gs, row = codec.rtn_nvfp4_table_item(w, group[2].data_ptr() + 4 * len(group[1]))
-                group[0].extend(row)
-                group[1].append((m, w, packed, s8, gs))  # the table holds raw pointers: the jobs keep the tensors alive
-            for (device, dtype), (flat, jobs, keys) in tables.items():
-                stream = torch.cuda.current_stream(device)
-                codec.launch_rtn_nvfp4_words(flat, len(jobs), dtype, device).record_stream(stream)
-                keys.record_stream(stream)
-            for flat, jobs, keys in tables.values():  # from here on the host works under the kernels
-                for m, w, packed, s8, gs in jobs:
-                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
-                    swap_direct_entries(m, remove, {"weight_packed": packed, "weight_scale": s8, "weight_global_scale": gs}, status=QuantizationStatus.COMPRESSED)
-            for m in rest:
-                cls.compress_rtn_module(m)
+    def compress_rtn_modules(cls, modules) -> None:
+        """the window hook (`run_rtn_windows`): the modules with a 16-bit weight on a GPU (cols % 32 == 0, float8 scales) leave in one fill of the
+        window's amax keys and TWO table launches per (device, dtype) (codec.launch_rtn_nvfp4_words: `generate_gparam` of every weight, then the
+        one-pass compress under it) instead of three launches per module; the others go through `compress_rtn_module`."""
+        def item(m, w, table):
+            if (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.float8_e4m3fn) is not torch.float8_e4m3fn or not codec.rtn_nvfp4_takes(w):
+                return None
+            key = (w.device, w.dtype)
+            _, jobs, keys = table(key)
+            outs = codec.rtn_nvfp4_table_item(w, keys.data_ptr() + 4 * len(jobs))  # a table's keys: one word per item
+            return key, outs[3], outs
+
+        run_rtn_windows(cls, modules, item, lambda key, flat, jobs: codec.launch_rtn_nvfp4_words(flat, len(jobs), key[1], key[0]),
+                        lambda w, o: {"weight_packed": o[0], "weight_scale": o[1], "weight_global_scale": o[2]}, state=codec.rtn_nvfp4_keys)
 
     @classmethod
     def decompress(cls, state_dict: dict, scheme) -> dict:
@@ -250,7 +235,10 @@ class NVFP4PackedCompressor(BaseCompressor):
 @BaseCompressor.register(name=CompressionFormat.mxfp4_pack_quantized.value)
 class MXFP4PackedCompressor(NVFP4PackedCompressor):
     GROUP = 32
-    compress_rtn_tables = None  # NVFP4's window hook is not inherited: this class has its own, `compress_rtn_modules`
+    # stated, not inherited: the MXFP4 table is measured faster than the per-module loop on both trees by more than the spread of the two runs
+    # (profiles/rtn_bench.jsonl, scheme mxfp4, medians of the two runs: 3.58 / 3.58 ms against 3.81 / 3.82 on the 8B-shaped tree, 1.62 / 1.59
+    # against 2.40 / 2.31 on the TinyLlama-shaped one)
+    RTN_TABLE_MEASURED_FASTER = True
 
     @classmethod
     def compression_param_names(cls, scheme) -> tuple:
@@ -275,33 +263,18 @@ class MXFP4PackedCompressor(NVFP4PackedCompressor):
 
     @classmethod
     def compress_rtn_modules(cls, modules) -> None:
-        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`): the ones with a 16-bit weight on a GPU (cols % 32 ==
-        0, E8M0 codes stored as uint8) leave in ONE table launch per (device, dtype) (codec.launch_rtn_mxfp4_words) and the parameter dictionaries are
-        rewritten under the kernel.  Every module ends in exactly the state `compress_rtn_module` leaves it in; the others go through that, from
-        this call."""
-        for window in rtn_windows(modules):
-            tables, rest = {}, []
-            for m in window:
-                w = direct_entry(m, "weight")
-                item = None
-                if w is not None and (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.uint8) is torch.uint8:
-                    item = codec.rtn_mxfp4_table_item(w)
-                if item is None:
-                    rest.append(m)
-                    continue
-                packed, code, row = item
-                flat, jobs = tables.setdefault((w.device, w.dtype), ([], []))
-                flat += row
-                jobs.append((m, w, packed, code))  # the table holds raw pointers: the jobs keep the tensors alive
-            for (device, dtype), (flat, jobs) in tables.items():
-                table = codec.launch_rtn_mxfp4_words(flat, len(jobs), dtype, device)
-                table.record_stream(torch.cuda.current_stream(device))
-            for flat, jobs in tables.values():  # from here on the host works under the kernel
-                for m, w, packed, code in jobs:
-                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
-                    swap_direct_entries(m, remove, {"weight_packed": packed, "weight_scale": code}, status=QuantizationStatus.COMPRESSED)
-            for m in rest:
-                cls.compress_rtn_module(m)
+        """the window hook (`run_rtn_windows`): the modules with a 16-bit weight on a GPU (cols % 32 == 0, E8M0 codes stored as uint8) leave in ONE
+        table launch per (device, dtype) (codec.launch_rtn_mxfp4_words); the others go through `compress_rtn_module`."""
+        def item(m, w, table):
+            outs = None
+            if (getattr(m.quantization_scheme.weights, "scale_dtype", None) or torch.uint8) is torch.uint8:
+                outs = codec.rtn_mxfp4_table_item(w)
+            if outs is None:
+                return None
+            return (w.device, w.dtype), outs[2], outs
+
+        run_rtn_windows(cls, modules, item, lambda key, flat, jobs: codec.launch_rtn_mxfp4_words(flat, len(jobs), key[1], key[0]),
+                        lambda w, o: {"weight_packed": o[0], "weight_scale": o[1]})
 
     @classmethod
     def _compress_scale(cls, scale: torch.Tensor, weights) -> torch.Tensor:

@@ -132,11 +132,11 @@ class ModelCompressor:
         `compress_rtn`).  Bias and other parameters are kept.  Under torch.distributed the modules are sharded over the
         ranks exactly like `compress_model`.  No upstream counterpart: upstream separates calibration (observers,
         llm-compressor) from `compress_model`; the result equals that two-step flow with min-max observers.
-        `batched` (default): the modules are grouped by codec, and a codec with a window hook — `compress_rtn_modules` (pack-quantized, MXFP4) or, looked
-        up second and only while the codec's `RTN_TABLE_MEASURED_FASTER` holds, `compress_rtn_tables` (NVFP4: two launches per window, the tensor-wide
-        amax behind `generate_gparam` is a pass of its own; not dispatched until its bench rows are recorded) — turns its group into table launches per
-        window of 32 modules; the others (the 8-bit codecs) and the modules a table does not take run per module.  `batched=False`: per module
-        throughout — same result."""
+        `batched` (default): the modules are grouped by codec, and a codec with the window hook `compress_rtn_modules` (pack-quantized, MXFP4, NVFP4:
+        each a few lines over `compressors.base.run_rtn_windows`) whose gate `RTN_TABLE_MEASURED_FASTER` holds turns its group into table launches per
+        window of 32 modules.  NVFP4's gate is off (two launches per window, the tensor-wide amax behind `generate_gparam` is a pass of its own; not
+        dispatched on figures that have not decided it); it, the codecs without the hook (the 8-bit ones) and the modules a table does
+        not take run per module.  `batched=False`: per module throughout — same result."""
         from ...utils.module import direct_entry, swap_direct_entries
         from ..base import BaseCompressor
         from ..format import infer_module_format
@@ -170,9 +170,7 @@ class ModelCompressor:
                 swap_direct_entries(module, remove, new, status=QuantizationStatus.COMPRESSED)
             for comp, group in groups.items():  # in module order within a codec
                 many = getattr(comp, "compress_rtn_modules", None)
-                if many is None and getattr(comp, "RTN_TABLE_MEASURED_FASTER", False):
-                    many = getattr(comp, "compress_rtn_tables", None)
-                if many is not None:
+                if many is not None and getattr(comp, "RTN_TABLE_MEASURED_FASTER", False):
                     many(group)
                 else:
                     for module in group:

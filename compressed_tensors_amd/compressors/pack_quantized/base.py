@@ -14,7 +14,7 @@ from ... import _lib, codec
 from ...config import CompressionFormat
 from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, rtn_windows, run_planned, symmetric_zp_keys
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, run_rtn_windows, symmetric_zp_keys
 
 __all__ = ["PackedQuantizationCompressor"]
 
@@ -44,6 +44,21 @@ def _plain_w4_scheme(scheme):
     if st == "group" and getattr(wa, "group_size", None):
         return True, int(wa.group_size), asym
     return False, -1, False
+
+
+def _w4_scheme_info(schemes: dict, scheme):
+    """what only depends on the scheme, worked out once per scheme object and kept in the caller's `schemes` under id(scheme) (the module loops look there
+    first: a dictionary look-up per module, not a call): None unless int4 group / channel, else (group size or None for channel-wise — `compress_rtn`'s
+    argument —, symmetric, the group of the calibrated table `compress_modules` builds: 0 for channel-wise, -1 where that table does not take the group
+    size — unset or no multiple of 32)"""
+    wa = scheme.weights
+    st = enum_value(wa.strategy)
+    info = None
+    if int(wa.num_bits) == 4 and enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel"):
+        g = 0 if st == "channel" else int(getattr(wa, "group_size", 0) or -1)
+        info = (getattr(wa, "group_size", None) if st == "group" else None, bool(wa.symmetric), g if g % 32 == 0 else -1)
+    schemes[id(scheme)] = info
+    return info
 
 
 def _w8_info(scheme) -> int:
@@ -256,55 +271,44 @@ class PackedQuantizationCompressor(BaseCompressor):
             out["weight_zero_point"] = codec.pack_to_int32(zp, weights.num_bits, packed_dim=0)
         return out
 
+    RTN_TABLE_MEASURED_FASTER = True  # the window hook's gate (see NVFP4PackedCompressor): profiles/rtn_bench.jsonl, schemes w4 and w4asym, both trees
+
     @classmethod
     def compress_rtn_modules(cls, modules) -> None:
-        """`compress_rtn` + the parameter swap for a list of modules, in windows (`rtn_windows`): the int4 group / channel modules of a window with a
-        16-bit weight on a GPU leave in ONE table launch per (device, dtype, symmetric) (codec.launch_rtn_w4_words), the stored zero points of the
-        asymmetric ones in one `zp4_batch(..., "pack")` behind it, and the parameter dictionaries are rewritten under the kernels.  Every module ends
-        in exactly the state `compress_rtn_module` leaves it in; the modules the table does not take go through that, from this call."""
-        from ...quantization.quant_args import QuantizationStatus
-        from ...utils.module import direct_entry, swap_direct_entries
-
+        """the window hook (`run_rtn_windows`): the int4 group / channel modules with a 16-bit weight on a GPU leave in ONE table launch per
+        (device, dtype, symmetric) (codec.launch_rtn_w4_words), the stored zero points of the asymmetric ones in one `zp4_batch(..., "pack")`
+        behind it; the others go through `compress_rtn_module`."""
         schemes = {}
-        for window in rtn_windows(modules):
-            tables, rest = {}, []
-            for m in window:
-                scheme = m.quantization_scheme
-                info = schemes.get(id(scheme), 0)
-                if info == 0:  # (group or None for channel, symmetric) | None: what only depends on the scheme
-                    wa = scheme.weights
-                    st = enum_value(wa.strategy)
-                    info = None
-                    if int(wa.num_bits) == 4 and enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel"):
-                        info = (getattr(wa, "group_size", None) if st == "group" else None, bool(wa.symmetric))
-                    schemes[id(scheme)] = info
-                w = direct_entry(m, "weight")
-                item = codec.rtn_w4_table_item(w, info[0], not info[1]) if info is not None and w is not None else None
-                if item is None:
-                    rest.append(m)
-                    continue
-                packed, scale, zp, row = item
-                zpp = None
-                if zp is not None:
-                    rows, groups = zp.shape
-                    zpp = torch.empty((math.ceil(rows * 4 / 32), groups), dtype=torch.int32, device=w.device)
-                flat, jobs = tables.setdefault((w.device, w.dtype, info[1]), ([], []))
-                flat += row
-                jobs.append((m, w, packed, scale, zp, zpp))  # the table holds raw pointers: the jobs keep the tensors alive
-            for (device, dtype, symmetric), (flat, jobs) in tables.items():
-                table = codec.launch_rtn_w4_words(flat, len(jobs), dtype, device, symmetric)
-                table.record_stream(torch.cuda.current_stream(device))
-                if not symmetric:  # pack_to_int32(zp, 4, packed_dim=0) of every module, behind the launch that computes the zero points
-                    codec.zp4_batch([(j[4], j[5]) for j in jobs], "pack")
-            for flat, jobs in tables.values():  # from here on the host works under the kernels
-                for m, w, packed, scale, zp, zpp in jobs:
-                    add = {"weight_packed": packed, "weight_scale": scale, "weight_shape": torch.tensor(w.shape)}
-                    if zpp is not None:
-                        add["weight_zero_point"] = zpp
-                    remove = [k for k in (*m._parameters, *m._buffers) if k.startswith("weight")]
-                    swap_direct_entries(m, remove, add, status=QuantizationStatus.COMPRESSED)
-            for m in rest:
-                cls.compress_rtn_module(m)
+
+        def item(m, w, table):
+            scheme = m.quantization_scheme
+            info = schemes.get(id(scheme), 0)
+            if info == 0:
+                info = _w4_scheme_info(schemes, scheme)
+            got = codec.rtn_w4_table_item(w, info[0], not info[1]) if info is not None else None
+            if got is None:
+                return None
+            packed, scale, zp, row = got
+            zpp = None
+            if zp is not None:
+                rows, groups = zp.shape
+                zpp = torch.empty((math.ceil(rows * 4 / 32), groups), dtype=torch.int32, device=w.device)
+            return (w.device, w.dtype, info[1]), row, (packed, scale, zp, zpp)
+
+        def launch(key, flat, jobs):
+            device, dtype, symmetric = key
+            dev_table = codec.launch_rtn_w4_words(flat, len(jobs), dtype, device, symmetric)
+            if not symmetric:  # pack_to_int32(zp, 4, packed_dim=0) of every module, behind the launch that computes the zero points
+                codec.zp4_batch([(o[2], o[3]) for _, _, o in jobs], "pack")
+            return dev_table
+
+        def entries(w, o):
+            add = {"weight_packed": o[0], "weight_scale": o[1], "weight_shape": torch.tensor(w.shape)}
+            if o[3] is not None:
+                add["weight_zero_point"] = o[3]
+            return add
+
+        run_rtn_windows(cls, modules, item, launch, entries)
 
     # ------------------------------------------------------------------ batched module paths
     @classmethod
@@ -336,20 +340,13 @@ class PackedQuantizationCompressor(BaseCompressor):
 
         batches = {}  # (device, dtype) -> (entries, jobs): one table and one launch per GPU and weight dtype
         rest = []
-        schemes = {}  # id(scheme) -> (group or 0 for channel, asymmetric with packed zero points) | None: what only depends on the scheme
+        schemes = {}
         f16 = (torch.bfloat16, torch.float16)
         for m in modules:
             scheme = m.quantization_scheme
             info = schemes.get(id(scheme), 0)
             if info == 0:
-                wa = scheme.weights
-                st = enum_value(wa.strategy)
-                info = None
-                if int(wa.num_bits) == 4 and enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel"):
-                    g = 0 if st == "channel" else int(getattr(wa, "group_size", 0) or -1)
-                    if g >= 0 and g % 32 == 0:
-                        info = (g, not wa.symmetric)
-                schemes[id(scheme)] = info
+                info = _w4_scheme_info(schemes, scheme)  # this table's group is info[2]: 0 for channel-wise, -1 for one it does not take
             params, buffers = m._parameters, m._buffers
             w = params.get("weight")
             if w is None:
@@ -361,13 +358,13 @@ class PackedQuantizationCompressor(BaseCompressor):
             if zp is None:
                 zp = buffers.get("weight_zero_point")
             # the conditions of codec.w4_batch_eligible, on the module's own entries
-            ok = (info is not None and w is not None and scale is not None and w.dim() == 2 and w.dtype in f16 and scale.dtype is w.dtype
+            ok = (info is not None and info[2] >= 0 and w is not None and scale is not None and w.dim() == 2 and w.dtype in f16 and scale.dtype is w.dtype
                   and w.is_cuda and w.is_contiguous() and w.data_ptr() % 16 == 0
                   and scale.is_contiguous() and scale.data_ptr() % 16 == 0 and scale.device == w.device
                   and "weight_g_idx" not in params and "weight_g_idx" not in buffers)
             if ok:
                 rows, cols = w.shape
-                group = info[0] or cols
+                group = info[2] or cols
                 ok = rows > 0 and cols % 32 == 0 and cols % group == 0 and scale.shape == (rows, cols // group)
                 if ok and zp is not None:
                     ok = (zp.dtype is torch.int8 and zp.shape == scale.shape and zp.is_contiguous() and zp.data_ptr() % 16 == 0
@@ -378,7 +375,7 @@ class PackedQuantizationCompressor(BaseCompressor):
             packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=w.device)
             entries, jobs = batches.setdefault((w.device, w.dtype), ([], []))
             zpp = None
-            if info[1] and enum_value(scheme.weights.strategy) in PACK_ZP_STRATS:
+            if not info[1] and enum_value(scheme.weights.strategy) in PACK_ZP_STRATS:
                 assert zp is not None, "Asymmetric quant requires zero-point values"
                 # the stored form of the zero points (pack_to_int32(zp, 4, packed_dim=0)): written by tail workgroups of the SAME launch
                 zpp = torch.empty((math.ceil(rows * 4 / 32), zp.shape[1]), dtype=torch.int32, device=w.device)

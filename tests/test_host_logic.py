@@ -766,10 +766,10 @@ def test_the_launcher_table_names_every_item_table_once(cta):
     from compressed_tensors_amd import _lib, codec
 
     item_plans = {"ct_w4_batch_plan", "ct_q8_batch_plan", "ct_fp4_batch_plan", "ct_mx_scale_batch_plan", "ct_zp4_batch_plan", "ct_rtn_w4_batch_plan",
-                  "ct_rtn_mxfp4_batch_plan"}
+                  "ct_rtn_mxfp4_batch_plan", "ct_rtn_nvfp4_batch_plan"}
     assert item_plans <= set(_lib.EXPORTED_SYMBOLS)
     plans = [plan for plan, _, _ in codec._TABLES.values()]
-    assert sorted(plans) == sorted(item_plans)  # each of the seven in exactly one kind
+    assert sorted(plans) == sorted(item_plans)  # each of the eight in exactly one kind
     cpu = torch.device("cpu")
     for kind, (plan, directed, launch) in codec._TABLES.items():
         symbols = (launch,) if isinstance(launch, str) else launch
@@ -778,6 +778,7 @@ def test_the_launcher_table_names_every_item_table_once(cta):
         assert codec._launch_table(kind, None, 0, cpu) is None  # (words None: nothing reads them)
     # an empty table returns before anything about it is looked at, a dtype the library does not know included
     assert codec.launch_rtn_w4_words(None, 0, None, cpu, True) is None and codec.launch_rtn_mxfp4_words(None, 0, None, cpu) is None
+    assert codec.launch_rtn_nvfp4_words(None, 0, None, cpu) is None
     assert codec.launch_w4_words(None, 0, "compress", None, cpu) is None and codec.launch_q8_words(None, 0, "decompress", None, cpu, 0) is None
     assert codec.launch_fp4_words(None, 0, "compress", cpu, 32) is None and codec.launch_mx_scale_words(None, 0, "compress", cpu) is None
     assert codec.launch_zp4_words(None, 0, "pack", cpu) is None and codec.zp4_batch([], "pack") is None
@@ -790,6 +791,94 @@ def test_the_launcher_table_names_every_item_table_once(cta):
         with pytest.raises(ValueError) as err:
             codec.launch_w4_words(words, 1, "compress", torch.bfloat16, cpu)
         assert "ct_w4_batch_plan" in str(err.value) and "item 0" in str(err.value), str(err.value)
+
+
+def test_rtn_window_driver_against_a_recording_codec(cta, monkeypatch):
+    """compressors.base.run_rtn_windows with RTN_WINDOW = 3 and 7 modules: windows of 3 / 3 / 1, tables keyed as the codec says (two keys inside one window),
+    a table's state opened at its first item with the window's length, every launch of a window before its first swap, the device table recorded
+    before the state, and the rest — a module the codec refuses, a module without a `weight` entry — through `compress_rtn_module` behind the swaps,
+    in module order"""
+    from compressed_tensors_amd.compressors import base
+
+    monkeypatch.setattr(base, "RTN_WINDOW", 3)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: ("stream", device))
+    log = []
+
+    class Recorded:
+        def __init__(self, what):
+            self.what = what
+
+        def record_stream(self, stream):
+            log.append(("record", self.what, stream))
+
+    class Codec:
+        @classmethod
+        def compress_rtn_module(cls, m):
+            log.append(("rest", m.k))
+
+    def item(m, w, table):
+        log.append(("item", m.k))
+        if m.k == 1:
+            return None  # refused before a table is asked for: no table opens for it
+        key = (w.device, w.dtype)
+        t = table(key)
+        assert t is table(key) and t[2].what == ("state", key)  # opened once; the state exists before the row is built
+        return key, (m.k, len(t[1])), ("out", m.k)  # the row: (module, its index in the table)
+
+    def state(n, device):  # (the key a state belongs to: that of the item that opened it)
+        k = [e for e in log if e[0] == "item"][-1][1]
+        log.append(("state", n, device, k))
+        return Recorded(("state", (device, model[k].weight.dtype)))
+
+    def launch(key, flat, jobs):
+        log.append(("launch", key, list(flat), [(m.k, w.data_ptr(), outs) for m, w, outs in jobs]))
+        return Recorded(("table", key))
+
+    def entries(w, outs):
+        log.append(("swap", outs[1]))
+        return {"weight_packed": torch.zeros(1)}
+
+    base.run_rtn_windows(Codec, [], item, launch, entries, state=state)
+    assert log == []  # an empty list does nothing
+
+    model = [torch.nn.Linear(4, 2, bias=(k == 5)) for k in range(7)]
+    model[2] = model[2].to(torch.float16)  # a second key inside window 0
+    del model[4]._parameters["weight"]     # no `weight` entry: the codec is not asked
+    for k, m in enumerate(model):
+        m.k = k
+    ptrs = {k: m.weight.data_ptr() for k, m in enumerate(model) if k != 4}
+    bias5 = model[5].bias.data_ptr()
+    base.run_rtn_windows(Codec, iter(model), item, launch, entries, state=state)
+    cpu, f32, f16 = torch.device("cpu"), torch.float32, torch.float16
+    assert [e[1] for e in log if e[0] == "item"] == [0, 1, 2, 3, 5, 6]
+    assert [e[1:] for e in log if e[0] == "state"] == [(3, cpu, 0), (3, cpu, 2), (3, cpu, 3), (1, cpu, 6)]  # at the first item, sized by the window
+    launches = [e for e in log if e[0] == "launch"]
+    assert [(e[1], e[2]) for e in launches] == [((cpu, f32), [0, 0]), ((cpu, f16), [2, 0]), ((cpu, f32), [3, 0, 5, 1]), ((cpu, f32), [6, 0])]
+    assert [e[3] for e in launches] == [[(0, ptrs[0], ("out", 0))], [(2, ptrs[2], ("out", 2))], [(3, ptrs[3], ("out", 3)), (5, ptrs[5], ("out", 5))],
+                                        [(6, ptrs[6], ("out", 6))]]
+    # per window: items, then every launch (table recorded before state), then the swaps, then the rest
+    short = [e[:2] if e[0] in ("item", "swap", "rest") else e[0] for e in log]
+    rec = ["launch", "record", "record"]
+    assert short == [("item", 0), "state", ("item", 1), ("item", 2), "state", *rec, *rec, ("swap", 0), ("swap", 2), ("rest", 1),
+                     ("item", 3), "state", ("item", 5), *rec, ("swap", 3), ("swap", 5), ("rest", 4),
+                     ("item", 6), "state", *rec, ("swap", 6)]
+    records = [e for e in log if e[0] == "record"]
+    assert [r[1][0] for r in records] == ["table", "state"] * 4 and all(r[2] == ("stream", cpu) for r in records)
+    assert [r[1][1] for r in records[:4]] == [(cpu, f32), (cpu, f32), (cpu, f16), (cpu, f16)]
+    for k, m in enumerate(model):
+        if k in (1, 4):  # left to compress_rtn_module, which the fake only records
+            assert not hasattr(m, "quantization_status")
+            continue
+        assert m.quantization_status == cta.QuantizationStatus.COMPRESSED
+        assert list(m._parameters) == ["bias", "weight_packed"] and not m.weight_packed.requires_grad  # every `weight*` entry went, the rest stays
+    assert model[5].bias.data_ptr() == bias5 and model[0].bias is None
+
+    # without `state` a table has none, and nothing but the device table is recorded
+    log.clear()
+    fresh = torch.nn.Linear(4, 2)
+    fresh.k = 0
+    base.run_rtn_windows(Codec, [fresh], lambda m, w, table: ((w.device, w.dtype), (0,), ("out", 0)), launch, entries)  # (the driver opens the table)
+    assert [e[0] for e in log] == ["launch", "record", "swap"] and log[0][2] == [0]
 
 
 def _tree(cta, scheme, shapes, *, trainable_scale=False, buffer_zp=False, odd_class=False, g_idx=False):

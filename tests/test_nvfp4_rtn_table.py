@@ -209,8 +209,9 @@ def test_window_hook_groups_by_device_and_dtype_and_hands_the_rest_on(monkeypatc
     from compressed_tensors_amd.compressors.base import RTN_WINDOW
 
     NV, MX = cta.NVFP4PackedCompressor, cta.MXFP4PackedCompressor
-    assert "compress_rtn_tables" in vars(NV) and not hasattr(NV, "compress_rtn_modules")
-    assert MX.compress_rtn_tables is None and "compress_rtn_modules" in vars(MX)  # the subclass keeps its own hook and does not inherit this one
+    assert "compress_rtn_modules" in vars(NV) and "compress_rtn_modules" in vars(MX)  # the subclass keeps its own hook and does not inherit this one
+    for c in (NV, MX):  # one hook name: nothing else that begins like it
+        assert {n for n in dir(c) if n.startswith("compress_rtn")} == {"compress_rtn", "compress_rtn_module", "compress_rtn_modules"}
     fake = _Fake(monkeypatch, lambda x: x.dim() == 2 and x.dtype in (BF16, F16) and x.shape[1] % 32 == 0)
     monkeypatch.setattr(NV, "compress_rtn", classmethod(lambda cls, w, s: fake.single.append(w) or {"weight_packed": w}))
     n = RTN_WINDOW + 2
@@ -223,7 +224,7 @@ def test_window_hook_groups_by_device_and_dtype_and_hands_the_rest_on(monkeypatc
         m.quantization_scheme = bf16_scales if k == 6 else (f8 if k % 2 else plain)  # a non-float8 scale_dtype: per module
     weights = [m.weight.data for m in model]
     bias1 = model[1].bias.data_ptr()
-    NV.compress_rtn_tables(list(model))
+    NV.compress_rtn_modules(list(model))
     # window 0: one table of the bf16 modules, one of the fp16 module; window 1: the last two modules
     launches = [e for e in fake.log if e[0] == "launch"]
     taken0 = [k for k in range(RTN_WINDOW) if k not in (3, 4, 5, 6)]
@@ -246,12 +247,12 @@ def test_window_hook_groups_by_device_and_dtype_and_hands_the_rest_on(monkeypatc
     assert model[0].weight_scale.dtype == F8 and model[0].weight_global_scale.dtype == F32 and not model[0].weight_packed.requires_grad
 
 
-def test_compress_model_rtn_looks_the_table_hook_up_second(monkeypatch):
+def test_compress_model_rtn_honours_the_table_hooks_gate(monkeypatch):
     import compressed_tensors_amd as cta
 
     NV, MX = cta.NVFP4PackedCompressor, cta.MXFP4PackedCompressor
     calls = []
-    monkeypatch.setattr(NV, "compress_rtn_tables", classmethod(lambda cls, ms: calls.append(("tables", cls, len(list(ms))))))
+    monkeypatch.setattr(NV, "compress_rtn_modules", classmethod(lambda cls, ms: calls.append(("tables", cls, len(list(ms))))))
     monkeypatch.setattr(MX, "compress_rtn_modules", classmethod(lambda cls, ms: calls.append(("modules", cls, len(list(ms))))))
     for c in (NV, MX):
         monkeypatch.setattr(c, "compress_rtn", classmethod(lambda cls, w, s: calls.append(("one", cls, 1)) or {"weight": w}))

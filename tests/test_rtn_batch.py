@@ -159,8 +159,9 @@ def test_many_on_cpu_tensors_behaves_like_the_single_call():
 
 
 def test_compress_model_rtn_groups_by_compressor_in_module_order(monkeypatch):
-    """compress_model_rtn(batched=True) hands each compressor class with a `compress_rtn_modules` ONE list, in module order; NVFP4 and the 8-bit
-    codecs have none and go through `compress_rtn` per module; batched=False calls `compress_rtn` for every module and no table entry"""
+    """compress_model_rtn(batched=True) hands each compressor class with a `compress_rtn_modules` whose gate holds ONE list, in module order; NVFP4
+    (its gate is off) and the 8-bit codecs (they have no hook) go through `compress_rtn` per module; batched=False calls `compress_rtn` for every
+    module and no table entry"""
     import compressed_tensors_amd as cta
     from compressed_tensors_amd.compressors.base import BaseCompressor
 
@@ -183,7 +184,8 @@ def test_compress_model_rtn_groups_by_compressor_in_module_order(monkeypatch):
     names = ("pack-quantized", "mxfp4-pack-quantized", "nvfp4-pack-quantized", "float-quantized", "int-quantized", "naive-quantized")
     classes = {n: BaseCompressor.get_value_from_registry(n) for n in names}
     assert hasattr(classes["pack-quantized"], "compress_rtn_modules") and hasattr(classes["mxfp4-pack-quantized"], "compress_rtn_modules")
-    assert not any(hasattr(classes[n], "compress_rtn_modules") for n in names[2:])
+    assert not any(hasattr(classes[n], "compress_rtn_modules") for n in names[3:])
+    assert "compress_rtn_modules" in vars(classes["nvfp4-pack-quantized"]) and classes["nvfp4-pack-quantized"].RTN_TABLE_MEASURED_FASTER is False
     calls = []
     for n, c in classes.items():
         if "compress_rtn_modules" in vars(c):
