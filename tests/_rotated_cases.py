@@ -18,7 +18,11 @@ which SIMD lanes held the NaN, not on any value: the reference run by tools/gen_
 all NaN or ends in one NaN (the layout tests/_dynamic_cases.py pins, and the kernels' rule) and +inf for a group whose second half
 is NaN.  NaN payloads are not modelled.  Behind a rotation with n < 32 a NaN spreads over half an MX group, so
 the MX cases with n = 8 and 16 keep every row but that one: their NaN row is a second +inf row (`nan_row: false` in the recipe).
-MX behind small rotations with NaNs is covered by the bit-identity with the two existing launches (tests/test_gpu_rotated_quant.py)."""
+MX behind small rotations with NaNs is covered by the bit-identity with the two existing launches (tests/test_gpu_rotated_quant.py).
+
+Where the whole tensor is one segment (the tensor strategy, token on a 2-D input) the +inf and NaN rows make the one scale and
+the whole output NaN.  Those cases have a twin with `finite: true` in the recipe: the two rows hold +128 and -128 in place of
++inf and NaN, so the twin's scale is a number and its output takes many values."""
 import hashlib
 import math
 
@@ -43,12 +47,13 @@ def synth(recipe) -> torch.Tensor:
     flat = x.reshape(-1, cols)
     k = torch.arange(cols)
     base = ints[:cols].to(torch.float32)
+    finite = recipe.get("finite", False)
     edge = [
         torch.zeros(cols),
         torch.where(k == cols // 3, torch.tensor(64.0), torch.tensor(0.0)),  # one non-zero
         torch.where(k == 0, torch.tensor(-0.0), base),  # a -0.0 among ordinary values
-        torch.where(k == cols // 2, torch.tensor(float("inf")), base),
-        torch.where(k == cols - 1, torch.tensor(float("nan") if recipe.get("nan_row", True) else float("inf")), base),
+        torch.where(k == cols // 2, torch.tensor(128.0 if finite else float("inf")), base),
+        torch.where(k == cols - 1, torch.tensor(-128.0 if finite else float("nan") if recipe.get("nan_row", True) else float("inf")), base),
         torch.full((cols,), 3.0),  # constant
     ]
     assert len(edge) == EDGE_ROWS
@@ -58,21 +63,23 @@ def synth(recipe) -> torch.Tensor:
 
 
 def case_list():
-    """[(key, recipe)]: recipe = preset, dtype, shape, size (the rotation block n), salt, gs (NVFP4 global-scale name or None), nan_row"""
+    """[(key, recipe)]: recipe = preset, dtype, shape, size (the rotation block n), salt, gs (NVFP4 global-scale name or None), nan_row,
+    and `finite: true` for the twins without a +inf or NaN row"""
     out = []
     dts = list(DTYPES)
 
-    def add(preset, dt, shape, size, gs=None):
+    def add(preset, dt, shape, size, gs=None, finite=False):
         group = PRESETS[preset].get("group_size")
         if group and shape[-1] % group:
             return
         if preset == "nvfp4" and gs is None:
             gs = "nogs"
-        key = f"{preset}.{dt}.{'x'.join(map(str, shape))}.n{size}" + (f".{gs}" if gs else "")
+        key = f"{preset}.{dt}.{'x'.join(map(str, shape))}.n{size}" + (f".{gs}" if gs else "") + (".finite" if finite else "")
         if key in dict(out):
             return
         out.append((key, dict(preset=preset, dtype=dt, shape=list(shape), size=size, salt=len(out) % 11 + 1, gs=gs,
-                              nan_row=not (preset in ("mxfp4", "mxfp8") and size < 32))))  # a half-NaN MX group: module docstring
+                              nan_row=not (preset in ("mxfp4", "mxfp8") and size < 32),  # a half-NaN MX group: module docstring
+                              **({"finite": True} if finite else {}))))
 
     kinds = ["fp8_token", "int8_token", "fp8_group128", "nvfp4", "mxfp4", "mxfp8", "int8_token_asym", "int4_group32_asym"]
     # n <= 512 with in-wave segments (groups, short token rows); every kind, bf16 always and a second dtype in rotation
@@ -112,6 +119,9 @@ def case_list():
     add("fp8_token", "bf16", (1, 9, 4096), 1024)  # a token row of several workgroup-sized blocks
     add("int8_token", "f16", (1, 9, 2048), 1024)
     add("fp8_token", "bf16", (1, 2, 65536), 128)  # a row longer than the staged form
+    # the tensor form on finite values: the two cases above whose one scale is NaN, without their +inf and NaN rows
+    add("fp8_token", "bf16", (9, 4096), 128, finite=True)
+    add("fp8_tensor", "bf16", (1, 9, 1024), 64, finite=True)
     return out
 
 
@@ -122,6 +132,8 @@ DECLINED = {
     "fp8_token.bf16.1x9x4096.n1024": 2,
     "int8_token.f16.1x9x2048.n1024": 2,
     "fp8_token.bf16.1x2x65536.n128": 2,
+    "fp8_token.bf16.9x4096.n128.finite": 3,
+    "fp8_tensor.bf16.1x9x1024.n64.finite": 3,
 }
 
 

@@ -43,6 +43,58 @@ def test_planned_shapes_and_dtypes_match_the_reference(key):
     assert plan.tensor_form == (token_2d or C.PRESETS[r["preset"]]["strategy"] == "tensor")
 
 
+def test_manifest_matches_the_case_list():
+    cases = dict(C.case_list())
+    assert set(MANIFEST) == set(cases)
+    for key, recipe in cases.items():
+        assert MANIFEST[key]["recipe"] == recipe and MANIFEST[key]["stored"] == C.stored(recipe), key
+
+
+def test_finite_whole_tensor_fixtures_are_meaningful():
+    """A condition on the fixtures: where the whole tensor is one segment, synth's NaN row makes the reference's scale and output
+    all NaN, which pins NaN propagation and nothing else.  Every preset with such a form also has cases marked `finite`, and in
+    those the reference's output has no NaN and takes many values (`out_nan`, `out_distinct`: tools/gen_golden_dynamic.py), so a
+    wrong scale, zero point, qmin or qmax changes the bytes that tests/test_gpu_dynamic_quant.py compares."""
+    finite = {}
+    for key, entry in MANIFEST.items():
+        r = entry["recipe"]
+        if not C.tensor_form(r):
+            continue
+        finite.setdefault(r["preset"], [])
+        if r.get("finite"):
+            numel = torch.Size(r["shape"]).numel()
+            assert entry["out_nan"] == 0, key
+            assert entry["out_distinct"] >= min(numel // 2, 2 ** (C.PRESETS[r["preset"]]["num_bits"] - 2)), (key, entry["out_distinct"])
+            finite[r["preset"]].append(key)
+        else:
+            assert entry["out_nan"] == torch.Size(r["shape"]).numel(), key  # the all-NaN cases stay what they are
+    with_tensor_form = {p for p, a in C.PRESETS.items() if a["strategy"] in ("tensor", "token")}
+    assert set(finite) == with_tensor_form
+    assert all(finite[p] for p in with_tensor_form), {p for p in with_tensor_form if not finite[p]}
+
+
+def test_make_input_recipes():
+    """entries without the optional keys synthesise what they always did; `finite` drops the edge rows; `plant` decides the extremes"""
+    base = dict(preset="int8_tensor_asym", dtype="bf16", shape=[33, 1001], salt=4, gs=None)
+    assert C.sha(C.make_input(base)) == C.sha(C.synth((33, 1001), C.BF16, 4))
+    x = C.make_input(dict(base, finite=True))
+    assert x.shape == (33, 1001) and x.is_contiguous() and C.sha(x) == C.sha(C.synth((41, 1001), C.BF16, 4)[8:])
+    assert bool(torch.isfinite(x).all()) and float(x.abs().max()) <= 128 < C.PLANT_OTHER < C.PLANT_MAX < torch.finfo(torch.float16).max
+    n = x.numel()
+    for plant, at in (("first", 0), ("last", n - 1), ("middle", n // 2 + 3)):
+        for salt, sign in ((4, 1.0), (5, -1.0)):
+            y = C.make_input(dict(base, salt=salt, finite=True, plant=plant)).reshape(-1)
+            other = (at + C.PLANT_APART) % n
+            assert float(y[at]) == sign * C.PLANT_MAX and float(y[other]) == -sign * C.PLANT_OTHER
+            assert float(y.max()) == max(float(y[at]), float(y[other])) and float(y.min()) == min(float(y[at]), float(y[other]))
+            assert (at // 8 // 256) % 3 != (other // 8 // 256) % 3  # 33033 elements: three partials, 256 units of 8 apart
+            rest = torch.ones(n, dtype=torch.bool)
+            rest[[at, other]] = False
+            assert torch.equal(y[rest], C.make_input(dict(base, salt=salt, finite=True)).reshape(-1)[rest])
+            z = C.make_input(dict(base, preset="fp8_tensor", salt=salt, finite=True, plant=plant)).reshape(-1)  # symmetric: one extreme
+            assert float(z[at]) == sign * C.PLANT_MAX and float(z.abs().max()) == C.PLANT_MAX and int((z.abs() > 128).sum()) == 1
+
+
 def _args(**kw):
     return QuantizationArgs(**{"num_bits": 8, "type": "float", "strategy": "token", "symmetric": True, "dynamic": True, **kw})
 

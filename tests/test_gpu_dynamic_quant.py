@@ -1,6 +1,7 @@
 """The fused dynamic activation QDQ (csrc/ct_dynamic.hip) on the MI355X: against the reference's outputs on every fixture case
-(tests/golden/dynamic*, tools/gen_golden_dynamic.py), launch counts, no host synchronisation, an exhaustive bf16 / fp16 sweep
-against an eager restatement, and quantized Linear modules under install(patch_forward=True)."""
+(tests/golden/dynamic*, tools/gen_golden_dynamic.py) — the QDQ, the scales-only entry, and the same inputs at a base address
+that is not 16-byte aligned — launch counts, no host synchronisation, an exhaustive bf16 / fp16 sweep against an eager
+restatement, and quantized Linear modules under install(patch_forward=True)."""
 import collections
 import json
 import os
@@ -53,10 +54,38 @@ def counted():
         codec_mod.call = saved
 
 
+_GOLDEN, _BIG_INPUTS = {}, {}
+
+
 def _golden_tensors():
     from safetensors.torch import load_file
 
-    return load_file(os.path.join(GOLDEN, "dynamic.safetensors"))
+    if not _GOLDEN:
+        _GOLDEN.update(load_file(os.path.join(GOLDEN, "dynamic.safetensors")))
+    return _GOLDEN
+
+
+def _input(key):
+    """the recipe's input; the few inputs of millions of elements are synthesised once for the tests that share them"""
+    r = MANIFEST[key]["recipe"]
+    if torch.Size(r["shape"]).numel() < 1 << 20:
+        return C.make_input(r)
+    if key not in _BIG_INPUTS:
+        _BIG_INPUTS[key] = C.make_input(r)
+    return _BIG_INPUTS[key]
+
+
+def _assert_matches(key, got):
+    """every tensor of `got` (name -> result) has the dtype, the shape and the values of the reference's: by sha256, and byte for
+    byte where the fixture keeps the tensor"""
+    entry = MANIFEST[key]
+    for name, t in got.items():
+        assert str(t.dtype).replace("torch.", "") == entry[name]["dtype"], (name, t.dtype)
+        assert list(t.shape) == entry[name]["shape"], (name, t.shape)
+        assert C.sha(t) == entry[name]["sha256"], f"{name} differs from the reference"
+        if entry["stored"]:
+            ref = _golden_tensors()[f"{key}.{name}"]
+            assert C.canonical_bytes(t.view(torch.uint8) if t.dtype == C.F8 else t) == C.canonical_bytes(ref), f"{name} differs from the stored reference"
 
 
 @pytest.mark.parametrize("key", sorted(MANIFEST))
@@ -65,7 +94,7 @@ def test_dynamic_qdq_matches_the_reference(key, counted):
 
     entry = MANIFEST[key]
     r = entry["recipe"]
-    x = C.synth(tuple(r["shape"]), C.DTYPES[r["dtype"]], r["salt"])
+    x = _input(key)
     assert C.sha(x) == entry["x_sha256"], "the recipe no longer synthesises the reference's input"
     gs = C.global_scale_of(r["gs"]) if r["gs"] else None
     out, scale, zp = dynamic_fake_quantize(x.to(DEV), _args(r["preset"]), gs.to(DEV) if gs is not None else None, return_qparams=True)
@@ -82,6 +111,66 @@ def test_dynamic_qdq_matches_the_reference(key, counted):
                 t = t.view(torch.uint8)
             assert C.canonical_bytes(t) == C.canonical_bytes(ref), f"{name} differs from the stored reference"
     assert sum(counted.values()) == 1, counted  # one C-ABI entry per call (the tensor form launches twice inside it)
+
+
+@pytest.mark.parametrize("key", sorted(MANIFEST))
+def test_scales_only_entry_matches_the_reference(key, counted):
+    """compute_dynamic_scales_and_zp (out == nullptr in every kernel): the reference's scale and zero point, and nothing else launched"""
+    from compressed_tensors_amd.quantization.dynamic import compute_dynamic_scales_and_zp
+
+    r = MANIFEST[key]["recipe"]
+    gs = C.global_scale_of(r["gs"]) if r["gs"] else None
+    scale, zp = compute_dynamic_scales_and_zp(_input(key).to(DEV), _args(r["preset"]), global_scale=gs.to(DEV) if gs is not None else None)
+    torch.cuda.synchronize()
+    _assert_matches(key, dict(scale=scale, zp=zp))
+    assert sum(counted.values()) == 1, counted
+
+
+# a contiguous input one element into its buffer: no 16-byte alignment, so every load and store takes its scalar form, and groups
+# (with and without the NVFP4 global scale) go to the one-workgroup-per-segment kernel; the tensor form and the twice-read rows too
+MISALIGNED = [
+    "fp8_group128.bf16.2x4x256", "nvfp4.bf16.2x4x256.gs", "nvfp4.bf16.2x4x256.nogs", "mxfp4.bf16.2x4x256", "fp8_token.bf16.2x4x256",
+    "int8_token_asym.bf16.2x4x256", "int4_group32_asym.bf16.2x2x4x128", "nvfp4.f32.2x4x256.gs", "fp8_group128.f16.1x9x4096",
+    "fp8_tensor.bf16.8x256.finite", "int8_tensor_asym.f32.33x1001.finite.first", "int8_token_asym.f16.1x3x32776.finite",
+]
+
+
+@pytest.mark.parametrize("key", MISALIGNED)
+def test_misaligned_contiguous_input(key, counted, monkeypatch):
+    from compressed_tensors_amd.quantization.dynamic import compute_dynamic_scales_and_zp, dynamic_fake_quantize
+
+    entry = MANIFEST[key]
+    r = entry["recipe"]
+    x = _input(key)
+    pad = 16 // x.element_size()
+    buf = torch.full((x.numel() + 2 * pad,), 3.0, dtype=x.dtype, device=DEV)  # a fresh allocation: 16-byte aligned
+    view = buf[1:1 + x.numel()].view(x.shape)
+    view.copy_(x)
+    before = buf.clone()
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 != 0 and view.is_contiguous()
+    gs = C.global_scale_of(r["gs"]) if r["gs"] else None  # "nogs" is None too
+    gs = gs.to(DEV) if gs is not None else None
+    # the output the codec allocates for this input sits one element into a buffer of its own, so a store outside it shows
+    out_buf = torch.full_like(buf, 3.0)
+    empty_like, handed = torch.empty_like, []
+
+    def guarded_empty_like(t, *a, **kw):
+        if t is not view:
+            return empty_like(t, *a, **kw)
+        handed.append(out_buf[1:1 + x.numel()].view(x.shape))
+        return handed[-1]
+
+    monkeypatch.setattr(torch, "empty_like", guarded_empty_like)
+    out, scale, zp = dynamic_fake_quantize(view, _args(r["preset"]), gs, return_qparams=True)
+    monkeypatch.undo()
+    only_scale, only_zp = compute_dynamic_scales_and_zp(view, _args(r["preset"]), global_scale=gs)
+    torch.cuda.synchronize()
+    assert len(handed) == 1 and out.data_ptr() == handed[0].data_ptr() and out.data_ptr() % 16 != 0
+    _assert_matches(key, dict(out=out, scale=scale, zp=zp))
+    _assert_matches(key, dict(scale=only_scale, zp=only_zp))
+    assert sum(counted.values()) == 2, counted
+    assert torch.equal(buf.view(torch.uint8), before.view(torch.uint8)), "the input's buffer was written to"
+    assert bool((out_buf[:1] == 3).all()) and bool((out_buf[1 + x.numel():] == 3).all()), "a store outside the output"
 
 
 def _launches_of(fn):

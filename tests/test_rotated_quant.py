@@ -181,11 +181,28 @@ def test_recipes_resynthesise_the_inputs(key):
     if rows.shape[0] >= C.EDGE_ROWS:
         assert not rows[0].any() and int((rows[1] != 0).sum()) == 1
         assert torch.signbit(rows[2][0]) and rows[2][0] == 0
-        assert int(torch.isinf(rows[3]).sum()) == 1
         nan_row = entry["recipe"]["nan_row"]  # false only for MX behind n < 32 (tests/_rotated_cases.py)
         assert nan_row == (not (entry["recipe"]["preset"].startswith("mx") and entry["recipe"]["size"] < 32))
-        assert int(torch.isnan(rows[4]).sum()) == int(nan_row) and int(torch.isinf(rows[4]).sum()) == int(not nan_row)
+        if entry["recipe"].get("finite"):  # the twins of the tensor-form cases: +128 and -128 where the others hold +inf and NaN
+            assert bool(torch.isfinite(x).all()) and rows[3][x.shape[-1] // 2] == 128 and rows[4][-1] == -128
+        else:
+            assert int(torch.isinf(rows[3]).sum()) == 1
+            assert int(torch.isnan(rows[4]).sum()) == int(nan_row) and int(torch.isinf(rows[4]).sum()) == int(not nan_row)
         assert bool((rows[5] == 3).all())
+
+
+def test_finite_twins_of_the_tensor_form_cases():
+    """the tensor-form cases with a +inf and a NaN row expect an all-NaN output; each has a finite twin that expects anything else"""
+    twins = {k for k, e in MANIFEST.items() if e["recipe"].get("finite")}
+    assert twins and all(_plan(MANIFEST[k]["recipe"]).dynamic.tensor_form for k in twins)
+    for key, entry in MANIFEST.items():
+        if not _plan(entry["recipe"]).dynamic.tensor_form:
+            continue
+        all_nan = {n: C.sha(torch.full(entry[n]["shape"], float("nan"), dtype=C.DTYPES[entry["recipe"]["dtype"]])) for n in ("out", "scale")}
+        if key in twins:
+            assert all(entry[n]["sha256"] != all_nan[n] for n in all_nan), key
+        else:
+            assert all(entry[n]["sha256"] == all_nan[n] for n in all_nan) and key + ".finite" in twins, key
 
 
 def test_by_value_comparison():

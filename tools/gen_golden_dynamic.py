@@ -7,7 +7,9 @@ Usage (from the repo root, where the reference sources exist):
 
 Writes tests/golden/dynamic.safetensors (the small bfloat16 cases: `<key>.out`, `<key>.scale`, `<key>.zp`) and
 tests/golden/dynamic_manifest.json (every case: its recipe, the sha256 of the synthesised input, the dtypes and shapes of the
-reference's outputs and the sha256 of each output with NaNs canonicalised).  The inputs are integer-synthesised: two runs write byte-identical files.
+reference's outputs and the sha256 of each output with NaNs canonicalised, and `out_nan` / `out_distinct`: how many elements
+of the reference's output are NaN and how many distinct values the others take — tests/test_dynamic_quant.py holds the finite
+whole-tensor cases to them).  The inputs are integer-synthesised: two runs write byte-identical files.
 TEST INFRASTRUCTURE ONLY.  Nothing in the product imports this.
 """
 import json
@@ -33,7 +35,7 @@ OUT = os.path.join(ROOT, "tests", "golden")
 
 
 def reference(recipe):
-    x = C.synth(tuple(recipe["shape"]), C.DTYPES[recipe["dtype"]], recipe["salt"])
+    x = C.make_input(recipe)
     args = QuantizationArgs(**C.PRESETS[recipe["preset"]])
     gs = C.global_scale_of(recipe["gs"]) if recipe["gs"] else None
     scale, zp = compute_dynamic_scales_and_zp(value=x, args=args, module=None, global_scale=gs)
@@ -45,14 +47,18 @@ def main():
     tensors, manifest = {}, {"cases": {}}
     for key, recipe in C.case_list():
         x, out, scale, zp = reference(recipe)
-        entry = dict(recipe=recipe, stored=C.stored(recipe), x_sha256=C.sha(x))
+        nan = torch.isnan(out)
+        entry = dict(recipe=recipe, stored=C.stored(recipe), x_sha256=C.sha(x), out_nan=int(nan.sum()),
+                     out_distinct=int(torch.unique(out[~nan].float()).numel()))
         for name, t in (("out", out), ("scale", scale), ("zp", zp)):
             entry[name] = dict(dtype=str(t.dtype).replace("torch.", ""), shape=list(t.shape), sha256=C.sha(t))
         if entry["stored"]:
             for name, t in (("out", out), ("scale", scale), ("zp", zp)):
                 tensors[f"{key}.{name}"] = t.contiguous() if t.dtype != C.F8 else t.contiguous().view(torch.uint8)
         manifest["cases"][key] = entry
-    save_file(tensors, os.path.join(OUT, "dynamic.safetensors"))
+    path = os.path.join(OUT, "dynamic.safetensors")
+    save_file(tensors, path)
+    os.chmod(path, 0o644)
     with open(os.path.join(OUT, "dynamic_manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
         f.write("\n")
