@@ -45,6 +45,8 @@ __all__ = [
     "rtn_quantize_and_pack_many",
     "rtn_mxfp4_quantize_and_pack_many",
     "rtn_nvfp4_quantize_and_pack_many",
+    "rtn_quantize_block8",
+    "rtn_quantize_block8_many",
     "launch_rtn_w4_words",
     "launch_rtn_mxfp4_words",
     "launch_rtn_nvfp4_words",
@@ -98,6 +100,8 @@ __all__ = [
     "rtn_w4_table_item",
     "rtn_mxfp4_table_item",
     "rtn_nvfp4_table_item",
+    "rtn_block8_table_item",
+    "rtn_block8_group",
     "rtn_nvfp4_takes",
     "rtn_nvfp4_keys",
     "attn_observe_global_scale",
@@ -1545,6 +1549,44 @@ def rtn_quantize_channel8(x: torch.Tensor, *, qtype: str = "int", symmetric: boo
     return _home(out, x), _home(scale, x), _home(zp, x)
 
 
+def rtn_block8_group(shape, block_structure) -> int:
+    """the table's `group` — -((bh << 24) | bw), as the 8-bit tables encode blocks (`q8_batch_group`) — when `ct_rtn_quant_block8` and its table
+    form take a weight of this shape under this block structure: 2-D, rows > 0, bh and bw powers of two, bw >= 16, bh * bw <= 16384,
+    cols % bw == 0 (the last row of blocks may be ragged); else 0"""
+    if len(shape) != 2 or block_structure is None or len(block_structure) != 2:
+        return 0
+    rows, cols, bh, bw = int(shape[0]), int(shape[1]), int(block_structure[0]), int(block_structure[1])
+    if rows <= 0 or cols <= 0 or bh < 1 or bw < 16 or bh & (bh - 1) or bw & (bw - 1) or bh * bw > 16384 or cols % bw:
+        return 0
+    return -((bh << 24) | bw)
+
+
+def rtn_quantize_block8(x: torch.Tensor, *, block_structure, qtype: str = "float", symmetric: bool = True, codes: bool = True):
+    """Block-wise 8-bit round-to-nearest in ONE pass over the weight (FP8_BLOCK; INT8 blocks): the min-max observer over blocks of
+    `block_structure` = [bh, bw] elements + calculate_qparams + quantize to float8_e4m3fn (qtype "float") or int8 ("int").  Returns (codes (R, C),
+    scale (ceil(R / bh), C / bw) in x.dtype, zero_point of the scale's shape: int8 for INT, float8 zeros for FLOAT) — bit-identical to
+    `calculate_qparams_from_weight`'s fallback composition followed by `quantize_tensor`.  `codes=False`: the block observer alone, (None, scale,
+    zero_point).  Raises NotImplementedError for what the kernel's plan refuses (`rtn_block8_group`; float32 weights)."""
+    if x.dim() != 2:
+        raise ValueError("rtn_quantize_block8 expects a 2-D weight")
+    qtype = getattr(qtype, "value", qtype)
+    if x.dtype not in (torch.bfloat16, torch.float16) or not rtn_block8_group(x.shape, block_structure) or (qtype == "float" and not symmetric):
+        raise NotImplementedError("the one-pass block-wise compress takes 16-bit weights and blocks with power-of-two sides, a width >= 16 that divides "
+                                  "cols and at most 16384 elements (symmetric for FLOAT)")
+    rows, cols = x.shape
+    bh, bw = int(block_structure[0]), int(block_structure[1])
+    dev = _compute_device(x)
+    xd = _dev(x, dev).contiguous()
+    fp8 = qtype == "float"
+    grid = (-(-rows // bh), cols // bw)
+    out = torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=dev) if codes else None
+    scale = torch.empty(grid, dtype=x.dtype, device=dev)
+    zp = torch.zeros(grid, dtype=_F8, device=dev) if fp8 else torch.empty(grid, dtype=torch.int8, device=dev)
+    call("ct_rtn_quant_block8", ptr(xd), DT[xd.dtype], rows, cols, bh, bw, int(fp8), int(bool(symmetric)), ptr(out), ptr(scale), None if fp8 else ptr(zp),
+         stream_of(xd))
+    return (_home(out, x) if codes else None), _home(scale, x), _home(zp, x)
+
+
 def _aligned16(*tensors) -> bool:
     return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
 
@@ -1630,6 +1672,9 @@ _TABLES = {
     "rtn_mxfp4": ("ct_rtn_mxfp4_batch_plan", False, "ct_rtn_mxfp4_quant_pack_batch"),
     "rtn_nvfp4": ("ct_rtn_nvfp4_batch_plan", False, ("ct_rtn_nvfp4_amax_batch", "ct_rtn_nvfp4_quant_pack_batch")),
 }
+# the same kind of row for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`), handed to `_launch_table` as the row itself: the registry
+# above is pinned to its eight plans by tests/test_host_logic.py, so the ninth stands beside it
+_RTN_BLOCK8_TABLE = ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
@@ -1640,7 +1685,7 @@ def _q8_scalars(dt: int, kind: int, bits: int, d: int) -> tuple:
 
 def _plan_table(kind: str, words, n: int, device, d: int = 0):
     """the first half of `_launch_table`: plan `words` in place and upload them -> (device table, workgroups)"""
-    plan, directed, _ = _TABLES[kind]
+    plan, directed, _ = _TABLES[kind] if isinstance(kind, str) else kind
     if isinstance(words, list):
         words = array.array("q", words)
     addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
@@ -1653,12 +1698,12 @@ def _plan_table(kind: str, words, n: int, device, d: int = 0):
 
 def _run_table(kind: str, table, n: int, blocks: int, device, d: int, scalars, stream=None) -> None:
     """the second half: ONE launch of a planned, uploaded table"""
-    symbol = _TABLES[kind][2]
+    symbol = (_TABLES[kind] if isinstance(kind, str) else kind)[2]
     call(symbol if isinstance(symbol, str) else symbol[d], table.data_ptr(), n, blocks, *scalars, _lib.stream_on(device, stream))
 
 
 def _launch_table(kind: str, words, n: int, device, d: int = 0, scalars=(), stream=None):
-    """plan, upload and launch one table of `struct ct_w4_item` rows: `words` is `n` rows (`item_row`) as a flat CPU int64 tensor or an
+    """plan, upload and launch one table of `struct ct_w4_item` rows (`kind`: a name of `_TABLES`, or such a row itself): `words` is `n` rows (`item_row`) as a flat CPU int64 tensor or an
     `array.array("q")`, planned in place, or as a flat list of ints, copied into one; `d`: 0 compress / pack, 1 decompress / unpack (handed to the
     plans that take it, and picking the launch of the kinds that have two); `scalars`: the launch's arguments between the workgroup count and the stream; `stream`: a raw hipStream_t of `device` (default:
     the caller's current stream there).  Returns the device table, or None for an empty one, before touching the library.
@@ -1845,6 +1890,12 @@ def launch_rtn_nvfp4_words(words, n: int, dtype: torch.dtype, device: torch.devi
     return table
 
 
+def launch_rtn_block8_words(words, n: int, dtype: torch.dtype, device: torch.device, fp8: bool, symmetric: bool) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass block-wise 8-bit compress (`ct_rtn_quant_block8_batch`): src = weights, dst = codes,
+    scale / zp = OUTPUTS (zp 0 in a FLOAT or symmetric table), group = -((bh << 24) | bw)"""
+    return _launch_table(_RTN_BLOCK8_TABLE, words, n, device, 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))) if n else None
+
+
 def rtn_w4_group(shape, group_size) -> int:
     """the group (elements per scale) when `ct_rtn_quant_pack_w4` and its table form take a weight of this shape — 2-D, rows > 0, a group of
     32 * 2^k <= 2048 columns that divides the row (group_size None / 0: the whole row) — else 0"""
@@ -1873,6 +1924,20 @@ def rtn_w4_table_item(x, group_size, with_zp: bool = True):
     scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
     zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
     return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
+
+
+def rtn_block8_table_item(x, block_structure, fp8: bool = True, with_zp: bool = False):
+    """`rtn_w4_table_item` for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`; `rtn_block8_group`): (codes float8_e4m3fn — int8
+    without `fp8` — (R, C), scale (ceil(R / bh), C / bw), int8 zero point of that shape or None without `with_zp`, row) or None"""
+    g = rtn_block8_group(x.shape, block_structure) if _rtn_table_tensor(x) else 0
+    if not g:
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    grid = (-(-rows // int(block_structure[0])), cols // int(block_structure[1]))
+    q = torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
+    scale = torch.empty(grid, dtype=x.dtype, device=x.device)
+    zp = torch.empty(grid, dtype=torch.int8, device=x.device) if with_zp else None
+    return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, g)
 
 
 def _rtn_fp4_takes(x) -> bool:
@@ -1982,6 +2047,26 @@ def rtn_nvfp4_quantize_and_pack_many(weights):
         return rtn_nvfp4_table_item(x, keys[0].data_ptr() + 4 * n)
 
     return _rtn_many(weights, item, lambda i, x: rtn_nvfp4_quantize_and_pack(x), launch_rtn_nvfp4_words, keys)
+
+
+def rtn_quantize_block8_many(weights, *, block_structure, qtype: str = "float", symmetric: bool = True):
+    """`rtn_quantize_block8` for a LIST of weights: the tensors the table takes (`rtn_block8_table_item`, of the first such tensor's device and
+    dtype) leave in ONE `ct_rtn_quant_block8_batch` launch, the others one by one.  Returns [(codes, scale, zero_point)] in input order,
+    bit-identical to the single-tensor call per item."""
+    qtype = getattr(qtype, "value", qtype)
+    fp8 = qtype == "float"
+    if fp8 and not symmetric:
+        raise NotImplementedError("FLOAT 8-bit round-to-nearest is symmetric")
+
+    def item(i, x, n):
+        got = rtn_block8_table_item(x, block_structure, fp8, not fp8)
+        if got is None:
+            return None
+        q, scale, zp, row = got
+        return q, scale, (torch.zeros(scale.shape, dtype=_F8, device=x.device) if fp8 else zp), row
+
+    return _rtn_many(list(weights), item, lambda i, x: rtn_quantize_block8(x, block_structure=block_structure, qtype=qtype, symmetric=symmetric),
+                     lambda flat, n, dtype, device: launch_rtn_block8_words(flat, n, dtype, device, fp8, symmetric))
 
 
 def zp4_batch(pairs, direction: str) -> None:

@@ -13,9 +13,9 @@ from ... import codec
 from ...config import CompressionFormat
 from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, zp_drop_mask
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, run_rtn_windows, zp_drop_mask
 
-__all__ = ["NaiveQuantizationCompressor", "IntQuantizationCompressor", "FloatQuantizationCompressor"]
+__all__ = ["NaiveQuantizationCompressor", "IntQuantizationCompressor", "FloatQuantizationCompressor", "rtn_block8_windows"]
 
 _DTYPE_OF_CODE = {1: torch.float16, 2: torch.bfloat16}
 _STRATEGY_CODE = {"tensor": 0, "channel": 1, "group": 2, "block": 3}
@@ -65,6 +65,39 @@ def _native_q8(modules, direction: str, status):
     return run_planned(modules, lambda ms: plan(ms, info), launch, lambda jobs: hp.q8_finish(jobs, status))
 
 
+def rtn_block8_windows(cls, modules) -> None:
+    """`compress_rtn` + the parameter swap for a list of modules of the 8-bit codec `cls`, in windows (`run_rtn_windows`): the block-strategy
+    modules whose weight the one-pass kernel's plan takes (`block_one_pass`, on a GPU, contiguous, 16-byte aligned) leave in ONE table launch per
+    (device, dtype, FLOAT, symmetric) (codec.launch_rtn_block8_words); the others go through `compress_rtn_module`.  Every module ends in the state
+    `compress_rtn_module` leaves it in.  Not a `compress_rtn_modules` hook of the classes: `compress_model_rtn` runs the 8-bit codecs per module, which
+    tests/test_rtn_batch.py pins; tools/rtn_bench.py (scheme fp8block) measures this form against that loop, DESIGN.md 5.18 has the figures."""
+    from ...quantization.utils import block_one_pass
+
+    def item(m, w, table):
+        scheme = m.quantization_scheme
+        wa = scheme.weights
+        if enum_value(wa.strategy) != "block" or not block_one_pass(w, wa):
+            return None
+        fp8, symmetric = enum_value(getattr(wa, "type", "int")) == "float", bool(wa.symmetric)
+        got = codec.rtn_block8_table_item(w.data, wa.block_structure, fp8, not symmetric)
+        if got is None:
+            return None
+        q, scale, zp, row = got
+        return (w.device, w.dtype, fp8, symmetric), row, (q, scale, zp)
+
+    def launch(key, flat, jobs):
+        device, dtype, fp8, symmetric = key
+        return codec.launch_rtn_block8_words(flat, len(jobs), dtype, device, fp8, symmetric)
+
+    def entries(w, o):  # compress_rtn's entries, a symmetric scheme's zero point dropped
+        add = {"weight": o[0], "weight_scale": o[1]}
+        if o[2] is not None:
+            add["weight_zero_point"] = o[2]
+        return add
+
+    run_rtn_windows(cls, modules, item, launch, entries)
+
+
 @BaseCompressor.register(name=CompressionFormat.naive_quantized.value)
 class NaiveQuantizationCompressor(BaseCompressor):
     @classmethod
@@ -98,14 +131,18 @@ class NaiveQuantizationCompressor(BaseCompressor):
     def compress_rtn(cls, weight, scheme) -> dict:
         """Round-to-nearest compression straight from the dense weight (min-max qparams): what `compress` returns for
         {"weight", "weight_scale", "weight_zero_point"} of calculate_qparams over the weight's min / max.  Channel-wise
-        8-bit schemes (W8A8 int8 / FP8) take ONE pass over the weight (codec.rtn_quantize_channel8); the rest composes the
-        observer kernel with `compress`."""
+        8-bit schemes (W8A8 int8 / FP8) take ONE pass over the weight (codec.rtn_quantize_channel8), and so do block-wise ones (FP8_BLOCK, INT8
+        blocks: codec.rtn_quantize_block8) where the kernel's plan takes the weight (`block_one_pass`); the rest composes the observer kernel with
+        `compress`."""
         import torch
 
-        from ...quantization.utils import calculate_qparams_from_weight
+        from ...quantization.utils import block_one_pass, calculate_qparams_from_weight
 
         weights = scheme.weights
         qtype = enum_value(getattr(weights, "type", "int"))
+        if enum_value(weights.strategy) == "block" and block_one_pass(weight, weights):
+            q, scale, zp = codec.rtn_quantize_block8(weight, block_structure=weights.block_structure, qtype=qtype, symmetric=bool(weights.symmetric))
+            return cls._remove_symmetric_zp({"weight": q, "weight_scale": scale, "weight_zero_point": zp}, scheme)
         one_pass = (enum_value(weights.strategy) == "channel" and int(weights.num_bits) == 8 and weight.dim() == 2
                     and weight.dtype in (torch.bfloat16, torch.float16) and weight.shape[1] % 8 == 0 and weight.shape[1] <= 16384
                     and (qtype == "int" or (weights.symmetric and getattr(weights, "scale_dtype", None) is None)))
@@ -114,6 +151,10 @@ class NaiveQuantizationCompressor(BaseCompressor):
             return cls.compress({"weight": weight, "weight_scale": scale, "weight_zero_point": zp}, scheme)
         q, scale, zp = codec.rtn_quantize_channel8(weight, qtype=qtype, symmetric=bool(weights.symmetric))
         return cls._remove_symmetric_zp({"weight": q, "weight_scale": scale, "weight_zero_point": zp}, scheme)
+
+    # the gate `compress_model_rtn(batched=True)` asks before it hands a codec's modules to a window hook (see NVFP4PackedCompressor).  The 8-bit codecs
+    # have no such hook — `rtn_block8_windows` is a function beside them —, so nothing is dispatched on it yet: False until the driver becomes the hook
+    RTN_TABLE_MEASURED_FASTER = False
 
     @classmethod
     def decompress(cls, state_dict: dict, scheme) -> dict:

@@ -1506,6 +1506,120 @@ __global__ __launch_bounds__(kBlock) void rtn_channel8_wave_kernel(const u32x4* 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Block-wise 8-bit round-to-nearest in ONE pass (FP8_BLOCK weights, and INT8 blocks: the block min-max observer —
+// maybe_pad_tensor_for_block_quant, helpers.py:400-428, whose zero padding calculate_qparams' clamp min <= 0 <= max makes
+// invisible — + calculate_qparams + quantize(strategy = block), forward_helpers.py:62-115): one workgroup per block of bh x bw
+// elements holds the block in registers (MAXU 16-byte units per thread, kBlock apart in the block's own row-major order: with
+// bw = 128 a wave load covers 4 block rows of 256 contiguous bytes), reduces through DPP + LDS behind one barrier, every
+// thread evaluates the identical scale and quantizes its own units.  2 + 1 B per element.  A block row past `rows` (the ragged
+// last row of blocks) is masked, never read.  dst == NULL: the qparams only (the block observer).
+// The item is read as the 8-bit tables read a block item (q8_batch_params): upg_shift = log2(bw / 8), main_blocks = log2(bh) + 1,
+// g_magic / g_shift = the multiply-high for (block index) / (blocks per row of blocks); `blk` = the block's index in the item.
+// ------------------------------------------------------------------------------------------
+template <int DT, int MAXU, bool FP8>
+__device__ __forceinline__ void rtn_block8_body(const ct_w4_item& it, int64_t blk, int symmetric) {
+    __shared__ float s_mn[kBlock / 64], s_mx[kBlock / 64];
+    __shared__ int s_nan[kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ushift = it.upg_shift, hshift = (int)it.main_blocks - 1;
+    const int64_t upr = it.cols >> 3;
+    const int64_t br = (int64_t)(((uint64_t)blk * it.g_magic) >> it.g_shift);
+    const int64_t bc = blk - br * (upr >> ushift);
+    const int64_t row0 = br << hshift;
+    const int live_rows = (int)((it.rows - row0) < ((int64_t)1 << hshift) ? (it.rows - row0) : ((int64_t)1 << hshift));
+    const int live = live_rows << ushift;  // units of the block's in-range rows: they come first in the block's order
+    const u32x4* bin = static_cast<const u32x4*>(it.src) + row0 * upr + (bc << ushift);
+    // unit u of the block (row-major inside it, at most 2048: the plan) -> its offset from the block's first unit
+    auto at = [&](int u) { return (int64_t)(u >> ushift) * upr + (u & ((1 << ushift) - 1)); };
+    u32x4 r[MAXU];
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * kBlock + tid;
+        if (u < live) r[i] = bin[at(u)];
+    }
+    MinMax m;
+    m.mn = __builtin_inff(); m.mx = -__builtin_inff(); m.nan = 0;
+    if (FP8 || symmetric) {  // block-uniform: max |x| on the raw bit pairs (ct_minmax.h)
+        uint32_t acc = 0;
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * kBlock + tid;
+            if (u < live) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
+        }
+        acc = absmax_group_reduce(acc, 64);
+        if (lane == 0) s_mn[wave] = __builtin_bit_cast(float, acc);
+        __syncthreads();
+        uint32_t all = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) all = absmax_acc(all, __builtin_bit_cast(uint32_t, s_mn[w]));
+        m = absmax_finish<DT>(all);
+    } else {
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * kBlock + tid;
+            if (u < live) {
+                const uint32_t ws[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float a, b;
+                    unpack2<DT>(ws[j], a, b);
+                    m.nan |= (a != a) | (b != b);
+                    m.mn = __builtin_fminf(m.mn, __builtin_fminf(a, b));
+                    m.mx = __builtin_fmaxf(m.mx, __builtin_fmaxf(a, b));
+                }
+            }
+        }
+        m = group_reduce(m, 64);
+        if (lane == 0) { s_mn[wave] = m.mn; s_mx[wave] = m.mx; s_nan[wave] = m.nan; }
+        __syncthreads();
+        m.mn = __builtin_fminf(__builtin_fminf(s_mn[0], s_mn[1]), __builtin_fminf(s_mn[2], s_mn[3]));
+        m.mx = __builtin_fmaxf(__builtin_fmaxf(s_mx[0], s_mx[1]), __builtin_fmaxf(s_mx[2], s_mx[3]));
+        m.nan = s_nan[0] | s_nan[1] | s_nan[2] | s_nan[3];
+    }
+    float s, z = 0.0f;
+    if constexpr (FP8) s = compute_qparams_float<DT>(m, QP_FP8, 1.0f);
+    else compute_qparams<DT>(m, 8, symmetric, s, z);
+    if (tid == 0) {  // scale / zero point (ceil(rows / bh), cols / bw): the block's index is its place
+        store1<DT>(const_cast<void*>(it.scale), blk, s);
+        if (it.zp) static_cast<int8_t*>(const_cast<void*>(it.zp))[blk] = (int8_t)(int)z;
+    }
+    if (it.dst == nullptr) return;  // block-uniform, behind the only barrier
+    const bool fast = fast_scale_ok<DT>(s);  // fp16: see rtn_channel8_kernel
+    const float rs = 1.0f / s;
+    const bool use_zp = !FP8 && !symmetric && z != 0.0f;  // block-uniform
+    u32x2* bout = static_cast<u32x2*>(it.dst) + row0 * upr + (bc << ushift);
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * kBlock + tid;
+        if (u >= live) continue;
+        uint32_t lo, hi;
+        if constexpr (FP8) {
+            // with the (all-zero) zero point of a calibrated scheme present, as in the compressor's call: -0.0 + 0 = +0.0
+            if (fast) f8_quant_words<DT, true, true>(r[i], s, rs, 0.0f, lo, hi);
+            else f8_quant_words<DT, false, true>(r[i], s, rs, 0.0f, lo, hi);
+        } else {
+            if (fast) { if (use_zp) q8_quant_words<DT, true, true>(r[i], s, rs, z, -128, 127, lo, hi); else q8_quant_words<DT, true, false>(r[i], s, rs, z, -128, 127, lo, hi); }
+            else { if (use_zp) q8_quant_words<DT, false, true>(r[i], s, rs, z, -128, 127, lo, hi); else q8_quant_words<DT, false, false>(r[i], s, rs, z, -128, 127, lo, hi); }
+            lo ^= 0x80808080u; hi ^= 0x80808080u;  // (code + 128) -> two's-complement code
+        }
+        stream_store8(bout + at(u), u32x2{lo, hi});
+    }
+}
+
+// one tensor: the item by value (no table in device memory), MAXU fitted to its block
+template <int DT, int MAXU, bool FP8>
+__global__ __launch_bounds__(kBlock) void rtn_block8_kernel(ct_w4_item it, int symmetric) {
+    rtn_block8_body<DT, MAXU, FP8>(it, blockIdx.x, symmetric);
+}
+
+// a table of tensors (ct_rtn_block8_batch_plan): every workgroup finds its item, then its block; blocks of any admitted size share the 8-unit body
+template <int DT, bool FP8>
+__global__ __launch_bounds__(kBlock) void rtn_block8_batch_kernel(const ct_w4_item* __restrict__ items, int n, int symmetric) {
+    const ct_w4_item& it = batch_find(items, n, blockIdx.x);
+    rtn_block8_body<DT, 8, FP8>(it, (int64_t)blockIdx.x - it.first_block, symmetric);
+}
+
 // fake_quantize fast path (forward_helpers.py:180-215): x, scale and the result share one 16-bit dtype.
 // Same flat unit stream: lane = UNROLL units one block apart, 16 B in, 16 B out.
 template <int DT, int UNROLL, bool HAS_ZP>
@@ -2148,6 +2262,87 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
 #undef CT_RC8_U
 #undef CT_RC8
     CT_LAUNCH_CHECK("ct_rtn_quant_channel8");
+}
+
+// fills the derived fields of one block item; returns its workgroup (= block) count or -1 with the reason named
+static int64_t block8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    const int64_t bh = it.group < 0 ? (-it.group) >> 24 : 0, bw = it.group < 0 ? (-it.group) & 0xffffff : 0;
+#define CT_B8_REFUSE(why) do { set_error("ct_rtn_block8_batch_plan: item %d (rows %lld, cols %lld, block %lld x %lld): " why, i, (long long)it.rows, \
+                                         (long long)it.cols, (long long)bh, (long long)bw); return -1; } while (0)
+    if (it.group >= 0) CT_B8_REFUSE("group must encode a block, -((rows per block << 24) | columns per block)");
+    if (it.rows <= 0 || it.cols <= 0) CT_B8_REFUSE("empty tensor");
+    if (log2_exact(bh) < 0 || log2_exact(bw) < 0) CT_B8_REFUSE("block sides must be powers of two");
+    if (bw < 16) CT_B8_REFUSE("block width must be at least 16");
+    if (bh * bw > 16384) CT_B8_REFUSE("a block holds at most 16384 elements");
+    if (it.cols % bw != 0) CT_B8_REFUSE("ragged columns: cols must be a multiple of the block width");
+    if (!it.src || !it.scale) CT_B8_REFUSE("the weights and the scale output are required");
+    if (!aligned16(it.src) || !aligned16(it.dst)) CT_B8_REFUSE("misaligned pointer: src and dst must be 16-byte aligned");
+    const int64_t G = it.cols / bw, blocks = ((it.rows + bh - 1) / bh) * G;
+    if (blocks >= ((int64_t)1 << 31)) CT_B8_REFUSE("2^31 blocks or more");
+#undef CT_B8_REFUSE
+    it.units = it.rows * (it.cols / 8);
+    it.upg = (int32_t)(bw / 8);
+    it.upg_shift = log2_exact(it.upg);
+    it.main_blocks = log2_exact(bh) + 1;
+    int L = 0;  // n / G as (n * magic) >> shift, exact for n < 2^31 (Granlund-Montgomery, N = 31)
+    while (((int64_t)1 << L) < G) ++L;
+    it.g_shift = 31 + L;
+    it.g_magic = (uint32_t)((((uint64_t)1 << it.g_shift) + (uint64_t)(G - 1)) / (uint64_t)G);
+    it.first_block = first_block;
+    return blocks;
+}
+
+int64_t ct_rtn_block8_batch_plan(ct_w4_item* items, int n) {
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_block8_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t b = block8_plan_item(items[i], i, blocks);
+        if (b < 0) return -1;
+        blocks += b;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_block8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t block_h, int64_t block_w, int fp8, int symmetric, void* out,
+                        void* scale_out, int8_t* zp_out, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "the one-pass block-wise compress takes 16-bit float weights, got dtype %d", xdt);
+    CT_REQUIRE(rows >= 0 && cols >= 0, "negative shape");
+    CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
+    CT_REQUIRE(symmetric || zp_out != nullptr, "asymmetric quantization needs the zero-point output");
+    CT_REQUIRE(block_h >= 1 && block_w >= 1 && block_h < (1 << 24) && block_w < (1 << 24), "bad block structure %lld x %lld", (long long)block_h, (long long)block_w);
+    if (rows == 0 || cols == 0) return CT_OK;
+    ct_w4_item it{};
+    it.src = x; it.scale = scale_out; it.zp = fp8 ? nullptr : zp_out; it.dst = out; it.rows = rows; it.cols = cols; it.group = -((block_h << 24) | block_w);
+    const int64_t blocks = block8_plan_item(it, 0, 0);
+    if (blocks < 0) return CT_ERR_INVALID_ARG;
+    const int need = (int)((block_h * block_w / 8 + kBlock - 1) / kBlock);
+    const dim3 grid((unsigned)blocks);
+#define CT_RB8(DT, MU, F8) hipLaunchKernelGGL((rtn_block8_kernel<DT, MU, F8>), grid, dim3(kBlock), 0, as_stream(stream), it, symmetric)
+#define CT_RB8_U(DT, F8) do { if (need <= 1) CT_RB8(DT, 1, F8); else if (need <= 2) CT_RB8(DT, 2, F8); else if (need <= 4) CT_RB8(DT, 4, F8); else CT_RB8(DT, 8, F8); } while (0)
+    if (xdt == CT_BF16) { if (fp8) CT_RB8_U(CT_BF16, true); else CT_RB8_U(CT_BF16, false); }
+    else { if (fp8) CT_RB8_U(CT_F16, true); else CT_RB8_U(CT_F16, false); }
+#undef CT_RB8_U
+#undef CT_RB8
+    CT_LAUNCH_CHECK("ct_rtn_quant_block8");
+}
+
+int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass block-wise compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+#define CT_RB8B(DT, F8) hipLaunchKernelGGL((rtn_block8_batch_kernel<DT, F8>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric)
+    if (xdt == CT_BF16) { if (fp8) CT_RB8B(CT_BF16, true); else CT_RB8B(CT_BF16, false); }
+    else { if (fp8) CT_RB8B(CT_F16, true); else CT_RB8B(CT_F16, false); }
+#undef CT_RB8B
+    CT_LAUNCH_CHECK("ct_rtn_quant_block8_batch");
 }
 
 int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_t cols, int bits,

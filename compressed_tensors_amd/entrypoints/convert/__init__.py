@@ -3,8 +3,8 @@ GPU decompress, safetensors out — the on-disk consumer of the decompress hot p
 from .autoawq import AutoAWQConverter
 from .convert_checkpoint import convert_checkpoint, convert_file, exec_jobs, validate_file
 from .converters import CompressedTensorsDequantizer, Converter, build_inverse_weight_maps
-from .fp8block import FP8BlockDequantizer
+from .fp8block import FP8BlockDequantizer, FP8BlockQuantizer
 from .modelopt import ModelOptNvfp4Converter
 
 __all__ = ["convert_checkpoint", "convert_file", "validate_file", "exec_jobs", "Converter", "build_inverse_weight_maps",
-           "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "ModelOptNvfp4Converter"]
+           "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter"]

@@ -259,6 +259,22 @@ int ct_zp4_pack_dim0_batch(const ct_w4_item* items_dev, int n, int64_t total_blo
 int64_t ct_rtn_w4_batch_plan(ct_w4_item* items_host, int n);
 int ct_rtn_quant_pack_w4_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int symmetric, ct_stream_t stream);
 
+/* Block-wise 8-bit round-to-nearest in one pass (FP8_BLOCK weights; INT8 blocks, symmetric or not): the block min-max observer over
+ * block_h x block_w blocks (maybe_pad_tensor_for_block_quant, helpers.py:400-428: the zero padding of a ragged last row of blocks never exists
+ * here, calculate_qparams clamps min <= 0 <= max anyway) + calculate_qparams (helpers.py:50-137) + quantize(strategy = block)
+ * (forward_helpers.py:62-115).  out: one byte per element, or NULL = the qparams only (the block observer); scale_out (ceil(rows / block_h),
+ * cols / block_w) in x's dtype; zp_out int8 of the same shape, required when !symmetric (int8 only).  FLOAT codes are quantized as with the
+ * all-zero zero point of a calibrated scheme present (a -0.0 code becomes +0.0), like ct_rtn_quant_channel8.  Needs bf16 / fp16 weights, block
+ * sides powers of two, block_w >= 16, block_h * block_w <= 16384, cols % block_w == 0, 16-byte aligned x and out.  One workgroup per block.
+ * The table form takes `struct ct_w4_item` rows read this way: src = the weights, dst = the codes or NULL, scale / zp = OUTPUTS (zp NULL in a FLOAT
+ * or symmetric table), group = -((block_h << 24) | block_w) as the 8-bit tables encode blocks; ct_rtn_block8_batch_plan (host only) admits per item what
+ * ct_rtn_quant_block8 admits, fills the derived fields and returns the workgroup count — ceil(rows / block_h) * (cols / block_w) per item —, or -1 with
+ * the reason named in ct_last_error.  Bit-identical to ct_rtn_quant_block8 per item. */
+int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t block_h, int64_t block_w, int fp8, int symmetric, void* out,
+                        void* scale_out, int8_t* zp_out, ct_stream_t stream);
+int64_t ct_rtn_block8_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream);
+
 /* Batched 8-bit codecs (Naive / Int / FloatQuantizationCompressor.compress / decompress, compressors/naive_quantized/
  * base.py:48-126, looped per module by model_compressor.py:167-169,196-198): quantize to int8 (num_bits <= 8, clamped to the
  * num_bits range) or float8_e4m3fn, and the inverse, for a whole table of 16-bit tensors in one launch.  Same table type and

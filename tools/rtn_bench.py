@@ -1,10 +1,11 @@
 """ModelCompressor.compress_model_rtn wall time, table launches (batched=True) against one launch per module (batched=False, the path before the
 tables existed), alternated in one process on the same trees: a Llama-3-8B-shaped tree (32 layers, 224 modules) and a TinyLlama-shaped one (22
-layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4.  A compress consumes the model, so the dense weights are kept and re-attached
+layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4, and FP8_BLOCK (`fp8block`: its table form is
+`naive_quantized.base.rtn_block8_windows`, which `compress_model_rtn` does not dispatch to).  A compress consumes the model, so the dense weights are kept and re-attached
 between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
 their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
 
-    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4] [--out FILE]
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block] [--out FILE]
 """
 import argparse
 import json
@@ -17,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import compressed_tensors_amd as cta  # noqa: E402
+from compressed_tensors_amd.compressors.naive_quantized.base import FloatQuantizationCompressor, rtn_block8_windows  # noqa: E402
 
 HBM_PEAK = 8e12  # bytes / s, the figure every table of DESIGN.md is relative to
 TINY = ((2048, 2048), (256, 2048), (256, 2048), (2048, 2048), (5632, 2048), (5632, 2048), (2048, 5632))
@@ -33,6 +35,10 @@ def scheme_of(name):
         args = cta.QuantizationArgs(num_bits=4, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8)
     elif name == "nvfp4":
         args = cta.QuantizationArgs(num_bits=4, type="float", strategy="tensor_group", symmetric=True, group_size=16, scale_dtype=torch.float8_e4m3fn)
+    elif name == "fp8block":  # the FP8_BLOCK preset: float-quantized needs its input activations
+        act = cta.QuantizationArgs(num_bits=8, type="float", strategy="group", symmetric=True, dynamic=True, group_size=128)
+        return cta.QuantizationScheme(targets=["Linear"], input_activations=act,
+                                      weights=cta.QuantizationArgs(num_bits=8, type="float", strategy="block", symmetric=True, block_structure=[128, 128]))
     else:
         raise SystemExit(f"unknown scheme {name}")
     return cta.QuantizationScheme(targets=["Linear"], weights=args)
@@ -43,6 +49,8 @@ def algorithmic_bytes(name, rows, cols):
     n = rows * cols
     if name == "mxfp4":
         return 2 * n + n // 2 + n // 32
+    if name == "fp8block":
+        return 2 * n + n + 2 * (-(-rows // 128) * (cols // 128))  # one byte per element and one 16-bit scale per block of 128 x 128
     if name == "nvfp4":
         return 2 * 2 * n + n // 2 + n // 16 + 4  # the weight twice (the tensor-wide amax of generate_gparam is a pass of its own), the float8 scales, the global scale
     out = 2 * n + n // 2 + 2 * (n // 128)
@@ -104,7 +112,12 @@ def main():
                     attach(model, pool, scheme, mc)
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    mc.compress_model_rtn(model, batched=batched)
+                    if name == "fp8block" and batched:  # the 8-bit codecs have no window hook: their table form is the block-wise window driver
+                        for lin, _ in pool:
+                            lin.quantization_scheme.format = "float-quantized"
+                        rtn_block8_windows(FloatQuantizationCompressor, [lin for lin, _ in pool])
+                    else:
+                        mc.compress_model_rtn(model, batched=batched)
                     t1 = time.perf_counter()
                     torch.cuda.synchronize()
                     t2 = time.perf_counter()
