@@ -13,6 +13,7 @@
 #include "ct_quant_core.h"
 #include "ct_quant_lean.h"
 #include "ct_minmax.h"
+#include "ct_w4_variant.h"
 
 #include <cstdlib>
 
@@ -618,16 +619,9 @@ __global__ __launch_bounds__(kBlock) void f32_quant_units_kernel(W4Params p, int
 // (Round 3, for the 4096^2 launches: F = 2 / 3 / 4 consecutive chunks per workgroup with every chunk's loads requested up
 // front measured 9.9 / 11.7 / 12.1 us against 8.8 us for this one-chunk form, and 31.0 / 32.7 / 34.2 against 29.4 us at 8192^2;
 // block sizes 128 ... 1024 and the traffic-only stand-in all sit at 8.4-8.5 us: the exact grid of small workgroups stays.)
+// the lean body behind its loads: `r` = the lane's 64 bytes of weights, `sbits` / `z` = its group's scale bits and zero point
 template <int DT, bool HAS_ZP>
-__device__ __forceinline__ void w4_quant_pack_lean(const u32x4* __restrict__ in, const uint16_t* __restrict__ scale,
-                                                   const int8_t* __restrict__ zp, u32x4* __restrict__ out, int64_t g, int gshift) {
-    const int64_t si = g >> gshift;
-    const uint32_t sbits = __builtin_nontemporal_load(scale + si);
-    const float z = HAS_ZP ? (float)__builtin_nontemporal_load(zp + si) : 0.0f;  // int8 -> exact in bf16 / fp16
-    asm volatile("" ::: "memory");  // keep the small loads ahead of the big ones
-    u32x4 r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = in[g * 4 + i];
+__device__ __forceinline__ void w4_quant_pack_lean_words(const u32x4 (&r)[4], uint32_t sbits, float z, u32x4* __restrict__ out, int64_t g) {
     const float s = DT == CT_BF16 ? bf16_bits_to_f(sbits) : f16_bits_to_f(sbits);
     const bool fast = fast_scale_ok<DT>(s) && fast_data_ok<DT, 4>(r);
     const float rs = 1.0f / s;
@@ -654,11 +648,63 @@ __device__ __forceinline__ void w4_quant_pack_lean(const u32x4* __restrict__ in,
 }
 
 template <int DT, bool HAS_ZP>
+__device__ __forceinline__ void w4_quant_pack_lean(const u32x4* __restrict__ in, const uint16_t* __restrict__ scale,
+                                                   const int8_t* __restrict__ zp, u32x4* __restrict__ out, int64_t g, int gshift) {
+    const int64_t si = g >> gshift;
+    const uint32_t sbits = __builtin_nontemporal_load(scale + si);
+    const float z = HAS_ZP ? (float)__builtin_nontemporal_load(zp + si) : 0.0f;  // int8 -> exact in bf16 / fp16
+    asm volatile("" ::: "memory");  // keep the small loads ahead of the big ones
+    u32x4 r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = in[g * 4 + i];
+    w4_quant_pack_lean_words<DT, HAS_ZP>(r, sbits, z, out, g);
+}
+
+template <int DT, bool HAS_ZP>
 __global__ __launch_bounds__(kBlock) void w4_quant_pack_lean_kernel(const u32x4* __restrict__ in, const uint16_t* __restrict__ scale,
                                                                     const int8_t* __restrict__ zp, u32x4* __restrict__ out, int64_t groups,
                                                                     int gshift /* log2(lanes per scale group) */) {
     const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (g < groups) w4_quant_pack_lean<DT, HAS_ZP>(in, scale, zp, out, g, gshift);
+}
+
+// The same body with its 64 bytes per lane brought in by LDS-DMA (global_load_lds_dwordx4 ... nt).  The lean kernel's four 16-byte loads of a
+// lane sit 64 bytes apart, so a wave touches every 128-byte line four times and relies on L1 to merge the touches — which is why non-temporal
+// loads cost it 29.3 -> 42 us (ct_common.h, stream_store16).  Here one wave-instruction moves 1 KiB of CONSECUTIVE global bytes into the wave's
+// own 4 KiB of LDS (destination = wave-uniform base + 16 x lane, the only shape the instruction has): every line is touched once, so the
+// stream can be non-temporal, and the lane then reads ITS 64 bytes back with four ds_read_b128 — the DMA engine does the transposition,
+// the registers, the arithmetic and the one 16-byte store per lane are those of the lean kernel.
+// No workgroup barrier: a wave reads only what it issued itself, and its own `s_waitcnt vmcnt(0)` is what orders a ds_read behind an
+// LDS-DMA (a read issued earlier returns the OLD bytes, no stall).  The region is written once per workgroup: no reuse hazard.
+// A wave that is not whole (groups % 64 != 0: the tensor's last one) takes the guarded plain body, chosen wave-uniformly: no DMA is issued
+// for lanes beyond the tensor, and every other wave reads exactly its own 4 KiB of the input.
+template <int DT, bool HAS_ZP>
+__global__ __launch_bounds__(kBlock) void w4_quant_pack_lds_kernel(const u32x4* __restrict__ in, const uint16_t* __restrict__ scale,
+                                                                   const int8_t* __restrict__ zp, u32x4* __restrict__ out, int64_t groups,
+                                                                   int gshift) {
+    __shared__ u32x4 stage[kBlock * 4];  // 16 KiB: wave w owns [256 w, 256 w + 256)
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t g0 = g - lane;  // the wave's first lane
+    if (g0 + 64 > groups) {
+        if (g < groups) w4_quant_pack_lean<DT, HAS_ZP>(in, scale, zp, out, g, gshift);
+        return;
+    }
+    const int64_t si = g >> gshift;
+    const uint32_t sbits = __builtin_nontemporal_load(scale + si);
+    const float z = HAS_ZP ? (float)__builtin_nontemporal_load(zp + si) : 0.0f;
+    asm volatile("" ::: "memory");
+    u32x4* mine = stage + (threadIdx.x & ~63u) * 4;
+    const u32x4* src = in + g0 * 4 + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 64 * i),
+                                         (__attribute__((address_space(3))) void*)(mine + 64 * i), 16, 0, 2 /* nt */);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    u32x4 r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = mine[lane * 4 + i];
+    w4_quant_pack_lean_words<DT, HAS_ZP>(r, sbits, z, out, g);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2140,10 +2186,21 @@ int ct_quant_pack(const void* x, int xdt, const void* scale, int sdt, const void
             const int gshift = w.upg_shift - 2;
             const int64_t groups = w.units / 4;
             dim3 gl((unsigned)cdiv64(groups, kBlock));
-#define CT_W4L(DT, ZP) hipLaunchKernelGGL((w4_quant_pack_lean_kernel<DT, ZP>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), reinterpret_cast<u32x4*>(packed), groups, gshift)
+            // Which kernel streams the weights: w4_compress_variant (ct_w4_variant.h, with the measured table).  The diagnostics build reads
+            // CT_W4_COMPRESS = plain | lds | auto per call, for the tests and the A/B measurements; the product follows the rule alone.
+#ifdef CT_DIAG
+            const char* forced = std::getenv("CT_W4_COMPRESS");
+#else
+            const char* forced = nullptr;
+#endif
+            const int variant = w4_compress_variant(forced, groups, reinterpret_cast<uintptr_t>(x));
+            CT_REQUIRE(variant != kW4CompressBad, "CT_W4_COMPRESS must be plain, lds or auto, got '%s'", forced);
+#define CT_W4L(DT, ZP) do { if (variant == kW4CompressLds) CT_W4L_(w4_quant_pack_lds_kernel, DT, ZP); else CT_W4L_(w4_quant_pack_lean_kernel, DT, ZP); } while (0)
+#define CT_W4L_(K, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), reinterpret_cast<u32x4*>(packed), groups, gshift)
             if (xdt == CT_BF16) { if (zp) CT_W4L(CT_BF16, true); else CT_W4L(CT_BF16, false); }
             else { if (zp) CT_W4L(CT_F16, true); else CT_W4L(CT_F16, false); }
 #undef CT_W4L
+#undef CT_W4L_
             CT_LAUNCH_CHECK("ct_quant_pack[w4 lean]");
         }
 #define CT_W4Q(DT, ZP, SH) hipLaunchKernelGGL((w4_quant_pack_kernel<DT, ZP, SH>), grid, dim3(kBlock), 0, as_stream(stream), w)

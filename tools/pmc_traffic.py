@@ -15,6 +15,7 @@ import sys
 ALIAS = {
     "ct::w4_quant_pack_kernel<2, true, true>": "w4_quant_pack_kernel<bf16>",
     "ct::w4_quant_pack_lean_kernel<2, true>": "w4_quant_pack_lean_kernel<bf16>",
+    "ct::w4_quant_pack_lds_kernel<2, true>": "w4_quant_pack_lean_kernel<bf16>",  # the headline's ct_quant_pack launch since the LDS-DMA form (the row name bench.py reports)
     "ct::w4_unpack_dequant_kernel<2, 2, false>": "w4_unpack_dequant_kernel<bf16>",
     "ct::w4_unpack_dequant_kernel<2, 2, false, false>": "w4_unpack_dequant_kernel<bf16>",
     "ct::w4_unpack_dequant_kernel<2, 2, false, 2>": "w4_unpack_dequant_kernel<bf16>",
