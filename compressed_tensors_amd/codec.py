@@ -102,6 +102,11 @@ __all__ = [
     "rtn_nvfp4_table_item",
     "rtn_block8_table_item",
     "rtn_block8_group",
+    "rtn_quantize_group8",
+    "rtn_quantize_group8_many",
+    "rtn_group8_table_item",
+    "rtn_group8_group",
+    "launch_rtn_group8_words",
     "rtn_nvfp4_takes",
     "rtn_nvfp4_keys",
     "attn_observe_global_scale",
@@ -1587,6 +1592,70 @@ def rtn_quantize_block8(x: torch.Tensor, *, block_structure, qtype: str = "float
     return (_home(out, x) if codes else None), _home(scale, x), _home(zp, x)
 
 
+_RTN_GROUP8_MAX = 1024  # one wave reduces a group: 64 lanes of 16 elements (ct_rtn_group8_batch_plan)
+_QP_INT, _QP_FP8, _QP_MXFP8 = 0, 1, 4  # the observer's kinds (csrc/ct_minmax.h)
+
+
+def rtn_group8_group(shape, group_size) -> int:
+    """the group (elements per scale) when `ct_rtn_quant_group8` and its table form take a weight of this shape — 2-D, rows > 0, a group of
+    32 * 2^k <= 1024 columns that divides the row (group_size None / 0: the whole row as one group) — else 0"""
+    if len(shape) != 2 or int(shape[0]) <= 0 or int(shape[1]) <= 0:
+        return 0
+    cols = int(shape[1])
+    g = int(group_size) if group_size else cols
+    if g <= 0 or cols % g or g % 32 or g > _RTN_GROUP8_MAX or (g // 32) & (g // 32 - 1):
+        return 0
+    return g
+
+
+def _rtn_group8_kind(qtype, symmetric: bool, mx: bool, words: bool) -> int:
+    qtype = getattr(qtype, "value", qtype)
+    if qtype not in ("int", "float"):
+        raise ValueError(f"qtype must be 'int' or 'float', got {qtype!r}")
+    if qtype == "int" and mx:
+        raise ValueError("MX scales belong to the FLOAT scheme")
+    if qtype == "float" and (not symmetric or words):
+        raise NotImplementedError("FLOAT 8-bit round-to-nearest is symmetric and has no word form")
+    return _QP_INT if qtype == "int" else _QP_MXFP8 if mx else _QP_FP8
+
+
+def rtn_quantize_group8(x: torch.Tensor, *, group_size, qtype: str = "int", symmetric: bool = True, mx: bool = False, words: bool = False):
+    """Group-wise 8-bit round-to-nearest in ONE pass over the weight (MXFP8, W8A16, any FLOAT / INT 8-bit group scheme): the min-max observer
+    over groups of `group_size` columns (None: the row) + calculate_qparams + quantize to int8 (qtype "int") or float8_e4m3fn ("float").
+    Returns (codes (R, C), scale (R, C / g) in x.dtype, zero_point) and, with `mx` (FLOAT, g == 32), the E8M0 codes uint8 (R, C / 32) as a
+    fourth entry: the zero point is int8 for INT and None for FLOAT.  `words` (INT): the codes are the (code + 128) bytes of pack-quantized's
+    8-bit words, as int32 (R, C / 4).  Bit-identical to `minmax_qparams` / `minmax_qparams_float` followed by `quantize_tensor` /
+    `quantize_and_pack` (and `compress_mx_scale`).  Raises the reference's ValueError for cols % g != 0 and NotImplementedError for what the
+    kernel's plan refuses (`rtn_group8_group`; float32 weights)."""
+    if x.dim() != 2:
+        raise ValueError("rtn_quantize_group8 expects a 2-D weight")
+    kind = _rtn_group8_kind(qtype, symmetric, mx, words)
+    rows, cols = x.shape
+    g = int(group_size) if group_size else cols
+    if g <= 0 or cols % g != 0:
+        raise ValueError(f"tensor column shape must be divisble by the given group_size {g} but got {cols}")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"the one-pass group-wise compress takes 16-bit float weights, got {x.dtype}")
+    if rows and cols and not rtn_group8_group(x.shape, g):
+        raise NotImplementedError(f"the one-pass group-wise compress needs group sizes 32 * 2^k <= {_RTN_GROUP8_MAX}, got {g}")
+    if mx and g != 32:
+        raise NotImplementedError(f"MXFP8 groups hold 32 elements, got {g}")
+    dev = _compute_device(x)
+    xd = _dev(x, dev).contiguous()
+    if xd.data_ptr() % 16:
+        xd = xd.clone()
+    fp8 = kind != _QP_INT
+    out = torch.empty((rows, cols // 4), dtype=torch.int32, device=dev) if words else torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=dev)
+    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=dev)
+    zp = None if fp8 else torch.empty((rows, cols // g), dtype=torch.int8, device=dev)
+    code = torch.empty((rows, cols // g), dtype=torch.uint8, device=dev) if mx else None
+    lut = _mx_code_table(x.dtype, dev) if mx else None  # read for an inf / NaN scale only: the byte `compress_mx_scale` gives it
+    call("ct_rtn_quant_group8", ptr(xd), DT[xd.dtype], rows, cols, g, kind, int(bool(symmetric)), int(bool(words)), ptr(out), ptr(scale), ptr(zp), ptr(code),
+         ptr(lut), stream_of(xd))
+    got = (_home(out, x), _home(scale, x), None if fp8 else _home(zp, x))
+    return got + (_home(code, x),) if mx else got
+
+
 def _aligned16(*tensors) -> bool:
     return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
 
@@ -1675,6 +1744,7 @@ _TABLES = {
 # the same kind of row for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`), handed to `_launch_table` as the row itself: the registry
 # above is pinned to its eight plans by tests/test_host_logic.py, so the ninth stands beside it
 _RTN_BLOCK8_TABLE = ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
+_RTN_GROUP8_TABLE = ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # the one-pass group-wise 8-bit table (`launch_rtn_group8_words`), likewise
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
@@ -1896,6 +1966,17 @@ def launch_rtn_block8_words(words, n: int, dtype: torch.dtype, device: torch.dev
     return _launch_table(_RTN_BLOCK8_TABLE, words, n, device, 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))) if n else None
 
 
+def launch_rtn_group8_words(words, n: int, dtype: torch.dtype, device: torch.device, kind: int, symmetric: bool = True, as_words: bool = False) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass group-wise 8-bit compress (`ct_rtn_quant_group8_batch`): src = weights, dst = codes,
+    scale / zp = OUTPUTS (scale may be 0 in an MXFP8 table, zp 0 in a FLOAT or symmetric one), zp_packed = the E8M0 code output of an MXFP8
+    table, group = the group size; `kind` 0 INT (`as_words`: the (code + 128) bytes of pack-quantized), 1 FP8, 4 MXFP8 (with `_mx_code_table` of the
+    weights' dtype behind it)"""
+    if not n:
+        return None
+    lut = _mx_code_table(dtype, device).data_ptr() if int(kind) == _QP_MXFP8 else None  # cached per (dtype, device): outlives the launch
+    return _launch_table(_RTN_GROUP8_TABLE, words, n, device, 0, (DT[dtype], int(kind), int(bool(symmetric)), int(bool(as_words)), lut))
+
+
 def rtn_w4_group(shape, group_size) -> int:
     """the group (elements per scale) when `ct_rtn_quant_pack_w4` and its table form take a weight of this shape — 2-D, rows > 0, a group of
     32 * 2^k <= 2048 columns that divides the row (group_size None / 0: the whole row) — else 0"""
@@ -1938,6 +2019,23 @@ def rtn_block8_table_item(x, block_structure, fp8: bool = True, with_zp: bool = 
     scale = torch.empty(grid, dtype=x.dtype, device=x.device)
     zp = torch.empty(grid, dtype=torch.int8, device=x.device) if with_zp else None
     return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, g)
+
+
+def rtn_group8_table_item(x, group_size, qtype: str = "int", with_zp: bool = False, mx: bool = False, words: bool = False, with_scale: bool = True):
+    """`rtn_w4_table_item` for the one-pass group-wise 8-bit table (`launch_rtn_group8_words`; `rtn_group8_group`): (codes — float8_e4m3fn for
+    qtype "float", int8 for "int", int32 (R, C / 4) with `words` —, scale (R, C / g) or None without `with_scale` (MXFP8 only), int8 zero point of
+    that shape or None without `with_zp`, [E8M0 codes uint8 (R, C / 32) with `mx`,] row) or None"""
+    g = rtn_group8_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
+    if not g or (mx and g != 32):
+        return None
+    fp8 = getattr(qtype, "value", qtype) == "float"
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    q = torch.empty((rows, cols // 4), dtype=torch.int32, device=x.device) if words else torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
+    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device) if with_scale or not mx else None
+    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp and not fp8 else None
+    code = torch.empty((rows, cols // g), dtype=torch.uint8, device=x.device) if mx else None
+    row = item_row(x.data_ptr(), _word(scale), _word(zp), q.data_ptr(), rows, cols, g, _word(code))
+    return (q, scale, zp, code, row) if mx else (q, scale, zp, row)
 
 
 def _rtn_fp4_takes(x) -> bool:
@@ -2067,6 +2165,20 @@ def rtn_quantize_block8_many(weights, *, block_structure, qtype: str = "float", 
 
     return _rtn_many(list(weights), item, lambda i, x: rtn_quantize_block8(x, block_structure=block_structure, qtype=qtype, symmetric=symmetric),
                      lambda flat, n, dtype, device: launch_rtn_block8_words(flat, n, dtype, device, fp8, symmetric))
+
+
+def rtn_quantize_group8_many(weights, *, group_size, qtype: str = "int", symmetric: bool = True, mx: bool = False, words: bool = False):
+    """`rtn_quantize_group8` for a LIST of weights: the tensors the table takes (`rtn_group8_table_item`, of the first such tensor's device and
+    dtype) leave in ONE `ct_rtn_quant_group8_batch` launch, the others one by one.  `group_size`: one value for all, or one per weight (None = one
+    group per row).  Returns the single call's tuples in input order, bit-identical to the single-tensor call per item."""
+    kind = _rtn_group8_kind(qtype, symmetric, mx, words)
+    weights = list(weights)
+    groups = list(group_size) if isinstance(group_size, (list, tuple)) else [group_size] * len(weights)
+    if len(groups) != len(weights):
+        raise ValueError(f"{len(groups)} group sizes for {len(weights)} weights")
+    return _rtn_many(weights, lambda i, x, n: rtn_group8_table_item(x, groups[i], qtype, kind == _QP_INT, mx, words),
+                     lambda i, x: rtn_quantize_group8(x, group_size=groups[i], qtype=qtype, symmetric=symmetric, mx=mx, words=words),
+                     lambda flat, n, dtype, device: launch_rtn_group8_words(flat, n, dtype, device, kind, symmetric, words))
 
 
 def zp4_batch(pairs, direction: str) -> None:

@@ -128,14 +128,14 @@ class ModelCompressor:
     def compress_model_rtn(self, model: torch.nn.Module, recouple: bool = True, batched: bool = True):
         """Data-free (round-to-nearest) compression of a model whose modules carry a `quantization_scheme` but no scales yet:
         for every quantized module the min-max observer, calculate_qparams and the codec run fused — one pass over each
-        weight where the scheme allows it (int4 group / channel, MXFP4, NVFP4, channel-wise and block-wise int8 / float8 — FP8_BLOCK —; see
-        the codecs' `compress_rtn`).  Bias and other parameters are kept.  Under torch.distributed the modules are sharded over the
+        weight where the scheme allows it (int4 group / channel, MXFP4, NVFP4, channel-wise, block-wise — FP8_BLOCK — and group-wise — MXFP8,
+        W8A16 — int8 / float8; see the codecs' `compress_rtn`).  Bias and other parameters are kept.  Under torch.distributed the modules are sharded over the
         ranks exactly like `compress_model`.  No upstream counterpart: upstream separates calibration (observers,
         llm-compressor) from `compress_model`; the result equals that two-step flow with min-max observers.
-        `batched` (default): the modules are grouped by codec, and a codec with the window hook `compress_rtn_modules` (pack-quantized, MXFP4, NVFP4:
+        `batched` (default): the modules are grouped by codec, and a codec with the window hook `compress_rtn_modules` (pack-quantized, MXFP4, NVFP4, MXFP8:
         each a few lines over `compressors.base.run_rtn_windows`) whose gate `RTN_TABLE_MEASURED_FASTER` holds turns its group into table launches per
         window of 32 modules.  NVFP4's gate is off (two launches per window, the tensor-wide amax behind `generate_gparam` is a pass of its own; not
-        dispatched on figures that have not decided it); it, the codecs without the hook (the 8-bit ones; their block-wise table form is the function
+        dispatched on figures that have not decided it); it, the codecs without the hook (the other 8-bit ones; their block-wise table form is the function
         `naive_quantized.base.rtn_block8_windows`, which a caller runs itself) and the modules a table does not take run
         per module.  `batched=False`: per module throughout — same result."""
         from ...utils.module import direct_entry, swap_direct_entries

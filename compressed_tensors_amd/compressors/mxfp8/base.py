@@ -6,7 +6,7 @@ import torch
 from ... import codec
 from ...config import CompressionFormat
 from ...quantization.quant_args import enum_value
-from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor
+from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_rtn_windows
 from ..naive_quantized import NaiveQuantizationCompressor
 
 __all__ = ["MXFP8QuantizationCompressor"]
@@ -38,6 +38,45 @@ class MXFP8QuantizationCompressor(NaiveQuantizationCompressor):
         """mxfp8/base.py:74-101: the exponent comes back as a bfloat16 power of two, so the weight is bfloat16 too"""
         widened = dict(state_dict, weight_scale=cls._decompress_scale(state_dict["weight_scale"]))
         return _naive_decompress(cls, widened, scheme)
+
+    @classmethod
+    def compress_rtn(cls, weight, scheme) -> dict:
+        """Round-to-nearest compression straight from the dense weight: what `compress` returns for calculate_qparams of the weight's group
+        min / max — the codes and the E8M0 exponents from ONE pass over the weight (codec.rtn_quantize_group8, mx) where the kernel's plan takes
+        it (`group_one_pass`) and the measurement says so; the observer + quantize + compress_mx_scale composition otherwise."""
+        from ...quantization.utils import group_one_pass
+        from ..naive_quantized.base import RTN_GROUP8_MEASURED_FASTER
+
+        weights = scheme.weights
+        base = MXFP8QuantizationCompressor
+        if (RTN_GROUP8_MEASURED_FASTER["mxfp8"] and cls.compress.__func__ is base.compress.__func__ and group_one_pass(weight, weights) == "mxfp8"
+                and (getattr(weights, "scale_dtype", None) or torch.uint8) is torch.uint8):
+            q, _, _, code = codec.rtn_quantize_group8(weight, group_size=32, qtype="float", mx=True)
+            return {"weight_scale": code, "weight": q}  # the composition's entry order
+        return super().compress_rtn(weight, scheme)
+
+    # the window hook's gate (see NVFP4PackedCompressor): True only where the table was below the per-module loop's minimum on both trees in both runs
+    # (profiles/rtn_bench.jsonl, scheme mxfp8; DESIGN.md 5.19): medians 4.66 / 4.72 ms (at most 4.79) against a per-module minimum of 5.06 / 5.07 on the
+    # 8B-shaped tree, 1.99 / 2.00 (at most 2.12) against 3.23 / 3.22 on the TinyLlama-shaped one — the per-module loop already on the one-pass kernel
+    RTN_TABLE_MEASURED_FASTER = True
+
+    @classmethod
+    def compress_rtn_modules(cls, modules) -> None:
+        """the window hook (`run_rtn_windows`): the modules with a 16-bit weight on a GPU that the one-pass kernel's plan takes leave in ONE table
+        launch per (device, dtype) (codec.launch_rtn_group8_words, kind MXFP8); the others go through `compress_rtn_module`."""
+        from ...quantization.utils import group_one_pass
+
+        def item(m, w, table):
+            wa = m.quantization_scheme.weights
+            if group_one_pass(w, wa) != "mxfp8" or (getattr(wa, "scale_dtype", None) or torch.uint8) is not torch.uint8:
+                return None
+            got = codec.rtn_group8_table_item(w.data, 32, "float", mx=True, with_scale=False)
+            if got is None:
+                return None
+            return (w.device, w.dtype), got[-1], got
+
+        run_rtn_windows(cls, modules, item, lambda key, flat, jobs: codec.launch_rtn_group8_words(flat, len(jobs), key[1], key[0], 4),
+                        lambda w, o: {"weight_scale": o[3], "weight": o[0]})
 
     # ------------------------------------------------------------------ module loops (round 6)
     # ModelCompressor's per-module loop in the C++ extension (csrc/host/ct_hostpath.cpp mx8_plan_compress / mx8_plan_decompress / mx8_finish): the weights of a

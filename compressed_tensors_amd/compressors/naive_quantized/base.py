@@ -65,6 +65,15 @@ def _native_q8(modules, direction: str, status):
     return run_planned(modules, lambda ms: plan(ms, info), launch, lambda jobs: hp.q8_finish(jobs, status))
 
 
+# which forms of the one-pass group-wise 8-bit kernel (quantization.utils.group_one_pass) `compress_rtn` dispatches: a form is True only where
+# tools/group8_rtn_bench.py measured the one pass faster than the composition it replaces on every shape by more than the spread of the two runs
+# (profiles/group8_rtn_bench.jsonl).  The entry points stay callable either way.
+# Measured (bf16, 8192^2 / 4096 x 14336 / 14336 x 4096, worst median of two runs against the composition's best): mxfp8 42.8 / 35.8 / 35.7 us against
+# 63.8 / 56.9 / 57.0; fp8 g128 35.8 / 32.0 / 32.0 against 56.9 / 50.9 / 50.9; int g128 35.7 / 31.7 / 31.7 against 57.4 / 51.0 / 50.9; asymmetric 39.2 / 34.9 /
+# 35.0 against 56.7 / 51.0 / 50.7; run spread at most 2.8 us.
+RTN_GROUP8_MEASURED_FASTER = {"mxfp8": True, "fp8": True, "int": True, "int_asym": True}
+
+
 def rtn_block8_windows(cls, modules) -> None:
     """`compress_rtn` + the parameter swap for a list of modules of the 8-bit codec `cls`, in windows (`run_rtn_windows`): the block-strategy
     modules whose weight the one-pass kernel's plan takes (`block_one_pass`, on a GPU, contiguous, 16-byte aligned) leave in ONE table launch per
@@ -136,13 +145,22 @@ class NaiveQuantizationCompressor(BaseCompressor):
         `compress`."""
         import torch
 
-        from ...quantization.utils import block_one_pass, calculate_qparams_from_weight
+        from ...quantization.utils import block_one_pass, calculate_qparams_from_weight, group_one_pass
 
         weights = scheme.weights
         qtype = enum_value(getattr(weights, "type", "int"))
         if enum_value(weights.strategy) == "block" and block_one_pass(weight, weights):
             q, scale, zp = codec.rtn_quantize_block8(weight, block_structure=weights.block_structure, qtype=qtype, symmetric=bool(weights.symmetric))
             return cls._remove_symmetric_zp({"weight": q, "weight_scale": scale, "weight_zero_point": zp}, scheme)
+        form = group_one_pass(weight, weights) if enum_value(weights.strategy) == "group" else ""
+        if form in ("int", "int_asym", "fp8") and RTN_GROUP8_MEASURED_FASTER[form]:
+            # group schemes (W8A8-style int8 / FP8 under group scales): codec.rtn_quantize_group8, the entries in the composition's order
+            q, scale, zp = codec.rtn_quantize_group8(weight, group_size=weights.group_size, qtype=qtype, symmetric=bool(weights.symmetric))
+            out = {"weight_scale": scale}
+            if zp is not None:
+                out["weight_zero_point"] = zp
+            out["weight"] = q
+            return cls._remove_symmetric_zp(out, scheme)
         one_pass = (enum_value(weights.strategy) == "channel" and int(weights.num_bits) == 8 and weight.dim() == 2
                     and weight.dtype in (torch.bfloat16, torch.float16) and weight.shape[1] % 8 == 0 and weight.shape[1] <= 16384
                     and (qtype == "int" or (weights.symmetric and getattr(weights, "scale_dtype", None) is None)))

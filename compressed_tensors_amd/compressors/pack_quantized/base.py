@@ -262,6 +262,21 @@ class PackedQuantizationCompressor(BaseCompressor):
         group = getattr(weights, "group_size", None) if strategy == "group" else None
         one_pass = (int(weights.num_bits) == 4 and enum_value(getattr(weights, "type", "int")) == "int" and strategy in ("group", "channel")
                     and weight.dim() == 2 and weight.dtype in (torch.bfloat16, torch.float16) and codec.rtn_w4_group((1, weight.shape[-1]), group))
+        if not one_pass and enum_value(getattr(weights, "type", "int")) == "int":
+            # 8-bit words (W8A16): the one-pass group-wise kernel in its word form, a channel as one group, where its plan takes the weight and the
+            # measurement says so (naive_quantized.base.RTN_GROUP8_MEASURED_FASTER)
+            from ...quantization.utils import group_one_pass
+            from ..naive_quantized.base import RTN_GROUP8_MEASURED_FASTER
+
+            form = group_one_pass(weight, weights)
+            if form in ("int", "int_asym") and RTN_GROUP8_MEASURED_FASTER[form]:
+                packed, scale, zp = codec.rtn_quantize_group8(weight, group_size=group, qtype="int", symmetric=bool(weights.symmetric), words=True)
+                out = {"weight_scale": scale}
+                if not weights.symmetric:
+                    out["weight_zero_point"] = codec.pack_to_int32(zp, 8, packed_dim=0)
+                out["weight_packed"] = packed
+                out["weight_shape"] = torch.tensor(weight.shape)
+                return out
         if not one_pass:
             scale, zp = codec.minmax_qparams(weight, num_bits=int(weights.num_bits), group_size=group, symmetric=bool(weights.symmetric))
             return cls.compress({"weight": weight, "weight_scale": scale, "weight_zero_point": zp}, scheme)

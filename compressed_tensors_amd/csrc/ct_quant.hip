@@ -1666,6 +1666,108 @@ __global__ __launch_bounds__(kBlock) void rtn_block8_batch_kernel(const ct_w4_it
     rtn_block8_body<DT, 8, FP8>(it, (int64_t)blockIdx.x - it.first_block, symmetric);
 }
 
+// ------------------------------------------------------------------------------------------
+// Group-wise 8-bit round-to-nearest in ONE pass (MXFP8: float8 in groups of 32 under E8M0 scales; W8A16: int8 in groups of 128; any
+// FLOAT / INT 8-bit group scheme): the group min-max observer + calculate_qparams + quantize (+ compress_mx_scale).  The tensor is a flat
+// stream of groups (cols % g == 0), the shape of rtn_w4_lane at half its lane width: a lane owns 16 consecutive elements (two 16-byte loads,
+// ONE 16-byte store: a wave store is 1 KiB contiguous), a group of g = 32 * 2^k <= 1024 elements is g / 16 adjacent lanes, reduced by DPP
+// (and two wave shuffles beyond 256): no LDS, no barrier.  Every lane of a group evaluates the identical scale / zero point and quantizes
+// its own 16 elements; lane 0 of the group stores the qparams.  2 + 1 + (2 or 3) / g bytes per element instead of (2 + 2 / g) + (2 + 1 + 2 / g)
+// (+ the scale round trip of compress_mx_scale).
+// KIND: the QP_* of ct_minmax.h — QP_INT (SYM or not; `flip` = 0x80808080 for int8 codes, 0 for the pack-quantized (code + 128) bytes),
+// QP_FP8, QP_MXFP8 (e8m0 = the exponent byte output, as rtn_mxfp4_lane derives it; scale_out may be NULL then).  The FLOAT codes are quantized
+// with the (all-zero) zero point of a calibrated scheme present, as rtn_channel8_kernel does.  Bit-identical to ct_minmax_qparams(_float) with
+// cdiv = g followed by ct_quantize / ct_quantize_fp8 / ct_quant_pack(8 bits) (and ct_mx_scale_compress) by construction (same helpers).
+// Every lane of the workgroup enters (the DPP reduction reads its neighbours): `live` guards the memory accesses, the return comes behind
+// the reduction.  lanes is a multiple of lpg, kBlock too: a group never straddles a workgroup.
+// ------------------------------------------------------------------------------------------
+template <int DT, int KIND, bool SYM>
+__device__ __forceinline__ void rtn_group8_lane(const u32x4* __restrict__ in, int64_t lanes, int lpg, u32x4* __restrict__ out, void* __restrict__ scale_out,
+                                                int8_t* __restrict__ zp_out, uint8_t* __restrict__ e8m0, const uint8_t* __restrict__ mx_table, uint32_t flip, int64_t l) {
+    static_assert(KIND == QP_INT || (SYM && (KIND == QP_FP8 || KIND == QP_MXFP8)), "FLOAT 8-bit round-to-nearest is symmetric");
+    const bool live = l < lanes;
+    u32x4 r[2];
+    if (live) {
+        r[0] = in[l * 2];
+        r[1] = in[l * 2 + 1];
+    }
+    MinMax m;
+    if constexpr (SYM) {  // max |x| on the raw bit pairs (ct_minmax.h)
+        uint32_t acc = 0;
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
+        }
+        m = absmax_finish<DT>(absmax_group_reduce(acc, lpg));
+    } else {  // min and max on the raw pairs as order-preserving int16 keys
+        MinMaxKey k = mmk_init();
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) k = mmk_acc(mmk_acc(mmk_acc(mmk_acc(k, r[i].x), r[i].y), r[i].z), r[i].w);
+        }
+        m = mmk_finish<DT>(mmk_group_reduce(k, lpg));
+    }
+    if (!live) return;
+    float s, z = 0.0f;
+    if constexpr (KIND == QP_INT) compute_qparams<DT>(m, 8, SYM ? 1 : 0, s, z);
+    else s = compute_qparams_float<DT>(m, KIND, 1.0f);
+    if ((threadIdx.x & (lpg - 1)) == 0) {
+        const int64_t gi = l / lpg;
+        if (scale_out) store1<DT>(scale_out, gi, s);
+        if constexpr (KIND == QP_INT) {
+            if (zp_out) zp_out[gi] = (int8_t)(int)z;
+        }
+        if constexpr (KIND == QP_MXFP8) {
+            // compress_mx_scale: 127 + floor(log2(s)).  s is a power of two — its exponent field is the code, as rtn_mxfp4_lane derives it (2^-127, the
+            // only subnormal one, is code 0) —, or inf (the group of a +- largest-finite bf16 row: 2^128 under MXFP8's offset of 8) or NaN, where upstream's
+            // code is what the host's float -> int32 cast makes of it: read from the table ct_mx_scale_compress reads (the very expression over every
+            // 16-bit pattern), so the byte is the composition's for every input
+            const uint32_t ef = (f_bits(s) >> 23) & 0xffu;
+            const bool finite = ef != 0xffu;
+            if (e8m0) e8m0[gi] = finite ? (uint8_t)ef : mx_table[DT == CT_BF16 ? f_to_bf16_bits(s) : f_to_f16_bits(s)];
+        }
+    }
+    const float rs = 1.0f / s;
+    uint32_t w[4];
+    if constexpr (KIND == QP_INT) {
+        const bool fast = fast_scale_ok<DT>(s) && fast_data_ok<DT, 2>(r);
+        const bool use_zp = !SYM && (__builtin_amdgcn_ballot_w64(z != 0.0f) != 0);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (fast) { if (use_zp) q8_quant_words<DT, true, true>(r[i], s, rs, z, -128, 127, w[2 * i], w[2 * i + 1]); else q8_quant_words<DT, true, false>(r[i], s, rs, z, -128, 127, w[2 * i], w[2 * i + 1]); }
+            else { if (use_zp) q8_quant_words<DT, false, true>(r[i], s, rs, z, -128, 127, w[2 * i], w[2 * i + 1]); else q8_quant_words<DT, false, false>(r[i], s, rs, z, -128, 127, w[2 * i], w[2 * i + 1]); }
+        }
+    } else {
+        const bool fast = fast_scale_ok<DT>(s);  // fp16: reciprocal + Newton step, exact fix-up below 2^-13 (fast_quotient)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            // -0.0 + 0 = +0.0: the zero-point add is kept (f8_quant_lane)
+            if (fast) f8_quant_words<DT, true, true>(r[i], s, rs, 0.0f, w[2 * i], w[2 * i + 1]);
+            else f8_quant_words<DT, false, true>(r[i], s, rs, 0.0f, w[2 * i], w[2 * i + 1]);
+        }
+        flip = 0u;
+    }
+    stream_store16(out + l, u32x4{w[0] ^ flip, w[1] ^ flip, w[2] ^ flip, w[3] ^ flip});
+}
+
+template <int DT, int KIND, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_group8_kernel(const u32x4* __restrict__ in, int64_t lanes, int lpg, u32x4* __restrict__ out, void* __restrict__ scale_out,
+                                                            int8_t* __restrict__ zp_out, uint8_t* __restrict__ e8m0, const uint8_t* __restrict__ mx_table, uint32_t flip) {
+    rtn_group8_lane<DT, KIND, SYM>(in, lanes, lpg, out, scale_out, zp_out, e8m0, mx_table, flip, (int64_t)blockIdx.x * kBlock + threadIdx.x);
+}
+
+// the same lane over a table (ct_rtn_group8_batch_plan): dst = the codes, scale / zp = OUTPUTS, zp_packed = the E8M0 codes (the role the field plays
+// in rtn_mxfp4_batch_kernel).  The plan gives every item whole workgroups from its own `first_block` and admits groups of 32 * 2^k <= 1024 only, so
+// lanes per group = 1 << (upg_shift - 1) is a power of two <= 64 that divides kBlock; the lanes behind an item's last one stay in the reduction as
+// dead lanes.
+template <int DT, int KIND, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_group8_batch_kernel(const ct_w4_item* __restrict__ items, int n, const uint8_t* __restrict__ mx_table, uint32_t flip) {
+    const ct_w4_item& it = batch_find(items, n, blockIdx.x);
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    rtn_group8_lane<DT, KIND, SYM>(static_cast<const u32x4*>(it.src), it.units >> 1, 1 << (it.upg_shift - 1), static_cast<u32x4*>(it.dst), const_cast<void*>(it.scale),
+                                   static_cast<int8_t*>(const_cast<void*>(it.zp)), static_cast<uint8_t*>(it.zp_packed), mx_table, flip, l);
+}
+
 // fake_quantize fast path (forward_helpers.py:180-215): x, scale and the result share one 16-bit dtype.
 // Same flat unit stream: lane = UNROLL units one block apart, 16 B in, 16 B out.
 template <int DT, int UNROLL, bool HAS_ZP>
@@ -2401,6 +2503,103 @@ int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_
 #undef CT_RB8B
     CT_LAUNCH_CHECK("ct_rtn_quant_block8_batch");
 }
+
+constexpr int64_t kGroup8Max = 64 * 16;  // one wave reduces a group: 64 lanes of 16 elements
+
+// fills the derived fields of one group item; returns its workgroup count or -1 with the reason named
+static int64_t group8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    const int64_t g = it.group;
+#define CT_G8_REFUSE(why) do { set_error("ct_rtn_group8_batch_plan: item %d (rows %lld, cols %lld, group %lld): " why, i, (long long)it.rows, \
+                                         (long long)it.cols, (long long)g); return -1; } while (0)
+    if (it.rows <= 0 || it.cols <= 0) CT_G8_REFUSE("empty tensor");
+    if (g < 32 || g % 32 != 0 || log2_exact(g / 32) < 0) CT_G8_REFUSE("unsupported group: the group size must be 32 * 2^k");
+    if (g > kGroup8Max) CT_G8_REFUSE("group too large: one wave reduces at most 1024 elements");
+    if (it.cols % g != 0) CT_G8_REFUSE("ragged columns: cols must be a multiple of the group size");
+    if (!it.src || !it.dst) CT_G8_REFUSE("the weights and the code output are required");
+    if (!it.scale && !it.zp_packed) CT_G8_REFUSE("a scale output is required: scale, or the E8M0 codes in zp_packed");
+    if (!aligned16(it.src) || !aligned16(it.dst)) CT_G8_REFUSE("misaligned pointer: src and dst must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(it.scale) & 1u) CT_G8_REFUSE("misaligned pointer: the scale output must be 2-byte aligned");
+#undef CT_G8_REFUSE
+    it.units = it.rows * (it.cols / 8);
+    it.upg = (int32_t)(g / 8);
+    it.upg_shift = log2_exact(it.upg);
+    it.first_block = first_block;
+    it.main_blocks = cdiv64(it.units / 2, kBlock);
+    it.g_magic = 0;
+    it.g_shift = 0;
+    return it.main_blocks;
+}
+
+int64_t ct_rtn_group8_batch_plan(ct_w4_item* items, int n) {
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_group8_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t b = group8_plan_item(items[i], i, blocks);
+        if (b < 0) return -1;
+        blocks += b;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_group8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+// kind / symmetric / words of the group entries, checked alike for one tensor and a table
+#define CT_G8_KIND_CHECK() do { \
+    CT_REQUIRE(kind == QP_INT || kind == QP_FP8 || kind == QP_MXFP8, "kind must be 0 (INT), 1 (FP8) or 4 (MXFP8), got %d", kind); \
+    CT_REQUIRE(kind == QP_INT || symmetric, "FLOAT 8-bit round-to-nearest is symmetric"); \
+    CT_REQUIRE(kind == QP_INT || !words, "the (code + 128) word form is INT only"); } while (0)
+// KERNEL<DT, KIND, SYM> by the runtime dtype, kind and symmetry
+#define CT_G8_DISPATCH(LAUNCH) do { \
+    if (xdt == CT_BF16) { if (kind == QP_MXFP8) LAUNCH(CT_BF16, QP_MXFP8, true); else if (kind == QP_FP8) LAUNCH(CT_BF16, QP_FP8, true); \
+                          else if (symmetric) LAUNCH(CT_BF16, QP_INT, true); else LAUNCH(CT_BF16, QP_INT, false); } \
+    else { if (kind == QP_MXFP8) LAUNCH(CT_F16, QP_MXFP8, true); else if (kind == QP_FP8) LAUNCH(CT_F16, QP_FP8, true); \
+           else if (symmetric) LAUNCH(CT_F16, QP_INT, true); else LAUNCH(CT_F16, QP_INT, false); } } while (0)
+
+int ct_rtn_quant_group8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int kind, int symmetric, int words, void* out, void* scale_out,
+                        int8_t* zp_out, uint8_t* e8m0_out, const uint8_t* code_table, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "the one-pass group-wise compress takes 16-bit float weights, got dtype %d", xdt);
+    CT_REQUIRE(rows >= 0 && cols >= 0, "negative shape");
+    CT_G8_KIND_CHECK();
+    CT_REQUIRE(kind == QP_INT || zp_out == nullptr, "FLOAT schemes store no zero point");
+    CT_REQUIRE(symmetric || zp_out != nullptr, "asymmetric quantization needs the zero-point output");
+    CT_REQUIRE(kind != QP_MXFP8 || (group == 32 && e8m0_out != nullptr && code_table != nullptr), "MXFP8 needs groups of 32, the E8M0 output and the code table");
+    CT_REQUIRE(kind == QP_MXFP8 || (scale_out != nullptr && e8m0_out == nullptr), "the scale output is required (and the E8M0 output is MXFP8's)");
+    if (rows == 0 || cols == 0) return CT_OK;
+    ct_w4_item it{};
+    it.src = x; it.dst = out; it.scale = scale_out; it.zp = zp_out; it.zp_packed = e8m0_out; it.rows = rows; it.cols = cols; it.group = group;
+    const int64_t blocks = group8_plan_item(it, 0, 0);
+    if (blocks < 0) return CT_ERR_INVALID_ARG;
+    CT_REQUIRE(blocks < ((int64_t)1 << 31), "tensor too large for one launch");
+    const int64_t lanes = it.units / 2;
+    const int lpg = (int)(group / 16);
+    const uint32_t flip = words ? 0u : 0x80808080u;
+#define CT_RG8(DT, KD, SY) hipLaunchKernelGGL((rtn_group8_kernel<DT, KD, SY>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), \
+                                              lanes, lpg, static_cast<u32x4*>(out), scale_out, zp_out, e8m0_out, code_table, flip)
+    CT_G8_DISPATCH(CT_RG8);
+#undef CT_RG8
+    CT_LAUNCH_CHECK("ct_rtn_quant_group8");
+}
+
+int ct_rtn_quant_group8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int kind, int symmetric, int words, const uint8_t* code_table,
+                              ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass group-wise compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_G8_KIND_CHECK();
+    CT_REQUIRE(kind != QP_MXFP8 || code_table != nullptr, "MXFP8 needs the code table");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+    const uint32_t flip = words ? 0u : 0x80808080u;
+#define CT_RG8B(DT, KD, SY) hipLaunchKernelGGL((rtn_group8_batch_kernel<DT, KD, SY>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, code_table, flip)
+    CT_G8_DISPATCH(CT_RG8B);
+#undef CT_RG8B
+    CT_LAUNCH_CHECK("ct_rtn_quant_group8_batch");
+}
+#undef CT_G8_DISPATCH
+#undef CT_G8_KIND_CHECK
 
 int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_t cols, int bits,
                       const void* scale, int sdt, const void* zp, int zdt, int64_t rdiv, int64_t cdiv,

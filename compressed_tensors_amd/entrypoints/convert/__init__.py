@@ -5,6 +5,8 @@ from .convert_checkpoint import convert_checkpoint, convert_file, exec_jobs, val
 from .converters import CompressedTensorsDequantizer, Converter, build_inverse_weight_maps
 from .fp8block import FP8BlockDequantizer, FP8BlockQuantizer
 from .modelopt import ModelOptNvfp4Converter
+from .mxfp8 import MXFP8Quantizer
 
 __all__ = ["convert_checkpoint", "convert_file", "validate_file", "exec_jobs", "Converter", "build_inverse_weight_maps",
-           "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter"]
+           "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter",
+           "MXFP8Quantizer"]

@@ -8,7 +8,7 @@ import torch
 from .. import codec
 from .quant_args import enum_value
 
-__all__ = ["calculate_qparams_from_weight", "block_one_pass", "is_module_quantized"]
+__all__ = ["calculate_qparams_from_weight", "block_one_pass", "group_one_pass", "is_module_quantized"]
 
 
 @torch.no_grad()
@@ -31,6 +31,30 @@ def block_one_pass(weight: torch.Tensor, args) -> bool:
     return (int(args.num_bits) == 8 and weight.dim() == 2 and weight.dtype in (torch.bfloat16, torch.float16)
             and bool(codec.rtn_block8_group(weight.shape, getattr(args, "block_structure", None)))
             and (qtype == "int" or (qtype == "float" and bool(args.symmetric) and getattr(args, "scale_dtype", None) is None)))
+
+
+def group_one_pass(weight: torch.Tensor, args) -> str:
+    """does the one-pass group-wise 8-bit kernel (codec.rtn_quantize_group8; its plan, ct_rtn_group8_batch_plan) take this weight under these
+    args?  Then which of its forms: "mxfp8" (FLOAT, groups of 32, uint8 scales), "fp8" (symmetric FLOAT, scales in the weight's dtype), "int" or
+    "int_asym"; else "".  8 bits, the group strategy (or a channel as one group), no activation ordering, a 2-D bf16 / fp16 weight — 16-byte
+    aligned where it already is on a GPU — and a group the plan admits"""
+    qtype, st = enum_value(getattr(args, "type", "int")), enum_value(args.strategy)
+    if (int(args.num_bits) != 8 or st not in ("group", "channel") or enum_value(getattr(args, "actorder", None)) == "group" or weight.dim() != 2
+            or weight.dtype not in (torch.bfloat16, torch.float16) or not weight.is_contiguous() or (weight.is_cuda and weight.data_ptr() % 16)):
+        return ""
+    group = getattr(args, "group_size", None) if st == "group" else None
+    if st == "group" and not group:
+        return ""
+    if not codec.rtn_group8_group(weight.shape, group):
+        return ""
+    if qtype == "int":
+        return "int" if args.symmetric else "int_asym"
+    if qtype != "float" or not args.symmetric:
+        return ""
+    sdt = getattr(args, "scale_dtype", None)
+    if sdt is None:
+        return "fp8"
+    return "mxfp8" if sdt == torch.uint8 and st == "group" and int(group) == 32 else ""
 
 
 def _block_rows(weight: torch.Tensor, block_structure):

@@ -275,6 +275,26 @@ int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int6
 int64_t ct_rtn_block8_batch_plan(ct_w4_item* items_host, int n);
 int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream);
 
+/* Group-wise 8-bit round-to-nearest in one pass (MXFP8; W8A16; any FLOAT / INT 8-bit group scheme): the min-max observer over groups of `group`
+ * consecutive columns + calculate_qparams (helpers.py:50-137, mxfp_utils.py:37-143) + quantize(strategy = group) (forward_helpers.py:62-115)
+ * (+ compress_mx_scale).  kind is the observer's numbering (ct_minmax_qparams_float): 0 INT (symmetric or not; int8 codes, or with words != 0
+ * the (code + 128) bytes of the 8-bit pack-quantized words), 1 FP8 (symmetric; float8_e4m3fn codes), 4 MXFP8 (symmetric, group == 32; float8_e4m3fn
+ * codes and one E8M0 exponent byte per group in e8m0_out; code_table = the table of ct_mx_scale_compress, 65536 bytes of the scale's dtype,
+ * read only for a scale that is inf or NaN, NULL for the other kinds).  out: one byte per element; scale_out (rows, cols / group) in x's dtype (optional
+ * for MXFP8, required otherwise); zp_out int8 of that shape: required when !symmetric, optional for symmetric INT, NULL for FLOAT.  FLOAT codes
+ * are quantized as with the all-zero zero point of a calibrated scheme present, like ct_rtn_quant_channel8.  Needs bf16 / fp16 weights,
+ * group = 32 * 2^k <= 1024 (one wave reduces a group), cols % group == 0, 16-byte aligned x and out.  Bit-identical to ct_minmax_qparams /
+ * ct_minmax_qparams_float with cdiv = group followed by ct_quantize / ct_quantize_fp8 / ct_quant_pack at 8 bits (and ct_mx_scale_compress).
+ * The table form takes `struct ct_w4_item` rows read this way: src = the weights, dst = the codes, scale = the float-scale OUTPUT (may be NULL in
+ * an MXFP8 table), zp = the int8 zero-point OUTPUT or NULL, zp_packed = the E8M0 OUTPUT of an MXFP8 table, group = the group size;
+ * ct_rtn_group8_batch_plan (host only) admits per item what ct_rtn_quant_group8 admits, fills the derived fields and returns the workgroup count
+ * — ceil(rows * cols / 4096) per item —, or -1 with the reason named in ct_last_error.  Bit-identical to ct_rtn_quant_group8 per item. */
+int ct_rtn_quant_group8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int kind, int symmetric, int words, void* out,
+                        void* scale_out, int8_t* zp_out, uint8_t* e8m0_out, const uint8_t* code_table, ct_stream_t stream);
+int64_t ct_rtn_group8_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_quant_group8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int kind, int symmetric, int words, const uint8_t* code_table,
+                              ct_stream_t stream);
+
 /* Batched 8-bit codecs (Naive / Int / FloatQuantizationCompressor.compress / decompress, compressors/naive_quantized/
  * base.py:48-126, looped per module by model_compressor.py:167-169,196-198): quantize to int8 (num_bits <= 8, clamped to the
  * num_bits range) or float8_e4m3fn, and the inverse, for a whole table of 16-bit tensors in one launch.  Same table type and

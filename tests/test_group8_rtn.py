@@ -1,0 +1,318 @@
+"""Host side of group-wise 8-bit round-to-nearest (MXFP8, W8A16 and the other 8-bit group schemes from a dense model): the C ABI's three symbols,
+the planner of the table form (ct_rtn_group8_batch_plan) and its named refusals, the Python forms of its rule, MXFP8Quantizer's name-only methods,
+and the fixture tests/golden/group8_rtn.safetensors against the pinned oracle and, where the reference sources exist, against the reference
+itself.  No GPU: the planner is a host function."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import _group8_rtn_cases as C
+import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "group8_rtn.safetensors")
+NEW = ("ct_rtn_quant_group8", "ct_rtn_group8_batch_plan", "ct_rtn_quant_group8_batch")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from compressed_tensors_amd import _lib
+
+    return _lib.load()
+
+
+def table(items):
+    """a host table of (rows, cols, group) with made-up, aligned addresses: the planner looks at pointers, it never follows them"""
+    from compressed_tensors_amd import _lib
+
+    tab = (_lib.W4Item * max(len(items), 1))()
+    for i, (rows, cols, group) in enumerate(items):
+        it, base = tab[i], 0x100000 * (i + 1)
+        it.src, it.dst, it.scale, it.zp, it.zp_packed = base, base + 0x80000, base + 0xC0000, base + 0xE0000, base + 0xF0000
+        it.rows, it.cols, it.group = rows, cols, group
+    return tab
+
+
+def plan(lib, tab, n=None):
+    return int(lib.ct_rtn_group8_batch_plan(ctypes.cast(tab, ctypes.c_void_p), len(tab) if n is None else n))
+
+
+FAST_ITEMS = [(shape[0], shape[1], group) for shape, group, _ in C.FAST]
+
+
+# ---- ABI ---------------------------------------------------------------------------------------------------------------------------
+def test_symbols_exported_declared_and_prototyped(lib):
+    from compressed_tensors_amd import _lib, codec
+
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ct_hip.h")).read(), flags=re.S)
+    header = re.sub(r"\s+", " ", header)
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    for name in NEW:
+        assert name in exported and name in _lib._PROTOTYPES and name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
+    assert ("int ct_rtn_quant_group8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int kind, int symmetric, int words, void* out, "
+            "void* scale_out, int8_t* zp_out, uint8_t* e8m0_out, const uint8_t* code_table, ct_stream_t stream);") in header
+    assert "int64_t ct_rtn_group8_batch_plan(ct_w4_item* items_host, int n);" in header
+    assert ("int ct_rtn_quant_group8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int kind, int symmetric, int words, "
+            "const uint8_t* code_table, ct_stream_t stream);") in header
+    assert [len(_lib._PROTOTYPES[name][0]) for name in NEW] == [14, 2, 9]
+    assert lib.ct_abi_version() == 2 and ctypes.sizeof(_lib.W4Item) == 13 * 8  # additive: nothing an existing caller sees moved
+    for name in ("rtn_quantize_group8", "rtn_quantize_group8_many", "rtn_group8_table_item", "rtn_group8_group", "launch_rtn_group8_words"):
+        assert callable(getattr(codec, name)) and name in codec.__all__
+    assert codec._RTN_GROUP8_TABLE == ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # a row of the kind codec._TABLES holds
+    assert len(codec._TABLES) == 8 and codec._RTN_GROUP8_TABLE not in codec._TABLES.values()
+    assert codec.launch_rtn_group8_words(None, 0, None, torch.device("cpu"), 4) is None  # an empty table: nothing is touched
+
+
+# ---- the plan ------------------------------------------------------------------------------------------------------------------------
+def test_plan_counts_workgroups_of_256_lanes_of_16_elements_and_fills_the_derived_fields(lib):
+    tab = table(FAST_ITEMS)
+    want = [-(-(rows * cols) // 4096) for rows, cols, _ in FAST_ITEMS]
+    assert want[:6] == [1, 1, 1, 1, 3, 3] and plan(lib, tab) == sum(want)  # 8224 / 8320 elements: two full workgroups and a partial one
+    first = 0
+    for it, (rows, cols, g), blocks in zip(tab, FAST_ITEMS, want):
+        assert it.first_block == first and it.units == rows * cols // 8 and it.main_blocks == blocks, (rows, cols, g)
+        assert it.upg == g // 8 and 1 << it.upg_shift == it.upg and 1 <= (1 << (it.upg_shift - 1)) <= 64  # lanes per group
+        first += blocks
+    assert plan(lib, table([(8192, 8192, 32)])) == 8192 * 8192 // 4096
+    assert plan(lib, table(FAST_ITEMS), 0) == 0
+    mx = table([(4, 64, 32)])
+    mx[0].scale = None  # an MXFP8 item may leave the float scale out
+    mx[0].zp = None
+    assert plan(lib, mx) == 1
+
+
+@pytest.mark.parametrize("what,names", [("ragged_cols", "ragged columns"), ("group48", "32 * 2^k"), ("group16", "32 * 2^k"), ("group96", "32 * 2^k"),
+                                        ("group0", "32 * 2^k"), ("too_large", "one wave reduces at most 1024"), ("misaligned_src", "misaligned"),
+                                        ("misaligned_dst", "misaligned"), ("misaligned_scale", "misaligned"), ("no_scale", "scale output"),
+                                        ("no_dst", "code output"), ("no_rows", "empty")])
+def test_plan_refuses_and_names_the_reason(lib, what, names):
+    from compressed_tensors_amd import _lib
+
+    items = [(4, 128, 32), (8, 256, 128), (2, 1024, 1024)]
+    change = dict(ragged_cols=(8, 200, 128), group48=(8, 96, 48), group16=(8, 256, 16), group96=(8, 192, 96), group0=(8, 256, 0),
+                  too_large=(8, 2048, 2048), no_rows=(0, 256, 128))
+    if what in change:
+        items[1] = change[what]
+    tab = table(items)
+    if what == "misaligned_src":
+        tab[1].src += 8
+    elif what == "misaligned_dst":
+        tab[1].dst += 4
+    elif what == "misaligned_scale":
+        tab[1].scale += 1
+    elif what == "no_scale":
+        tab[1].scale = None
+        tab[1].zp_packed = None
+    elif what == "no_dst":
+        tab[1].dst = None
+    assert plan(lib, tab) == -1
+    msg = _lib.last_error()
+    assert "ct_rtn_group8_batch_plan" in msg and "item 1" in msg and names in msg, msg
+
+
+def test_plan_refuses_bad_arguments_and_two_to_the_31_workgroups(lib):
+    from compressed_tensors_amd import _lib
+
+    assert plan(lib, table(FAST_ITEMS), -1) == -1 and "bad arguments" in _lib.last_error()
+    assert int(lib.ct_rtn_group8_batch_plan(None, 1)) == -1 and "bad arguments" in _lib.last_error()
+    assert plan(lib, table([(1 << 21, 1 << 21, 32)] * 2)) == -1 and "exceed one launch" in _lib.last_error()
+
+
+def test_launch_entries_refuse_float32_and_bad_kinds_by_name(lib):
+    """the dtype and the kind belong to the launch, not to the plan: refused before anything touches a GPU"""
+    from compressed_tensors_amd import _lib
+
+    a = 0x100000
+    assert lib.ct_rtn_quant_group8(a, _lib.F32, 4, 64, 32, 1, 1, 0, a, a, None, None, None, None) == _lib.CT_ERR_INVALID_ARG and "16-bit float weights" in _lib.last_error()
+    assert lib.ct_rtn_quant_group8_batch(a, 1, 1, _lib.F32, 1, 1, 0, None, None) == _lib.CT_ERR_INVALID_ARG and "16-bit weights only" in _lib.last_error()
+    for kind, sym, words, msg in ((2, 1, 0, "kind must be"), (1, 0, 0, "symmetric"), (4, 1, 1, "INT only")):
+        assert lib.ct_rtn_quant_group8_batch(a, 1, 1, _lib.BF16, kind, sym, words, a, None) == _lib.CT_ERR_INVALID_ARG and msg in _lib.last_error()
+    assert lib.ct_rtn_quant_group8(a, _lib.BF16, 4, 128, 64, 4, 1, 0, a, a, None, a, a, None) == _lib.CT_ERR_INVALID_ARG and "groups of 32" in _lib.last_error()
+    assert lib.ct_rtn_quant_group8(a, _lib.BF16, 4, 128, 32, 4, 1, 0, a, a, None, a, None, None) == _lib.CT_ERR_INVALID_ARG and "code table" in _lib.last_error()
+    assert lib.ct_rtn_quant_group8(a, _lib.BF16, 4, 128, 32, 0, 0, 0, a, a, None, None, None, None) == _lib.CT_ERR_INVALID_ARG and "zero-point output" in _lib.last_error()
+    assert lib.ct_rtn_quant_group8(a, _lib.BF16, 4, 96, 48, 0, 1, 0, a, a, None, None, None, None) == _lib.CT_ERR_INVALID_ARG and "32 * 2^k" in _lib.last_error()
+    assert lib.ct_rtn_quant_group8(a, _lib.BF16, 0, 96, 48, 0, 1, 0, a, a, None, None, None, None) == _lib.CT_OK  # an empty tensor: nothing to do
+
+
+def test_codec_group_rule_is_the_plans(lib):
+    """`codec.rtn_group8_group` and `quantization.utils.group_one_pass` decide in Python what the plan decides in the library"""
+    import compressed_tensors_amd as cta
+    from compressed_tensors_amd import codec
+    from compressed_tensors_amd.quantization.utils import group_one_pass
+
+    for rows in (1, 3):
+        for cols in (32, 96, 200, 256, 1024, 2048, 4096):
+            for g in (16, 32, 48, 64, 96, 128, 256, 512, 1024, 2048, 4096):
+                took = plan(lib, table([(rows, cols, g)])) >= 0
+                assert bool(codec.rtn_group8_group((rows, cols), g)) == took, (rows, cols, g)
+                assert not took or codec.rtn_group8_group((rows, cols), g) == g
+                if cols % g:
+                    continue
+                for dtype, ok in ((C.BF16, True), (C.F16, True), (C.F32, False)):
+                    w = torch.empty((rows, cols), dtype=dtype, device="meta")
+                    forms = {kind: group_one_pass(w, cta.QuantizationArgs(strategy="group", group_size=g, **C.KINDS[kind])) for kind in C.KINDS}
+                    want = {"mxfp8": "mxfp8" if g == 32 else "", "fp8": "fp8", "int8": "int", "int8_zp": "int_asym"} if took and ok else dict.fromkeys(C.KINDS, "")
+                    assert forms == want, (rows, cols, g, dtype)
+    assert codec.rtn_group8_group((0, 64), 32) == 0 and codec.rtn_group8_group((4, 64, 2), 32) == 0
+    assert codec.rtn_group8_group((4, 512), None) == 512 and codec.rtn_group8_group((4, 2048), None) == 0  # a channel as one group
+    w = torch.empty((4, 256), dtype=C.BF16, device="meta")
+    assert group_one_pass(w, cta.QuantizationArgs(num_bits=4, strategy="group", group_size=128)) == ""
+    assert group_one_pass(w, cta.QuantizationArgs(num_bits=8, strategy="channel")) == "int"
+    assert group_one_pass(w, cta.QuantizationArgs(num_bits=8, strategy="tensor")) == ""
+    assert group_one_pass(w, cta.QuantizationArgs(num_bits=8, strategy="group", group_size=128, actorder="group")) == ""
+    assert group_one_pass(w.t(), cta.QuantizationArgs(num_bits=8, strategy="group", group_size=4)) == ""
+
+
+def test_codec_refuses_by_name_before_any_device_is_touched():
+    from compressed_tensors_amd import codec
+
+    x = torch.zeros((2, 96), dtype=C.BF16)
+    with pytest.raises(ValueError, match="divisble by the given group_size"):
+        codec.rtn_quantize_group8(x, group_size=64)
+    with pytest.raises(NotImplementedError, match="32 \\* 2\\^k"):
+        codec.rtn_quantize_group8(x, group_size=48)
+    with pytest.raises(NotImplementedError, match="16-bit float"):
+        codec.rtn_quantize_group8(x.float(), group_size=32)
+    with pytest.raises(NotImplementedError, match="MXFP8 groups"):
+        codec.rtn_quantize_group8(torch.zeros((2, 128), dtype=C.BF16), group_size=64, qtype="float", mx=True)
+    with pytest.raises(NotImplementedError, match="symmetric"):
+        codec.rtn_quantize_group8(x, group_size=32, qtype="float", symmetric=False)
+    with pytest.raises(ValueError, match="2-D"):
+        codec.rtn_quantize_group8(x[0], group_size=32)
+    with pytest.raises(ValueError, match="group sizes for"):
+        codec.rtn_quantize_group8_many([x], group_size=[32, 32])
+
+
+def test_dispatch_constants_and_the_hook_live_where_the_issue_puts_them():
+    import compressed_tensors_amd as cta
+    from compressed_tensors_amd.compressors.mxfp8.base import MXFP8QuantizationCompressor as MX
+    from compressed_tensors_amd.compressors.naive_quantized import base as naive
+
+    assert set(naive.RTN_GROUP8_MEASURED_FASTER) == {"mxfp8", "fp8", "int", "int_asym"} and all(isinstance(v, bool) for v in naive.RTN_GROUP8_MEASURED_FASTER.values())
+    assert "compress_rtn_modules" in vars(MX) and "compress_rtn" in vars(MX) and isinstance(vars(MX)["RTN_TABLE_MEASURED_FASTER"], bool)
+    for name in ("float-quantized", "int-quantized", "naive-quantized"):
+        assert not hasattr(cta.BaseCompressor.get_value_from_registry(name), "compress_rtn_modules")
+
+
+# ---- MXFP8Quantizer: names only --------------------------------------------------------------------------------------------------------
+def test_quantizer_constructor_validate_dependencies_and_config():
+    from compressed_tensors_amd.entrypoints import convert
+    from compressed_tensors_amd.entrypoints.convert import MXFP8Quantizer
+    from compressed_tensors_amd.entrypoints.convert.converters import Converter
+
+    assert "MXFP8Quantizer" in convert.__all__ and issubclass(MXFP8Quantizer, Converter)
+    c = MXFP8Quantizer()
+    assert tuple(c.ignore) == ("lm_head", "re:.*embed_tokens$") and tuple(c.targets) == () and c.device is None
+    assert MXFP8Quantizer(device="cuda:1").device == torch.device("cuda", 1)
+    with pytest.raises(TypeError):
+        MXFP8Quantizer((), (), "cuda:0")  # device is keyword-only
+
+    meta = torch.empty((4, 64), dtype=C.BF16, device="meta")
+    names = {"model.embed_tokens.weight": meta, "model.layers.0.self_attn.q_proj.weight": meta, "model.layers.0.mlp.down_proj.weight": meta,
+             "model.layers.0.input_layernorm.weight": meta, "model.norm.weight": meta, "lm_head.weight": meta}
+    c.validate(names)  # names only: the values are meta tensors
+    c.validate({k: None for k in names})
+    c.validate(dict(names, **{"lm_head.weight_scale": None}))  # ignored modules may carry anything
+    for partner in ("weight_scale", "weight_scale_inv", "weight_packed"):
+        with pytest.raises(ValueError, match="q_proj"):
+            c.validate(dict(names, **{f"model.layers.0.self_attn.q_proj.{partner}": None}))
+    assert c._targeted(names) == ["model.layers.0.self_attn.q_proj", "model.layers.0.mlp.down_proj"]
+    assert MXFP8Quantizer(targets=["re:.*q_proj$"])._targeted(names) == ["model.layers.0.self_attn.q_proj"]
+    for name in names:
+        assert c.get_dependencies(name) == set()
+    untouched = {"model.norm.weight": torch.ones(8), "lm_head.weight": torch.ones((4, 64), dtype=C.BF16)}
+    out = c.process(dict(untouched))  # nothing targeted: no device is asked for
+    assert list(out) == list(untouched) and all(out[k] is untouched[k] for k in untouched)
+
+    cfg = MXFP8Quantizer(ignore=["lm_head"], targets=["re:.*proj$"]).create_config().model_dump()
+    assert cfg["quant_method"] == "compressed-tensors" and cfg["quantization_status"] == "compressed" and cfg["format"] == "mxfp8-quantized"
+    assert cfg["ignore"] == ["lm_head"] and list(cfg["config_groups"]) == ["config_group_0"]
+    group = cfg["config_groups"]["config_group_0"]
+    assert group["format"] == "mxfp8-quantized" and group["targets"] == ["re:.*proj$"] and group["output_activations"] is None
+    w, a = group["weights"], group["input_activations"]
+    for args, dynamic in ((w, False), (a, True)):
+        assert (args["num_bits"], args["type"], args["strategy"], args["symmetric"], args["dynamic"], args["group_size"], args["scale_dtype"]) == \
+            (8, "float", "group", True, dynamic, 32, "torch.uint8")
+    json.dumps(cfg)  # what write_checkpoint_quantization_config stores
+    scheme = c._scheme()
+    assert cta_can_compress(scheme)
+
+
+def cta_can_compress(scheme) -> bool:
+    from compressed_tensors_amd.compressors.mxfp8.base import MXFP8QuantizationCompressor
+
+    return MXFP8QuantizationCompressor.can_compress(torch.nn.Linear, scheme)
+
+
+def test_quantizer_config_is_the_references_preset():
+    """the weights and input activations of create_config are the reference's MXFP8 preset as its model_dump() writes it"""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ref_import
+
+    if not ref_import.available():
+        pytest.skip("the reference sources are not on this machine")
+    ref_import.import_reference()
+    from compressed_tensors.quantization.quant_scheme import MXFP8
+
+    from compressed_tensors_amd.entrypoints.convert import MXFP8Quantizer
+
+    group = MXFP8Quantizer().create_config().model_dump()["config_groups"]["config_group_0"]
+    for key, args in (("weights", MXFP8["weights"]), ("input_activations", MXFP8["input_activations"])):
+        want = {k: (str(v) if isinstance(v, torch.dtype) else getattr(v, "value", v)) for k, v in args.model_dump().items()}
+        assert group[key] == want, key
+
+
+# ---- the fixture ---------------------------------------------------------------------------------------------------------------------
+def test_fixture_inputs_and_oracle_composition_reproduce_the_fixture():
+    """the recipes give the recorded inputs, and the oracle composition the GPU tests use gives the reference's recorded scale, zero point, codes,
+    exponent bytes and 8-bit words for every case and kind, bit for bit; the fixture holds nothing else and fits the size limit"""
+    from safetensors.torch import load_file
+
+    stored = load_file(GOLDEN)
+    assert os.path.getsize(GOLDEN) < (1 << 20)
+    seen = set()
+    for key, r in C.case_list():
+        x = C.make_weight(r)
+        assert x.dtype == C.DTYPES[r["dtype"]] and list(x.shape) == r["shape"] and bool(torch.isfinite(x.float()).all())
+        assert torch.equal(C.bits(stored[f"{key}.x"]), C.bits(x)), key
+        seen.add(f"{key}.x")
+        for kind in C.kinds_of(r):
+            for name, t in C.oracle_outputs(O, x, r["group"], kind).items():
+                want = stored[f"{key}.{kind}.{name}"]
+                assert t.shape == want.shape and t.dtype.itemsize == want.dtype.itemsize, (key, kind, name)
+                assert torch.equal(C.bits(t.contiguous()), C.bits(want)), (key, kind, name)
+                seen.add(f"{key}.{kind}.{name}")
+    assert seen == set(stored)
+
+
+def test_the_cases_hold_what_they_are_there_for():
+    cases = dict(C.case_list())
+    x = C.make_weight(cases["3x96.g32.bf16.planted"])
+    assert not x[0, 32:64].any() and bool((x[1, :32] < 0).any()) and float(x[1, :32].abs().max()) == 4.0
+    assert torch.equal(C.bits(x[1, 36:37]), torch.tensor([-0.0], dtype=C.BF16).view(torch.int16))
+    for dtype in ("bf16", "f16"):
+        x = C.make_weight(cases[f"3x128.g32.{dtype}.extremes"])
+        fi = torch.finfo(x.dtype)
+        assert float(x[0].abs().min()) == fi.max and float(x[1].abs().max()) == fi.tiny and 0 < float(x[2].abs().max()) < fi.tiny
+        assert bool((x < 0).any()) and bool((x > 0).any())
+        x = C.make_weight(cases[f"2x256.g128.{dtype}.maxima"])
+        assert float(x[0, 0]) == 3.0 and float(x[0, 255]) == -5.0 and float(x[1, 255]) == 7.0 and float(x.abs().flatten()[1:255].max()) < 1.0
+    assert {tuple(r["shape"]) for r in cases.values() if r["fast"]} >= {(1, 32), (1, 128), (3, 96), (3, 384), (1, 8224), (1, 8320), (4, 512), (2, C.GROUP_MAX)}
+
+
+def test_generator_check_mode_matches_the_reference():
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ref_import
+
+    if not ref_import.available():
+        pytest.skip("the reference sources are not on this machine")
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_golden_group8_rtn.py"), "--check"], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr

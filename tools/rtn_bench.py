@@ -1,11 +1,12 @@
 """ModelCompressor.compress_model_rtn wall time, table launches (batched=True) against one launch per module (batched=False, the path before the
 tables existed), alternated in one process on the same trees: a Llama-3-8B-shaped tree (32 layers, 224 modules) and a TinyLlama-shaped one (22
-layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4, and FP8_BLOCK (`fp8block`: its table form is
-`naive_quantized.base.rtn_block8_windows`, which `compress_model_rtn` does not dispatch to).  A compress consumes the model, so the dense weights are kept and re-attached
+layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4, FP8_BLOCK (`fp8block`: its table form is
+`naive_quantized.base.rtn_block8_windows`, which `compress_model_rtn` does not dispatch to) and MXFP8 (`mxfp8`: the window hook of
+mxfp8-quantized against its `compress_rtn` per module, as that is dispatched).  A compress consumes the model, so the dense weights are kept and re-attached
 between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
 their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
 
-    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block] [--out FILE]
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block,mxfp8] [--out FILE]
 """
 import argparse
 import json
@@ -39,6 +40,11 @@ def scheme_of(name):
         act = cta.QuantizationArgs(num_bits=8, type="float", strategy="group", symmetric=True, dynamic=True, group_size=128)
         return cta.QuantizationScheme(targets=["Linear"], input_activations=act,
                                       weights=cta.QuantizationArgs(num_bits=8, type="float", strategy="block", symmetric=True, block_structure=[128, 128]))
+    elif name == "mxfp8":  # the MXFP8 preset
+        mx = dict(num_bits=8, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8, zp_dtype=torch.uint8)
+        scheme = cta.QuantizationScheme(targets=["Linear"], weights=cta.QuantizationArgs(dynamic=False, **mx), input_activations=cta.QuantizationArgs(dynamic=True, **mx))
+        scheme.format = "mxfp8-quantized"
+        return scheme
     else:
         raise SystemExit(f"unknown scheme {name}")
     return cta.QuantizationScheme(targets=["Linear"], weights=args)
@@ -49,6 +55,8 @@ def algorithmic_bytes(name, rows, cols):
     n = rows * cols
     if name == "mxfp4":
         return 2 * n + n // 2 + n // 32
+    if name == "mxfp8":
+        return 2 * n + n + n // 32  # one byte per element and one exponent byte per group of 32
     if name == "fp8block":
         return 2 * n + n + 2 * (-(-rows // 128) * (cols // 128))  # one byte per element and one 16-bit scale per block of 128 x 128
     if name == "nvfp4":
@@ -99,6 +107,7 @@ def main():
         raise SystemExit("rtn_bench.py measures on the GPU: no device is visible")
     dev = torch.device("cuda:0")
     cta.NVFP4PackedCompressor.RTN_TABLE_MEASURED_FASTER = True  # batched=True measures the NVFP4 table whatever the dispatch constant holds: this is its input
+    cta.BaseCompressor.get_value_from_registry("mxfp8-quantized").RTN_TABLE_MEASURED_FASTER = True  # likewise MXFP8's
     for tree in a.trees.split(","):
         label, shapes, nlayers = TREES[tree]
         model, pool = build(shapes, nlayers, dev)
