@@ -119,6 +119,7 @@ _PROTOTYPES = {
     "ct_attn_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_rot_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_observe": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
+    "ct_attn_dyn_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_generate_gparam": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_pack_bitmasks": ([_P, _L, _L, _P, _S], _I),
     "ct_unpack_bitmasks": ([_P, _L, _L, _P, _S], _I),
@@ -200,6 +201,12 @@ class AttnTensor(ctypes.Structure):
     """struct ct_attn_tensor of include/ct_hip.h (one descriptor of ct_attn_qdq: host memory, passed on as kernel arguments)"""
     _fields_ = [("x", _P), ("out", _P), ("scale", _P), ("zp", _P), ("B", _L), ("H", _L), ("S", _L), ("D", _L),
                 ("x_stride", _L * 3), ("out_stride", _L * 3), ("per_head", _L)]
+
+
+class AttnDynTensor(ctypes.Structure):
+    """struct ct_attn_dyn_tensor of include/ct_hip.h (one descriptor of ct_attn_dyn_qdq: host memory, passed on as kernel arguments)"""
+    _fields_ = [("x", _P), ("out", _P), ("scale_out", _P), ("zp_out", _P), ("global_scale", _P), ("B", _L), ("H", _L), ("S", _L), ("D", _L),
+                ("x_stride", _L * 3), ("out_stride", _L * 3)]
 
 
 class AttnObserveTensor(ctypes.Structure):

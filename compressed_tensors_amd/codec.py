@@ -10,6 +10,7 @@ import array
 import functools
 import math
 import operator
+from types import SimpleNamespace
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -96,6 +97,12 @@ __all__ = [
     "attn_rotated_fake_quantize_pair",
     "ATTN_ROTATED_MEASURED_FASTER",
     "ATTN_ROTATED_MAX_SIZE",
+    "AttnDynPlan",
+    "plan_attn_dynamic",
+    "attn_dynamic_fake_quantize",
+    "attn_dynamic_fake_quantize_pair",
+    "attn_dynamic_qparams",
+    "ATTN_DYNAMIC_MEASURED_FASTER",
     "item_row",
     "rtn_w4_table_item",
     "rtn_mxfp4_table_item",
@@ -1042,6 +1049,228 @@ def attn_rotated_fake_quantize_pair(k, v, size: int, k_scale, v_scale, k_zero_po
         return out[0], out[1]
     return attn_fake_quantize_pair(hadamard_transform(k.contiguous(), size), v, k_scale, v_scale, k_zero_point, v_zero_point, num_bits=num_bits,
                                    strategy=strategy, qtype=qtype)
+
+
+# --------------------------------------------------------------------------- attention: dynamic group QDQ of the same states
+ATTN_DYNAMIC_MAX_GROUP = 512  # the groups csrc/ct_attn_dyn.hip serves: group / 8 lanes of one wave
+ATTN_DYNAMIC_MAX_UNITS = 256  # D / 8: a row is one pass of a workgroup's lanes
+
+# Which calls `form=None` dispatches to the strided launch (ct_attn_dyn_qdq): "single" — one state read through its strides
+# instead of `.contiguous()` + ct_dynamic_qdq + the copy into the reference's strides — and "pair" — K and V of one cache update in
+# ONE launch instead of two.  A key is True only where tools/attn_dynamic_bench.py measured that form faster than its baseline by
+# more than the spread between its runs, in every row and scheme that speaks for the key (profiles/attn_dynamic_bench.jsonl, DESIGN
+# 5.20).  False means: "single" — the copy form; "pair" — two launches.
+# As measured (two runs, us per call): 13 of the 15 verdicts say "faster" — q (1, 32, 8192, 128) 45.4-51.1 strided against 127.5-130.1
+# copied, k+v (1, 8, 8192, 128) 26.0-27.3 paired against 29.3-31.2 in two launches — but decode k+v MXFP4 strided had medians of 35.3-36.4
+# (minima 22.7-23.1) against 33.6-33.8 copied, and prefill k+v NVFP4 paired medians of 32.9-35.3 (minima 26.7-27.0) against 29.3-29.5: one
+# "not faster" verdict per key, so both keys stay False until a measurement clears them.
+ATTN_DYNAMIC_MEASURED_FASTER = {"single": False, "pair": False}
+
+
+class AttnDynPlan(NamedTuple):
+    """what the attn_dynamic_* functions do with one tensor: `form` "strided" (ct_attn_dyn_qdq reads it through its strides) or
+    "copy" (`reason` says why: ct_dynamic_qdq on `.contiguous()`, then one copy into the reference's strides); the (B, H, S, D)
+    view and b / h / s strides of the strided form; `group` (elements of one scale inside a row; 0 in the copy form); the strides
+    of the reference's result; `dynamic`: quantization.dynamic.plan_dynamic's plan (kind, scale / zero-point shapes and dtypes)"""
+    form: str
+    reason: Optional[str]
+    B: int
+    H: int
+    S: int
+    D: int
+    strides: tuple
+    group: int
+    out_strides: tuple
+    dynamic: object
+
+    @property
+    def scale_shape(self):
+        return self.dynamic.scale_shape
+
+    @property
+    def scale_dtype(self):
+        return self.dynamic.scale_dtype
+
+    @property
+    def zp_dtype(self):
+        return self.dynamic.zp_dtype
+
+
+@functools.lru_cache(maxsize=1024)
+def _attn_dyn_out_strides(shape, strides, dtype, group: int, scale_shape, scale_dtype, has_global: bool, kind: str):
+    """the strides the reference's dynamic fake_quantize leaves: asked of torch itself on meta tensors, once per layout — the group
+    chain (forward_helpers.py:118-177: unflatten, the elementwise ops against a contiguous scale, flatten(-2), .to(x.dtype)) or the
+    plain chain (token / tensor: forward_helpers.py:180-215), with the rounding step of the kind (quant_args.py:460-496)"""
+    x = torch.empty_strided(shape, strides, dtype=dtype, device="meta")
+    scale = torch.empty(scale_shape, dtype=scale_dtype, device="meta")
+    zp = torch.empty(scale_shape, dtype=torch.int8, device="meta")
+    if group:
+        x = x.unflatten(-1, (shape[-1] // group, group))
+        scale, zp = scale.unsqueeze(-1), zp.unsqueeze(-1)
+    if has_global:
+        scale = scale / torch.empty((1,), dtype=torch.float32, device="meta")
+    t = x / scale
+    t += zp.to(x.dtype)
+    bound = torch.empty((), dtype=torch.float32, device="meta")
+    t = torch.clamp(t, bound, bound)
+    if kind == "int":
+        if t.is_contiguous():
+            t = torch.empty(tuple(t.shape), dtype=t.dtype, device="meta")  # torch.round of a contiguous tensor allocates the plain strides
+    elif kind in ("fp8", "mxfp8"):
+        t = t.to(_F8).to(t.dtype)
+    else:
+        t = torch.abs(t) * torch.sign(t)  # cast_to_fp4 (fp4_utils.py:78-98)
+    t = t.to(scale.dtype)
+    t = (t - zp.to(scale.dtype)) * scale
+    if group:
+        t = t.flatten(start_dim=-2).to(dtype)
+    return tuple(t.stride())
+
+
+@functools.lru_cache(maxsize=4096)
+def _plan_attn_dynamic(shape, strides, dtype, offset_bytes, strategy, group_size, kind_key, has_global):
+    from .quantization.dynamic import plan_dynamic
+    args = SimpleNamespace(strategy=strategy, group_size=group_size, **dict(kind_key))
+    dp = plan_dynamic(shape, dtype, args, True if has_global else None)
+    in_place, (B, H, S, D), xs, reason = _attn_view(shape, strides, writes=True)
+    group = 0
+    if dp.tensor_form:
+        reason = "one scale for the whole tensor: its reduction crosses rows"
+    elif strategy == "token":
+        if S != 1 or dp.seg_len != D:
+            reason = f"a token scale over {dp.seg_len} elements crosses the rows of {D}"
+        else:
+            group = D
+    else:
+        group = dp.seg_len
+    if reason is None:
+        units = group // 8
+        if D % 8:
+            reason = f"rows of {D} elements are not whole 8-element units"
+        elif D // 8 > ATTN_DYNAMIC_MAX_UNITS:
+            reason = f"rows of {D} elements exceed one pass of {ATTN_DYNAMIC_MAX_UNITS} units"
+        elif group % 8 or group > ATTN_DYNAMIC_MAX_GROUP or units & (units - 1):
+            reason = f"groups of {group} elements are not 8 * 2^k <= {ATTN_DYNAMIC_MAX_GROUP}"
+        elif not _attn_unit_aligned(offset_bytes, (B, H, S), xs, dtype.itemsize, D):
+            reason = "the storage offset or a stride breaks the alignment of the 8-element units"
+    out_strides = _attn_dyn_out_strides(shape, strides, dtype, 0 if strategy in ("token", "tensor") else dp.seg_len, dp.scale_shape, dp.scale_dtype,
+                                        bool(has_global), dp.kind)
+    out_bhs = None
+    if reason is None:
+        view = _attn_fold(shape, out_strides) if (shape[-1] <= 1 or out_strides[-1] == 1) else None
+        if view is None or view[0] != (B, H, S, D) or not _attn_unit_aligned(0, (B, H, S), view[1], dtype.itemsize, D):
+            reason = "the reference's output strides are not rows the kernel writes"
+        else:
+            out_bhs = view[1]
+    if reason is not None:
+        return AttnDynPlan("copy", reason, B, H, S, D, xs, 0, out_strides, dp), None
+    return AttnDynPlan("strided", None, B, H, S, D, xs, group, out_strides, dp), out_bhs
+
+
+def _attn_dyn_key(args):
+    """the hashable part of the arguments a plan depends on"""
+    return (_strategy_name(args.strategy), getattr(args, "group_size", None),
+            (("num_bits", int(args.num_bits)), ("type", _strategy_name(getattr(args, "type", "int"))), ("symmetric", bool(args.symmetric)),
+             ("scale_dtype", getattr(args, "scale_dtype", None)), ("zp_dtype", getattr(args, "zp_dtype", None))))
+
+
+def plan_attn_dynamic(shape, strides, dtype, args, *, offset_bytes: int = 0, global_scale: bool = False) -> AttnDynPlan:
+    """The host plan of the attn_dynamic_* functions for a state of `shape` / `strides` (elements) / `dtype` whose first element
+    sits `offset_bytes` past a 16-byte boundary, under the dynamic arguments `args` (and a global scale or not): no tensor is
+    touched.  Raises what quantization.dynamic.plan_dynamic raises — the reference's ValueError for a strategy outside token /
+    tensor / group / tensor_group, NotImplementedError for what no kernel computes.  "strided": group / tensor_group with
+    D % 8 == 0, D / 8 <= 256, group = 8 * 2^k <= 512 dividing D, on a view read in place with aligned units on both sides; and
+    token where S == 1 and D is such a group.  Everything else is "copy", with the reason."""
+    shape, strides = tuple(int(d) for d in shape), tuple(int(s) for s in strides)
+    st, gs, kind_key = _attn_dyn_key(args)
+    if len(shape) == 0:
+        shape, strides = (1,), (1,)
+    return _plan_attn_dynamic(shape, strides, dtype, int(offset_bytes) % 16, st, gs, kind_key, bool(global_scale))[0]
+
+
+def _attn_dyn_copy(x, plan: AttnDynPlan, global_scale, want_out: bool, want_qparams: bool):
+    """the copy form: ct_dynamic_qdq on the contiguous copy, then one copy_ into the reference's strides"""
+    dp = plan.dynamic
+    out, scale, zp = dynamic_qdq(x.contiguous(), kind=dp.kind, segs=dp.segs, seg_len=dp.seg_len, num_bits=dp.num_bits, symmetric=dp.symmetric,
+                                 global_scale=global_scale, scale_shape=dp.scale_shape, scale_dtype=dp.scale_dtype if want_qparams else None,
+                                 zp_dtype=dp.zp_dtype if want_qparams else None, want_out=want_out)
+    if want_out and tuple(out.stride()) != plan.out_strides:
+        laid = torch.empty_strided(out.shape, plan.out_strides, dtype=out.dtype, device=out.device)
+        laid.copy_(out)
+        out = laid
+    return out, scale, zp
+
+
+def _attn_dynamic(tensors, args, *, want_out: bool = True, want_qparams: bool = False, form: Optional[str] = None, pair: Optional[bool] = None):
+    """tensors: [(x, global_scale)] of one or two states sharing dtype and arguments -> [(out, scale, zero_point)].  `form`: "strided"
+    — ct_attn_dyn_qdq wherever the plan allows it —, "copy", or None: ATTN_DYNAMIC_MEASURED_FASTER["single"] decides.  Two strided
+    tensors that both take a global scale, or neither, share ONE launch (`pair`; None: ATTN_DYNAMIC_MEASURED_FASTER["pair"])."""
+    st, gs, kind_key = _attn_dyn_key(args)
+    want_strided = ATTN_DYNAMIC_MEASURED_FASTER["single"] if form is None else form == "strided"
+    if form not in (None, "strided", "copy"):
+        raise ValueError(f"form is 'strided', 'copy' or None, got {form!r}")
+    plans = []
+    for x, g in tensors:
+        _check_float(x, "activation")
+        if not x.is_cuda:
+            raise NotImplementedError("the dynamic QDQ kernels take GPU activations")
+        shape, strides = (tuple(x.shape), tuple(x.stride())) if x.ndim else ((1,), (1,))
+        plans.append(_plan_attn_dynamic(shape, strides, x.dtype, x.data_ptr() % 16, st, gs, kind_key, g is not None))
+    results = [None] * len(tensors)
+    strided = [i for i, (plan, _) in enumerate(plans) if want_strided and plan.form == "strided" and tensors[i][0].numel()]
+    for i, (x, g) in enumerate(tensors):
+        if i not in strided:
+            results[i] = _attn_dyn_copy(x, plans[i][0], g, want_out, want_qparams)
+    if not strided:
+        return results
+    together = len(strided) == 2 and (ATTN_DYNAMIC_MEASURED_FASTER["pair"] if pair is None else pair) \
+        and (tensors[0][1] is None) == (tensors[1][1] is None) and tensors[0][0].dtype == tensors[1][0].dtype \
+        and tensors[0][0].device == tensors[1][0].device
+    for batch in ([strided] if together else [[i] for i in strided]):
+        descs = (_lib.AttnDynTensor * len(batch))()
+        keep = []
+        for d, i in zip(descs, batch):
+            (x, g), (plan, out_bhs) = tensors[i], plans[i]
+            dp, dev = plan.dynamic, x.device
+            out = torch.empty_strided(x.shape, plan.out_strides, dtype=x.dtype, device=dev) if want_out else None
+            scale = torch.empty(dp.scale_shape, dtype=dp.scale_dtype, device=dev) if want_qparams else None
+            zp = torch.empty(dp.scale_shape, dtype=dp.zp_dtype, device=dev) if want_qparams else None
+            gd = _gs_arg(g, dev)
+            d.x, d.out, d.scale_out, d.zp_out, d.global_scale = ptr(x), ptr(out), ptr(scale), ptr(zp), ptr(gd)
+            d.B, d.H, d.S, d.D = plan.B, plan.H, plan.S, plan.D
+            d.x_stride[:] = plan.strides
+            d.out_stride[:] = out_bhs
+            keep.append(gd)
+            results[i] = (out, scale, zp)
+        x0, dp0 = tensors[batch[0]][0], plans[batch[0]][0].dynamic
+        call("ct_attn_dyn_qdq", descs, len(batch), int(plans[batch[0]][0].group), DYNAMIC_KINDS[dp0.kind], int(dp0.num_bits), int(bool(dp0.symmetric)),
+             DT[x0.dtype], DT[dp0.zp_dtype] if want_qparams else -1, stream_of(x0))
+    return results
+
+
+def attn_dynamic_fake_quantize(x, args, global_scale=None, *, return_qparams: bool = False, form: Optional[str] = None):
+    """quantization.dynamic.dynamic_fake_quantize(x.contiguous(), args, global_scale) of a query / key / value state (..., H, S, D)
+    — the same bits — laid out with the strides the reference's op chain leaves.  "strided" form: ONE launch reads the view through
+    its strides (csrc/ct_attn_dyn.hip), no copy; "copy" form: the contiguous kernel on `.contiguous()` and one copy_ into those
+    strides.  `form` None: the strided form where the plan allows it and ATTN_DYNAMIC_MEASURED_FASTER["single"] says it was
+    measured faster.  With return_qparams: (out, scale, zero_point) in the reference's shapes and dtypes."""
+    out, scale, zp = _attn_dynamic([(x, global_scale)], args, want_qparams=return_qparams, form=form)[0]
+    return (out, scale, zp) if return_qparams else out
+
+
+def attn_dynamic_qparams(x, args, global_scale=None, *, form: Optional[str] = None):
+    """compute_dynamic_scales_and_zp of such a state: (scale, zero_point), nothing else written"""
+    _, scale, zp = _attn_dynamic([(x, global_scale)], args, want_out=False, want_qparams=True, form=form)[0]
+    return scale, zp
+
+
+def attn_dynamic_fake_quantize_pair(k, v, args, k_global_scale=None, v_global_scale=None, *, return_qparams: bool = False, form: Optional[str] = None,
+                                    pair: Optional[bool] = None):
+    """(attn_dynamic_fake_quantize(k, ...), attn_dynamic_fake_quantize(v, ...)): in ONE launch where both take the strided form
+    and both global scales are present or both absent (`pair` None: where ATTN_DYNAMIC_MEASURED_FASTER["pair"] says so).  K and V
+    keep their own shapes, strides and global scales (MLA: different head dims); they share the dtype."""
+    res = _attn_dynamic([(k, k_global_scale), (v, v_global_scale)], args, want_qparams=return_qparams, form=form, pair=pair)
+    return (res[0], res[1]) if return_qparams else (res[0][0], res[1][0])
 
 
 def quantize_and_pack(x, scale, zero_point, *, num_bits, strategy, group_size=None, block_structure=None,

@@ -1,7 +1,8 @@
 // ct_attn.h — the strided row walker of the attention q / k / v launches: the descriptors a kernel gets, the prologue every
 // kernel opens with, the row decomposition, the per-row quantize step, the alignment rule of the vector form and the
 // host's checks, descriptor fill and dispatch.  Shared by csrc/ct_attn.hip (ct_attn_qdq), csrc/ct_attn_rot.hip (ct_attn_rot_qdq: the
-// same walk behind a head-dim Hadamard rotation) and csrc/ct_attn_observe.hip (ct_attn_observe: the same walk, reading only).
+// same walk behind a head-dim Hadamard rotation), csrc/ct_attn_observe.hip (ct_attn_observe: the same walk, reading only) and
+// csrc/ct_attn_dyn.hip (ct_attn_dyn_qdq: the same walk with ct_dynamic.h's group arithmetic on each row).
 #pragma once
 #include "ct_quant_core.h"
 
@@ -131,9 +132,10 @@ static inline void attn_params(AttnParams& p, int n, int kind, int bits, int xdt
 // host: the geometry of descriptor i — (B, H, S, D) read at `x` through the b / h / s strides `xs` and, where the launch writes,
 // written at `out` through `os` (both NULL: a launch that only reads) — and its share of the grid, added to `blocks`.
 // i >= p.n: an empty copy (no rows).  codes_vec: the input side has a vector form (always, except dequantize from a wide code
-// dtype).  The rows are enumerated by output stride (input_order: by input stride).
+// dtype).  The rows are enumerated by output stride (input_order: by input stride); ord_out receives that order (the logical dimension
+// at each enumeration position) for a caller that places more than x and out by it.
 static inline int attn_fill(AttnParams& p, int i, const void* x, int64_t B, int64_t H, int64_t S, int64_t D, const int64_t* xs, void* out, const int64_t* os,
-                            int per_head, bool codes_vec, bool input_order, int64_t& blocks, const char* entry) {
+                            int per_head, bool codes_vec, bool input_order, int64_t& blocks, const char* entry, int* ord_out = nullptr) {
     static const int64_t none[3] = {0, 0, 0};
     if (os == nullptr) os = none;
     AttnT& t = p.t[i];
@@ -153,6 +155,8 @@ static inline int attn_fill(AttnParams& p, int i, const void* x, int64_t B, int6
             const int tmp = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = tmp;
         }
     for (int k = 0; k < 3; ++k) { t.xs[k] = xs[ord[k]]; t.os[k] = os[ord[k]]; }
+    if (ord_out)
+        for (int k = 0; k < 3; ++k) ord_out[k] = ord[k];
     t.n1 = (uint32_t)(size[ord[1]] > 0 ? size[ord[1]] : 1); t.n2 = (uint32_t)(size[ord[2]] > 0 ? size[ord[2]] : 1); t.D = (uint32_t)D;
     t.rows = (i < p.n && D > 0) ? (uint32_t)rows : 0u;
     t.head_pos = 0u;

@@ -417,7 +417,8 @@ def _patch_forward() -> None:
     `compute_dynamic_scales_and_zp` (quantization/utils/helpers.py:140-195) are rebound, in every already-imported
     `compressed_tensors.*` module that holds them, to wrappers that send contiguous GPU activations of a layout the kernels
     implement to quantization.dynamic (the fused dynamic QDQ of csrc/ct_dynamic.hip, or the static fake_quantize kernels; the q / k / v
-    states of upstream's attention hooks, strided as they come, under the tensor and attn_head strategies: csrc/ct_attn.hip) and
+    states of upstream's attention hooks, strided as they come, under the tensor and attn_head strategies: csrc/ct_attn.hip, and
+    under the dynamic schemes codec.plan_attn_dynamic does not refuse: csrc/ct_attn_dyn.hip or one copy) and
     everything else — CPU / meta tensors, other strategies or formats, group activations under an initialised weight_g_idx,
     a NotImplementedError from the HIP side — to the original.  upstream's `quantized_forward` looks `forward_quantize` up in
     its module's globals at call time, so modules set up by set_forward_quantized are covered."""
@@ -431,11 +432,17 @@ def _patch_forward() -> None:
 
     floats = (torch.float32, torch.float16, torch.bfloat16)
 
-    def plannable(value, args, global_scale) -> bool:
-        if not (value.is_cuda and value.dtype in floats and value.is_contiguous()):
+    def plannable(value, args, global_scale, base_name=None) -> bool:
+        if not (value.is_cuda and value.dtype in floats):
             return False
         if enum_value(args.strategy) not in ("token", "tensor", "group", "tensor_group"):
             return False  # the reference raises its own ValueError
+        if not value.is_contiguous():
+            if base_name not in ("q", "k", "v"):
+                return False
+            # the strided q / k / v states of upstream's attention hooks: csrc/ct_attn_dyn.hip, or one copy — the reference's bits either way
+            codec.plan_attn_dynamic(value.shape, value.stride(), value.dtype, args, offset_bytes=value.data_ptr() % 16, global_scale=global_scale is not None)
+            return True
         amd_dynamic.plan_dynamic(value.shape, value.dtype, args, global_scale)  # NotImplementedError -> original
         return True
 
@@ -448,7 +455,7 @@ def _patch_forward() -> None:
     def take_forward(module, value, base_name, args) -> bool:
         gs = getattr(module, f"{base_name}_global_scale", None)
         if enum_value(getattr(args, "dynamic", False)) in (True, "local"):
-            return plannable(value, args, gs)
+            return plannable(value, args, gs, base_name)
         scale = getattr(module, f"{base_name}_scale", None)
         return scale is not None and scale.is_cuda and scale.dtype in floats and static_ok(value, args, gs, base_name)
 

@@ -16,7 +16,7 @@ from ..quantization.dynamic import forward_quantize, take_prequantized
 from ..quantization.quant_args import enum_value
 
 __all__ = ["QuantizedKVCache", "initialize_hooked_kv_cache", "register_key_hook", "register_value_hook", "register_key_value_hook", "KV_CACHE_ATTR",
-           "PAIR_MEASURED_FASTER", "ROTATED_MEASURED_FASTER", "quantize_key_value"]
+           "PAIR_MEASURED_FASTER", "ROTATED_MEASURED_FASTER", "DYNAMIC_MEASURED_FASTER", "quantize_key_value"]
 
 KV_CACHE_ATTR = "kv_cache"
 
@@ -29,6 +29,10 @@ PAIR_MEASURED_FASTER = True
 # the head-dim rotation of q / k in the QDQ's launch (csrc/ct_attn_rot.hip): {"single": bool, "pair": bool}, the very dict
 # codec.attn_rotated_* dispatch by — held to profiles/attn_rot_bench.jsonl by tests/test_attn_rotated.py
 ROTATED_MEASURED_FASTER = codec.ATTN_ROTATED_MEASURED_FASTER
+
+# dynamic group schemes (MXFP4 / MXFP8 / NVFP4 / FP8 groups) on K and V: {"single": bool, "pair": bool}, the very dict
+# codec.attn_dynamic_* dispatch by — held to profiles/attn_dynamic_bench.jsonl by tests/test_attn_dynamic.py
+DYNAMIC_MEASURED_FASTER = codec.ATTN_DYNAMIC_MEASURED_FASTER
 
 
 def _static_pair_args(module, key_states, value_states, quant_args) -> bool:
@@ -44,10 +48,23 @@ def _static_pair_args(module, key_states, value_states, quant_args) -> bool:
     return getattr(module, "k_scale", None) is not None and getattr(module, "v_scale", None) is not None
 
 
+def _dynamic_pair_args(module, key_states, value_states, quant_args) -> bool:
+    """the dynamic pair launch serves: dynamic group / tensor_group arguments, GPU states of one dtype, and global scales on both
+    states or on neither (the global scale is a compile-time branch of the kernel)"""
+    if enum_value(getattr(quant_args, "dynamic", False)) not in (True, "local"):
+        return False
+    if enum_value(quant_args.strategy) not in ("group", "tensor_group"):
+        return False
+    if not (key_states.is_cuda and value_states.is_cuda and key_states.numel() and value_states.numel() and key_states.dtype == value_states.dtype):
+        return False
+    return (getattr(module, "k_global_scale", None) is None) == (getattr(module, "v_global_scale", None) is None)
+
+
 def quantize_key_value(module, key_states, value_states, quant_args, single=forward_quantize, pair: Optional[bool] = None):
     """forward_quantize(module, key_states, "k", args), forward_quantize(module, value_states, "v", args): as one launch where the
-    pair form is dispatched (`pair`; None: PAIR_MEASURED_FASTER) and the plan takes both, through `single` twice otherwise.  A state
-    that IS the tensor a fused rotation hook handed off (object identity) comes back untouched."""
+    pair form is dispatched (`pair`; None: PAIR_MEASURED_FASTER for static arguments, DYNAMIC_MEASURED_FASTER["pair"] for dynamic
+    group arguments) and the plan takes both, through `single` twice otherwise.  A state that IS the tensor a fused rotation hook
+    handed off (object identity) comes back untouched."""
     done_k, done_v = take_prequantized(module, key_states, "k"), take_prequantized(module, value_states, "v")
     if done_k or done_v:  # transform.fuse_attention_quantization: the rotation's pre-hook quantized these very tensors in its launch
         return (key_states if done_k else single(module, key_states, "k", quant_args),
@@ -59,6 +76,13 @@ def quantize_key_value(module, key_states, value_states, quant_args, single=forw
                 num_bits=int(quant_args.num_bits), strategy=enum_value(quant_args.strategy), qtype=enum_value(getattr(quant_args, "type", "int")))
         except NotImplementedError:
             pass  # a combination the launch does not serve: the two calls decide
+    if (DYNAMIC_MEASURED_FASTER["pair"] if pair is None else pair) and _dynamic_pair_args(module, key_states, value_states, quant_args) \
+            and getattr(module, "weight_g_idx", None) is None:
+        try:
+            return codec.attn_dynamic_fake_quantize_pair(key_states, value_states, quant_args, getattr(module, "k_global_scale", None),
+                                                         getattr(module, "v_global_scale", None), pair=True)
+        except NotImplementedError:
+            pass  # arguments no dynamic kernel computes: the two calls decide
     return single(module, key_states, "k", quant_args), single(module, value_states, "v", quant_args)
 
 

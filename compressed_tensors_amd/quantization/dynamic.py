@@ -119,6 +119,8 @@ def _run(value, plan: DynamicPlan, global_scale, want_out: bool, want_qparams: b
 def compute_dynamic_scales_and_zp(value: torch.Tensor, args, module: Optional[torch.nn.Module] = None,
                                   global_scale: Optional[torch.Tensor] = None):
     """quantization/utils/helpers.py:140-195: (scale, zero_point) of the activation, in the reference's shapes and dtypes"""
+    if value.is_cuda and not value.is_contiguous():
+        return codec.attn_dynamic_qparams(value, args, global_scale)  # read through its strides, or copied first: the plan decides
     plan = plan_dynamic(value.shape, value.dtype, args, global_scale)
     _, scale, zp = _run(value, plan, global_scale, want_out=False, want_qparams=True)
     return scale, zp
@@ -152,6 +154,10 @@ def forward_quantize(module: torch.nn.Module, value: torch.Tensor, base_name: st
         if _g_idx_initialised(g_idx) and enum_value(args.strategy) in ("group", "tensor_group"):
             # the reference permutes the activation by the WEIGHT's g_idx in fake_quantize but observes it unpermuted
             raise NotImplementedError("group activations under an initialised weight_g_idx are left to the reference")
+        if base_name in _ATTENTION_STATES:
+            # query / key / value states are transposed views: read through their strides (csrc/ct_attn_dyn.hip) where the plan
+            # allows it, copied once where it does not — laid out as the reference lays its result out either way
+            return codec.attn_dynamic_fake_quantize(value, args, global_scale)
         return dynamic_fake_quantize(value, args, global_scale)
     scale = getattr(module, f"{base_name}_scale")
     zero_point = getattr(module, f"{base_name}_zero_point", None)

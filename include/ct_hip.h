@@ -469,6 +469,33 @@ typedef struct ct_attn_observe_tensor {
 int ct_attn_observe(const ct_attn_observe_tensor* tensors, int n, int kind, int bits, int symmetric, int xdt, int sdt, int zdt, int keep,
                     ct_stream_t stream);
 
+/* Dynamic group QDQ of the states ct_attn_qdq serves: compute_dynamic_scales_and_zp + fake_quantize (helpers.py:140-195,
+ * lifecycle/forward.py:292-329) of one or two 4-D tensors (B, H, S, D) read and written IN PLACE through their strides (as
+ * ct_attn_tensor), over groups of `group` elements that lie inside a row of D — the group / tensor_group strategies, and a
+ * per-row scale as group == D.  `out` NULL: scales only.  `scale_out` (x's dtype; float32 under a global scale) / `zp_out` (zdt)
+ * receive B * H * S * (D / group) entries, contiguous in logical (b, h, s, group) order whatever the strides of x; NULL: the
+ * values stay in registers.  `global_scale`: device float32[1], NVFP4 only, or NULL. */
+typedef struct ct_attn_dyn_tensor {
+    const void* x;
+    void* out;                     /* NULL: qparams only */
+    void* scale_out;               /* NULL: not written */
+    void* zp_out;                  /* NULL: not written */
+    const float* global_scale;     /* NULL: none */
+    int64_t B, H, S, D;
+    int64_t x_stride[3];           /* b, h, s: elements */
+    int64_t out_stride[3];
+} ct_attn_dyn_tensor;              /* 15 64-bit words */
+
+/* kind / bits / symmetric / zdt as ct_dynamic_qdq (kind 0 INT .. 4 MXFP8); xdt: a float dtype, of x and out alike.  n = 2: both
+ * tensors (K and V) share dtypes, kind, bits and group — shapes, strides, outputs and global-scale pointers are their own, but both
+ * take a global scale or neither does (CT_ERR_INVALID_ARG otherwise) — and are served by ONE launch.  The results are the bits
+ * ct_dynamic_qdq gives on the contiguous copy.  The descriptors travel as kernel arguments; the entry allocates nothing, never
+ * synchronises and keeps no device state.  CT_ERR_UNSUPPORTED (nothing launched) unless D % 8 == 0, D / 8 <= 256 (a row is one
+ * pass of one 8-element unit per lane), group = 8 * 2^k <= 512, D % group == 0, and bases and strides keep the units aligned on
+ * both sides (ct_attn_qdq's vector form).  B * H * S < 2^31 per tensor. */
+int ct_attn_dyn_qdq(const ct_attn_dyn_tensor* tensors, int n, int group, int kind, int bits, int symmetric, int xdt, int zdt,
+                    ct_stream_t stream);
+
 /* generate_gparam of a whole weight (quantization/utils/helpers.py:308-337, the NVFP4 global scale): amax = max |x| (NaN if any
  * element is), clamped from below to finfo(x dtype).tiny; global_scale = rnd_X(rnd_X(1 / amax) * 2688) as float32 — `float / tensor`
  * is evaluated by torch as reciprocal times float, two roundings to x's dtype; a non-finite result becomes 1.  Two launches: the
