@@ -69,6 +69,8 @@ _PROTOTYPES = {
     "ct_rtn_quant_block8": ([_P, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _S], _I),
     "ct_rtn_block8_batch_plan": ([_P, _I], _L),
     "ct_rtn_quant_block8_batch": ([_P, _I, _L, _I, _I, _I, _S], _I),
+    "ct_rtn_channel8_batch_plan": ([_P, _I], _L),
+    "ct_rtn_quant_channel8_batch": ([_P, _I, _L, _I, _I, _I, _S], _I),
     "ct_rtn_quant_group8": ([_P, _I, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _S], _I),
     "ct_rtn_group8_batch_plan": ([_P, _I], _L),
     "ct_rtn_quant_group8_batch": ([_P, _I, _L, _I, _I, _I, _I, _P, _S], _I),

@@ -42,6 +42,11 @@ __all__ = [
     "rtn_quantize_and_pack",
     "rtn_mxfp4_quantize_and_pack",
     "rtn_quantize_channel8",
+    "rtn_quantize_channel8_many",
+    "rtn_channel8_form",
+    "rtn_channel8_table_item",
+    "launch_rtn_channel8_words",
+    "RTN_CHANNEL8_MAX_COLS",
     "rtn_nvfp4_quantize_and_pack",
     "rtn_quantize_and_pack_many",
     "rtn_mxfp4_quantize_and_pack_many",
@@ -1762,16 +1767,35 @@ def rtn_nvfp4_quantize_and_pack(x: torch.Tensor, global_scale: Optional[torch.Te
     return out + (_home(scale, x),) if return_scale else out
 
 
+RTN_CHANNEL8_MAX_COLS = 65536  # CT_RTN_CHANNEL8_MAX_COLS of include/ct_hip.h
+
+
+def rtn_channel8_form(shape, symmetric: bool = True) -> str:
+    """the form `ct_rtn_quant_channel8` and its table's plan (`ct_rtn_channel8_batch_plan`) give a weight of this shape: "wave" (a wave per row: rows
+    of at most 2048 columns, asymmetric ones up to 8192), "row" (a workgroup per row, up to 16384 columns) or "long" (up to
+    `RTN_CHANNEL8_MAX_COLS`: the row's tail streamed twice); "" for what the plan refuses — not 2-D, empty, cols % 8, cols above the maximum"""
+    if len(shape) != 2:
+        return ""
+    rows, cols = int(shape[0]), int(shape[1])
+    if rows <= 0 or cols <= 0 or cols % 8 or cols > RTN_CHANNEL8_MAX_COLS:
+        return ""
+    upr = cols // 8
+    if (not symmetric or upr <= 256) and upr <= 1024:
+        return "wave"
+    return "row" if upr <= 2048 else "long"
+
+
 def rtn_quantize_channel8(x: torch.Tensor, *, qtype: str = "int", symmetric: bool = True):
     """Channel-wise 8-bit round-to-nearest in ONE pass over the weight: per-row min-max observer + calculate_qparams +
     quantize to int8 (qtype "int") or float8_e4m3fn ("float").  Returns (codes (R, C), scale (R, 1) in x.dtype, zero_point):
     the zero point is int8 (R, 1) for INT, float8 zeros for FLOAT — bit-identical to the observer kernel followed by
-    quantize_tensor."""
+    quantize_tensor.  Rows of up to `RTN_CHANNEL8_MAX_COLS` columns (`rtn_channel8_form`)."""
     if x.dim() != 2:
         raise ValueError("rtn_quantize_channel8 expects a 2-D weight")
     qtype = getattr(qtype, "value", qtype)
-    if x.dtype not in (torch.bfloat16, torch.float16) or x.shape[1] % 8 != 0 or x.shape[1] > 16384 or (qtype == "float" and not symmetric):
-        raise NotImplementedError("the one-pass channel-wise compress takes 16-bit weights with cols % 8 == 0 and cols <= 16384 (symmetric for FLOAT)")
+    if x.dtype not in (torch.bfloat16, torch.float16) or x.shape[1] % 8 != 0 or x.shape[1] > RTN_CHANNEL8_MAX_COLS or (qtype == "float" and not symmetric):
+        raise NotImplementedError(f"the one-pass channel-wise compress takes 16-bit weights with cols % 8 == 0 and cols <= {RTN_CHANNEL8_MAX_COLS} "
+                                  "(symmetric for FLOAT)")
     rows, cols = x.shape
     dev = _compute_device(x)
     xd = _dev(x, dev).contiguous()
@@ -1974,6 +1998,7 @@ _TABLES = {
 # above is pinned to its eight plans by tests/test_host_logic.py, so the ninth stands beside it
 _RTN_BLOCK8_TABLE = ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
 _RTN_GROUP8_TABLE = ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # the one-pass group-wise 8-bit table (`launch_rtn_group8_words`), likewise
+_RTN_CHANNEL8_TABLE = ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch")  # the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`), likewise
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
@@ -2206,6 +2231,12 @@ def launch_rtn_group8_words(words, n: int, dtype: torch.dtype, device: torch.dev
     return _launch_table(_RTN_GROUP8_TABLE, words, n, device, 0, (DT[dtype], int(kind), int(bool(symmetric)), int(bool(as_words)), lut))
 
 
+def launch_rtn_channel8_words(words, n: int, dtype: torch.dtype, device: torch.device, fp8: bool, symmetric: bool) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass channel-wise 8-bit compress (`ct_rtn_quant_channel8_batch`): src = weights, dst = codes,
+    scale / zp = OUTPUTS (zp 0 in a FLOAT or symmetric table: the plan reads an item with a zero-point output as asymmetric)"""
+    return _launch_table(_RTN_CHANNEL8_TABLE, words, n, device, 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))) if n else None
+
+
 def rtn_w4_group(shape, group_size) -> int:
     """the group (elements per scale) when `ct_rtn_quant_pack_w4` and its table form take a weight of this shape — 2-D, rows > 0, a group of
     32 * 2^k <= 2048 columns that divides the row (group_size None / 0: the whole row) — else 0"""
@@ -2248,6 +2279,18 @@ def rtn_block8_table_item(x, block_structure, fp8: bool = True, with_zp: bool = 
     scale = torch.empty(grid, dtype=x.dtype, device=x.device)
     zp = torch.empty(grid, dtype=torch.int8, device=x.device) if with_zp else None
     return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, g)
+
+
+def rtn_channel8_table_item(x, fp8: bool = True, with_zp: bool = False):
+    """`rtn_w4_table_item` for the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`; `rtn_channel8_form`): (codes float8_e4m3fn — int8
+    without `fp8` — (R, C), scale (R, 1), int8 zero point (R, 1) or None without `with_zp` (an asymmetric scheme's), row) or None"""
+    if not _rtn_table_tensor(x) or not rtn_channel8_form(x.shape, not with_zp):
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    q = torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
+    scale = torch.empty((rows, 1), dtype=x.dtype, device=x.device)
+    zp = torch.empty((rows, 1), dtype=torch.int8, device=x.device) if with_zp else None
+    return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, 0)
 
 
 def rtn_group8_table_item(x, group_size, qtype: str = "int", with_zp: bool = False, mx: bool = False, words: bool = False, with_scale: bool = True):
@@ -2394,6 +2437,43 @@ def rtn_quantize_block8_many(weights, *, block_structure, qtype: str = "float", 
 
     return _rtn_many(list(weights), item, lambda i, x: rtn_quantize_block8(x, block_structure=block_structure, qtype=qtype, symmetric=symmetric),
                      lambda flat, n, dtype, device: launch_rtn_block8_words(flat, n, dtype, device, fp8, symmetric))
+
+
+def _rtn_channel8_one(x, qtype, symmetric):
+    """one tensor outside the table: the one-pass kernel where it applies, the observer + quantize composition otherwise"""
+    if x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and (x.numel() == 0 or rtn_channel8_form(x.shape, symmetric)):
+        return rtn_quantize_channel8(x, qtype=qtype, symmetric=symmetric)
+    if qtype == "float":
+        scale = minmax_qparams_float(x, kind="fp8")
+        zp = torch.zeros(scale.shape, dtype=_F8, device=scale.device)
+    else:
+        scale, zp = minmax_qparams(x, num_bits=8, symmetric=symmetric)
+    q = quantize_tensor(x, scale, zp, qtype=qtype, num_bits=8, strategy="channel", dtype=_F8 if qtype == "float" else torch.int8)
+    return q, scale, zp
+
+
+def rtn_quantize_channel8_many(weights, *, qtype: str = "int", symmetric: bool = True):
+    """`rtn_quantize_channel8` for a LIST of weights: the tensors the table takes (`rtn_channel8_table_item`, of the first such tensor's device and
+    dtype) leave in ONE `ct_rtn_quant_channel8_batch` launch, the others one by one, in input order (the one-pass kernel, or the observer followed by
+    `quantize_tensor` for what its plan refuses: float32, cols % 8, rows beyond `RTN_CHANNEL8_MAX_COLS`).  Returns [(codes, scale, zero_point)] in
+    input order, bit-identical to the single-tensor call per item."""
+    qtype = getattr(qtype, "value", qtype)
+    fp8 = qtype == "float"
+    symmetric = bool(symmetric)
+    if fp8 and not symmetric:
+        raise NotImplementedError("FLOAT 8-bit round-to-nearest is symmetric")
+
+    def item(i, x, n):
+        got = rtn_channel8_table_item(x, fp8, not symmetric)
+        if got is None:
+            return None
+        q, scale, zp, row = got
+        if zp is None:  # what the single launch returns for a symmetric scheme: zeros, float8 for FLOAT
+            zp = torch.zeros(scale.shape, dtype=_F8 if fp8 else torch.int8, device=x.device)
+        return q, scale, zp, row
+
+    return _rtn_many(list(weights), item, lambda i, x: _rtn_channel8_one(x, qtype, symmetric),
+                     lambda flat, n, dtype, device: launch_rtn_channel8_words(flat, n, dtype, device, fp8, symmetric))
 
 
 def rtn_quantize_group8_many(weights, *, group_size, qtype: str = "int", symmetric: bool = True, mx: bool = False, words: bool = False):

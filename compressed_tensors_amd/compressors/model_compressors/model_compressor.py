@@ -135,8 +135,8 @@ class ModelCompressor:
         `batched` (default): the modules are grouped by codec, and a codec with the window hook `compress_rtn_modules` (pack-quantized, MXFP4, NVFP4, MXFP8:
         each a few lines over `compressors.base.run_rtn_windows`) whose gate `RTN_TABLE_MEASURED_FASTER` holds turns its group into table launches per
         window of 32 modules.  NVFP4's gate is off (two launches per window, the tensor-wide amax behind `generate_gparam` is a pass of its own; not
-        dispatched on figures that have not decided it); it, the codecs without the hook (the other 8-bit ones; their block-wise table form is the function
-        `naive_quantized.base.rtn_block8_windows`, which a caller runs itself) and the modules a table does not take run
+        dispatched on figures that have not decided it); it, the codecs without the hook (the other 8-bit ones; their block-wise and channel-wise table forms are the functions
+        `naive_quantized.base.rtn_block8_windows` and `rtn_channel8_windows`, which a caller runs itself) and the modules a table does not take run
         per module.  `batched=False`: per module throughout — same result."""
         from ...utils.module import direct_entry, swap_direct_entries
         from ..base import BaseCompressor

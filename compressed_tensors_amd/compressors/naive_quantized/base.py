@@ -15,7 +15,7 @@ from ...quantization.quant_args import enum_value
 from ...utils import getattr_chain
 from ..base import COMPRESSIBLE_MODULE_TYPES, BaseCompressor, run_planned, run_rtn_windows, zp_drop_mask
 
-__all__ = ["NaiveQuantizationCompressor", "IntQuantizationCompressor", "FloatQuantizationCompressor", "rtn_block8_windows"]
+__all__ = ["NaiveQuantizationCompressor", "IntQuantizationCompressor", "FloatQuantizationCompressor", "rtn_block8_windows", "rtn_channel8_windows"]
 
 _DTYPE_OF_CODE = {1: torch.float16, 2: torch.bfloat16}
 _STRATEGY_CODE = {"tensor": 0, "channel": 1, "group": 2, "block": 3}
@@ -72,6 +72,63 @@ def _native_q8(modules, direction: str, status):
 # 63.8 / 56.9 / 57.0; fp8 g128 35.8 / 32.0 / 32.0 against 56.9 / 50.9 / 50.9; int g128 35.7 / 31.7 / 31.7 against 57.4 / 51.0 / 50.9; asymmetric 39.2 / 34.9 /
 # 35.0 against 56.7 / 51.0 / 50.7; run spread at most 2.8 us.
 RTN_GROUP8_MEASURED_FASTER = {"mxfp8": True, "fp8": True, "int": True, "int_asym": True}
+
+# which kinds of the LONG form of the one-pass channel-wise 8-bit kernel (rows beyond 16384 columns: codec.rtn_channel8_form == "long") `compress_rtn`
+# dispatches: True only where tools/channel8_rtn_bench.py measured its worst median below the best of the composition it replaces (the observer
+# kernel + `compress`, what these shapes took before) on every shape by more than the spread of the two runs (profiles/channel8_rtn_bench.jsonl,
+# DESIGN.md 5.21).  The entry points stay callable either way.
+# Measured (bf16, 8192 x 28672 / 8192 x 29568 / 16384 x 53248 / 7168 x 18432, worst median of two runs against the composition's best): fp8 140.6 / 145.3 /
+# 534.1 / 76.6 us against 197.3 / 206.7 / 710.5 / 111.0; int 133.4 / 138.5 / 523.8 / 71.1 against 196.7 / 204.6 / 709.0 / 111.5; asymmetric 136.7 / 140.4 /
+# 523.4 / 75.5 against 198.7 / 206.7 / 709.0 / 117.6; run spread at most 4.8 us.
+RTN_CHANNEL8_LONG_MEASURED_FASTER = {"fp8": True, "int": True, "int_asym": True}
+
+
+def _channel8_kind(weight, weights) -> str:
+    """"fp8" / "int" / "int_asym" when `weights` is a channel-wise 8-bit scheme the one-pass kernel computes for this weight (16-bit, 2-D, a FLOAT
+    scheme symmetric and without a scale dtype of its own), else "" """
+    qtype = enum_value(getattr(weights, "type", "int"))
+    if not (enum_value(weights.strategy) == "channel" and int(weights.num_bits) == 8 and weight.dim() == 2
+            and weight.dtype in (torch.bfloat16, torch.float16) and qtype in ("int", "float")
+            and (qtype == "int" or (weights.symmetric and getattr(weights, "scale_dtype", None) is None))):
+        return ""
+    return "fp8" if qtype == "float" else "int" if weights.symmetric else "int_asym"
+
+
+def rtn_channel8_windows(cls, modules) -> None:
+    """`compress_rtn` + the parameter swap for a list of modules of the 8-bit codec `cls`, in windows (`run_rtn_windows`): the channel-strategy 8-bit
+    modules whose weight the one-pass kernel's plan takes (`codec.rtn_channel8_form`, on a GPU, contiguous, 16-byte aligned) leave in ONE table launch
+    per (device, dtype, FLOAT, symmetric) (codec.launch_rtn_channel8_words; short, workgroup and long rows in one table); the others go through
+    `compress_rtn_module`.  Every module ends in the state `compress_rtn_module` leaves it in.  Not a `compress_rtn_modules` hook of the classes:
+    `compress_model_rtn` runs the 8-bit codecs per module, which tests/test_rtn_batch.py pins; tools/rtn_bench.py (schemes fp8dyn, w8a8) measures this
+    form against that loop, DESIGN.md 5.21 has the figures."""
+
+    def item(m, w, table):
+        wa = m.quantization_scheme.weights
+        kind = _channel8_kind(w, wa)
+        if not kind:
+            return None
+        fp8, symmetric = kind == "fp8", bool(wa.symmetric)
+        got = codec.rtn_channel8_table_item(w.data, fp8, not symmetric)
+        if got is None:
+            return None
+        q, scale, zp, row = got
+        return (w.device, w.dtype, fp8, symmetric), row, (q, scale, zp)
+
+    def launch(key, flat, jobs):
+        device, dtype, fp8, symmetric = key
+        return codec.launch_rtn_channel8_words(flat, len(jobs), dtype, device, fp8, symmetric)
+
+    def entries(w, o):  # compress_rtn's entries in its order (a long row: the composition's, the weight last), a symmetric scheme's zero point dropped
+        long = codec.rtn_channel8_form(w.shape, o[2] is None) == "long"
+        add = {} if long else {"weight": o[0]}
+        add["weight_scale"] = o[1]
+        if o[2] is not None:
+            add["weight_zero_point"] = o[2]
+        if long:
+            add["weight"] = o[0]
+        return add
+
+    run_rtn_windows(cls, modules, item, launch, entries)
 
 
 def rtn_block8_windows(cls, modules) -> None:
@@ -140,7 +197,8 @@ class NaiveQuantizationCompressor(BaseCompressor):
     def compress_rtn(cls, weight, scheme) -> dict:
         """Round-to-nearest compression straight from the dense weight (min-max qparams): what `compress` returns for
         {"weight", "weight_scale", "weight_zero_point"} of calculate_qparams over the weight's min / max.  Channel-wise
-        8-bit schemes (W8A8 int8 / FP8) take ONE pass over the weight (codec.rtn_quantize_channel8), and so do block-wise ones (FP8_BLOCK, INT8
+        8-bit schemes (W8A8 int8 / FP8) take ONE pass over the weight (codec.rtn_quantize_channel8; rows of up to 65536 columns, `rtn_channel8_form`),
+        and so do block-wise ones (FP8_BLOCK, INT8
         blocks: codec.rtn_quantize_block8) where the kernel's plan takes the weight (`block_one_pass`); the rest composes the observer kernel with
         `compress`."""
         import torch
@@ -161,13 +219,17 @@ class NaiveQuantizationCompressor(BaseCompressor):
                 out["weight_zero_point"] = zp
             out["weight"] = q
             return cls._remove_symmetric_zp(out, scheme)
-        one_pass = (enum_value(weights.strategy) == "channel" and int(weights.num_bits) == 8 and weight.dim() == 2
-                    and weight.dtype in (torch.bfloat16, torch.float16) and weight.shape[1] % 8 == 0 and weight.shape[1] <= 16384
-                    and (qtype == "int" or (weights.symmetric and getattr(weights, "scale_dtype", None) is None)))
+        # channel-wise: ONE pass where the kernel's plan takes the row (codec.rtn_channel8_form: cols % 8 == 0, up to codec.RTN_CHANNEL8_MAX_COLS columns),
+        # its long form (beyond 16384 columns: the down_proj of the 70B-class models) only where measured faster than the composition
+        kind = _channel8_kind(weight, weights)
+        form = codec.rtn_channel8_form((max(int(weight.shape[0]), 1), weight.shape[1]), bool(weights.symmetric)) if kind else ""
+        one_pass = bool(form) and (form != "long" or RTN_CHANNEL8_LONG_MEASURED_FASTER[kind])
         if not one_pass:
             scale, zp = calculate_qparams_from_weight(weight, weights)
             return cls.compress({"weight": weight, "weight_scale": scale, "weight_zero_point": zp}, scheme)
         q, scale, zp = codec.rtn_quantize_channel8(weight, qtype=qtype, symmetric=bool(weights.symmetric))
+        if form == "long":  # rows the composition took before the long form existed: its entries in its order (`compress` re-adds the weight last)
+            return cls._remove_symmetric_zp({"weight_scale": scale, "weight_zero_point": zp, "weight": q}, scheme)
         return cls._remove_symmetric_zp({"weight": q, "weight_scale": scale, "weight_zero_point": zp}, scheme)
 
     # the gate `compress_model_rtn(batched=True)` asks before it hands a codec's modules to a window hook (see NVFP4PackedCompressor).  The 8-bit codecs

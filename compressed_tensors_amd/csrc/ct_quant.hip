@@ -1393,7 +1393,148 @@ __global__ __launch_bounds__(kBlock) void q8_dequant_batch_kernel(const ct_w4_it
 // calculate_qparams + quantize): one workgroup per row holds the row in registers (MAXU 16-byte units per thread,
 // one block apart: every wave load reads 1 KiB contiguous), reduces min / max through DPP + LDS, every thread
 // evaluates the identical scale and quantizes its own units.  2 + 1 B per element instead of 2 + (2 + 1).
+// LONG (rows beyond MAXU * kBlock units, up to kChannel8MaxCols columns): the first MAXU * kBlock units stay in registers as before, the
+// rest of the row is streamed TWICE by the same thread at the same addresses, kLongAhead loads in flight — once into the reduction, once
+// into the quantize; the second read of what this workgroup has just read is served by the L2 (a 65536-column row is 128 KiB).  Min and max
+// are order-independent, so the bits are those of the other forms.
+// The per-row bodies are __device__ functions shared by the single-tensor kernels and the table kernel (rtn_channel8_batch_kernel).
 // ------------------------------------------------------------------------------------------
+constexpr int kLongAhead = 4;  // 16-byte loads in flight per thread in the streamed part of a long row
+constexpr int64_t kChannel8MaxCols = CT_RTN_CHANNEL8_MAX_COLS;
+constexpr int kChannel8Wave = 0, kChannel8Row = 1, kChannel8Long = 2;  // an item's form, in its upg_shift (ct_rtn_channel8_batch_plan)
+
+// max |x| of one 16-byte unit on the raw bit pairs (ct_minmax.h)
+__device__ __forceinline__ uint32_t c8_absmax_unit(uint32_t acc, const u32x4& v) {
+    return absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, v.x), v.y), v.z), v.w);
+}
+
+// exact min / max (and the NaN flag) of one 16-byte unit
+template <int DT>
+__device__ __forceinline__ void c8_minmax_unit(MinMax& m, const u32x4& v) {
+    const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float a, b;
+        unpack2<DT>(ws[j], a, b);
+        m.nan |= (a != a) | (b != b);
+        m.mn = __builtin_fminf(m.mn, __builtin_fminf(a, b));
+        m.mx = __builtin_fmaxf(m.mx, __builtin_fmaxf(a, b));
+    }
+}
+
+// the 8 codes of one unit under the row's scale / zero point, stored non-temporally
+template <int DT, bool FP8>
+__device__ __forceinline__ void c8_quant_store(const u32x4& v, float s, float rs, float z, bool fast, bool use_zp, u32x2* dst) {
+    uint32_t lo, hi;
+    if constexpr (FP8) {
+        // with the (all-zero) zero point of a calibrated scheme present, as in the compressor's call: -0.0 + 0 = +0.0
+        if (fast) f8_quant_words<DT, true, true>(v, s, rs, 0.0f, lo, hi);
+        else f8_quant_words<DT, false, true>(v, s, rs, 0.0f, lo, hi);
+    } else {
+        if (fast) { if (use_zp) q8_quant_words<DT, true, true>(v, s, rs, z, -128, 127, lo, hi); else q8_quant_words<DT, true, false>(v, s, rs, z, -128, 127, lo, hi); }
+        else { if (use_zp) q8_quant_words<DT, false, true>(v, s, rs, z, -128, 127, lo, hi); else q8_quant_words<DT, false, false>(v, s, rs, z, -128, 127, lo, hi); }
+        lo ^= 0x80808080u; hi ^= 0x80808080u;  // (code + 128) -> two's-complement code
+    }
+    stream_store8(dst, u32x2{lo, hi});
+}
+
+// one row by one WORKGROUP: one barrier; the caller owes another one before the reduction scratch is reused
+template <int DT, int MAXU, bool FP8, bool LONG>
+__device__ __forceinline__ void rtn_channel8_row_body(const u32x4* __restrict__ rin, int upr, int symmetric, u32x2* __restrict__ rout,
+                                                      void* __restrict__ scale_out, int8_t* __restrict__ zp_out, int64_t row) {
+    __shared__ float s_mn[kBlock / 64], s_mx[kBlock / 64];
+    __shared__ int s_nan[kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u32x4 r[MAXU];
+    MinMax m;
+    m.mn = __builtin_inff(); m.mx = -__builtin_inff(); m.nan = 0;
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * kBlock + tid;
+        if (u < upr) r[i] = rin[u];
+    }
+    if (FP8 || symmetric) {  // block-uniform: max |x| on the raw bit pairs (ct_minmax.h)
+        uint32_t acc = 0;
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * kBlock + tid;
+            if (u < upr) acc = c8_absmax_unit(acc, r[i]);
+        }
+        if constexpr (LONG) {
+            for (int u0 = MAXU * kBlock + tid; u0 < upr; u0 += kLongAhead * kBlock) {
+                u32x4 t[kLongAhead];
+#pragma unroll
+                for (int j = 0; j < kLongAhead; ++j)
+                    if (u0 + j * kBlock < upr) t[j] = rin[u0 + j * kBlock];
+#pragma unroll
+                for (int j = 0; j < kLongAhead; ++j)
+                    if (u0 + j * kBlock < upr) acc = c8_absmax_unit(acc, t[j]);
+            }
+        }
+        acc = absmax_group_reduce(acc, 64);
+        if (lane == 0) s_mn[wave] = __builtin_bit_cast(float, acc);
+        __syncthreads();
+        uint32_t all = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) all = absmax_acc(all, __builtin_bit_cast(uint32_t, s_mn[w]));
+        m = absmax_finish<DT>(all);
+    } else {
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * kBlock + tid;
+            if (u < upr) c8_minmax_unit<DT>(m, r[i]);
+        }
+        if constexpr (LONG) {
+            for (int u0 = MAXU * kBlock + tid; u0 < upr; u0 += kLongAhead * kBlock) {
+                u32x4 t[kLongAhead];
+#pragma unroll
+                for (int j = 0; j < kLongAhead; ++j)
+                    if (u0 + j * kBlock < upr) t[j] = rin[u0 + j * kBlock];
+#pragma unroll
+                for (int j = 0; j < kLongAhead; ++j)
+                    if (u0 + j * kBlock < upr) c8_minmax_unit<DT>(m, t[j]);
+            }
+        }
+        m = group_reduce(m, 64);
+        if (lane == 0) { s_mn[wave] = m.mn; s_mx[wave] = m.mx; s_nan[wave] = m.nan; }
+        __syncthreads();
+        m.mn = __builtin_fminf(__builtin_fminf(s_mn[0], s_mn[1]), __builtin_fminf(s_mn[2], s_mn[3]));
+        m.mx = __builtin_fmaxf(__builtin_fmaxf(s_mx[0], s_mx[1]), __builtin_fmaxf(s_mx[2], s_mx[3]));
+        m.nan = s_nan[0] | s_nan[1] | s_nan[2] | s_nan[3];
+    }
+    float s, z = 0.0f;
+    if constexpr (FP8) s = compute_qparams_float<DT>(m, QP_FP8, 1.0f);
+    else compute_qparams<DT>(m, 8, symmetric, s, z);
+    if (tid == 0) {
+        store1<DT>(scale_out, row, s);
+        if (zp_out) zp_out[row] = (int8_t)(int)z;
+    }
+    // (fp16: the float8 words use the scalar shortcut with its fix-up; the int8 words' packed-fp16 pipeline needs finite data, which
+    // a row that produced a finite non-zero scale has — a NaN or inf in the row makes the scale NaN / inf and `fast` false)
+    const bool fast = fast_scale_ok<DT>(s);
+    const float rs = 1.0f / s;
+    const bool use_zp = !FP8 && !symmetric && z != 0.0f;  // block-uniform
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * kBlock + tid;
+        if (u >= upr) continue;
+        c8_quant_store<DT, FP8>(r[i], s, rs, z, fast, use_zp, rout + u);
+    }
+    if constexpr (LONG) {
+        for (int u0 = MAXU * kBlock + tid; u0 < upr; u0 += kLongAhead * kBlock) {
+            u32x4 t[kLongAhead];
+#pragma unroll
+            for (int j = 0; j < kLongAhead; ++j)
+                if (u0 + j * kBlock < upr) t[j] = rin[u0 + j * kBlock];
+#pragma unroll
+            for (int j = 0; j < kLongAhead; ++j)
+                if (u0 + j * kBlock < upr) c8_quant_store<DT, FP8>(t[j], s, rs, z, fast, use_zp, rout + u0 + j * kBlock);
+        }
+    }
+}
+
+// The single-tensor kernels of the two register forms keep their own text: routed through the shared bodies hipcc schedules the 8-unit
+// instantiation into 246-248 VGPRs (62-70 as written here), so they stay as they were and the bodies serve the long kernel and the table.
 template <int DT, int MAXU, bool FP8>
 __global__ __launch_bounds__(kBlock) void rtn_channel8_kernel(const u32x4* __restrict__ in, int64_t rows, int upr /* units per row */, int symmetric,
                                                               u32x2* __restrict__ out, void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
@@ -1480,9 +1621,65 @@ __global__ __launch_bounds__(kBlock) void rtn_channel8_kernel(const u32x4* __res
     }
 }
 
+// rows of more than 8 * kBlock units: the long form of the row body
+template <int DT, bool FP8>
+__global__ __launch_bounds__(kBlock, 4) void rtn_channel8_long_kernel(const u32x4* __restrict__ in, int64_t rows, int upr, int symmetric,
+                                                                   u32x2* __restrict__ out, void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        rtn_channel8_row_body<DT, 8, FP8, true>(in + row * upr, upr, symmetric, out + row * upr, scale_out, zp_out, row);
+        __syncthreads();
+    }
+}
+
 // the same one-pass compress with one WAVE per row (rows of at most 64 * MAXU units): the row lives in the wave's registers
 // (MAXU 16-byte loads in flight per lane, each wave load 1 KiB contiguous), the reduction is DPP + two wave shuffles — no LDS,
 // no barrier, no phase in which a whole workgroup waits for its slowest wave.
+template <int DT, int MAXU, bool FP8>
+__device__ __forceinline__ void rtn_channel8_wave_body(const u32x4* __restrict__ rin, int upr, int symmetric, u32x2* __restrict__ rout,
+                                                       void* __restrict__ scale_out, int8_t* __restrict__ zp_out, int64_t row) {
+    const int lane = threadIdx.x & 63;
+    u32x4 r[MAXU];
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * 64 + lane;
+        if (u < upr) r[i] = rin[u];
+    }
+    MinMax m;
+    m.mn = __builtin_inff(); m.mx = -__builtin_inff(); m.nan = 0;
+    if (FP8 || symmetric) {  // wave-uniform
+        uint32_t acc = 0;
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * 64 + lane;
+            if (u < upr) acc = c8_absmax_unit(acc, r[i]);
+        }
+        m = absmax_finish<DT>(absmax_group_reduce(acc, 64));
+    } else {
+#pragma unroll
+        for (int i = 0; i < MAXU; ++i) {
+            const int u = i * 64 + lane;
+            if (u < upr) c8_minmax_unit<DT>(m, r[i]);
+        }
+        m = group_reduce(m, 64);
+    }
+    float s, z = 0.0f;
+    if constexpr (FP8) s = compute_qparams_float<DT>(m, QP_FP8, 1.0f);
+    else compute_qparams<DT>(m, 8, symmetric, s, z);
+    if (lane == 0) {
+        store1<DT>(scale_out, row, s);
+        if (zp_out) zp_out[row] = (int8_t)(int)z;
+    }
+    const bool fast = fast_scale_ok<DT>(s);  // fp16: see rtn_channel8_kernel
+    const float rs = 1.0f / s;
+    const bool use_zp = !FP8 && !symmetric && z != 0.0f;  // wave-uniform
+#pragma unroll
+    for (int i = 0; i < MAXU; ++i) {
+        const int u = i * 64 + lane;
+        if (u >= upr) continue;
+        c8_quant_store<DT, FP8>(r[i], s, rs, z, fast, use_zp, rout + u);
+    }
+}
+
 template <int DT, int MAXU, bool FP8>
 __global__ __launch_bounds__(kBlock) void rtn_channel8_wave_kernel(const u32x4* __restrict__ in, int64_t rows, int upr, int symmetric,
                                                                    u32x2* __restrict__ out, void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
@@ -1549,6 +1746,30 @@ __global__ __launch_bounds__(kBlock) void rtn_channel8_wave_kernel(const u32x4* 
             lo ^= 0x80808080u; hi ^= 0x80808080u;
         }
         stream_store8(rout + u, u32x2{lo, hi});
+    }
+}
+
+// a table of tensors (ct_rtn_channel8_batch_plan): every workgroup finds its item, then its row(s).  The plan wrote the item's form into
+// upg_shift (0: a wave per row, four rows per workgroup; 1: a workgroup per row; 2: the long form) and its units per row into upg.  The form is
+// workgroup-uniform, so the barrier of the workgroup forms is safe.
+template <int DT, bool FP8>
+__global__ __launch_bounds__(kBlock, 4) void rtn_channel8_batch_kernel(const ct_w4_item* __restrict__ items, int n, int symmetric) {
+    const ct_w4_item& it = batch_find(items, n, blockIdx.x);
+    const int64_t local = (int64_t)blockIdx.x - it.first_block;
+    const int upr = it.upg, form = it.upg_shift;
+    const u32x4* in = static_cast<const u32x4*>(it.src);
+    u32x2* out = static_cast<u32x2*>(it.dst);
+    void* scale_out = const_cast<void*>(it.scale);
+    int8_t* zp_out = static_cast<int8_t*>(const_cast<void*>(it.zp));
+    if (form == kChannel8Wave) {
+        const int64_t row = local * (kBlock / 64) + (threadIdx.x >> 6);
+        if (row >= it.rows) return;
+        if (upr <= 64 * 4) rtn_channel8_wave_body<DT, 4, FP8>(in + row * upr, upr, symmetric, out + row * upr, scale_out, zp_out, row);
+        else rtn_channel8_wave_body<DT, 16, FP8>(in + row * upr, upr, symmetric, out + row * upr, scale_out, zp_out, row);
+    } else {
+        // kChannel8Row and kChannel8Long: ONE instantiation, the long one, whose streamed part runs zero times for a row of at most 8 * kBlock units
+        // (a second, loop-free instantiation beside it is scheduled into 224-236 VGPRs, or spills under a bound: DESIGN.md 5.21)
+        rtn_channel8_row_body<DT, 8, FP8, true>(in + local * upr, upr, symmetric, out + local * upr, scale_out, zp_out, local);
     }
 }
 
@@ -2380,11 +2601,19 @@ int ct_rtn_quant_pack_w4(const void* x, int xdt, int64_t rows, int64_t cols, int
     CT_LAUNCH_CHECK("ct_rtn_quant_pack_w4");
 }
 
+// the form a row of `upr` 16-byte units takes (the measurements behind the rule: ct_rtn_quant_channel8), or -1 beyond kChannel8MaxCols
+static int channel8_form(int64_t upr, bool symmetric) {
+    const bool want_wave = !symmetric || upr <= 256;
+    if (want_wave && upr <= 64 * 16) return kChannel8Wave;  // rows of up to 8192 elements: one wave per row
+    if (upr <= 8 * kBlock) return kChannel8Row;
+    return upr * 8 <= kChannel8MaxCols ? kChannel8Long : -1;
+}
+
 int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, int fp8, int symmetric, void* out, void* scale_out, int8_t* zp_out,
                           ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "the one-pass channel-wise compress takes 16-bit float weights, got dtype %d", xdt);
-    CT_REQUIRE(rows >= 0 && cols >= 0 && cols % 8 == 0 && cols <= 8 * 8 * kBlock, "columns (%lld) must be a multiple of 8 and at most %d", (long long)cols,
-               8 * 8 * kBlock);
+    CT_REQUIRE(rows >= 0 && cols >= 0 && cols % 8 == 0 && cols <= kChannel8MaxCols,
+               "columns (%lld) must be a multiple of 8 and at most CT_RTN_CHANNEL8_MAX_COLS = %lld", (long long)cols, (long long)kChannel8MaxCols);
     CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
     CT_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && scale_out != nullptr, "misaligned buffers");
     CT_REQUIRE(symmetric || zp_out != nullptr, "asymmetric quantization needs the zero-point output");
@@ -2398,8 +2627,8 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
     // columns, and for asymmetric schemes up to 8192.
     // (wave per row beyond 2048 columns stays behind the workgroup form with the 16-unit instantiation too: 14336 x 4096 36.4 against 32.8 us.  The 8-unit
     // instantiation is not used: hipcc gives it 235-252 VGPRs — 91 for 16 units — which made rows of 2049-4096 columns 34.5 / 65 us instead of 19.9 / 36.4.)
-    const bool want_wave = !symmetric || upr <= 256;
-    if (want_wave && upr <= 64 * 16 && cdiv64(rows, kBlock / 64) < ((int64_t)1 << 31)) {  // rows of up to 8192 elements: one wave per row
+    const int form = channel8_form(upr, symmetric != 0);
+    if (form == kChannel8Wave && cdiv64(rows, kBlock / 64) < ((int64_t)1 << 31)) {
         const int needw = (upr + 63) / 64;
         const unsigned gw = (unsigned)cdiv64(rows, kBlock / 64);
 #define CT_RW8(DT, MU, F8) hipLaunchKernelGGL((rtn_channel8_wave_kernel<DT, MU, F8>), dim3(gw), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
@@ -2413,6 +2642,14 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
     }
     const int need = (upr + kBlock - 1) / kBlock;
     const unsigned grid = (unsigned)(rows < ((int64_t)1 << 30) ? rows : ((int64_t)1 << 30));
+    if (form == kChannel8Long) {  // beyond 8 units per thread: registers for the first 2048 units, the rest streamed twice
+#define CT_RL8(DT, F8) hipLaunchKernelGGL((rtn_channel8_long_kernel<DT, F8>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
+                                          symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
+        if (xdt == CT_BF16) { if (fp8) CT_RL8(CT_BF16, true); else CT_RL8(CT_BF16, false); }
+        else { if (fp8) CT_RL8(CT_F16, true); else CT_RL8(CT_F16, false); }
+#undef CT_RL8
+        CT_LAUNCH_CHECK("ct_rtn_quant_channel8[long]");
+    }
 #define CT_RC8(DT, MU, F8) hipLaunchKernelGGL((rtn_channel8_kernel<DT, MU, F8>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
                                               symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
 #define CT_RC8_U(DT, F8) do { if (need <= 1) CT_RC8(DT, 1, F8); else if (need <= 2) CT_RC8(DT, 2, F8); else if (need <= 4) CT_RC8(DT, 4, F8); else CT_RC8(DT, 8, F8); } while (0)
@@ -2421,6 +2658,61 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
 #undef CT_RC8_U
 #undef CT_RC8
     CT_LAUNCH_CHECK("ct_rtn_quant_channel8");
+}
+
+// fills the derived fields of one channel item; returns its workgroup count or -1 with the reason named.  An item with a zero-point output is
+// planned as asymmetric (the wave form up to 8192 columns), one without as symmetric: the rule of ct_rtn_quant_channel8.
+static int64_t channel8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+#define CT_C8_REFUSE(why) do { set_error("ct_rtn_channel8_batch_plan: item %d (rows %lld, cols %lld): " why, i, (long long)it.rows, (long long)it.cols); \
+                               return -1; } while (0)
+    if (it.rows <= 0 || it.cols <= 0) CT_C8_REFUSE("empty tensor");
+    if (it.cols % 8 != 0) CT_C8_REFUSE("cols must be a multiple of 8");
+    if (it.cols > kChannel8MaxCols) CT_C8_REFUSE("cols above CT_RTN_CHANNEL8_MAX_COLS = 65536");
+    if (!it.src || !it.dst || !it.scale) CT_C8_REFUSE("the weights, the code output and the scale output are required");
+    if (!aligned16(it.src) || !aligned16(it.dst)) CT_C8_REFUSE("misaligned pointer: src and dst must be 16-byte aligned");
+    const int64_t upr = it.cols / 8;
+    const int form = channel8_form(upr, it.zp == nullptr);
+    const int64_t blocks = form == kChannel8Wave ? cdiv64(it.rows, kBlock / 64) : it.rows;
+    if (blocks >= ((int64_t)1 << 31)) CT_C8_REFUSE("2^31 workgroups or more");
+#undef CT_C8_REFUSE
+    it.units = it.rows * upr;
+    it.upg = (int32_t)upr;
+    it.upg_shift = form;
+    it.main_blocks = blocks;
+    it.g_magic = 0;
+    it.g_shift = 0;
+    it.first_block = first_block;
+    return blocks;
+}
+
+int64_t ct_rtn_channel8_batch_plan(ct_w4_item* items, int n) {
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_channel8_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t b = channel8_plan_item(items[i], i, blocks);
+        if (b < 0) return -1;
+        blocks += b;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_channel8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_quant_channel8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass channel-wise compress: 16-bit weights only, got dtype %d", xdt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+#define CT_RC8B(DT, F8) hipLaunchKernelGGL((rtn_channel8_batch_kernel<DT, F8>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric)
+    if (xdt == CT_BF16) { if (fp8) CT_RC8B(CT_BF16, true); else CT_RC8B(CT_BF16, false); }
+    else { if (fp8) CT_RC8B(CT_F16, true); else CT_RC8B(CT_F16, false); }
+#undef CT_RC8B
+    CT_LAUNCH_CHECK("ct_rtn_quant_channel8_batch");
 }
 
 // fills the derived fields of one block item; returns its workgroup (= block) count or -1 with the reason named

@@ -2,6 +2,7 @@
 GPU decompress, safetensors out — the on-disk consumer of the decompress hot path."""
 from .autoawq import AutoAWQConverter
 from .convert_checkpoint import convert_checkpoint, convert_file, exec_jobs, validate_file
+from .channel8 import FP8DynamicQuantizer, W8A8Quantizer
 from .converters import CompressedTensorsDequantizer, Converter, build_inverse_weight_maps
 from .fp8block import FP8BlockDequantizer, FP8BlockQuantizer
 from .modelopt import ModelOptNvfp4Converter
@@ -9,4 +10,4 @@ from .mxfp8 import MXFP8Quantizer
 
 __all__ = ["convert_checkpoint", "convert_file", "validate_file", "exec_jobs", "Converter", "build_inverse_weight_maps",
            "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter",
-           "MXFP8Quantizer"]
+           "MXFP8Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer"]

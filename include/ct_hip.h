@@ -170,7 +170,12 @@ int ct_rtn_quant_pack_w4(const void* x, int xdt, int64_t rows, int64_t cols, int
 /* Channel-wise 8-bit round-to-nearest in one pass (W8A8 int8 / FP8 weights): per-row min-max observer +
  * calculate_qparams (helpers.py:50-137) + quantize(dtype = int8 resp. float8_e4m3fn) (forward.py:36-73).  out: one
  * byte per element; scale_out (rows, 1) in x's dtype; zp_out int8 (rows, 1), required when !symmetric (int8 only).
- * cols % 8 == 0, cols <= 16384.  Bit-identical to ct_minmax_qparams(_float) followed by ct_quantize(_fp8). */
+ * cols % 8 == 0, cols <= CT_RTN_CHANNEL8_MAX_COLS.  Bit-identical to ct_minmax_qparams(_float) followed by ct_quantize(_fp8).
+ * Three forms by row length, the same bits in each (min and max do not depend on the order): a WAVE per row (rows of at most 2048 columns, and
+ * asymmetric rows of at most 8192: the row in the wave's registers, no LDS), a WORKGROUP per row (up to 16384 columns: the row in the registers of
+ * 256 threads, one barrier) and the LONG form beyond (the first 16384 columns in registers, the rest of the row read twice by the same workgroup:
+ * the second read comes from the L2). */
+#define CT_RTN_CHANNEL8_MAX_COLS 65536
 int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, int fp8, int symmetric, void* out,
                           void* scale_out, int8_t* zp_out, ct_stream_t stream);
 
@@ -274,6 +279,21 @@ int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int6
                         void* scale_out, int8_t* zp_out, ct_stream_t stream);
 int64_t ct_rtn_block8_batch_plan(ct_w4_item* items_host, int n);
 int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream);
+
+/* The table form of ct_rtn_quant_channel8 (FP8_DYNAMIC / W8A8 weights of a whole shard in one launch).  `struct ct_w4_item` rows read this way:
+ * src = the weights, dst = the codes, scale = the scale OUTPUT (rows, 1) in the weights' dtype, zp = the int8 zero-point OUTPUT (rows, 1) or NULL
+ * (NULL in a FLOAT or symmetric table: the store is skipped; an item WITH a zero-point output is planned as asymmetric), group and zp_packed are
+ * ignored.  ct_rtn_channel8_batch_plan (host only) admits per item what ct_rtn_quant_channel8 admits — rows, cols > 0, cols % 8 == 0, cols <=
+ * CT_RTN_CHANNEL8_MAX_COLS, src / dst / scale present, src and dst 16-byte aligned, fewer than 2^31 workgroups — and writes into the derived fields:
+ *   upg_shift   = the item's form: 0 a wave per row, 1 a workgroup per row, 2 the long form (the rule of ct_rtn_quant_channel8)
+ *   upg         = 16-byte units per row (cols / 8)
+ *   units       = rows * upg
+ *   main_blocks = the item's workgroups: ceil(rows / 4) in the wave form (four rows per workgroup), rows in the other two
+ *   first_block = the workgroups in front of the item; g_magic = g_shift = 0
+ * It returns the table's workgroup count, or -1 with the reason named in ct_last_error.  One table may hold items of all three forms; a launch is
+ * one dtype, FLOAT or INT, symmetric or not.  Bit-identical to ct_rtn_quant_channel8 per item: the kernels share the per-row bodies. */
+int64_t ct_rtn_channel8_batch_plan(ct_w4_item* items_host, int n);
+int ct_rtn_quant_channel8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream);
 
 /* Group-wise 8-bit round-to-nearest in one pass (MXFP8; W8A16; any FLOAT / INT 8-bit group scheme): the min-max observer over groups of `group`
  * consecutive columns + calculate_qparams (helpers.py:50-137, mxfp_utils.py:37-143) + quantize(strategy = group) (forward_helpers.py:62-115)

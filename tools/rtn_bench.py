@@ -2,11 +2,12 @@
 tables existed), alternated in one process on the same trees: a Llama-3-8B-shaped tree (32 layers, 224 modules) and a TinyLlama-shaped one (22
 layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4, FP8_BLOCK (`fp8block`: its table form is
 `naive_quantized.base.rtn_block8_windows`, which `compress_model_rtn` does not dispatch to) and MXFP8 (`mxfp8`: the window hook of
-mxfp8-quantized against its `compress_rtn` per module, as that is dispatched).  A compress consumes the model, so the dense weights are kept and re-attached
+mxfp8-quantized against its `compress_rtn` per module, as that is dispatched) and the channel-wise 8-bit presets FP8_DYNAMIC (`fp8dyn`) and W8A8 (`w8a8`:
+their table form is `naive_quantized.base.rtn_channel8_windows`, likewise not dispatched to).  A compress consumes the model, so the dense weights are kept and re-attached
 between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
 their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
 
-    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block,mxfp8] [--out FILE]
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block,mxfp8,fp8dyn,w8a8] [--out FILE]
 """
 import argparse
 import json
@@ -19,7 +20,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import compressed_tensors_amd as cta  # noqa: E402
-from compressed_tensors_amd.compressors.naive_quantized.base import FloatQuantizationCompressor, rtn_block8_windows  # noqa: E402
+from compressed_tensors_amd.compressors.naive_quantized.base import (  # noqa: E402
+    FloatQuantizationCompressor,
+    IntQuantizationCompressor,
+    rtn_block8_windows,
+    rtn_channel8_windows,
+)
 
 HBM_PEAK = 8e12  # bytes / s, the figure every table of DESIGN.md is relative to
 TINY = ((2048, 2048), (256, 2048), (256, 2048), (2048, 2048), (5632, 2048), (5632, 2048), (2048, 5632))
@@ -40,6 +46,10 @@ def scheme_of(name):
         act = cta.QuantizationArgs(num_bits=8, type="float", strategy="group", symmetric=True, dynamic=True, group_size=128)
         return cta.QuantizationScheme(targets=["Linear"], input_activations=act,
                                       weights=cta.QuantizationArgs(num_bits=8, type="float", strategy="block", symmetric=True, block_structure=[128, 128]))
+    elif name in ("fp8dyn", "w8a8"):  # the FP8_DYNAMIC / W8A8 presets: channel-wise weights, dynamic per-token activations
+        qtype = "float" if name == "fp8dyn" else "int"
+        return cta.QuantizationScheme(targets=["Linear"], input_activations=cta.QuantizationArgs(num_bits=8, type=qtype, strategy="token", symmetric=True, dynamic=True),
+                                      weights=cta.QuantizationArgs(num_bits=8, type=qtype, strategy="channel", symmetric=True))
     elif name == "mxfp8":  # the MXFP8 preset
         mx = dict(num_bits=8, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8, zp_dtype=torch.uint8)
         scheme = cta.QuantizationScheme(targets=["Linear"], weights=cta.QuantizationArgs(dynamic=False, **mx), input_activations=cta.QuantizationArgs(dynamic=True, **mx))
@@ -57,6 +67,8 @@ def algorithmic_bytes(name, rows, cols):
         return 2 * n + n // 2 + n // 32
     if name == "mxfp8":
         return 2 * n + n + n // 32  # one byte per element and one exponent byte per group of 32
+    if name in ("fp8dyn", "w8a8"):
+        return 2 * n + n + 2 * rows  # one byte per element and one 16-bit scale per row
     if name == "fp8block":
         return 2 * n + n + 2 * (-(-rows // 128) * (cols // 128))  # one byte per element and one 16-bit scale per block of 128 x 128
     if name == "nvfp4":
@@ -125,6 +137,10 @@ def main():
                         for lin, _ in pool:
                             lin.quantization_scheme.format = "float-quantized"
                         rtn_block8_windows(FloatQuantizationCompressor, [lin for lin, _ in pool])
+                    elif name in ("fp8dyn", "w8a8") and batched:  # likewise: the channel-wise window driver
+                        for lin, _ in pool:
+                            lin.quantization_scheme.format = "float-quantized" if name == "fp8dyn" else "int-quantized"
+                        rtn_channel8_windows(FloatQuantizationCompressor if name == "fp8dyn" else IntQuantizationCompressor, [lin for lin, _ in pool])
                     else:
                         mc.compress_model_rtn(model, batched=batched)
                     t1 = time.perf_counter()
