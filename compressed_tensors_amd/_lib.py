@@ -117,6 +117,8 @@ _PROTOTYPES = {
     "ct_hadamard_k_rows": ([_P, _P, _I, _L, _L, _L, _P, _P, _I, _I, _P, _S], _I),
     "ct_hadamard_k_cols": ([_P, _P, _I, _L, _L, _L, _L, _P, _P, _I, _I, _P, _S], _I),
     "ct_hadamard_k_workspace_bytes": ([_I, _L, _L, _L, _I, _I], _L),
+    "ct_hadamard_perm_rows": ([_P, _P, _I, _L, _L, _I, _P, _P, _P, _I, _S], _I),
+    "ct_hadamard_perm_cols": ([_P, _P, _P, _I, _L, _L, _L, _I, _P, _P, _P, _I, _S], _I),
     "ct_hadamard_dynamic_qdq": ([_P, _I, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_attn_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_rot_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),

@@ -39,6 +39,12 @@ __all__ = [
     "HadamardKPlan",
     "plan_hadamard_k",
     "hadamard_k_transform",
+    "HadamardPermTables",
+    "hadamard_perm_tables",
+    "HadamardPermPlan",
+    "plan_hadamard_perm",
+    "HADAMARD_PERM_MEASURED_FASTER",
+    "HADAMARD_PERM_MAX_SIZE",
     "rtn_quantize_and_pack",
     "rtn_mxfp4_quantize_and_pack",
     "rtn_quantize_channel8",
@@ -1516,13 +1522,17 @@ def plan_hadamard(shape, dtype, size: int, dim: int = -1, precision=torch.float3
     return HadamardPlan("cols", size, (shape[dim] // size) * inner, acc64, shape[dim], inner)
 
 
-def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=torch.float32) -> torch.Tensor:
+def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=torch.float32, perm: Optional["HadamardPermTables"] = None,
+                       form: Optional[str] = None) -> torch.Tensor:
     """HadamardTransform.forward (transform/factory/hadamard.py:91-108) for the Sylvester matrix of
     deterministic_hadamard_matrix(size): every run of `size` elements along `dim` is multiplied by H_size / sqrt(size) (the
     block-diagonal `_multihead_matmul` of transform/utils/matrix.py:124-158 when the dimension is longer), accumulated in
     `precision` and rounded once to x's dtype.  A fast Walsh-Hadamard butterfly on the GPU: no matrix, no GEMM.  The matrix is
     symmetric, so `inverse=True` upstream is the same call.  dim == last (or any dimension followed only by 1s): one launch;
-    dim == 0 of a matrix: ct_hadamard_cols."""
+    dim == 0 of a matrix: ct_hadamard_cols.  `perm` (hadamard_perm_tables): the permuted rotation of `randomize=True`, see
+    plan_hadamard_perm (`form` forces its "fused" or "composed" form)."""
+    if perm is not None:
+        return _hadamard_perm_transform(x, size, None, None, dim, precision, False, perm, form)
     plan = plan_hadamard(x.shape, x.dtype, size, dim, precision, contiguous=x.is_contiguous())
     _lib.require_device()
     if not x.is_cuda:
@@ -1615,14 +1625,18 @@ def plan_hadamard_k(shape, dtype, size: int, k: int = 1, dim: int = -1, precisio
 
 
 def hadamard_k_transform(x: torch.Tensor, n: int, had_k: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None, *, dim: int = -1,
-                         precision=torch.float32, transposed: bool = False) -> torch.Tensor:
+                         precision=torch.float32, transposed: bool = False, perm: Optional["HadamardPermTables"] = None,
+                         form: Optional[str] = None) -> torch.Tensor:
     """HadamardTransform.forward (transform/factory/hadamard.py:91-108) for the matrix of `random_hadamard_matrix(n)`
     (transform/utils/hadamard.py:53-151), W = diag(signs) * (had_k (x) H_M)^T with M = n / k a power of two: every run of n
     elements along `dim` becomes value @ W / sqrt(n) (`transposed=False`: the online locations, Embedding weight_output, Linear
     weight_output along dim 0) or value @ W.T / sqrt(n) (`transposed=True`), accumulated in `precision`, rounded once to x's
     dtype.  `had_k`: int8 (k, k) of +-1 on x's device, None for k == 1; `signs`: int8 (n,) of +-1, None for none.  No n x n
     matrix: signs, a Walsh-Hadamard butterfly over M and a k x k mix, which for 16-bit activations runs on the matrix cores in
-    one launch (csrc/ct_hadamard_k.hip)."""
+    one launch (csrc/ct_hadamard_k.hip).  `perm` (hadamard_perm_tables): the weight W[p][:, p] of `randomize=True`, see
+    plan_hadamard_perm (`form` forces its "fused" or "composed" form)."""
+    if perm is not None:
+        return _hadamard_perm_transform(x, n, had_k, signs, dim, precision, transposed, perm, form)
     k = 1 if had_k is None else int(had_k.shape[0])
     plan = plan_hadamard_k(x.shape, x.dtype, n, k, dim, precision, device_type=x.device.type, contiguous=x.is_contiguous())
     for name, t, shape in (("had_k", had_k, (k, k)), ("signs", signs, (plan.size,))):
@@ -1645,6 +1659,141 @@ def hadamard_k_transform(x: torch.Tensor, n: int, had_k: Optional[torch.Tensor] 
         call("ct_hadamard_k_rows", ptr(x), ptr(out), DT[x.dtype], x.numel(), *tail)
     else:
         call("ct_hadamard_k_cols", ptr(x), ptr(out), DT[x.dtype], plan.rows, plan.cols, *tail)
+    return out
+
+
+# ---- the permuted rotation of TransformScheme.randomize=True (csrc/ct_hadamard_perm.hip) ------------------------------------------------
+# Upstream's permuted weight is W' = W[p][:, p] (transform/factory/hadamard.py:94-95), so for every location, module type and inverse
+#     T_W'(x) = G_p(T_W(G_q(x)))   with G_i(v)[j] = v[i[j]] and q = argsort(p):
+# gather every block by q, the unpermuted rotation, gather the result by p.  "fused" does that in one launch, "composed" with two
+# index_select around the existing entry.
+HADAMARD_PERM_MAX_SIZE = {torch.float32: 16384, torch.float64: 8192}  # kHadPMaxF32 / kHadPMaxF64 of csrc/ct_hadamard_perm.hip
+_HADAMARD_PERM_MAX_TABLE = 32768  # what a non-negative 16-bit entry indexes
+
+# Which fused forms the plan dispatches: a key is True only if every verdict of profiles/hadamard_perm_bench.jsonl that speaks for it
+# says the one launch is faster than the composition by more than the spread between its runs (tools/hadamard_perm_bench.py;
+# tests/test_hadamard_perm.py holds the constants to that file).  "group": n <= 512 (hadp_group_kernel), "block": n = 1024 .. 16384
+# (hadp_block_kernel), each per accumulator; "cols": the column form around either — measured SLOWER than its composition, whose
+# gathers along dim 0 move whole rows: it stays off.
+HADAMARD_PERM_MEASURED_FASTER = {"group": True, "block": True, "group_f64": True, "block_f64": True, "cols": False}
+
+
+class HadamardPermTables(NamedTuple):
+    """a validated permutation p of 0 .. n - 1 on one device: `gather_out` = p and `gather_in` = q = argsort(p) as 16-bit tables
+    (what ct_hadamard_perm_rows reads; None for n > 32768), `index_in` / `index_out` the same as int32 for index_select"""
+    n: int
+    gather_in: Optional[torch.Tensor]
+    gather_out: Optional[torch.Tensor]
+    index_in: torch.Tensor
+    index_out: torch.Tensor
+
+
+def hadamard_perm_tables(perm: torch.Tensor, device) -> HadamardPermTables:
+    """The tables of one permutation for `device`.  Validates ONCE, on the host, that `perm` is a 1-D integer tensor holding every
+    index 0 .. n - 1 exactly once (ValueError otherwise) and uploads q = argsort(perm) and perm; the calls that take the tables
+    validate nothing and synchronise nothing."""
+    if not isinstance(perm, torch.Tensor) or perm.dim() != 1 or perm.dtype.is_floating_point or perm.dtype.is_complex or perm.dtype is torch.bool:
+        raise ValueError("perm must be a 1-D integer tensor")
+    if perm.is_meta:
+        raise ValueError("perm holds no data (a meta tensor)")
+    p = perm.detach().to("cpu", torch.int64)
+    n = int(p.numel())
+    if n == 0:
+        raise ValueError("perm is empty")
+    if int(p.min()) < 0 or int(p.max()) >= n:
+        raise ValueError(f"perm holds an index outside 0 .. {n - 1}")
+    if not bool((torch.bincount(p, minlength=n) == 1).all()):
+        raise ValueError(f"perm repeats an index: it is not a permutation of 0 .. {n - 1}")
+    q = torch.empty_like(p)
+    q[p] = torch.arange(n, dtype=torch.int64)
+    device = torch.device(device)
+    small = n <= _HADAMARD_PERM_MAX_TABLE
+    return HadamardPermTables(n, q.to(torch.int16).to(device) if small else None, p.to(torch.int16).to(device) if small else None,
+                              q.to(torch.int32).to(device), p.to(torch.int32).to(device))
+
+
+class HadamardPermPlan(NamedTuple):
+    """what a permuted rotation launches: `form` "fused" (ct_hadamard_perm_rows / ct_hadamard_perm_cols) or "composed"
+    (index_select, the unpermuted entry of `base`, index_select); `key` of HADAMARD_PERM_MEASURED_FASTER that speaks for the fused
+    form (None where there is none) and `reason` for a composed plan.  `launches()` counts the unpermuted entry as its own plan
+    does: one call is one launch except the vector form of the mix (two) and the column forms (two transposes more)"""
+    form: str
+    base: tuple  # HadamardPlan (the `hadamard` type) or HadamardKPlan (`random-hadamard`)
+    key: Optional[str]
+    reason: Optional[str]
+
+    def launches(self) -> int:
+        cols = (self.base.form if isinstance(self.base, HadamardPlan) else self.base.entry) == "cols"
+        if self.form == "fused":
+            return 3 if cols else 1
+        inner = 1 if isinstance(self.base, HadamardPlan) or self.base.form != "valu" else 2
+        return 2 + inner + (2 if cols else 0)
+
+
+def plan_hadamard_perm(shape, dtype, size: int, dim: int = -1, precision=torch.float32, *, k: int = 1, random: bool = False,
+                       device_type: str = "cuda", contiguous: bool = True, form: Optional[str] = None) -> HadamardPermPlan:
+    """The host-side decision of a permuted rotation, from shapes and dtypes alone.  First the errors and declines of the
+    unpermuted plan, unchanged: plan_hadamard for the `hadamard` type, plan_hadamard_k for `random-hadamard` (`random=True`, or
+    k > 1).  Then the form.  The fused launch exists for k == 1 and n up to HADAMARD_PERM_MAX_SIZE; it is dispatched where
+    HADAMARD_PERM_MEASURED_FASTER says it was measured faster.  Everything else is the composition, which is available wherever the
+    unpermuted plan is.  `form`: "fused" / "composed" force a form ("fused" raises NotImplementedError where no fused launch exists)."""
+    if form not in (None, "fused", "composed"):
+        raise ValueError(f"form must be None, 'fused' or 'composed', got {form!r}")
+    if random or int(k) != 1:
+        base = plan_hadamard_k(shape, dtype, size, k, dim, precision, device_type=device_type, contiguous=contiguous)
+        cols = base.entry == "cols"
+    else:
+        base = plan_hadamard(shape, dtype, size, dim, precision, device_type=device_type, contiguous=contiguous)
+        cols = base.form == "cols"
+    key, reason = None, None
+    if isinstance(base, HadamardKPlan) and base.k != 1:
+        reason = f"k = {base.k} > 1: the mix has no permuted launch"
+    elif base.size > HADAMARD_PERM_MAX_SIZE[precision]:
+        reason = f"hadamard size {base.size} exceeds the maximum {HADAMARD_PERM_MAX_SIZE[precision]} of the permuted launch at precision {precision}"
+    else:
+        key = "cols" if cols else ("group" if base.size <= 512 else "block") + ("_f64" if base.acc64 else "")
+    if form == "fused" and key is None:
+        raise NotImplementedError(f"no fused permuted launch: {reason}")
+    if key is not None and form is None and not HADAMARD_PERM_MEASURED_FASTER[key]:
+        reason = f"the {key} form is not measured faster than the composition (HADAMARD_PERM_MEASURED_FASTER)"
+    fused = key is not None and (form == "fused" or (form is None and HADAMARD_PERM_MEASURED_FASTER[key]))
+    return HadamardPermPlan("fused" if fused else "composed", base, key, None if fused else (reason or "forced"))
+
+
+def _hadamard_perm_transform(x, n, had_k, signs, dim, precision, transposed, perm, form):
+    """hadamard_transform / hadamard_k_transform with `perm`"""
+    if not isinstance(perm, HadamardPermTables):
+        raise ValueError("perm must be the HadamardPermTables of hadamard_perm_tables")
+    if perm.n != int(n):
+        raise ValueError(f"the permutation has {perm.n} entries, the rotation size is {int(n)}")
+    k = 1 if had_k is None else int(had_k.shape[0])
+    random = had_k is not None or signs is not None
+    plan = plan_hadamard_perm(x.shape, x.dtype, n, dim, precision, k=k, random=random, device_type=x.device.type, contiguous=x.is_contiguous(), form=form)
+    if perm.index_in.device != x.device:
+        raise ValueError(f"the permutation tables are on {perm.index_in.device}, the value on {x.device}")
+    d = dim % x.dim()
+    if plan.form == "composed":
+        g = x.unflatten(d, (-1, perm.n)).index_select(d + 1, perm.index_in).flatten(d, d + 1)
+        y = hadamard_k_transform(g, n, had_k, signs, dim=dim, precision=precision, transposed=transposed) if random \
+            else hadamard_transform(g, n, dim=dim, precision=precision)
+        return y.unflatten(d, (-1, perm.n)).index_select(d + 1, perm.index_out).flatten(d, d + 1)
+    if signs is not None and (signs.dtype is not torch.int8 or tuple(signs.shape) != (perm.n,) or not signs.is_contiguous()):
+        raise ValueError(f"signs must be a contiguous int8 tensor of shape {(perm.n,)}, got {signs.dtype} {tuple(signs.shape)}")
+    _lib.require_device()
+    if signs is not None and signs.device != x.device:
+        raise ValueError(f"signs is on {signs.device}, the value on {x.device}")
+    if x.data_ptr() % 16 or (signs is not None and signs.data_ptr() % 8) or perm.gather_in.data_ptr() % 16 or perm.gather_out.data_ptr() % 16:
+        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    base = plan.base
+    tail = (base.size, int(base.acc64), ptr(perm.gather_in), ptr(perm.gather_out), ptr(signs), int(bool(transposed)), stream_of(x))
+    if plan.key != "cols":
+        call("ct_hadamard_perm_rows", ptr(x), ptr(out), DT[x.dtype], x.numel(), *tail)
+    else:
+        ws = torch.empty_like(x)
+        call("ct_hadamard_perm_cols", ptr(x), ptr(out), ptr(ws), DT[x.dtype], base.rows, base.cols, *tail)
     return out
 
 

@@ -502,9 +502,24 @@ def _patch_forward() -> None:
 
 _TR_SAVED = {}  # install(patch_transforms=True): the two originals of transform/factory/hadamard.py
 _TR_RANDOM = [False]  # install(patch_transforms=True, patch_random_hadamard=True)
+_TR_PERMUTED = [False]  # install(patch_transforms=True, patch_permuted_hadamard=True)
 
 
-def _random_hadamard_forward(transform, value):
+def _perm_tables_of(transform, device):
+    """the device tables of an upstream transform's `perm` (codec.hadamard_perm_tables: validated once), cached on the transform and
+    keyed by the device and the permutation's `_version` / `data_ptr`; None without a permutation or while permuted transforms are
+    upstream's to compute"""
+    perm = transform.perm
+    if perm is None or not _TR_PERMUTED[0]:
+        return None
+    key = (device, perm._version, perm.data_ptr())
+    cached = getattr(transform, "_ct_perm_tables", None)
+    if cached is None or cached[0] != key:
+        cached = transform._ct_perm_tables = (key, codec.hadamard_perm_tables(perm.data, device))
+    return cached[1]
+
+
+def _random_hadamard_forward(transform, value, perm=None):
     """a tagged RandomHadamardFactory transform on a GPU value: the weight is factored once (transform/random_hadamard.py; the
     factors, or the fact that there are none, are cached on the transform) and the call goes to codec.hadamard_k_transform
     (csrc/ct_hadamard_k.hip).  None when the call is upstream's to compute."""
@@ -524,6 +539,8 @@ def _random_hadamard_forward(transform, value):
         factors = factors._replace(had_k=None if factors.had_k is None else factors.had_k.to(value.device), signs=factors.signs.to(value.device))
         transform._ct_factors = (factors,)
     transposed = transform_transposed(transform.args.location, transform.module_type, transform.args.inverse)
+    if perm is not None:
+        return codec.hadamard_k_transform(value, factors.n, factors.had_k, factors.signs, dim=dim, precision=weight.dtype, transposed=transposed, perm=perm)
     return codec.hadamard_k_transform(value, factors.n, factors.had_k, factors.signs, dim=dim, precision=weight.dtype, transposed=transposed)
 
 
@@ -532,7 +549,8 @@ def _patch_transforms() -> None:
     the class alone does not identify a Sylvester transform.  `HadamardFactory.create_transform` is wrapped to tag what a factory
     whose type is EXACTLY HadamardFactory makes, and `HadamardTransform.forward` (transform/factory/hadamard.py:91-108) to send a
     tagged transform without a permutation, on a GPU value the kernels plan, to codec.hadamard_transform (csrc/ct_hadamard.hip)
-    with the precision of the materialised weight; everything else — randomize=True, random-hadamard, CPU / meta / non-contiguous
+    with the precision of the materialised weight; everything else — randomize=True (unless install(patch_permuted_hadamard=True):
+    then the same call with the tables of the transform's `perm`, csrc/ct_hadamard_perm.hip), random-hadamard, CPU / meta / non-contiguous
     values, a NotImplementedError from the HIP side — runs the original.  The n x n weight stays where upstream put it."""
     import functools
 
@@ -556,6 +574,21 @@ def _patch_transforms() -> None:
 
     @functools.wraps(orig_forward)
     def forward(self, value):
+        if self.perm is not None:
+            # randomize=True: upstream's unless install(patch_permuted_hadamard=True) — then the same two branches with the tables
+            if _TR_PERMUTED[0] and value.is_cuda and (getattr(self, "_ct_sylvester", False) or (_TR_RANDOM[0] and getattr(self, "_ct_random", False))):
+                try:
+                    tables = _perm_tables_of(self, value.device)
+                    if getattr(self, "_ct_sylvester", False):
+                        out = codec.hadamard_transform(value, self.weight.size(0), dim=transform_dim(self.args.location, self.module_type),
+                                                       precision=self.weight.dtype, perm=tables)
+                    else:
+                        out = _random_hadamard_forward(self, value, tables)
+                    if out is not None:
+                        return out.to(value.dtype)
+                except (NotImplementedError, ValueError):
+                    pass  # upstream computes it, or raises its own error
+            return orig_forward(self, value)
         if getattr(self, "_ct_sylvester", False) and self.perm is None and value.is_cuda:
             try:
                 out = codec.hadamard_transform(value, self.weight.size(0), dim=transform_dim(self.args.location, self.module_type),
@@ -584,6 +617,7 @@ def _unpatch_transforms() -> None:
         _TR_SAVED["cls_transform"].forward = _TR_SAVED["forward"]
         _TR_SAVED.clear()
     _TR_RANDOM[0] = False
+    _TR_PERMUTED[0] = False
 
 
 _KV_SAVED = {}  # install(patch_modeling=True): upstream's QuantizedKVCache class and its own forward
@@ -638,7 +672,8 @@ def _unpatch_modeling() -> None:
 
 
 def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch_functions: bool = False,
-            patch_forward: bool = False, patch_transforms: bool = False, patch_random_hadamard: bool = False, patch_modeling: bool = False):
+            patch_forward: bool = False, patch_transforms: bool = False, patch_random_hadamard: bool = False, patch_modeling: bool = False,
+            patch_permuted_hadamard: bool = False):
     """registry swap + ImplBackend registration
     (+ the by-name bindings of the codec classes inside upstream's own modules unless rebind_names=False;
      + batched launches behind upstream's ModelCompressor.compress_model / decompress_model unless wrap_model_compressor=False;
@@ -647,9 +682,14 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
      + with patch_transforms=True the deterministic HadamardTransform.forward;
      + with patch_transforms=True AND patch_random_hadamard=True the forward of what a RandomHadamardFactory makes, without a permutation:
        the n x n weight is factored once and the call runs on the kernels of csrc/ct_hadamard_k.hip;
+     + with patch_transforms=True AND patch_permuted_hadamard=True a tagged transform WITH a permutation (randomize=True): the tables of
+       codec.hadamard_perm_tables are built once per device and the call runs on the kernels (csrc/ct_hadamard_perm.hip, or the
+       composition around the unpermuted entry) — the Sylvester type, and under patch_random_hadamard the random-hadamard type;
      + with patch_modeling=True the forward of upstream's QuantizedKVCache: K and V through modeling.quantize_key_value)."""
     if patch_random_hadamard and not patch_transforms:
         raise ValueError("patch_random_hadamard=True needs patch_transforms=True")
+    if patch_permuted_hadamard and not patch_transforms:
+        raise ValueError("patch_permuted_hadamard=True needs patch_transforms=True")
     import compressed_tensors  # the upstream package; ImportError if it is not installed
     from compressed_tensors.compressors import BaseCompressor
     from compressed_tensors.registry import registry as up_registry
@@ -670,6 +710,7 @@ def install(rebind_names: bool = True, wrap_model_compressor: bool = True, patch
     if patch_transforms:
         _patch_transforms()
         _TR_RANDOM[0] = _TR_RANDOM[0] or bool(patch_random_hadamard)
+        _TR_PERMUTED[0] = _TR_PERMUTED[0] or bool(patch_permuted_hadamard)
     if patch_modeling:
         _patch_modeling()
     return compressed_tensors

@@ -51,10 +51,10 @@ def _is_pretrained_model(model) -> bool:
     return isinstance(model, PreTrainedModel)
 
 
-def _check_supported(name, scheme, random_hadamard: bool = False, model=None) -> None:
+def _check_supported(name, scheme, random_hadamard: bool = False, model=None, randomize: bool = False) -> None:
     if scheme.type != "hadamard" and not (random_hadamard and scheme.type == "random-hadamard"):
         raise NotImplementedError(f"config group {name!r}: type={scheme.type!r} is not built here (only the deterministic 'hadamard' type is)")
-    if scheme.randomize:
+    if scheme.randomize and not randomize:
         raise NotImplementedError(f"config group {name!r}: randomize=True needs upstream's permutation, which is not built here")
     if scheme.requires_grad:
         raise NotImplementedError(f"config group {name!r}: requires_grad=True (training, parametrization) is not built here")
@@ -97,6 +97,8 @@ class InputRotation:
         args = getattr(scheme, "input_activations", None)
         if args is None or not _dynamic_args(args, module) or self.transform.precision is not torch.float32 or self.transform.dim != -1:
             return None
+        if self.transform.perm is not None:
+            return None  # the fused launch rotates by size alone: it would drop the permutation
         value = value.contiguous()
         global_scale = getattr(module, "input_global_scale", None)
         try:
@@ -136,8 +138,8 @@ def fuse_input_quantization(model: torch.nn.Module) -> list:
     for name, module in model.named_modules():
         hooks = module.__dict__.get(_INPUT_ROTATIONS, ())
         args = getattr(getattr(module, "quantization_scheme", None), "input_activations", None)
-        if len(hooks) != 1 or args is None or not _dynamic_args(args, module):
-            continue  # several rotations: only the last one could share the QDQ's launch, and the hooks do not know their order
+        if len(hooks) != 1 or args is None or not _dynamic_args(args, module) or hooks[0].transform.perm is not None:
+            continue  # a permuted rotation has no fused launch; several rotations: only the last one could share the QDQ's launch, and the hooks do not know their order
         hooks[0].fuse_quantization = True
         fused.append(name)
     return fused
@@ -179,7 +181,8 @@ class _AttentionRotation:
         self.handle = None
 
     def fusable(self) -> bool:
-        return isinstance(self.transform, HadamardTransform) and self.transform.precision is torch.float32 and self.transform.dim == -1
+        return (isinstance(self.transform, HadamardTransform) and self.transform.perm is None  # the fused launch would drop a permutation
+                and self.transform.precision is torch.float32 and self.transform.dim == -1)
 
     def _kw(self, args):
         from ..quantization import dynamic
@@ -201,7 +204,7 @@ class QueryRotation(_AttentionRotation):
         from .. import codec
         from ..quantization import dynamic
 
-        args = _static_attn_args(module, ("q",))
+        args = _static_attn_args(module, ("q",)) if self.fusable() else None
         if args is None or not codec.ATTN_ROTATED_MEASURED_FASTER["single"]:
             return None
         scale = module.q_scale
@@ -231,7 +234,7 @@ class KeyRotation(_AttentionRotation):
         from ..modeling.kvcache import _static_pair_args
         from ..quantization import dynamic
 
-        args = _static_attn_args(module, ("k", "v"))
+        args = _static_attn_args(module, ("k", "v")) if self.fusable() else None
         if args is None or not codec.ATTN_ROTATED_MEASURED_FASTER["pair"] or not _static_pair_args(module, key_states, value_states, args):
             return None
         ks, vs = module.k_scale, module.v_scale
@@ -278,9 +281,11 @@ class _RandomWeights:
     as TransformFactory.__init__ leaves it without a seed), one draw per size in order of first use (ParameterizedDefaultDict keys
     the cache by size alone), drawn at the precision of that first use — and factored once"""
 
-    def __init__(self, name, hadamard_weights):
+    def __init__(self, name, hadamard_weights, seed=None):
         self.name, self.hadamard_weights = name, hadamard_weights
         self.generator = torch.Generator()
+        if seed is not None:  # TransformFactory.__init__: `if seed is not None: self.generator.manual_seed(seed)`
+            self.generator.manual_seed(seed)
         self.factors = {}
 
     def get(self, size, precision, device):
@@ -293,15 +298,31 @@ class _RandomWeights:
         return self.factors[size]
 
 
-def _apply_to_module(name, scheme, module, args, random_weights=None, model=None) -> None:
+class _Permutations:
+    """the permutations of one config group with randomize=True, as HadamardFactory keeps them (transform/factory/hadamard.py:53,
+    67-69): a CPU int64 `torch.randperm(size, generator=g)` per size, drawn at first use from the group's generator and shared by
+    every transform of that size, online or offline"""
+
+    def __init__(self, generator):
+        self.generator = generator
+        self.perms = {}
+
+    def get(self, size):
+        if size not in self.perms:
+            self.perms[size] = torch.randperm(size, generator=self.generator)
+        return self.perms[size]
+
+
+def _apply_to_module(name, scheme, module, args, random_weights=None, model=None, perms=None) -> None:
     location = TransformLocation(args.location)
     size = get_transform_size(module, location, scheme.head_dim)
     if scheme.type == "random-hadamard":
         device = next((p.device for p in module.parameters()), torch.device("cpu"))
         factors = random_weights.get(size, scheme.precision if location.is_online() else torch.float64, device)
-        transform = RandomHadamardTransform(factors, scheme, args, type(module))
+        perm = perms.get(size) if perms is not None else None  # after that size's weight, from the same generator
+        transform = RandomHadamardTransform(factors, scheme, args, type(module), perm=perm)
     else:
-        transform = HadamardTransform(size, scheme, args, type(module))
+        transform = HadamardTransform(size, scheme, args, type(module), perm=perms.get(size) if perms is not None else None)
     transform_name = f"{name}_{location.value}"
     if location == TransformLocation.INPUT:
         module.register_module(transform_name, transform)
@@ -337,7 +358,7 @@ def _apply_to_module(name, scheme, module, args, random_weights=None, model=None
                 module.bias.copy_(transform(module.bias.unsqueeze(-1)).squeeze(-1))
 
 
-def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=None) -> None:
+def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=None, randomize: bool = False, seed=None) -> None:
     """Weight locations are fused into the weights (and the bias, for weight_output) under no_grad; `input` becomes a prepended
     forward pre-hook and `output` a forward hook on a HadamardTransform submodule.  `config` (ours or upstream's pydantic
     object) is attached to the model as `transform_config`, where ModelCompressor.from_pretrained_model picks it up.  Everything
@@ -349,13 +370,25 @@ def apply_transform_config(model: torch.nn.Module, config, *, hadamard_weights=N
     (transform/utils/hadamard.py:53-77).  With it the `random-hadamard` type is accepted: every weight is drawn as
     RandomHadamardFactory draws it, factored (transform/random_hadamard.py) and applied by the kernels of csrc/ct_hadamard_k.hip;
     the table of known matrices behind that callable is upstream's and is not part of this package.  Without it the type
-    raises as every other unsupported type does."""
+    raises as every other unsupported type does.
+    `randomize=True` accepts schemes with `randomize=True`: the weight W[p][:, p] of transform/factory/hadamard.py:94-95, applied as
+    a gather on each side of the rotation (csrc/ct_hadamard_perm.hip), never as a matrix.  The permutations are drawn as
+    HadamardFactory draws them: one `torch.Generator()` per config group — seeded with `seed` when given, as
+    TransformFactory.__init__ does; for `random-hadamard` the generator the weights are drawn from —, one CPU
+    `torch.randperm(size)` per size at first use (after that size's weight), shared by every transform of the group with that
+    size.  A scheme with `randomize=False` draws nothing.  Each transform keeps its permutation as the buffer `perm`."""
     ours = TransformConfig.coerce(config)
     for name, scheme in ours.config_groups.items():
-        _check_supported(name, scheme, random_hadamard=hadamard_weights is not None, model=model)
+        _check_supported(name, scheme, random_hadamard=hadamard_weights is not None, model=model, randomize=randomize)
     for name, scheme in ours.config_groups.items():
-        random_weights = _RandomWeights(name, hadamard_weights) if scheme.type == "random-hadamard" else None
+        random_weights = _RandomWeights(name, hadamard_weights, seed) if scheme.type == "random-hadamard" else None
+        perms = None
+        if scheme.randomize:
+            generator = random_weights.generator if random_weights is not None else torch.Generator()
+            if random_weights is None and seed is not None:
+                generator.manual_seed(seed)
+            perms = _Permutations(generator)
         for args in scheme.apply:
             for _, module in list(match_named_modules(model, args.targets, args.ignore)):
-                _apply_to_module(name, scheme, module, args, random_weights, model)
+                _apply_to_module(name, scheme, module, args, random_weights, model, perms)
     setattr(model, TRANSFORM_CONFIG_NAME, config)

@@ -39,12 +39,38 @@ def transform_dim(location, module_type) -> int:
     raise NotImplementedError(f"Applying transforms to {module_type} {location} is not supported")
 
 
-class HadamardTransform(torch.nn.Module):
+class _PermutedMixin:
+    """the permutation of `randomize=True` on a transform: `perm` is a persistent int64 buffer (upstream's state_dict key
+    `<name>_<location>.perm`: the draw cannot be regenerated); its device tables (codec.hadamard_perm_tables) are built once per
+    device and rebuilt when the buffer is replaced or written"""
+
+    def _init_perm(self, perm, size):
+        if perm is not None:
+            perm = torch.as_tensor(perm).detach().to(torch.int64)
+            codec.hadamard_perm_tables(perm, "cpu")  # validates; the device tables come with the first call
+            if perm.numel() != size:
+                raise ValueError(f"the permutation has {perm.numel()} entries, the rotation size is {size}")
+        self.register_buffer("perm", perm, persistent=True)
+        self._perm_tables = {}
+
+    def perm_tables(self, device):
+        """None for an unpermuted transform"""
+        if self.perm is None:
+            return None
+        device = torch.device(device)
+        key = (self.perm._version, self.perm.data_ptr())
+        hit = self._perm_tables.get(device)
+        if hit is None or hit[0] != key:
+            hit = self._perm_tables[device] = (key, codec.hadamard_perm_tables(self.perm, device))
+        return hit[1]
+
+
+class HadamardTransform(_PermutedMixin, torch.nn.Module):
     """value -> value rotated by H_size / sqrt(size) at `args.location` of a module of `module_type`.  Fused (offline) locations
     accumulate in float64, online ones in `scheme.precision` (hadamard.py:44).  The Sylvester matrix is symmetric, so
-    `args.inverse` selects the same rotation."""
+    `args.inverse` selects the same rotation.  `perm` (randomize=True upstream): the matrix H[perm][:, perm], still symmetric."""
 
-    def __init__(self, size: int, scheme, args, module_type=torch.nn.Linear):
+    def __init__(self, size: int, scheme, args, module_type=torch.nn.Linear, perm=None):
         super().__init__()
         self.size = int(size)
         self.scheme = TransformScheme.coerce(scheme)
@@ -52,12 +78,16 @@ class HadamardTransform(torch.nn.Module):
         self.module_type = module_type
         self.dim = transform_dim(self.args.location, module_type)
         self.precision = self.scheme.precision if self.args.is_online() else torch.float64
+        self._init_perm(perm, self.size)
 
     def forward(self, value: torch.Tensor) -> torch.Tensor:
-        return codec.hadamard_transform(value.contiguous(), self.size, dim=self.dim, precision=self.precision)
+        if self.perm is None:
+            return codec.hadamard_transform(value.contiguous(), self.size, dim=self.dim, precision=self.precision)
+        return codec.hadamard_transform(value.contiguous(), self.size, dim=self.dim, precision=self.precision, perm=self.perm_tables(value.device))
 
     def right_inverse(self, value: torch.Tensor) -> torch.Tensor:
         return self.forward(value)
 
     def extra_repr(self) -> str:
-        return f"size={self.size}, location={self.args.location}, inverse={self.args.inverse}, precision={self.precision}"
+        return (f"size={self.size}, location={self.args.location}, inverse={self.args.inverse}, precision={self.precision}, "
+                f"permuted={self.perm is not None}")

@@ -10,7 +10,7 @@ import torch
 
 from .. import codec
 from .config import TransformArgs, TransformLocation, TransformScheme
-from .hadamard import transform_dim
+from .hadamard import _PermutedMixin, transform_dim
 
 __all__ = ["HadamardFactors", "factor_hadamard_weight", "RandomHadamardTransform", "transform_transposed"]
 
@@ -82,12 +82,13 @@ def transform_transposed(location, module_type, inverse: bool) -> bool:
     return (location == TransformLocation.WEIGHT_INPUT) != bool(inverse)
 
 
-class RandomHadamardTransform(torch.nn.Module):
+class RandomHadamardTransform(_PermutedMixin, torch.nn.Module):
     """value -> value @ W / sqrt(n) (or W.T, per location, module type and `args.inverse`) for a factored random-hadamard weight.
     Fused (offline) locations accumulate in float64, online ones in `scheme.precision`, as HadamardTransform does.  Not a
-    HadamardTransform: fuse_input_quantization, which fuses the Sylvester rotation into the QDQ launch, leaves it alone."""
+    HadamardTransform: fuse_input_quantization, which fuses the Sylvester rotation into the QDQ launch, leaves it alone.
+    `perm` (randomize=True upstream): the weight W[perm][:, perm]."""
 
-    def __init__(self, factors: HadamardFactors, scheme, args, module_type=torch.nn.Linear):
+    def __init__(self, factors: HadamardFactors, scheme, args, module_type=torch.nn.Linear, perm=None):
         super().__init__()
         self.size, self.k, self.m = int(factors.n), int(factors.k), int(factors.m)
         self.register_buffer("had_k", factors.had_k, persistent=False)
@@ -98,11 +99,15 @@ class RandomHadamardTransform(torch.nn.Module):
         self.dim = transform_dim(self.args.location, module_type)
         self.transposed = transform_transposed(self.args.location, module_type, self.args.inverse)
         self.precision = self.scheme.precision if self.args.is_online() else torch.float64
+        self._init_perm(perm, self.size)
 
     def forward(self, value: torch.Tensor) -> torch.Tensor:
+        if self.perm is None:
+            return codec.hadamard_k_transform(value.contiguous(), self.size, self.had_k, self.signs, dim=self.dim, precision=self.precision,
+                                              transposed=self.transposed)
         return codec.hadamard_k_transform(value.contiguous(), self.size, self.had_k, self.signs, dim=self.dim, precision=self.precision,
-                                          transposed=self.transposed)
+                                          transposed=self.transposed, perm=self.perm_tables(value.device))
 
     def extra_repr(self) -> str:
         return (f"size={self.size} ({self.k} x {self.m}), location={self.args.location}, inverse={self.args.inverse}, "
-                f"transposed={self.transposed}, precision={self.precision}")
+                f"transposed={self.transposed}, precision={self.precision}, permuted={self.perm is not None}")

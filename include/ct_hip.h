@@ -405,6 +405,23 @@ int ct_hadamard_k_cols(const void* x, void* out, int dt, int64_t rows, int64_t c
 /* bytes of device workspace the two entries above need for `numel` elements (host arithmetic only); -1 for bad arguments */
 int64_t ct_hadamard_k_workspace_bytes(int dt, int64_t numel, int64_t n, int64_t k, int acc64, int cols_form);
 
+/* The permuted rotation of `TransformScheme.randomize=True` (transform/factory/hadamard.py:94-95: the weight W[p][:, p]) in one
+ * launch: over every run of n consecutive elements, out[j] = z[p[j]] with z = T(g), g[k] = x[q[k]], q = argsort(p) and T the
+ * rotation of ct_hadamard_rows (signs == NULL) or of ct_hadamard_k_rows with k == 1 (signs, transposed as there; the signs sit
+ * at the natural positions of g / z).  The bits are those of gather by q -> that entry -> gather by p.
+ *   gather_in   q: n entries of 16 bits, 16-byte aligned device memory
+ *   gather_out  p: likewise
+ * Every entry is masked with n - 1 before it is used: no table content addresses outside its run (the caller validates that
+ * the tables are permutations).  n a power of two up to 16384 (acc64 == 0) or 8192 (acc64 == 1), beyond that
+ * CT_ERR_UNSUPPORTED; x and out are 16-byte aligned and may be the same tensor. */
+int ct_hadamard_perm_rows(const void* x, void* out, int dt, int64_t numel, int64_t n, int acc64, const void* gather_in,
+                          const void* gather_out, const int8_t* signs, int transposed, ct_stream_t stream);
+
+/* The same along dim 0 of a row-major rows x cols matrix (n divides rows), as ct_hadamard_cols: transpose into `workspace`
+ * (rows * cols elements of dt), the permuted row form in place, transpose back.  Three launches. */
+int ct_hadamard_perm_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64,
+                          const void* gather_in, const void* gather_out, const int8_t* signs, int transposed, ct_stream_t stream);
+
 /* HadamardTransform.forward (online, float32 accumulation) followed by the dynamic branch of forward_quantize, one launch:
  * r = round_to_xdt(FWHT_n(x) / sqrt(n)) over runs of n elements, then ct_dynamic_qdq's observer / calculate_qparams /
  * fake_quantize over runs of seg_len elements of r.  rotated_out (nullable) receives r.  out / scale_out / zp_out / zdt /
