@@ -66,6 +66,9 @@ _PROTOTYPES = {
     "ct_rtn_quant_pack_w4": ([_P, _I, _L, _L, _L, _I, _P, _P, _P, _S], _I),
     "ct_rtn_w4_batch_plan": ([_P, _I], _L),
     "ct_rtn_quant_pack_w4_batch": ([_P, _I, _L, _I, _I, _S], _I),
+    "ct_rtn_quant_pack_wb": ([_P, _I, _L, _L, _L, _I, _I, _P, _P, _P, _S], _I),
+    "ct_rtn_wb_batch_plan": ([_P, _I, _I], _L),
+    "ct_rtn_quant_pack_wb_batch": ([_P, _I, _L, _I, _I, _I, _S], _I),
     "ct_rtn_quant_block8": ([_P, _I, _L, _L, _L, _L, _I, _I, _P, _P, _P, _S], _I),
     "ct_rtn_block8_batch_plan": ([_P, _I], _L),
     "ct_rtn_quant_block8_batch": ([_P, _I, _L, _I, _I, _I, _S], _I),

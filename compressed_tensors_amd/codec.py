@@ -128,6 +128,9 @@ __all__ = [
     "rtn_nvfp4_takes",
     "rtn_nvfp4_keys",
     "attn_observe_global_scale",
+    "RTN_PACKW_BITS",
+    "rtn_wb_table_item",
+    "launch_rtn_wb_words",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -1847,11 +1850,28 @@ def generate_gparam(x: torch.Tensor) -> torch.Tensor:
     return _home(gs, x)
 
 
-def rtn_quantize_and_pack(x: torch.Tensor, *, group_size: Optional[int] = None, symmetric: bool = True):
-    """Round-to-nearest int4 compress in ONE pass over the weight: min-max observer + calculate_qparams
+RTN_PACKW_BITS = (2, 3, 5, 6, 7)  # the widths of `ct_rtn_quant_pack_wb` and its table; 4 has `ct_rtn_quant_pack_w4`, 8 `rtn_quantize_group8(words=True)`
+
+
+def _rtn_pack_bits(num_bits) -> int:
+    """`num_bits` of `rtn_quantize_and_pack` / `rtn_quantize_and_pack_many`, checked before anything touches a device"""
+    bits = int(num_bits)
+    if bits == 4 or bits in RTN_PACKW_BITS:
+        return bits
+    if bits == 8:
+        raise NotImplementedError("the one-pass pack-quantized compress of 8 bits is rtn_quantize_group8(words=True)")
+    if bits == 1:
+        raise NotImplementedError("1 bit has no one-pass compress; use minmax_qparams + quantize_and_pack")
+    raise ValueError(f"num_bits must be in 1..8, got {num_bits}")
+
+
+def rtn_quantize_and_pack(x: torch.Tensor, *, group_size: Optional[int] = None, symmetric: bool = True, num_bits: int = 4):
+    """Round-to-nearest integer compress in ONE pass over the weight: min-max observer + calculate_qparams
     (quantization/utils/helpers.py:50-137) + quantize + pack_to_int32 (compressors/pack_quantized/base.py:96-104).
-    Returns (packed int32 (R, C/8), scale (R, C/group) in x.dtype, zero_point int8 (R, C/group)) — bit-identical to
-    `minmax_qparams` followed by `quantize_and_pack`.  group_size None = one group per row (channel)."""
+    Returns (packed int32 (R, C * num_bits / 32), scale (R, C/group) in x.dtype, zero_point int8 (R, C/group)) — bit-identical to
+    `minmax_qparams` followed by `quantize_and_pack`.  group_size None = one group per row (channel).  num_bits 4 is
+    `ct_rtn_quant_pack_w4`, 2 / 3 / 5 / 6 / 7 are `ct_rtn_quant_pack_wb`; 1 and 8 raise NotImplementedError naming what serves them."""
+    bits = _rtn_pack_bits(num_bits)
     if x.dim() != 2:
         raise ValueError("rtn_quantize_and_pack expects a 2-D weight")
     if x.dtype not in (torch.bfloat16, torch.float16):
@@ -1864,10 +1884,13 @@ def rtn_quantize_and_pack(x: torch.Tensor, *, group_size: Optional[int] = None, 
         raise NotImplementedError(f"the one-pass compress needs group sizes 32 * 2^k <= 2048, got {group}; use minmax_qparams + quantize_and_pack")
     dev = _compute_device(x)
     xd = _dev(x, dev).contiguous()
-    packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=dev)
+    packed = torch.empty((rows, cols * bits // 32), dtype=torch.int32, device=dev)
     scale = torch.empty((rows, cols // group), dtype=x.dtype, device=dev)
     zp = torch.empty((rows, cols // group), dtype=torch.int8, device=dev)
-    call("ct_rtn_quant_pack_w4", ptr(xd), DT[xd.dtype], rows, cols, group, int(bool(symmetric)), ptr(packed), ptr(scale), ptr(zp), stream_of(xd))
+    if bits == 4:
+        call("ct_rtn_quant_pack_w4", ptr(xd), DT[xd.dtype], rows, cols, group, int(bool(symmetric)), ptr(packed), ptr(scale), ptr(zp), stream_of(xd))
+    else:
+        call("ct_rtn_quant_pack_wb", ptr(xd), DT[xd.dtype], rows, cols, group, bits, int(bool(symmetric)), ptr(packed), ptr(scale), ptr(zp), stream_of(xd))
     return _home(packed, x), _home(scale, x), _home(zp, x)
 
 
@@ -2148,6 +2171,8 @@ _TABLES = {
 _RTN_BLOCK8_TABLE = ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
 _RTN_GROUP8_TABLE = ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # the one-pass group-wise 8-bit table (`launch_rtn_group8_words`), likewise
 _RTN_CHANNEL8_TABLE = ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch")  # the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`), likewise
+# the one-pass table of the widths next to 4 and 8 (`launch_rtn_wb_words`), likewise; its plan's third argument is the WIDTH, handed over where the directed plans take their direction
+_RTN_WB_TABLE = ("ct_rtn_wb_batch_plan", True, "ct_rtn_quant_pack_wb_batch")
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
@@ -2344,6 +2369,15 @@ def launch_rtn_w4_words(words, n: int, dtype: torch.dtype, device: torch.device,
     return _launch_table("rtn_w4", words, n, device, 0, (DT[dtype], int(bool(symmetric)))) if n else None
 
 
+def launch_rtn_wb_words(words, n: int, dtype: torch.dtype, device: torch.device, num_bits: int, symmetric: bool) -> torch.Tensor:
+    """`launch_rtn_w4_words` for a table of the one-pass compress of the widths next to 4 and 8 (`ct_rtn_quant_pack_wb_batch`, `RTN_PACKW_BITS`): the same
+    rows, dst = packed int32 (R, C * num_bits / 32), ONE width per table"""
+    bits = int(num_bits)
+    if bits not in RTN_PACKW_BITS:
+        raise NotImplementedError(f"the one-pass table of the widths next to 4 and 8 takes num_bits in {RTN_PACKW_BITS}, got {num_bits}")
+    return _launch_table(_RTN_WB_TABLE, words, n, device, bits, (DT[dtype], bits, int(bool(symmetric)))) if n else None
+
+
 def launch_rtn_mxfp4_words(words, n: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
     """`launch_rtn_w4_words` for a table of the one-pass MXFP4 compress (`ct_rtn_mxfp4_quant_pack_batch`): src = weights, dst = packed bytes,
     zp_packed = the E8M0 code output, scale = the float-scale output or 0, group = 32"""
@@ -2411,6 +2445,19 @@ def rtn_w4_table_item(x, group_size, with_zp: bool = True):
         return None
     rows, cols = int(x.shape[0]), int(x.shape[1])
     packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=x.device)
+    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
+    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
+    return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
+
+
+def rtn_wb_table_item(x, group_size, num_bits: int, with_zp: bool = True):
+    """`rtn_w4_table_item` for the one-pass table of the widths next to 4 and 8 (`launch_rtn_wb_words`; the same admission, `rtn_w4_group`):
+    (packed int32 (R, C * num_bits / 32), scale (R, C / g), int8 zero point (R, C / g) or None without `with_zp`, row) or None"""
+    g = rtn_w4_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
+    if not g:
+        return None
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    packed = torch.empty((rows, cols * int(num_bits) // 32), dtype=torch.int32, device=x.device)
     scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
     zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
     return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
@@ -2496,12 +2543,12 @@ def rtn_nvfp4_table_item(x, key: int):
     return packed, s8, gs, item_row(x.data_ptr(), gs.data_ptr(), int(key), packed.data_ptr(), rows, cols, 16, s8.data_ptr())
 
 
-def _rtn_w4_one(x, group_size, symmetric):
+def _rtn_w4_one(x, group_size, symmetric, num_bits=4):
     """one tensor outside the table: the one-pass kernel where it applies, the observer + compress composition otherwise"""
     if x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and rtn_w4_group((1, x.shape[1]), group_size):
-        return rtn_quantize_and_pack(x, group_size=group_size, symmetric=symmetric)
-    scale, zp = minmax_qparams(x, num_bits=4, group_size=group_size, symmetric=symmetric)
-    packed = quantize_and_pack(x, scale, zp, num_bits=4, strategy="group" if group_size else "channel", group_size=group_size)
+        return rtn_quantize_and_pack(x, group_size=group_size, symmetric=symmetric, num_bits=num_bits)
+    scale, zp = minmax_qparams(x, num_bits=num_bits, group_size=group_size, symmetric=symmetric)
+    packed = quantize_and_pack(x, scale, zp, num_bits=num_bits, strategy="group" if group_size else "channel", group_size=group_size)
     return packed, scale, zp
 
 
@@ -2529,18 +2576,23 @@ def _rtn_many(weights, item, single, launch, held=()) -> list:
     return out
 
 
-def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True):
-    """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_w4_table_item`, of the first such tensor's device and
-    dtype) leave in ONE `ct_rtn_quant_pack_w4_batch` launch — a checkpoint is a few hundred
+def rtn_quantize_and_pack_many(weights, *, group_size=None, symmetric=True, num_bits=4):
+    """`rtn_quantize_and_pack` for a LIST of weights: the tensors the table takes (`rtn_w4_table_item` / `rtn_wb_table_item`, of the first such
+    tensor's device and dtype) leave in ONE `ct_rtn_quant_pack_w4_batch` (4 bits) or `ct_rtn_quant_pack_wb_batch` (2, 3, 5, 6, 7) launch — a
+    checkpoint is a few hundred
     launch-bound tensors — and the others one by one (the one-pass kernel, or `minmax_qparams` + `quantize_and_pack` where that does not apply).
     `group_size`: one value for all, or one per weight (None = one group per row).  Returns [(packed, scale, zero_point)] in input order,
     bit-identical to the single-tensor call per item (quantization/utils/helpers.py:50-137 + compressors/pack_quantized/base.py:96-104)."""
+    bits = _rtn_pack_bits(num_bits)
     weights = list(weights)
     groups = list(group_size) if isinstance(group_size, (list, tuple)) else [group_size] * len(weights)
     if len(groups) != len(weights):
         raise ValueError(f"{len(groups)} group sizes for {len(weights)} weights")
-    return _rtn_many(weights, lambda i, x, n: rtn_w4_table_item(x, groups[i]), lambda i, x: _rtn_w4_one(x, groups[i], symmetric),
-                     lambda flat, n, dtype, device: launch_rtn_w4_words(flat, n, dtype, device, symmetric))
+    if bits == 4:
+        return _rtn_many(weights, lambda i, x, n: rtn_w4_table_item(x, groups[i]), lambda i, x: _rtn_w4_one(x, groups[i], symmetric),
+                         lambda flat, n, dtype, device: launch_rtn_w4_words(flat, n, dtype, device, symmetric))
+    return _rtn_many(weights, lambda i, x, n: rtn_wb_table_item(x, groups[i], bits), lambda i, x: _rtn_w4_one(x, groups[i], symmetric, bits),
+                     lambda flat, n, dtype, device: launch_rtn_wb_words(flat, n, dtype, device, bits, symmetric))
 
 
 def rtn_mxfp4_quantize_and_pack_many(weights):

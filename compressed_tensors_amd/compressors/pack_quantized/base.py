@@ -20,6 +20,19 @@ __all__ = ["PackedQuantizationCompressor"]
 
 PACK_ZP_STRATS = ("group", "channel")
 
+# The one-pass round-to-nearest compress of the widths next to 4 and 8 (codec.RTN_PACKW_BITS; csrc/ct_quant_wb.hip, rtn_wb_kernel), keyed by
+# (num_bits, symmetric).  RTN_PACKW_MEASURED_FASTER gates `compress_rtn` (one pass against codec.minmax_qparams + cls.compress),
+# RTN_PACKW_TABLE_MEASURED_FASTER the window hook (one table launch against one `compress_rtn_module` per module).  An entry is True only where two
+# runs on the MI355X both put the new path below the old one by more than the old path's own min-max spread in that run; a width that was not
+# measured stays False.  Figures and commands: DESIGN.md §5.23, profiles/packw_rtn_bench.jsonl, profiles/rtn_bench.jsonl.
+# Single tensors: all ten keys measured at g128 on 8192 x 8192, 4096 x 14336 and 14336 x 4096 (W3 also channel-wise at 4096 x 2048), the one pass
+# 28-40 us against 42-56, the composition's spread 0.1-4.0 us: every verdict "faster" in both runs.
+RTN_PACKW_MEASURED_FASTER = {(b, s): True for b in codec.RTN_PACKW_BITS for s in (True, False)}
+# The table: W3 symmetric 3.59-3.66 ms against 4.71-4.95 per module (8B-shaped) and 2.09-2.15 against 3.17-3.30 (TinyLlama-shaped), spreads 0.08-0.55:
+# faster.  W3 asymmetric 6.30, 6.34 against 6.68, 6.83 on the 8B-shaped tree with spreads of 0.38, 0.26: the first run is inside the spread, so off
+# (its stored zero points still cost one launch per module).  The other widths' tables were not measured.
+RTN_PACKW_TABLE_MEASURED_FASTER = {(b, s): (b, s) == (3, True) for b in codec.RTN_PACKW_BITS for s in (True, False)}
+
 def _hostpath():
     """the C++ host loop of the batched module paths (`_lib.hostpath`), or None when it has not been built: the Python loop below does
     the same work, four times slower per module"""
@@ -57,6 +70,20 @@ def _w4_scheme_info(schemes: dict, scheme):
     if int(wa.num_bits) == 4 and enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel"):
         g = 0 if st == "channel" else int(getattr(wa, "group_size", 0) or -1)
         info = (getattr(wa, "group_size", None) if st == "group" else None, bool(wa.symmetric), g if g % 32 == 0 else -1)
+    schemes[id(scheme)] = info
+    return info
+
+
+def _rtn_scheme_info(schemes: dict, scheme):
+    """`_w4_scheme_info` for the data-free window hook: None unless an INT group / channel scheme of a width that has a one-pass table — 4 bits, or one of
+    `codec.RTN_PACKW_BITS` whose table gate holds (RTN_PACKW_TABLE_MEASURED_FASTER) —, else (group size or None for channel-wise, symmetric, num_bits)"""
+    wa = scheme.weights
+    st = enum_value(wa.strategy)
+    bits, symmetric = int(wa.num_bits), bool(wa.symmetric)
+    info = None
+    if (enum_value(getattr(wa, "type", "int")) == "int" and st in ("group", "channel")
+            and (bits == 4 or RTN_PACKW_TABLE_MEASURED_FASTER.get((bits, symmetric), False))):
+        info = (getattr(wa, "group_size", None) if st == "group" else None, symmetric, bits)
     schemes[id(scheme)] = info
     return info
 
@@ -260,7 +287,10 @@ class PackedQuantizationCompressor(BaseCompressor):
         weights = scheme.weights
         strategy = enum_value(weights.strategy)
         group = getattr(weights, "group_size", None) if strategy == "group" else None
-        one_pass = (int(weights.num_bits) == 4 and enum_value(getattr(weights, "type", "int")) == "int" and strategy in ("group", "channel")
+        bits = int(weights.num_bits)
+        # 4 bits, and the widths next to 4 and 8 where the measurement says so (RTN_PACKW_MEASURED_FASTER)
+        one_pass = ((bits == 4 or RTN_PACKW_MEASURED_FASTER.get((bits, bool(weights.symmetric)), False))
+                    and enum_value(getattr(weights, "type", "int")) == "int" and strategy in ("group", "channel")
                     and weight.dim() == 2 and weight.dtype in (torch.bfloat16, torch.float16) and codec.rtn_w4_group((1, weight.shape[-1]), group))
         if not one_pass and enum_value(getattr(weights, "type", "int")) == "int":
             # 8-bit words (W8A16): the one-pass group-wise kernel in its word form, a channel as one group, where its plan takes the weight and the
@@ -280,7 +310,14 @@ class PackedQuantizationCompressor(BaseCompressor):
         if not one_pass:
             scale, zp = codec.minmax_qparams(weight, num_bits=int(weights.num_bits), group_size=group, symmetric=bool(weights.symmetric))
             return cls.compress({"weight": weight, "weight_scale": scale, "weight_zero_point": zp}, scheme)
-        packed, scale, zp = codec.rtn_quantize_and_pack(weight, group_size=group, symmetric=bool(weights.symmetric))
+        packed, scale, zp = codec.rtn_quantize_and_pack(weight, group_size=group, symmetric=bool(weights.symmetric), num_bits=bits)
+        if bits != 4:  # the composition's entries in the composition's order (`compress` of the qparams' state dict), as the 8-bit words above
+            out = {"weight_scale": scale}
+            if not weights.symmetric:
+                out["weight_zero_point"] = codec.pack_to_int32(zp, bits, packed_dim=0)
+            out["weight_packed"] = packed
+            out["weight_shape"] = torch.tensor(weight.shape)
+            return out
         out = {"weight_packed": packed, "weight_scale": scale, "weight_shape": torch.tensor(weight.shape)}
         if not weights.symmetric:
             out["weight_zero_point"] = codec.pack_to_int32(zp, weights.num_bits, packed_dim=0)
@@ -292,15 +329,26 @@ class PackedQuantizationCompressor(BaseCompressor):
     def compress_rtn_modules(cls, modules) -> None:
         """the window hook (`run_rtn_windows`): the int4 group / channel modules with a 16-bit weight on a GPU leave in ONE table launch per
         (device, dtype, symmetric) (codec.launch_rtn_w4_words), the stored zero points of the asymmetric ones in one `zp4_batch(..., "pack")`
-        behind it; the others go through `compress_rtn_module`."""
+        behind it; the modules of the widths next to 4 and 8 whose gate holds (RTN_PACKW_TABLE_MEASURED_FASTER) in one table launch per
+        (device, dtype, symmetric, num_bits) (codec.launch_rtn_wb_words), their stored zero points per module behind it; the others go through
+        `compress_rtn_module`."""
         schemes = {}
 
         def item(m, w, table):
             scheme = m.quantization_scheme
             info = schemes.get(id(scheme), 0)
             if info == 0:
-                info = _w4_scheme_info(schemes, scheme)
-            got = codec.rtn_w4_table_item(w, info[0], not info[1]) if info is not None else None
+                info = _rtn_scheme_info(schemes, scheme)
+            if info is None:
+                return None
+            group, symmetric, bits = info
+            if bits != 4:  # the widths next to 4 and 8: one table per width (codec.launch_rtn_wb_words)
+                got = codec.rtn_wb_table_item(w, group, bits, not symmetric)
+                if got is None:
+                    return None
+                packed, scale, zp, row = got
+                return (w.device, w.dtype, symmetric, bits), row, [packed, scale, zp, None, bits]  # (a list: `launch` fills in the stored zero points)
+            got = codec.rtn_w4_table_item(w, group, not symmetric)
             if got is None:
                 return None
             packed, scale, zp, row = got
@@ -308,16 +356,29 @@ class PackedQuantizationCompressor(BaseCompressor):
             if zp is not None:
                 rows, groups = zp.shape
                 zpp = torch.empty((math.ceil(rows * 4 / 32), groups), dtype=torch.int32, device=w.device)
-            return (w.device, w.dtype, info[1]), row, (packed, scale, zp, zpp)
+            return (w.device, w.dtype, symmetric, 4), row, (packed, scale, zp, zpp, 4)
 
         def launch(key, flat, jobs):
-            device, dtype, symmetric = key
+            device, dtype, symmetric, bits = key
+            if bits != 4:
+                dev_table = codec.launch_rtn_wb_words(flat, len(jobs), dtype, device, bits, symmetric)
+                if not symmetric:  # pack_to_int32(zp, bits, packed_dim=0) per module: only 4 bits have a table for it
+                    for _, _, o in jobs:
+                        o[3] = codec.pack_to_int32(o[2], bits, packed_dim=0)
+                return dev_table
             dev_table = codec.launch_rtn_w4_words(flat, len(jobs), dtype, device, symmetric)
             if not symmetric:  # pack_to_int32(zp, 4, packed_dim=0) of every module, behind the launch that computes the zero points
                 codec.zp4_batch([(o[2], o[3]) for _, _, o in jobs], "pack")
             return dev_table
 
         def entries(w, o):
+            if o[4] != 4:  # `compress_rtn`'s order for these widths: the composition's
+                add = {"weight_scale": o[1]}
+                if o[3] is not None:
+                    add["weight_zero_point"] = o[3]
+                add["weight_packed"] = o[0]
+                add["weight_shape"] = torch.tensor(w.shape)
+                return add
             add = {"weight_packed": o[0], "weight_scale": o[1], "weight_shape": torch.tensor(w.shape)}
             if o[3] is not None:
                 add["weight_zero_point"] = o[3]

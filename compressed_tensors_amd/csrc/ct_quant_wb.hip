@@ -20,6 +20,7 @@
 //               1-2 loads + 1 store (+ the scale), as W4.
 //
 // Zero points of an asymmetric scheme travel as int8 here (their stored form for b != 4 is made by ct_pack_int32_dim0).
+#include "ct_minmax.h"
 #include "ct_quant_lean.h"
 
 namespace ct {
@@ -289,4 +290,202 @@ int launch_wb_unpack_dequant(const int32_t* packed, const void* scale, int sdt, 
     CT_LAUNCH_CHECK("ct_unpack_dequant[lean, any width]");
 }
 
+// ------------------------------------------------------------------------------------------
+// Round-to-nearest compress in ONE pass for the widths next to 4 and 8: rtn_w4_lane (ct_quant.hip) with the code builder and the bit
+// placement of wb_quant_pack_lean_kernel above.  The lane layout is the same in both — a lane owns one 32-element pack group (four 16-byte
+// loads), a scale group is lpg = group / 32 adjacent lanes — so the weight is read once: the lane's min / max on the raw pairs, the DPP
+// reduction inside the scale group, compute_qparams<DT>(m, BITS, ...) on every lane of the group (identical results), the lane's 32 codes
+// against it, BITS words out; the group's first lane stores the scale and the zero point (ordinary vector stores).
+// Bit-identical to ct_minmax_qparams followed by ct_quant_pack (same helpers), and tested against that composition.
+// Every lane of the workgroup enters (the DPP reduction reads its neighbours): `live` guards the memory accesses, and the return comes
+// after the reduction.  lanes is a multiple of lpg, kBlock too: a scale group never straddles workgroups.  zp_out == NULL: no zero-point store.
+template <int DT, int BITS, bool SYM>
+__device__ __forceinline__ void rtn_wb_lane(const u32x4* __restrict__ in, int64_t lanes, int lpg, uint32_t* __restrict__ out,
+                                            void* __restrict__ scale_out, int8_t* __restrict__ zp_out, int64_t l) {
+    constexpr int symmetric = SYM ? 1 : 0;
+    const bool live = l < lanes;
+    u32x4 r[4];
+    MinMax m;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = live ? in[l * 4 + i] : u32x4{0u, 0u, 0u, 0u};  // a dead lane only lends the reduction its identities
+    if constexpr (SYM) {
+        uint32_t acc = 0;
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
+        }
+        m = absmax_finish<DT>(absmax_group_reduce(acc, lpg));
+    } else {
+        MinMaxKey k = mmk_init();
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) k = mmk_acc(mmk_acc(mmk_acc(mmk_acc(k, r[i].x), r[i].y), r[i].z), r[i].w);
+        }
+        m = mmk_finish<DT>(mmk_group_reduce(k, lpg));
+    }
+    if (!live) return;
+    float s, z;
+    compute_qparams<DT>(m, BITS, symmetric, s, z);
+    if ((threadIdx.x & (lpg - 1)) == 0) {
+        store1<DT>(scale_out, l / lpg, s);
+        if (zp_out) zp_out[l / lpg] = (int8_t)(int)z;
+    }
+    const bool fast = fast_scale_ok<DT>(s) && fast_data_ok<DT, 4>(r);
+    const float rs = 1.0f / s;
+    const bool use_zp = !symmetric && (__builtin_amdgcn_ballot_w64(z != 0.0f) != 0);
+    uint32_t code[4][8];
+    // real branches, as wb_quant_pack_lean_kernel: the IEEE divide must not be issued on the fast path
+    if (fast) {
+        if (use_zp) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wb_codes8<DT, BITS, true, true>(r[i], s, rs, z, code[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wb_codes8<DT, BITS, true, false>(r[i], s, rs, z, code[i]);
+        }
+    } else {
+        if (use_zp) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wb_codes8<DT, BITS, false, true>(r[i], s, rs, z, code[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wb_codes8<DT, BITS, false, false>(r[i], s, rs, z, code[i]);
+        }
+    }
+    uint32_t words[BITS + 1];
+#pragma unroll
+    for (int j = 0; j <= BITS; ++j) words[j] = 0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int pos = i * BITS, w = pos >> 5, sh = pos & 31;  // compile-time after unrolling
+        const uint32_t c = code[i >> 3][i & 7];
+        words[w] |= c << sh;
+        if (sh + BITS > 32) words[w + 1] |= c >> (32 - sh);
+    }
+    wb_store_words<BITS>(out + l * BITS, words);
+}
+
+template <int DT, int BITS, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_wb_kernel(const u32x4* __restrict__ in, int64_t lanes, int lpg, uint32_t* __restrict__ out,
+                                                        void* __restrict__ scale_out, int8_t* __restrict__ zp_out) {
+    rtn_wb_lane<DT, BITS, SYM>(in, lanes, lpg, out, scale_out, zp_out, (int64_t)blockIdx.x * kBlock + threadIdx.x);
+}
+
+// the table form: `struct ct_w4_item` read as ct_rtn_quant_pack_w4_batch reads it (src = weights, dst = packed words, scale / zp = OUTPUTS).
+// ct_rtn_wb_batch_plan admits groups of 32 * 2^k <= 2048 elements only, so lanes per group = 1 << (upg_shift - 2) divides kBlock, and every
+// item owns whole workgroups from its `first_block`: the lanes behind an item's last one stay in the reduction as dead lanes.
+template <int DT, int BITS, bool SYM>
+__global__ __launch_bounds__(kBlock) void rtn_wb_batch_kernel(const ct_w4_item* __restrict__ items, int n) {
+    int lo = 0, hi = n - 1;  // the item of this workgroup: wave-uniform loads
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].first_block <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const ct_w4_item& it = items[lo];
+    const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
+    rtn_wb_lane<DT, BITS, SYM>(static_cast<const u32x4*>(it.src), it.units >> 2, 1 << (it.upg_shift - 2), static_cast<uint32_t*>(it.dst),
+                               const_cast<void*>(it.scale), static_cast<int8_t*>(const_cast<void*>(it.zp)), l);
+}
+
+#define CT_RTN_WB_BITS(bits, ...)                            \
+    switch (bits) {                                          \
+        case 2: { constexpr int B = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int B = 3; __VA_ARGS__; } break; \
+        case 5: { constexpr int B = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int B = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int B = 7; __VA_ARGS__; } break; \
+        default: break;                                      \
+    }
+
+// the widths this translation unit's one-pass kernels serve; every other width names the entry that serves it
+static bool rtn_wb_bits_ok(const char* who, int bits) {
+    if (bits == 2 || bits == 3 || bits == 5 || bits == 6 || bits == 7) return true;
+    if (bits == 4) set_error("%s: 4 bits are served by ct_rtn_quant_pack_w4 / ct_rtn_quant_pack_w4_batch", who);
+    else if (bits == 8) set_error("%s: 8 bits are served by ct_rtn_quant_group8 (words != 0) / ct_rtn_quant_group8_batch", who);
+    else set_error("%s: %d bits have no one-pass kernel (2, 3, 5, 6, 7 here); ct_minmax_qparams followed by ct_quant_pack serves 1..8", who, bits);
+    return false;
+}
+
 }  // namespace ct
+
+using namespace ct;
+
+extern "C" {
+
+int ct_rtn_quant_pack_wb(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int bits, int symmetric, int32_t* packed,
+                         void* scale_out, int8_t* zp_out, ct_stream_t stream) {
+    if (!rtn_wb_bits_ok("ct_rtn_quant_pack_wb", bits)) return CT_ERR_UNSUPPORTED;
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "the one-pass round-to-nearest compress takes 16-bit float weights, got dtype %d", xdt);
+    CT_REQUIRE(rows >= 0 && cols >= 0 && group >= 1, "bad shape");
+    CT_REQUIRE(group % 32 == 0 && group <= 2048 && log2_exact(group / 32) >= 0, "group size must be 32 * 2^k <= 2048, got %lld", (long long)group);
+    CT_REQUIRE(cols % group == 0, "columns (%lld) must be a multiple of the group size %lld", (long long)cols, (long long)group);
+    CT_REQUIRE(aligned16(x), "the weights must be 16-byte aligned");
+    CT_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 3u) == 0, "the packed words must be 4-byte aligned");
+    CT_REQUIRE(scale_out && zp_out, "scale and zero-point outputs are required");
+    if (rows == 0 || cols == 0) return CT_OK;
+    CT_REQUIRE(x && packed, "x and packed are required");
+    const int64_t lanes = rows * (cols / 32);
+    const int lpg = (int)(group / 32);
+    CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
+    const dim3 grid((unsigned)cdiv64(lanes, kBlock));
+#define CT_RTNWB(DT, SY) CT_RTN_WB_BITS(bits, hipLaunchKernelGGL((rtn_wb_kernel<DT, B, SY>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), \
+                                                                 lanes, lpg, reinterpret_cast<uint32_t*>(packed), scale_out, zp_out))
+    if (xdt == CT_BF16) { if (symmetric) { CT_RTNWB(CT_BF16, true); } else { CT_RTNWB(CT_BF16, false); } }
+    else { if (symmetric) { CT_RTNWB(CT_F16, true); } else { CT_RTNWB(CT_F16, false); } }
+#undef CT_RTNWB
+    CT_LAUNCH_CHECK("ct_rtn_quant_pack_wb");
+}
+
+int64_t ct_rtn_wb_batch_plan(ct_w4_item* items, int n, int bits) {
+    if (!rtn_wb_bits_ok("ct_rtn_wb_batch_plan", bits)) return -1;
+    if (n < 0 || (n > 0 && items == nullptr)) {
+        set_error("ct_rtn_wb_batch_plan: bad arguments");
+        return -1;
+    }
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        ct_w4_item& it = items[i];
+        const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
+        // the conditions of ct_rtn_quant_pack_wb, per item
+        const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
+                        aligned16(it.src) && (reinterpret_cast<uintptr_t>(it.dst) & 3u) == 0;
+        if (!ok) {
+            set_error("ct_rtn_wb_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W%d compress "
+                      "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, a 16-byte aligned src, a 4-byte aligned dst, the scale output)", i,
+                      (long long)it.rows, (long long)it.cols, (long long)it.group, bits);
+            return -1;
+        }
+        if (it.zp_packed) {
+            set_error("ct_rtn_wb_batch_plan: item %d gives zp_packed; the stored zero points come from ct_pack_int32_dim0 behind this launch", i);
+            return -1;
+        }
+        it.units = it.rows * (it.cols / 8);
+        it.upg = (int32_t)(g / 8);
+        it.upg_shift = log2_exact(it.upg);
+        it.first_block = blocks;
+        it.main_blocks = cdiv64(it.units / 4, kBlock);
+        it.g_magic = 0;
+        it.g_shift = 0;
+        blocks += it.main_blocks;
+    }
+    if (blocks >= ((int64_t)1 << 31)) {
+        set_error("ct_rtn_wb_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+        return -1;
+    }
+    return blocks;
+}
+
+int ct_rtn_quant_pack_wb_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int bits, int symmetric, ct_stream_t stream) {
+    if (!rtn_wb_bits_ok("ct_rtn_quant_pack_wb_batch", bits)) return CT_ERR_UNSUPPORTED;
+    CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched one-pass compress: 16-bit weights only, got dtype %d", dt);
+    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_REQUIRE(items_dev != nullptr, "the table is required");
+#define CT_RTNWBB(DT, SY) CT_RTN_WB_BITS(bits, hipLaunchKernelGGL((rtn_wb_batch_kernel<DT, B, SY>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n))
+    if (dt == CT_BF16) { if (symmetric) { CT_RTNWBB(CT_BF16, true); } else { CT_RTNWBB(CT_BF16, false); } }
+    else { if (symmetric) { CT_RTNWBB(CT_F16, true); } else { CT_RTNWBB(CT_F16, false); } }
+#undef CT_RTNWBB
+    CT_LAUNCH_CHECK("ct_rtn_quant_pack_wb_batch");
+}
+
+}  // extern "C"

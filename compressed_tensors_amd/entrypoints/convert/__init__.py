@@ -7,7 +7,8 @@ from .converters import CompressedTensorsDequantizer, Converter, build_inverse_w
 from .fp8block import FP8BlockDequantizer, FP8BlockQuantizer
 from .modelopt import ModelOptNvfp4Converter
 from .mxfp8 import MXFP8Quantizer
+from .packq import PackQuantizedQuantizer
 
 __all__ = ["convert_checkpoint", "convert_file", "validate_file", "exec_jobs", "Converter", "build_inverse_weight_maps",
            "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter",
-           "MXFP8Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer"]
+           "MXFP8Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer", "PackQuantizedQuantizer"]

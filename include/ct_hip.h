@@ -264,6 +264,22 @@ int ct_zp4_pack_dim0_batch(const ct_w4_item* items_dev, int n, int64_t total_blo
 int64_t ct_rtn_w4_batch_plan(ct_w4_item* items_host, int n);
 int ct_rtn_quant_pack_w4_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int symmetric, ct_stream_t stream);
 
+/* The same one pass for the integer widths next to 4 and 8 (the reference's W2A16 ... W7A16 presets): bits in {2, 3, 5, 6, 7}.  x is read once;
+ * packed int32 (rows, cols * bits / 32) = pack_to_int32(quantize(x), bits) (compressors/pack_quantized/helpers.py:74-93), scale (rows, cols / group)
+ * in x's dtype and zero point int8 (rows, cols / group) come out.  Bit-identical to ct_minmax_qparams followed by ct_quant_pack.  Needs bf16 / fp16
+ * weights, group = 32 * 2^k <= 2048, cols % group == 0, a 16-byte aligned x, 4-byte aligned packed words.  bits of 4 or 8 and anything outside 2..7
+ * return CT_ERR_UNSUPPORTED with the entry that serves that width named in ct_last_error (ct_rtn_quant_pack_w4, ct_rtn_quant_group8 with words != 0,
+ * ct_minmax_qparams + ct_quant_pack): there is no fallback inside the library.
+ * The table form reads `struct ct_w4_item` exactly as ct_rtn_quant_pack_w4_batch does — src = the weights, dst = packed int32 (rows, cols * bits / 32),
+ * scale / zp = OUTPUTS (zp NULL only in a table launched with symmetric != 0), group <= 0 or >= cols = one group per row, zp_packed = NULL — with ONE
+ * width per launch.  ct_rtn_wb_batch_plan (host only) admits per item what ct_rtn_quant_pack_wb admits, fills the derived fields and returns the
+ * workgroup count, or -1 with the reason in ct_last_error.  The stored zero points of an asymmetric scheme (pack_to_int32(zp, bits, packed_dim=0))
+ * come from ct_pack_int32_dim0 behind the launch.  Bit-identical to ct_rtn_quant_pack_wb per item. */
+int ct_rtn_quant_pack_wb(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int bits, int symmetric, int32_t* packed,
+                         void* scale_out, int8_t* zp_out, ct_stream_t stream);
+int64_t ct_rtn_wb_batch_plan(ct_w4_item* items_host, int n, int bits);
+int ct_rtn_quant_pack_wb_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int bits, int symmetric, ct_stream_t stream);
+
 /* Block-wise 8-bit round-to-nearest in one pass (FP8_BLOCK weights; INT8 blocks, symmetric or not): the block min-max observer over
  * block_h x block_w blocks (maybe_pad_tensor_for_block_quant, helpers.py:400-428: the zero padding of a ragged last row of blocks never exists
  * here, calculate_qparams clamps min <= 0 <= max anyway) + calculate_qparams (helpers.py:50-137) + quantize(strategy = block)

@@ -3,11 +3,12 @@ tables existed), alternated in one process on the same trees: a Llama-3-8B-shape
 layers, 154 modules); W4 g128 symmetric, W4 g128 asymmetric, MXFP4, NVFP4, FP8_BLOCK (`fp8block`: its table form is
 `naive_quantized.base.rtn_block8_windows`, which `compress_model_rtn` does not dispatch to) and MXFP8 (`mxfp8`: the window hook of
 mxfp8-quantized against its `compress_rtn` per module, as that is dispatched) and the channel-wise 8-bit presets FP8_DYNAMIC (`fp8dyn`) and W8A8 (`w8a8`:
-their table form is `naive_quantized.base.rtn_channel8_windows`, likewise not dispatched to).  A compress consumes the model, so the dense weights are kept and re-attached
+their table form is `naive_quantized.base.rtn_channel8_windows`, likewise not dispatched to) and W3 g128 symmetric / asymmetric (`w3`, `w3asym`: the table
+of the widths next to 4 and 8 with its gate forced on, against `compress_rtn` per module — `--packw-single` picks that module path).  A compress consumes the model, so the dense weights are kept and re-attached
 between iterations, outside the timed region.  Prints one JSON line per (tree, scheme): the median wall time per call of both paths after warm-up,
 their min / max (the spread of repeated runs), the time at which the host returns, and the fraction of the HBM peak from the algorithmic bytes.
 
-    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block,mxfp8,fp8dyn,w8a8] [--out FILE]
+    python tools/rtn_bench.py [--reps 7] [--warmup 2] [--trees 8b,tiny] [--schemes w4,w4asym,mxfp4,nvfp4,fp8block,mxfp8,fp8dyn,w8a8,w3,w3asym] [--packw-single shipped|one_pass|composition] [--out FILE]
 """
 import argparse
 import json
@@ -38,6 +39,8 @@ def scheme_of(name):
         args = cta.QuantizationArgs(num_bits=4, group_size=128, symmetric=True, strategy="group")
     elif name == "w4asym":
         args = cta.QuantizationArgs(num_bits=4, group_size=128, symmetric=False, strategy="group")
+    elif name in ("w3", "w3asym"):  # the W3A16 preset and its asymmetric form: the one-pass table of the widths next to 4 and 8
+        args = cta.QuantizationArgs(num_bits=3, group_size=128, symmetric=(name == "w3"), strategy="group")
     elif name == "mxfp4":
         args = cta.QuantizationArgs(num_bits=4, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8)
     elif name == "nvfp4":
@@ -73,6 +76,11 @@ def algorithmic_bytes(name, rows, cols):
         return 2 * n + n + 2 * (-(-rows // 128) * (cols // 128))  # one byte per element and one 16-bit scale per block of 128 x 128
     if name == "nvfp4":
         return 2 * 2 * n + n // 2 + n // 16 + 4  # the weight twice (the tensor-wide amax of generate_gparam is a pass of its own), the float8 scales, the global scale
+    if name in ("w3", "w3asym"):
+        out = 2 * n + 3 * n // 8 + 2 * (n // 128)
+        if name == "w3asym":
+            out += -(-rows * 3 // 32) * (cols // 128) * 4  # weight_zero_point, packed along the rows
+        return out
     out = 2 * n + n // 2 + 2 * (n // 128)
     if name == "w4asym":
         out += -(-rows // 8) * (cols // 128) * 4  # weight_zero_point, packed along the rows
@@ -112,6 +120,8 @@ def main():
     ap.add_argument("--trees", default="8b,tiny")
     ap.add_argument("--schemes", default="w4,w4asym,mxfp4,nvfp4")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--packw-single", default="shipped", choices=("shipped", "one_pass", "composition"),
+                    help="schemes w3 / w3asym: what batched=False runs per module (default: what compress_rtn dispatches)")
     a = ap.parse_args()
     if a.reps < 5:
         raise SystemExit("--reps must be at least 5")
@@ -120,6 +130,13 @@ def main():
     dev = torch.device("cuda:0")
     cta.NVFP4PackedCompressor.RTN_TABLE_MEASURED_FASTER = True  # batched=True measures the NVFP4 table whatever the dispatch constant holds: this is its input
     cta.BaseCompressor.get_value_from_registry("mxfp8-quantized").RTN_TABLE_MEASURED_FASTER = True  # likewise MXFP8's
+    # likewise the table of the widths next to 4 and 8 (schemes w3, w3asym); batched=False stays what `compress_rtn` dispatches per module, or what
+    # --packw-single asks for: "one_pass" = one launch per module, "composition" = the observer and the compress
+    from compressed_tensors_amd.compressors.pack_quantized import base as packq
+
+    packq.RTN_PACKW_TABLE_MEASURED_FASTER.update(dict.fromkeys(packq.RTN_PACKW_TABLE_MEASURED_FASTER, True))
+    if a.packw_single != "shipped":
+        packq.RTN_PACKW_MEASURED_FASTER.update(dict.fromkeys(packq.RTN_PACKW_MEASURED_FASTER, a.packw_single == "one_pass"))
     for tree in a.trees.split(","):
         label, shapes, nlayers = TREES[tree]
         model, pool = build(shapes, nlayers, dev)
@@ -150,6 +167,8 @@ def main():
                         wall[batched].append(t2 - t0)
                         host[batched].append(t1 - t0)
             line = {"tree": label, "modules": len(pool), "scheme": name, "reps": a.reps, "algorithmic_bytes": alg}
+            if name in ("w3", "w3asym"):
+                line["per_module_path"] = a.packw_single
             for batched, key in ((True, "table"), (False, "per_module")):
                 med = statistics.median(wall[batched])
                 line[key] = {"wall_ms_median": round(med * 1e3, 4), "wall_ms_min": round(min(wall[batched]) * 1e3, 4),
