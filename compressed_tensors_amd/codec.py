@@ -131,6 +131,15 @@ __all__ = [
     "RTN_PACKW_BITS",
     "rtn_wb_table_item",
     "launch_rtn_wb_words",
+    "rtn_wb_outputs",
+    "rtn_block8_outputs",
+    "rtn_group8_outputs",
+    "rtn_channel8_outputs",
+    "rtn_w4_launch",
+    "rtn_wb_launch",
+    "rtn_block8_launch",
+    "rtn_group8_launch",
+    "rtn_channel8_launch",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -2154,8 +2163,9 @@ def item_row(src=0, scale=0, zp=0, dst=0, rows=0, cols=0, group=0, zp_packed=0) 
     return _pick_row((src, scale, zp, dst, rows, cols, group, zp_packed, 0))
 
 
-# table kind -> (plan symbol, the plan takes the direction, launch symbol | the launch symbols `d` of `_run_table` picks from — (compress, decompress), or
-# the (fold, quantize) passes that ONE plan of "rtn_nvfp4" serves over the same rows): every table of ct_w4_item rows
+# table kind -> (plan symbol, the plan takes a third argument, launch symbol | the launch symbols `d` of `_run_table` picks from — (compress, decompress), or
+# the (fold, quantize) passes that ONE plan of "rtn_nvfp4" serves over the same rows): every table of ct_w4_item rows.  The plan's third argument is `d`:
+# the direction, or for "rtn_wb" the WIDTH of the table's words
 _TABLES = {
     "w4": ("ct_w4_batch_plan", True, ("ct_quant_pack_batch", "ct_unpack_dequant_batch")),
     "q8": ("ct_q8_batch_plan", True, ("ct_q8_quant_batch", "ct_q8_dequant_batch")),
@@ -2165,14 +2175,11 @@ _TABLES = {
     "rtn_w4": ("ct_rtn_w4_batch_plan", False, "ct_rtn_quant_pack_w4_batch"),
     "rtn_mxfp4": ("ct_rtn_mxfp4_batch_plan", False, "ct_rtn_mxfp4_quant_pack_batch"),
     "rtn_nvfp4": ("ct_rtn_nvfp4_batch_plan", False, ("ct_rtn_nvfp4_amax_batch", "ct_rtn_nvfp4_quant_pack_batch")),
+    "rtn_block8": ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch"),
+    "rtn_group8": ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch"),
+    "rtn_channel8": ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch"),
+    "rtn_wb": ("ct_rtn_wb_batch_plan", True, "ct_rtn_quant_pack_wb_batch"),
 }
-# the same kind of row for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`), handed to `_launch_table` as the row itself: the registry
-# above is pinned to its eight plans by tests/test_host_logic.py, so the ninth stands beside it
-_RTN_BLOCK8_TABLE = ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
-_RTN_GROUP8_TABLE = ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # the one-pass group-wise 8-bit table (`launch_rtn_group8_words`), likewise
-_RTN_CHANNEL8_TABLE = ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch")  # the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`), likewise
-# the one-pass table of the widths next to 4 and 8 (`launch_rtn_wb_words`), likewise; its plan's third argument is the WIDTH, handed over where the directed plans take their direction
-_RTN_WB_TABLE = ("ct_rtn_wb_batch_plan", True, "ct_rtn_quant_pack_wb_batch")
 _Q8_KINDS = {"int8": 0, "fp8": 1, "fp8z": 2}  # the `kind` argument of the 8-bit tables' launches; fp8z: float8 codes with float8 zero points
 
 
@@ -2183,7 +2190,7 @@ def _q8_scalars(dt: int, kind: int, bits: int, d: int) -> tuple:
 
 def _plan_table(kind: str, words, n: int, device, d: int = 0):
     """the first half of `_launch_table`: plan `words` in place and upload them -> (device table, workgroups)"""
-    plan, directed, _ = _TABLES[kind] if isinstance(kind, str) else kind
+    plan, directed, _ = _TABLES[kind]
     if isinstance(words, list):
         words = array.array("q", words)
     addr = words.data_ptr() if isinstance(words, torch.Tensor) else words.buffer_info()[0]
@@ -2196,14 +2203,14 @@ def _plan_table(kind: str, words, n: int, device, d: int = 0):
 
 def _run_table(kind: str, table, n: int, blocks: int, device, d: int, scalars, stream=None) -> None:
     """the second half: ONE launch of a planned, uploaded table"""
-    symbol = (_TABLES[kind] if isinstance(kind, str) else kind)[2]
+    symbol = _TABLES[kind][2]
     call(symbol if isinstance(symbol, str) else symbol[d], table.data_ptr(), n, blocks, *scalars, _lib.stream_on(device, stream))
 
 
 def _launch_table(kind: str, words, n: int, device, d: int = 0, scalars=(), stream=None):
-    """plan, upload and launch one table of `struct ct_w4_item` rows (`kind`: a name of `_TABLES`, or such a row itself): `words` is `n` rows (`item_row`) as a flat CPU int64 tensor or an
+    """plan, upload and launch one table of `struct ct_w4_item` rows (`kind`: a name of `_TABLES`): `words` is `n` rows (`item_row`) as a flat CPU int64 tensor or an
     `array.array("q")`, planned in place, or as a flat list of ints, copied into one; `d`: 0 compress / pack, 1 decompress / unpack (handed to the
-    plans that take it, and picking the launch of the kinds that have two); `scalars`: the launch's arguments between the workgroup count and the stream; `stream`: a raw hipStream_t of `device` (default:
+    plans that take it, and picking the launch of the kinds that have two; the width of an "rtn_wb" table); `scalars`: the launch's arguments between the workgroup count and the stream; `stream`: a raw hipStream_t of `device` (default:
     the caller's current stream there).  Returns the device table, or None for an empty one, before touching the library.
 
     Lifetime, for every entry point built on this: the caller keeps the tensors the rows point at alive.  The device table is allocated and
@@ -2362,20 +2369,54 @@ def unpack_and_dequantize_many(items, *, num_bits, strategy, group_size=None):
     return out
 
 
+def rtn_w4_launch(dtype: torch.dtype, symmetric: bool) -> tuple:
+    """the (kind, d, scalars) of the one-pass W4 table's launch: what `_launch_table` takes behind the words.  Each one-pass table has such a function, so
+    that its launch's arguments are written once: `launch_rtn_*_words` and the dense-checkpoint quantizers (entrypoints/convert/dense.py) both go through it"""
+    return "rtn_w4", 0, (DT[dtype], int(bool(symmetric)))
+
+
+def rtn_wb_launch(dtype: torch.dtype, num_bits: int, symmetric: bool) -> tuple:
+    """`rtn_w4_launch` for the table of the widths next to 4 and 8 (`RTN_PACKW_BITS`; the plan refuses any other): `d` is the width, the plan's third argument"""
+    return "rtn_wb", int(num_bits), (DT[dtype], int(num_bits), int(bool(symmetric)))
+
+
+def rtn_block8_launch(dtype: torch.dtype, fp8: bool, symmetric: bool) -> tuple:
+    """`rtn_w4_launch` for the one-pass block-wise 8-bit table"""
+    return "rtn_block8", 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))
+
+
+def rtn_group8_launch(dtype: torch.dtype, device: torch.device, kind: int, symmetric: bool = True, as_words: bool = False) -> tuple:
+    """`rtn_w4_launch` for the one-pass group-wise 8-bit table; an MXFP8 table (`kind` 4) reads `_mx_code_table` of the weights' dtype on `device`"""
+    lut = _mx_code_table(dtype, device).data_ptr() if int(kind) == _QP_MXFP8 else None  # cached per (dtype, device): outlives the launch
+    return "rtn_group8", 0, (DT[dtype], int(kind), int(bool(symmetric)), int(bool(as_words)), lut)
+
+
+def rtn_channel8_launch(dtype: torch.dtype, fp8: bool, symmetric: bool) -> tuple:
+    """`rtn_w4_launch` for the one-pass channel-wise 8-bit table"""
+    return "rtn_channel8", 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))
+
+
+def _launch_rtn(words, n: int, device, launch, *args):
+    """one launch of a one-pass table under `launch(*args)`'s (kind, d, scalars); an empty table returns None before anything about it is looked at"""
+    if not n:
+        return None
+    kind, d, scalars = launch(*args)
+    return _launch_table(kind, words, n, device, d, scalars)
+
+
 def launch_rtn_w4_words(words, n: int, dtype: torch.dtype, device: torch.device, symmetric: bool) -> torch.Tensor:
     """`launch_w4_words` for a table of the one-pass round-to-nearest W4 compress (`ct_rtn_quant_pack_w4_batch`): src = weights, dst = packed words,
     scale / zp = OUTPUTS, zp_packed = 0.  Returns the device table (the caller owes it a `record_stream` when its stream is not the allocator's) or
     None for an empty table."""
-    return _launch_table("rtn_w4", words, n, device, 0, (DT[dtype], int(bool(symmetric)))) if n else None
+    return _launch_rtn(words, n, device, rtn_w4_launch, dtype, symmetric)
 
 
 def launch_rtn_wb_words(words, n: int, dtype: torch.dtype, device: torch.device, num_bits: int, symmetric: bool) -> torch.Tensor:
     """`launch_rtn_w4_words` for a table of the one-pass compress of the widths next to 4 and 8 (`ct_rtn_quant_pack_wb_batch`, `RTN_PACKW_BITS`): the same
     rows, dst = packed int32 (R, C * num_bits / 32), ONE width per table"""
-    bits = int(num_bits)
-    if bits not in RTN_PACKW_BITS:
+    if int(num_bits) not in RTN_PACKW_BITS:
         raise NotImplementedError(f"the one-pass table of the widths next to 4 and 8 takes num_bits in {RTN_PACKW_BITS}, got {num_bits}")
-    return _launch_table(_RTN_WB_TABLE, words, n, device, bits, (DT[dtype], bits, int(bool(symmetric)))) if n else None
+    return _launch_rtn(words, n, device, rtn_wb_launch, dtype, num_bits, symmetric)
 
 
 def launch_rtn_mxfp4_words(words, n: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
@@ -2400,7 +2441,7 @@ def launch_rtn_nvfp4_words(words, n: int, dtype: torch.dtype, device: torch.devi
 def launch_rtn_block8_words(words, n: int, dtype: torch.dtype, device: torch.device, fp8: bool, symmetric: bool) -> torch.Tensor:
     """`launch_rtn_w4_words` for a table of the one-pass block-wise 8-bit compress (`ct_rtn_quant_block8_batch`): src = weights, dst = codes,
     scale / zp = OUTPUTS (zp 0 in a FLOAT or symmetric table), group = -((bh << 24) | bw)"""
-    return _launch_table(_RTN_BLOCK8_TABLE, words, n, device, 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))) if n else None
+    return _launch_rtn(words, n, device, rtn_block8_launch, dtype, fp8, symmetric)
 
 
 def launch_rtn_group8_words(words, n: int, dtype: torch.dtype, device: torch.device, kind: int, symmetric: bool = True, as_words: bool = False) -> torch.Tensor:
@@ -2408,16 +2449,13 @@ def launch_rtn_group8_words(words, n: int, dtype: torch.dtype, device: torch.dev
     scale / zp = OUTPUTS (scale may be 0 in an MXFP8 table, zp 0 in a FLOAT or symmetric one), zp_packed = the E8M0 code output of an MXFP8
     table, group = the group size; `kind` 0 INT (`as_words`: the (code + 128) bytes of pack-quantized), 1 FP8, 4 MXFP8 (with `_mx_code_table` of the
     weights' dtype behind it)"""
-    if not n:
-        return None
-    lut = _mx_code_table(dtype, device).data_ptr() if int(kind) == _QP_MXFP8 else None  # cached per (dtype, device): outlives the launch
-    return _launch_table(_RTN_GROUP8_TABLE, words, n, device, 0, (DT[dtype], int(kind), int(bool(symmetric)), int(bool(as_words)), lut))
+    return _launch_rtn(words, n, device, rtn_group8_launch, dtype, device, kind, symmetric, as_words)
 
 
 def launch_rtn_channel8_words(words, n: int, dtype: torch.dtype, device: torch.device, fp8: bool, symmetric: bool) -> torch.Tensor:
     """`launch_rtn_w4_words` for a table of the one-pass channel-wise 8-bit compress (`ct_rtn_quant_channel8_batch`): src = weights, dst = codes,
     scale / zp = OUTPUTS (zp 0 in a FLOAT or symmetric table: the plan reads an item with a zero-point output as asymmetric)"""
-    return _launch_table(_RTN_CHANNEL8_TABLE, words, n, device, 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))) if n else None
+    return _launch_rtn(words, n, device, rtn_channel8_launch, dtype, fp8, symmetric)
 
 
 def rtn_w4_group(shape, group_size) -> int:
@@ -2436,74 +2474,89 @@ def _rtn_table_tensor(x) -> bool:
     return x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and x.data_ptr() % 16 == 0
 
 
-def rtn_w4_table_item(x, group_size, with_zp: bool = True):
-    """does the one-pass W4 table (`launch_rtn_w4_words`) take this weight — on a GPU, 2-D, contiguous, 16-byte aligned, 16-bit, with a group
-    `rtn_w4_group` accepts?  Then its freshly allocated outputs and its row: (packed int32 (R, C / 8), scale (R, C / g), int8 zero point (R, C / g)
-    or None without `with_zp` — a symmetric table needs no zero-point output, the kernel skips the store —, row); else None"""
-    g = rtn_w4_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
-    if not g:
-        return None
-    rows, cols = int(x.shape[0]), int(x.shape[1])
-    packed = torch.empty((rows, cols // 8), dtype=torch.int32, device=x.device)
-    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
-    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
-    return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
+# Each scheme's outputs are written once, as a pure function (rows, cols, dtype, options) -> [(field, shape, dtype)]: `field` is the `ct_w4_item` field
+# that takes the output's address.  `rtn_*_table_item` allocates from it; a dense-checkpoint quantizer (entrypoints/convert/dense.py) lays out its output
+# buffer and fills its rows from it, also for a weight its table refuses — so a shape here is the reference's for EVERY weight (ceil where the table only
+# admits whole words or blocks).
+def rtn_wb_outputs(rows: int, cols: int, dtype, group: int, num_bits: int, with_zp: bool = True) -> list:
+    """the one-pass pack-quantized tables (`rtn_w4` at 4 bits, `rtn_wb` at the widths beside it): packed int32 (R, ceil(C * num_bits / 32)), scale
+    (R, C / g), int8 zero point (R, C / g) — a symmetric table needs no zero-point output, the kernel skips the store"""
+    grid = (rows, cols // group)
+    return [("dst", (rows, -(-cols * num_bits // 32)), torch.int32), ("scale", grid, dtype)] + ([("zp", grid, torch.int8)] if with_zp else [])
+
+
+def rtn_block8_outputs(rows: int, cols: int, dtype, block_structure, fp8: bool = True, with_zp: bool = False) -> list:
+    """the one-pass block-wise 8-bit table: codes float8_e4m3fn — int8 without `fp8` — (R, C), scale (ceil(R / bh), ceil(C / bw)), int8 zero point of
+    that shape"""
+    grid = (-(-rows // int(block_structure[0])), -(-cols // int(block_structure[1])))
+    return [("dst", (rows, cols), _F8 if fp8 else torch.int8), ("scale", grid, dtype)] + ([("zp", grid, torch.int8)] if with_zp else [])
+
+
+def rtn_channel8_outputs(rows: int, cols: int, dtype, fp8: bool = True, with_zp: bool = False) -> list:
+    """the one-pass channel-wise 8-bit table: codes float8_e4m3fn — int8 without `fp8` — (R, C), scale (R, 1), int8 zero point (R, 1) (an asymmetric
+    scheme's)"""
+    return [("dst", (rows, cols), _F8 if fp8 else torch.int8), ("scale", (rows, 1), dtype)] + ([("zp", (rows, 1), torch.int8)] if with_zp else [])
+
+
+def rtn_group8_outputs(rows: int, cols: int, dtype, group: int, qtype: str = "int", with_zp: bool = False, mx: bool = False, words: bool = False,
+                       with_scale: bool = True) -> list:
+    """the one-pass group-wise 8-bit table: codes — float8_e4m3fn for qtype "float", int8 for "int", int32 (R, C / 4) with `words` —, scale (R, C / g)
+    (an MXFP8 table may leave it out: `with_scale`), int8 zero point of that shape (INT only) and, with `mx`, the E8M0 codes uint8 (R, C / 32)"""
+    fp8 = getattr(qtype, "value", qtype) == "float"
+    grid = (rows, cols // group)
+    out = [("dst", (rows, cols // 4), torch.int32) if words else ("dst", (rows, cols), _F8 if fp8 else torch.int8)]
+    if with_scale or not mx:
+        out.append(("scale", grid, dtype))
+    if with_zp and not fp8:
+        out.append(("zp", grid, torch.int8))
+    return out + [("zp_packed", grid, torch.uint8)] if mx else out
+
+
+def _rtn_item(x, group: int, entries, fields=("dst", "scale", "zp")) -> tuple:
+    """the freshly allocated outputs of `entries` in the order of `fields` (None for one that `entries` leaves out) and, last, the table row of `x` that
+    points at them"""
+    outs = {field: torch.empty(shape, dtype=dtype, device=x.device) for field, shape, dtype in entries}
+    at = {field: t.data_ptr() for field, t in outs.items()}
+    row = item_row(x.data_ptr(), at.get("scale", 0), at.get("zp", 0), at["dst"], int(x.shape[0]), int(x.shape[1]), group, at.get("zp_packed", 0))
+    return tuple(outs.get(field) for field in fields) + (row,)
 
 
 def rtn_wb_table_item(x, group_size, num_bits: int, with_zp: bool = True):
-    """`rtn_w4_table_item` for the one-pass table of the widths next to 4 and 8 (`launch_rtn_wb_words`; the same admission, `rtn_w4_group`):
-    (packed int32 (R, C * num_bits / 32), scale (R, C / g), int8 zero point (R, C / g) or None without `with_zp`, row) or None"""
+    """does the one-pass table of this width (`launch_rtn_w4_words` at 4 bits, `launch_rtn_wb_words` at the widths beside it) take this weight — on a GPU,
+    2-D, contiguous, 16-byte aligned, 16-bit, with a group `rtn_w4_group` accepts?  Then its freshly allocated outputs (`rtn_wb_outputs`) and its row:
+    (packed, scale, zero point or None without `with_zp`, row); else None"""
     g = rtn_w4_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
-    if not g:
-        return None
-    rows, cols = int(x.shape[0]), int(x.shape[1])
-    packed = torch.empty((rows, cols * int(num_bits) // 32), dtype=torch.int32, device=x.device)
-    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device)
-    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp else None
-    return packed, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, packed.data_ptr(), rows, cols, g)
+    return _rtn_item(x, g, rtn_wb_outputs(int(x.shape[0]), int(x.shape[1]), x.dtype, g, int(num_bits), with_zp)) if g else None
+
+
+def rtn_w4_table_item(x, group_size, with_zp: bool = True):
+    """`rtn_wb_table_item` at 4 bits: (packed int32 (R, C / 8), scale, zero point or None, row) or None"""
+    return rtn_wb_table_item(x, group_size, 4, with_zp)
 
 
 def rtn_block8_table_item(x, block_structure, fp8: bool = True, with_zp: bool = False):
-    """`rtn_w4_table_item` for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`; `rtn_block8_group`): (codes float8_e4m3fn — int8
-    without `fp8` — (R, C), scale (ceil(R / bh), C / bw), int8 zero point of that shape or None without `with_zp`, row) or None"""
+    """`rtn_wb_table_item` for the one-pass block-wise 8-bit table (`launch_rtn_block8_words`; `rtn_block8_group`, `rtn_block8_outputs`): (codes, scale,
+    zero point or None without `with_zp`, row) or None"""
     g = rtn_block8_group(x.shape, block_structure) if _rtn_table_tensor(x) else 0
-    if not g:
-        return None
-    rows, cols = int(x.shape[0]), int(x.shape[1])
-    grid = (-(-rows // int(block_structure[0])), cols // int(block_structure[1]))
-    q = torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
-    scale = torch.empty(grid, dtype=x.dtype, device=x.device)
-    zp = torch.empty(grid, dtype=torch.int8, device=x.device) if with_zp else None
-    return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, g)
+    return _rtn_item(x, g, rtn_block8_outputs(int(x.shape[0]), int(x.shape[1]), x.dtype, block_structure, fp8, with_zp)) if g else None
 
 
 def rtn_channel8_table_item(x, fp8: bool = True, with_zp: bool = False):
-    """`rtn_w4_table_item` for the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`; `rtn_channel8_form`): (codes float8_e4m3fn — int8
-    without `fp8` — (R, C), scale (R, 1), int8 zero point (R, 1) or None without `with_zp` (an asymmetric scheme's), row) or None"""
+    """`rtn_wb_table_item` for the one-pass channel-wise 8-bit table (`launch_rtn_channel8_words`; `rtn_channel8_form`, `rtn_channel8_outputs`): (codes,
+    scale, zero point or None without `with_zp`, row) or None"""
     if not _rtn_table_tensor(x) or not rtn_channel8_form(x.shape, not with_zp):
         return None
-    rows, cols = int(x.shape[0]), int(x.shape[1])
-    q = torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
-    scale = torch.empty((rows, 1), dtype=x.dtype, device=x.device)
-    zp = torch.empty((rows, 1), dtype=torch.int8, device=x.device) if with_zp else None
-    return q, scale, zp, item_row(x.data_ptr(), scale.data_ptr(), zp.data_ptr() if with_zp else 0, q.data_ptr(), rows, cols, 0)
+    return _rtn_item(x, 0, rtn_channel8_outputs(int(x.shape[0]), int(x.shape[1]), x.dtype, fp8, with_zp))
 
 
 def rtn_group8_table_item(x, group_size, qtype: str = "int", with_zp: bool = False, mx: bool = False, words: bool = False, with_scale: bool = True):
-    """`rtn_w4_table_item` for the one-pass group-wise 8-bit table (`launch_rtn_group8_words`; `rtn_group8_group`): (codes — float8_e4m3fn for
-    qtype "float", int8 for "int", int32 (R, C / 4) with `words` —, scale (R, C / g) or None without `with_scale` (MXFP8 only), int8 zero point of
-    that shape or None without `with_zp`, [E8M0 codes uint8 (R, C / 32) with `mx`,] row) or None"""
+    """`rtn_wb_table_item` for the one-pass group-wise 8-bit table (`launch_rtn_group8_words`; `rtn_group8_group`, `rtn_group8_outputs`): (codes, scale
+    or None without `with_scale` (MXFP8 only), zero point or None without `with_zp`, [E8M0 codes with `mx`,] row) or None"""
     g = rtn_group8_group(x.shape, group_size) if _rtn_table_tensor(x) else 0
     if not g or (mx and g != 32):
         return None
-    fp8 = getattr(qtype, "value", qtype) == "float"
-    rows, cols = int(x.shape[0]), int(x.shape[1])
-    q = torch.empty((rows, cols // 4), dtype=torch.int32, device=x.device) if words else torch.empty((rows, cols), dtype=_F8 if fp8 else torch.int8, device=x.device)
-    scale = torch.empty((rows, cols // g), dtype=x.dtype, device=x.device) if with_scale or not mx else None
-    zp = torch.empty((rows, cols // g), dtype=torch.int8, device=x.device) if with_zp and not fp8 else None
-    code = torch.empty((rows, cols // g), dtype=torch.uint8, device=x.device) if mx else None
-    row = item_row(x.data_ptr(), _word(scale), _word(zp), q.data_ptr(), rows, cols, g, _word(code))
-    return (q, scale, zp, code, row) if mx else (q, scale, zp, row)
+    entries = rtn_group8_outputs(int(x.shape[0]), int(x.shape[1]), x.dtype, g, qtype, with_zp, mx, words, with_scale)
+    return _rtn_item(x, g, entries, ("dst", "scale", "zp", "zp_packed") if mx else ("dst", "scale", "zp"))
 
 
 def _rtn_fp4_takes(x) -> bool:

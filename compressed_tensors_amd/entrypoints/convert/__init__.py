@@ -2,12 +2,10 @@
 GPU decompress, safetensors out — the on-disk consumer of the decompress hot path."""
 from .autoawq import AutoAWQConverter
 from .convert_checkpoint import convert_checkpoint, convert_file, exec_jobs, validate_file
-from .channel8 import FP8DynamicQuantizer, W8A8Quantizer
 from .converters import CompressedTensorsDequantizer, Converter, build_inverse_weight_maps
-from .fp8block import FP8BlockDequantizer, FP8BlockQuantizer
+from .dense import FP8BlockQuantizer, FP8DynamicQuantizer, MXFP8Quantizer, PackQuantizedQuantizer, W8A8Quantizer
+from .fp8block import FP8BlockDequantizer
 from .modelopt import ModelOptNvfp4Converter
-from .mxfp8 import MXFP8Quantizer
-from .packq import PackQuantizedQuantizer
 
 __all__ = ["convert_checkpoint", "convert_file", "validate_file", "exec_jobs", "Converter", "build_inverse_weight_maps",
            "CompressedTensorsDequantizer", "AutoAWQConverter", "FP8BlockDequantizer", "FP8BlockQuantizer", "ModelOptNvfp4Converter",

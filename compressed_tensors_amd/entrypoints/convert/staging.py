@@ -1,7 +1,7 @@
 """The host side of one shard's round trip, shared by the converters: the shard's tensors go to the GPU through one pinned buffer
 and one copy (`_stage_to_device`), every output lives in ONE device buffer (`device_outputs`), one launch per table the library's
-planner accepts converts them (`launch_tables`), and the results come back through one pinned buffer with an event behind every
-~32 MB (`return_to_host`); `settle` synchronises unless the caller streams its results.  `output_layout` and `d2h_chunks` are
+planner accepts converts them (`launch_tables`; `table_calls` gives its plan and launch for a table of `codec._TABLES`), and the
+results come back through one pinned buffer with an event behind every ~32 MB (`return_to_host`); `settle` synchronises unless the caller streams its results.  `output_layout` and `d2h_chunks` are
 pure functions of the output specs `[(name, shape, dtype)]`."""
 import array
 import contextlib
@@ -143,6 +143,20 @@ def plan_tables(items, modules, item_type, plan):
         raise ValueError(f"{modules[0]}: {_lib.last_error()}")
     half = len(items) // 2
     return plan_tables(items[:half], modules[:half], item_type, plan) + plan_tables(items[half:], modules[half:], item_type, plan)
+
+
+def table_calls(kind: str, d: int, scalars):
+    """the `plan` and `launch` of `launch_tables` for a table of `codec._TABLES`, from the (kind, d, scalars) that codec's `rtn_*_launch` functions
+    give: the symbols are resolved through the registry, so a converter names no library function and rebuilds no argument list"""
+    from ... import _lib
+    from ...codec import _TABLES
+
+    plan_symbol, directed, launch_symbol = _TABLES[kind]
+    lib = _lib.load()
+    plan_fn = getattr(lib, plan_symbol)
+    launch_fn = getattr(lib, launch_symbol if isinstance(launch_symbol, str) else launch_symbol[d])
+    plan = (lambda table, n: plan_fn(table, n, d)) if directed else plan_fn
+    return plan, lambda table, n, blocks, handle: launch_fn(table, n, blocks, *scalars, handle)
 
 
 def launch_tables(items, modules, item_type, plan, launch, dev) -> None:

@@ -68,7 +68,7 @@ def test_symbols_exported_declared_and_prototyped(lib):
     assert lib.ct_abi_version() == 2 and ctypes.sizeof(_lib.W4Item) == 13 * 8  # additive: nothing an existing caller sees moved
     for name in ("rtn_quantize_block8", "rtn_quantize_block8_many", "rtn_block8_table_item"):
         assert callable(getattr(codec, name)) and name in codec.__all__
-    assert codec._RTN_BLOCK8_TABLE == ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")  # a row of the kind codec._TABLES holds
+    assert codec._TABLES["rtn_block8"] == ("ct_rtn_block8_batch_plan", False, "ct_rtn_quant_block8_batch")
     assert codec.launch_rtn_block8_words(None, 0, None, torch.device("cpu"), True, True) is None  # an empty table: nothing is touched
 
 

@@ -69,8 +69,7 @@ def test_symbols_exported_declared_and_prototyped(lib):
     for name in ("rtn_quantize_channel8", "rtn_quantize_channel8_many", "rtn_channel8_table_item", "rtn_channel8_form", "launch_rtn_channel8_words"):
         assert callable(getattr(codec, name)) and name in codec.__all__
     assert codec.RTN_CHANNEL8_MAX_COLS == C.MAX_COLS == 65536
-    assert codec._RTN_CHANNEL8_TABLE == ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch")  # a row of the kind codec._TABLES holds
-    assert codec._RTN_CHANNEL8_TABLE not in codec._TABLES.values()
+    assert codec._TABLES["rtn_channel8"] == ("ct_rtn_channel8_batch_plan", False, "ct_rtn_quant_channel8_batch")
     assert codec.launch_rtn_channel8_words(None, 0, None, torch.device("cpu"), True, True) is None  # an empty table: nothing is touched
 
 

@@ -329,6 +329,11 @@ def test_quantizer_process_on_a_two_module_shard(cta, dev, ref, golden, name, ki
     for key, t in tensors.items():
         if not (key.endswith(".weight") and key[:-7] in SHARD_KEYS):
             assert out[key] is t, key  # the same object: the ignored lm_head, the embedding, the 1-D norms, the bias
+    conv.stream_results = True
+    streamed = conv.process(dict(tensors))
+    assert streamed.ready
+    streamed.wait()
+    assert all(same(streamed[n], out[n]) for n in out)
 
 
 @pytest.mark.parametrize("name,kind,fmt", [("FP8DynamicQuantizer", "fp8", "float-quantized"), ("W8A8Quantizer", "int8", "int-quantized")])

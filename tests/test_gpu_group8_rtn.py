@@ -363,6 +363,11 @@ def test_quantizer_process_on_a_two_module_shard(cta, dev, golden):
     for name, t in tensors.items():
         if not (name.endswith(".weight") and name[:-7] in keys):
             assert out[name] is t, name  # the same object
+    conv.stream_results = True
+    streamed = conv.process(dict(tensors))
+    assert streamed.ready
+    streamed.wait()
+    assert all(same(streamed[n], out[n]) for n in out)
     ragged = dict(tensors)
     ragged["model.layers.0.mlp.up_proj.weight"] = torch.ones((2, 40), dtype=BF16)
     with pytest.raises(ValueError):

@@ -302,6 +302,11 @@ def test_quantizer_process_equals_compress_rtn_per_module(cta, dev, b, s):
     for name, t in tensors.items():
         if not (name.endswith(".weight") and name[:-7] in SHARD_KEYS):
             assert out[name] is t, name  # the same object
+    conv.stream_results = True
+    streamed = conv.process(dict(tensors))
+    assert streamed.ready
+    streamed.wait()
+    assert all(same(streamed[n], out[n]) for n in out)
     ragged = dict(tensors)
     ragged["model.layers.0.mlp.gate_proj.weight"] = torch.ones((2, 40), dtype=BF16)
     with pytest.raises(ValueError):

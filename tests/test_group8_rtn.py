@@ -65,8 +65,7 @@ def test_symbols_exported_declared_and_prototyped(lib):
     assert lib.ct_abi_version() == 2 and ctypes.sizeof(_lib.W4Item) == 13 * 8  # additive: nothing an existing caller sees moved
     for name in ("rtn_quantize_group8", "rtn_quantize_group8_many", "rtn_group8_table_item", "rtn_group8_group", "launch_rtn_group8_words"):
         assert callable(getattr(codec, name)) and name in codec.__all__
-    assert codec._RTN_GROUP8_TABLE == ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")  # a row of the kind codec._TABLES holds
-    assert len(codec._TABLES) == 8 and codec._RTN_GROUP8_TABLE not in codec._TABLES.values()
+    assert codec._TABLES["rtn_group8"] == ("ct_rtn_group8_batch_plan", False, "ct_rtn_quant_group8_batch")
     assert codec.launch_rtn_group8_words(None, 0, None, torch.device("cpu"), 4) is None  # an empty table: nothing is touched
 
 

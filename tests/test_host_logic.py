@@ -766,15 +766,16 @@ def test_the_launcher_table_names_every_item_table_once(cta):
     from compressed_tensors_amd import _lib, codec
 
     item_plans = {"ct_w4_batch_plan", "ct_q8_batch_plan", "ct_fp4_batch_plan", "ct_mx_scale_batch_plan", "ct_zp4_batch_plan", "ct_rtn_w4_batch_plan",
-                  "ct_rtn_mxfp4_batch_plan", "ct_rtn_nvfp4_batch_plan"}
+                  "ct_rtn_mxfp4_batch_plan", "ct_rtn_nvfp4_batch_plan", "ct_rtn_block8_batch_plan", "ct_rtn_group8_batch_plan", "ct_rtn_channel8_batch_plan",
+                  "ct_rtn_wb_batch_plan"}
     assert item_plans <= set(_lib.EXPORTED_SYMBOLS)
     plans = [plan for plan, _, _ in codec._TABLES.values()]
-    assert sorted(plans) == sorted(item_plans)  # each of the eight in exactly one kind
+    assert len(item_plans) == 12 and sorted(plans) == sorted(item_plans)  # each of the twelve in exactly one kind
     cpu = torch.device("cpu")
     for kind, (plan, directed, launch) in codec._TABLES.items():
         symbols = (launch,) if isinstance(launch, str) else launch
         assert len(symbols) in (1, 2) and {plan, *symbols} <= set(_lib.EXPORTED_SYMBOLS), kind
-        assert directed == (len(_lib._PROTOTYPES[plan][0]) == 3), kind  # (items, n[, direction])
+        assert directed == (len(_lib._PROTOTYPES[plan][0]) == 3), kind  # (items, n[, direction — the width for rtn_wb])
         assert codec._launch_table(kind, None, 0, cpu) is None  # (words None: nothing reads them)
     # an empty table returns before anything about it is looked at, a dtype the library does not know included
     assert codec.launch_rtn_w4_words(None, 0, None, cpu, True) is None and codec.launch_rtn_mxfp4_words(None, 0, None, cpu) is None
@@ -791,6 +792,49 @@ def test_the_launcher_table_names_every_item_table_once(cta):
         with pytest.raises(ValueError) as err:
             codec.launch_w4_words(words, 1, "compress", torch.bfloat16, cpu)
         assert "ct_w4_batch_plan" in str(err.value) and "item 0" in str(err.value), str(err.value)
+
+
+def test_the_dense_checkpoint_quantizers_share_one_body(cta):
+    """the five dense-checkpoint quantizers are subclasses of one base that owns `process`, `validate`, `get_dependencies` and `create_config`; each
+    class's config keeps the envelope and the `weights` / `input_activations` it wrote when it carried its own copy"""
+    from compressed_tensors_amd.entrypoints import convert
+    from compressed_tensors_amd.entrypoints.convert.dense import _DenseQuantizer
+
+    def args(**changed):
+        return {"num_bits": 8, "type": "float", "symmetric": True, "group_size": None, "strategy": "channel", "block_structure": None, "dynamic": False,
+                "actorder": None, "scale_dtype": None, "zp_dtype": None, "observer": "memoryless_minmax", "observer_kwargs": {}, **changed}
+
+    recorded = [  # (class, constructor arguments, format, weights, input_activations)
+        ("FP8BlockQuantizer", {}, "float-quantized", args(strategy="block", block_structure=[128, 128]),
+         args(group_size=128, strategy="group", dynamic=True, observer=None)),
+        ("FP8BlockQuantizer", dict(weight_block_size=(64, 32)), "float-quantized", args(strategy="block", block_structure=[64, 32]),
+         args(group_size=128, strategy="group", dynamic=True, observer=None)),
+        ("MXFP8Quantizer", {}, "mxfp8-quantized", args(group_size=32, strategy="group", scale_dtype="torch.uint8"),
+         args(group_size=32, strategy="group", scale_dtype="torch.uint8", dynamic=True, observer=None)),
+        ("FP8DynamicQuantizer", {}, "float-quantized", args(), args(strategy="token", dynamic=True, observer=None)),
+        ("W8A8Quantizer", {}, "int-quantized", args(type="int"), args(type="int", strategy="token", dynamic=True, observer=None)),
+        ("PackQuantizedQuantizer", {}, "pack-quantized", args(num_bits=4, type="int", group_size=128, strategy="group"), None),
+        ("PackQuantizedQuantizer", dict(num_bits=3, group_size=64, symmetric=False), "pack-quantized",
+         args(num_bits=3, type="int", symmetric=False, group_size=64, strategy="group", zp_dtype="torch.int8"), None),
+        ("PackQuantizedQuantizer", dict(num_bits=6, strategy="channel"), "pack-quantized", args(num_bits=6, type="int"), None),
+    ]
+    assert {name for name, *_ in recorded} == {"FP8BlockQuantizer", "MXFP8Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer", "PackQuantizedQuantizer"}
+    for name, kw, fmt, weights, inputs in recorded:
+        cls = getattr(convert, name)
+        assert issubclass(cls, _DenseQuantizer) and issubclass(cls, convert.Converter), name
+        for method in ("process", "validate", "get_dependencies", "create_config"):
+            assert getattr(cls, method) is getattr(_DenseQuantizer, method), (name, method)  # inherited, by every class on the way
+        cfg = cls(targets=["re:.*proj$"], ignore=["lm_head"], **kw).create_config().model_dump()
+        assert list(cfg) == ["config_groups", "quant_method", "kv_cache_scheme", "format", "quantization_status", "global_compression_ratio", "ignore"], name
+        assert (cfg["quant_method"], cfg["kv_cache_scheme"], cfg["format"], cfg["quantization_status"], cfg["global_compression_ratio"], cfg["ignore"]) == (
+            "compressed-tensors", None, fmt, "compressed", None, ["lm_head"]), name
+        assert list(cfg["config_groups"]) == ["config_group_0"]
+        group = cfg["config_groups"]["config_group_0"]
+        assert list(group) == ["targets", "weights", "input_activations", "output_activations", "format"], name
+        assert group["targets"] == ["re:.*proj$"] and group["output_activations"] is None and group["format"] == fmt, name
+        assert group["weights"] == weights and list(group["weights"]) == list(weights), (name, kw, group["weights"])
+        assert group["input_activations"] == inputs and (inputs is None or list(group["input_activations"]) == list(inputs)), (name, kw)
+        assert cls(**kw).create_config().model_dump()["config_groups"]["config_group_0"]["targets"] == ["Linear"]
 
 
 def test_rtn_window_driver_against_a_recording_codec(cta, monkeypatch):

@@ -65,8 +65,7 @@ def test_symbols_exported_declared_and_prototyped(lib):
     for name in ("rtn_quantize_and_pack", "rtn_quantize_and_pack_many", "rtn_wb_table_item", "launch_rtn_wb_words", "RTN_PACKW_BITS"):
         assert hasattr(codec, name) and name in codec.__all__
     assert codec.RTN_PACKW_BITS == C.BITS
-    assert codec._RTN_WB_TABLE == ("ct_rtn_wb_batch_plan", True, "ct_rtn_quant_pack_wb_batch")  # a row of the kind codec._TABLES holds: the plan's third argument is the width
-    assert len(codec._TABLES) == 8 and codec._RTN_WB_TABLE not in codec._TABLES.values()
+    assert codec._TABLES["rtn_wb"] == ("ct_rtn_wb_batch_plan", True, "ct_rtn_quant_pack_wb_batch")  # the plan's third argument is the width
     assert codec.launch_rtn_wb_words(None, 0, None, torch.device("cpu"), 3, True) is None  # an empty table: nothing is touched
 
 
