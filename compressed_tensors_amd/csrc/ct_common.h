@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/ct_hip.h"
 
@@ -50,6 +51,37 @@ inline int dt_size(int dt) {
     return 0;
 }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <unsigned N>  // N a power of two; NULL is aligned to everything
+inline bool aligned_to(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(N - 1)) == 0; }
+
+// the "bad batch size" check of a `_batch` entry; CT_BATCH_ARGS adds the early return for an empty table (an entry with checks of its own between
+// the two keeps its return where it is)
+#define CT_BATCH_SIZE(n, total_blocks) CT_REQUIRE((n) >= 0 && (total_blocks) >= 0 && (total_blocks) < ((int64_t)1 << 31), "bad batch size")
+#define CT_BATCH_ARGS(n, total_blocks)                     \
+    do {                                                   \
+        CT_BATCH_SIZE(n, total_blocks);                    \
+        if ((n) == 0 || (total_blocks) == 0) return CT_OK; \
+    } while (0)
+
+// ------------------------------------------------------------------------- runtime value -> template argument
+// A launch by a runtime dtype / flag is one expression in a generic lambda:
+//   for_dt16(xdt, [&](auto DT) { for_bool(symmetric, [&](auto SY) { hipLaunchKernelGGL((kernel<DT(), SY()>), ...); }); });
+template <typename F>
+inline void for_dt16(int dt, F&& f) {  // CT_BF16, else CT_F16 (the caller has checked the dtype)
+    if (dt == CT_BF16) f(std::integral_constant<int, CT_BF16>{});
+    else f(std::integral_constant<int, CT_F16>{});
+}
+template <typename F>
+inline void for_dt(int dt, F&& f) {  // CT_BF16, CT_F16, else CT_F32
+    if (dt == CT_BF16) f(std::integral_constant<int, CT_BF16>{});
+    else if (dt == CT_F16) f(std::integral_constant<int, CT_F16>{});
+    else f(std::integral_constant<int, CT_F32>{});
+}
+template <typename F>
+inline void for_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // log2 of a power of two, or -1
 inline int log2_exact(int64_t v) {

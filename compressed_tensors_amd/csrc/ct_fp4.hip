@@ -19,6 +19,7 @@
 // (tests/test_gpu_parity.py).  -0.0 inputs are folded to +0.0 with one add before the conversion.
 #include "ct_common.h"
 #include "ct_minmax.h"
+#include "ct_plan.h"
 
 namespace ct {
 
@@ -704,29 +705,22 @@ static int fp4_quant_pack_impl(const void* x, int xdt, const void* scale, int sd
     const int shift = group == 16 ? 1 : 2;
     CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     dim3 grid((unsigned)cdiv64(lanes, kBlock));
-    const bool lean = units % 4 == 0 && (reinterpret_cast<uintptr_t>(scale) & 7u) == 0;
+    const bool lean = units % 4 == 0 && aligned_to<8>(scale);
     if (stored) {  // the stored scales ride the lean kernel only; NVFP4 any float scale, MXFP4 16-bit scales through the caller's table
-        if (!lean || (group == 32 && (sdt == CT_F32 || mx_lut == nullptr)) || (group == 16 && (reinterpret_cast<uintptr_t>(stored) & 1u)))
+        if (!lean || (group == 32 && (sdt == CT_F32 || mx_lut == nullptr)) || (group == 16 && !aligned_to<2>(stored)))
             CT_UNSUPPORTED("ct_fp4_quant_pack_stored: this layout takes ct_fp4_quant_pack and the host's scale conversion");
     }
     if (lean) {
         dim3 lg((unsigned)cdiv64(lanes, kBlock));
-#define CT_FP4L(XD, SD, G, GL) hipLaunchKernelGGL((fp4_quant_pack_lean_kernel<XD, SD, G, GL>), lg, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), scale, \
-                                                  global_scale, reinterpret_cast<u32x4*>(packed), lanes, stored, mx_lut)
-#define CT_FP4L_G(XD, SD) do { if (group == 16) { if (global_scale) CT_FP4L(XD, SD, 16, true); else CT_FP4L(XD, SD, 16, false); } \
-                               else { if (global_scale) CT_FP4L(XD, SD, 32, true); else CT_FP4L(XD, SD, 32, false); } } while (0)
-#define CT_FP4L_S(XD) do { if (sdt == CT_F32) CT_FP4L_G(XD, CT_F32); else if (sdt == CT_BF16) CT_FP4L_G(XD, CT_BF16); else CT_FP4L_G(XD, CT_F16); } while (0)
-        if (xdt == CT_BF16) CT_FP4L_S(CT_BF16); else CT_FP4L_S(CT_F16);
-#undef CT_FP4L_S
-#undef CT_FP4L_G
+#define CT_FP4L(G) hipLaunchKernelGGL((fp4_quant_pack_lean_kernel<XD(), SD(), G, GL()>), lg, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), scale, \
+                                      global_scale, reinterpret_cast<u32x4*>(packed), lanes, stored, mx_lut)
+        for_dt16(xdt, [&](auto XD) { for_dt(sdt, [&](auto SD) { for_bool(global_scale != nullptr, [&](auto GL) { if (group == 16) CT_FP4L(16); else CT_FP4L(32); }); }); });
 #undef CT_FP4L
         CT_LAUNCH_CHECK("ct_fp4_quant_pack[lean]");
     }
-#define CT_FP4Q(DT, GL) hipLaunchKernelGGL((fp4_quant_pack_kernel<DT, GL>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), scale, sdt, \
-                                          global_scale, reinterpret_cast<u32x4*>(packed), units, shift)
-    if (xdt == CT_BF16) { if (global_scale) CT_FP4Q(CT_BF16, true); else CT_FP4Q(CT_BF16, false); }
-    else { if (global_scale) CT_FP4Q(CT_F16, true); else CT_FP4Q(CT_F16, false); }
-#undef CT_FP4Q
+    for_dt16(xdt, [&](auto DT) { for_bool(global_scale != nullptr, [&](auto GL) {
+        hipLaunchKernelGGL((fp4_quant_pack_kernel<DT(), GL()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), scale, sdt, global_scale,
+                           reinterpret_cast<u32x4*>(packed), units, shift); }); });
     CT_LAUNCH_CHECK("ct_fp4_quant_pack");
 }
 
@@ -749,7 +743,7 @@ static int fp4_unpack_dequant_impl(const uint8_t* packed, int64_t rows, int64_t 
     CT_REQUIRE(rows >= 0 && cols >= 0, "negative shape");
     CT_REQUIRE(group == 16 || group == 32, "FP4 group size must be 16 (nvfp4) or 32 (mxfp4), got %lld", (long long)group);
     CT_REQUIRE(cols % group == 0, "columns (%lld) must be a multiple of the group size %lld", (long long)cols, (long long)group);
-    CT_REQUIRE(aligned16(out) && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0, "misaligned buffers");
+    CT_REQUIRE(aligned16(out) && aligned_to<4>(packed), "misaligned buffers");
     if (rows == 0 || cols == 0) return CT_OK;
     const int64_t units = rows * (cols / 8);
     const int shift = group == 16 ? 1 : 2;
@@ -758,17 +752,14 @@ static int fp4_unpack_dequant_impl(const uint8_t* packed, int64_t rows, int64_t 
     dim3 grid((unsigned)cdiv64(units, (int64_t)kBlock * U));
     const int64_t stride = (int64_t)1 << 40;  // one trip; the loop form schedules better (see ct_quant.hip)
     if (scale_kind == SC_F8E4M3 && global_scale && group == 16) {
-        if (odt == CT_BF16) hipLaunchKernelGGL((fp4_unpack_dequant_nv_kernel<CT_BF16, U>), grid, dim3(kBlock), 0, as_stream(stream), reinterpret_cast<const uint32_t*>(packed),
-                                               static_cast<const uint8_t*>(scale), global_scale, out, units, stride, scale_out);
-        else hipLaunchKernelGGL((fp4_unpack_dequant_nv_kernel<CT_F16, U>), grid, dim3(kBlock), 0, as_stream(stream), reinterpret_cast<const uint32_t*>(packed),
-                                static_cast<const uint8_t*>(scale), global_scale, out, units, stride, scale_out);
+        for_dt16(odt, [&](auto DT) {
+            hipLaunchKernelGGL((fp4_unpack_dequant_nv_kernel<DT(), U>), grid, dim3(kBlock), 0, as_stream(stream), reinterpret_cast<const uint32_t*>(packed),
+                               static_cast<const uint8_t*>(scale), global_scale, out, units, stride, scale_out); });
         CT_LAUNCH_CHECK("ct_fp4_unpack_dequant[nvfp4]");
     }
-#define CT_FP4D(DT, GL) hipLaunchKernelGGL((fp4_unpack_dequant_kernel<DT, U, GL>), grid, dim3(kBlock), 0, as_stream(stream), reinterpret_cast<const uint32_t*>(packed), \
-                                          scale, scale_kind, sdt, global_scale, out, units, shift, stride, scale_out)
-    if (odt == CT_BF16) { if (global_scale) CT_FP4D(CT_BF16, true); else CT_FP4D(CT_BF16, false); }
-    else { if (global_scale) CT_FP4D(CT_F16, true); else CT_FP4D(CT_F16, false); }
-#undef CT_FP4D
+    for_dt16(odt, [&](auto DT) { for_bool(global_scale != nullptr, [&](auto GL) {
+        hipLaunchKernelGGL((fp4_unpack_dequant_kernel<DT(), U, GL()>), grid, dim3(kBlock), 0, as_stream(stream), reinterpret_cast<const uint32_t*>(packed), scale, scale_kind, sdt,
+                           global_scale, out, units, shift, stride, scale_out); }); });
     CT_LAUNCH_CHECK("ct_fp4_unpack_dequant");
 }
 
@@ -779,45 +770,33 @@ int ct_fp4_unpack_dequant(const uint8_t* packed, int64_t rows, int64_t cols, con
 
 int ct_fp4_unpack_dequant_scale(const uint8_t* packed, int64_t rows, int64_t cols, const void* scale, int scale_kind, int sdt, const float* global_scale,
                                 int64_t group, void* out, int odt, void* scale_bf16_out, ct_stream_t stream) {
-    CT_REQUIRE(scale_bf16_out != nullptr && (reinterpret_cast<uintptr_t>(scale_bf16_out) & 1u) == 0, "ct_fp4_unpack_dequant_scale needs the (2-byte aligned) scale output");
+    CT_REQUIRE(scale_bf16_out != nullptr && aligned_to<2>(scale_bf16_out), "ct_fp4_unpack_dequant_scale needs the (2-byte aligned) scale output");
     return fp4_unpack_dequant_impl(packed, rows, cols, scale, scale_kind, sdt, global_scale, group, out, odt, static_cast<uint16_t*>(scale_bf16_out), stream);
 }
 
+static int64_t fp4_plan_item(ct_w4_item& it, int i, int direction, int64_t first_block) {
+    const int64_t g = it.group;
+    // compress: the lean kernel's layout (every lane four full units, its scales one aligned small load); decompress: 4-byte aligned words, 16-byte aligned output
+    bool ok = it.rows > 0 && it.cols > 0 && (g == 16 || g == 32) && it.cols % g == 0 && (it.rows * it.cols) % 32 == 0 && it.src && it.scale && it.dst && it.zp_packed &&
+              (it.zp != nullptr) == (g == 16);
+    if (ok && direction == 0) ok = aligned16(it.src) && aligned16(it.dst) && aligned_to<8>(it.scale) && aligned_to<2>(it.zp_packed);
+    if (ok && direction == 1) ok = aligned_to<4>(it.src) && aligned16(it.dst) && aligned_to<2>(it.zp_packed);
+    if (!ok) {
+        set_error("ct_fp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched FP4 path (needs group 16 with a global scale or group 32 "
+                  "without one, cols %% group == 0, rows * cols %% 32 == 0, the scale outputs, aligned buffers)", i, (long long)it.rows, (long long)it.cols, (long long)g);
+        return -1;
+    }
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, (int32_t)(g / 8), g == 16 ? 1 : 2, first_block,
+                 direction == 0 ? cdiv64(units / 4, kBlock) : cdiv64(units, (int64_t)kBlock * kFp4BatchUnroll * kFp4BatchIter));
+    return it.main_blocks;
+}
+
 int64_t ct_fp4_batch_plan(ct_w4_item* items, int n, int direction) {
-    if (!items || n < 0 || (direction != 0 && direction != 1)) {
-        set_error("ct_fp4_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        const int64_t g = it.group;
-        // compress: the lean kernel's layout (every lane four full units, its scales one aligned small load); decompress: 4-byte aligned words, 16-byte aligned output
-        bool ok = it.rows > 0 && it.cols > 0 && (g == 16 || g == 32) && it.cols % g == 0 && (it.rows * it.cols) % 32 == 0 && it.src && it.scale && it.dst && it.zp_packed &&
-                  (it.zp != nullptr) == (g == 16);
-        if (ok && direction == 0)
-            ok = aligned16(it.src) && aligned16(it.dst) && (reinterpret_cast<uintptr_t>(it.scale) & 7u) == 0 && (reinterpret_cast<uintptr_t>(it.zp_packed) & 1u) == 0;
-        if (ok && direction == 1)
-            ok = (reinterpret_cast<uintptr_t>(it.src) & 3u) == 0 && aligned16(it.dst) && (reinterpret_cast<uintptr_t>(it.zp_packed) & 1u) == 0;
-        if (!ok) {
-            set_error("ct_fp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched FP4 path (needs group 16 with a global scale or group 32 "
-                      "without one, cols %% group == 0, rows * cols %% 32 == 0, the scale outputs, aligned buffers)", i, (long long)it.rows, (long long)it.cols, (long long)g);
-            return -1;
-        }
-        it.units = it.rows * (it.cols / 8);
-        it.upg = (int32_t)(g / 8);
-        it.upg_shift = g == 16 ? 1 : 2;
-        it.first_block = blocks;
-        it.main_blocks = direction == 0 ? cdiv64(it.units / 4, kBlock) : cdiv64(it.units, (int64_t)kBlock * kFp4BatchUnroll * kFp4BatchIter);
-        it.g_magic = 0;
-        it.g_shift = 0;
-        blocks += it.main_blocks;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_fp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    PlanRules rules;
+    rules.null_table_is_error = true;
+    rules.args_ok = direction == 0 || direction == 1;
+    return plan_table("ct_fp4_batch_plan", items, n, [&](ct_w4_item& it, int i, int64_t first_block) { return fp4_plan_item(it, i, direction, first_block); }, rules);
 }
 
 int ct_fp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int sdt, int group, const uint8_t* mx_code_table, ct_stream_t stream) {
@@ -825,14 +804,12 @@ int ct_fp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_bl
     CT_REQUIRE(is_float_dt(sdt), "scale dtype code %d is not a float type", sdt);
     CT_REQUIRE(group == 16 || group == 32, "FP4 group size must be 16 (nvfp4) or 32 (mxfp4), got %d", group);
     CT_REQUIRE(group == 16 || (sdt != CT_F32 && mx_code_table != nullptr), "MXFP4 tables take 16-bit scales and the E8M0 code table");
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     const dim3 grid((unsigned)total_blocks);
-#define CT_FP4B(XD, SD, G) hipLaunchKernelGGL((fp4_quant_pack_batch_kernel<XD, SD, G>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, mx_code_table)
-#define CT_FP4B_S(XD) do { if (group == 16) { if (sdt == CT_F32) CT_FP4B(XD, CT_F32, 16); else if (sdt == CT_BF16) CT_FP4B(XD, CT_BF16, 16); else CT_FP4B(XD, CT_F16, 16); } \
-                           else { if (sdt == CT_BF16) CT_FP4B(XD, CT_BF16, 32); else CT_FP4B(XD, CT_F16, 32); } } while (0)
-    if (xdt == CT_BF16) CT_FP4B_S(CT_BF16); else CT_FP4B_S(CT_F16);
-#undef CT_FP4B_S
+#define CT_FP4B(SD, G) hipLaunchKernelGGL((fp4_quant_pack_batch_kernel<XD(), SD(), G>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, mx_code_table)
+    for_dt16(xdt, [&](auto XD) {  // NVFP4 scales of any float dtype, MXFP4 scales of the two 16-bit ones
+        if (group == 16) for_dt(sdt, [&](auto SD) { CT_FP4B(SD, 16); });
+        else for_dt16(sdt, [&](auto SD) { CT_FP4B(SD, 32); }); });
 #undef CT_FP4B
     CT_LAUNCH_CHECK("ct_fp4_quant_pack_batch");
 }
@@ -840,46 +817,33 @@ int ct_fp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_bl
 int ct_fp4_unpack_dequant_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int group, int odt, ct_stream_t stream) {
     CT_REQUIRE(odt == CT_BF16 || odt == CT_F16, "FP4 decompression writes 16-bit floats, got dtype %d", odt);
     CT_REQUIRE(group == 16 || group == 32, "FP4 group size must be 16 (nvfp4) or 32 (mxfp4), got %d", group);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     const dim3 grid((unsigned)total_blocks);
-    if (odt == CT_BF16) {
-        if (group == 16) hipLaunchKernelGGL((fp4_unpack_dequant_batch_kernel<CT_BF16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n);
-        else hipLaunchKernelGGL((fp4_unpack_dequant_batch_kernel<CT_BF16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    } else {
-        if (group == 16) hipLaunchKernelGGL((fp4_unpack_dequant_batch_kernel<CT_F16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n);
-        else hipLaunchKernelGGL((fp4_unpack_dequant_batch_kernel<CT_F16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    }
+    for_dt16(odt, [&](auto DT) { for_bool(group == 16, [&](auto NV) {
+        hipLaunchKernelGGL((fp4_unpack_dequant_batch_kernel<DT(), NV()>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n); }); });
     CT_LAUNCH_CHECK("ct_fp4_unpack_dequant_batch");
 }
 
+// only first_block is derived: the kernel takes src / dst / rows as given
+static int64_t mx_scale_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    if (!(it.rows > 0 && it.src && it.dst && aligned_to<2>(it.src) && aligned_to<2>(it.dst))) {
+        set_error("ct_mx_scale_batch_plan: item %d needs src, dst (2-byte aligned) and rows = its element count > 0", i);
+        return -1;
+    }
+    it.first_block = first_block;
+    return cdiv64(cdiv64(it.rows, 8), kBlock);  // eight scales per lane
+}
+
 int64_t ct_mx_scale_batch_plan(ct_w4_item* items, int n) {
-    if (!items || n < 0) {
-        set_error("ct_mx_scale_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        if (!(it.rows > 0 && it.src && it.dst && (reinterpret_cast<uintptr_t>(it.src) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.dst) & 1u) == 0)) {
-            set_error("ct_mx_scale_batch_plan: item %d needs src, dst (2-byte aligned) and rows = its element count > 0", i);
-            return -1;
-        }
-        it.first_block = blocks;
-        blocks += cdiv64(cdiv64(it.rows, 8), kBlock);  // eight scales per lane
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_mx_scale_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    PlanRules rules;
+    rules.null_table_is_error = true;
+    return plan_table("ct_mx_scale_batch_plan", items, n, mx_scale_plan_item, rules);
 }
 
 int ct_mx_scale_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int direction, int sdt, const uint8_t* code_table, ct_stream_t stream) {
     CT_REQUIRE(direction == 0 || direction == 1, "direction must be 0 (compress) or 1 (decompress)");
     CT_REQUIRE(direction == 1 || ((sdt == CT_BF16 || sdt == CT_F16) && code_table != nullptr), "compress takes 16-bit scales and their code table");
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     if (direction == 0) hipLaunchKernelGGL((mx_scale_batch_kernel<true>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, code_table);
     else hipLaunchKernelGGL((mx_scale_batch_kernel<false>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, code_table);
     CT_LAUNCH_CHECK("ct_mx_scale_batch");
@@ -887,7 +851,7 @@ int ct_mx_scale_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, 
 
 int ct_mx_scale_compress(const void* scale, int sdt, int64_t n, const uint8_t* code_table, uint8_t* codes_out, ct_stream_t stream) {
     CT_REQUIRE(sdt == CT_BF16 || sdt == CT_F16, "ct_mx_scale_compress takes 16-bit scales (the table has one entry per 16-bit pattern), got dtype %d", sdt);
-    CT_REQUIRE(n >= 0 && code_table != nullptr && (reinterpret_cast<uintptr_t>(scale) & 1u) == 0, "bad arguments");
+    CT_REQUIRE(n >= 0 && code_table != nullptr && aligned_to<2>(scale), "bad arguments");
     if (n == 0) return CT_OK;
     CT_REQUIRE(cdiv64(n, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     hipLaunchKernelGGL(mx_scale_compress_kernel, dim3((unsigned)cdiv64(n, kBlock)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale), n, code_table, codes_out);
@@ -895,7 +859,7 @@ int ct_mx_scale_compress(const void* scale, int sdt, int64_t n, const uint8_t* c
 }
 
 int ct_mx_scale_decompress(const uint8_t* codes, int64_t n, void* scale_bf16_out, ct_stream_t stream) {
-    CT_REQUIRE(n >= 0 && (reinterpret_cast<uintptr_t>(scale_bf16_out) & 1u) == 0, "bad arguments");
+    CT_REQUIRE(n >= 0 && aligned_to<2>(scale_bf16_out), "bad arguments");
     if (n == 0) return CT_OK;
     CT_REQUIRE(cdiv64(n, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     hipLaunchKernelGGL(mx_scale_decompress_kernel, dim3((unsigned)cdiv64(n, kBlock)), dim3(kBlock), 0, as_stream(stream), codes, n, static_cast<uint16_t*>(scale_bf16_out));
@@ -910,14 +874,9 @@ static int fp4_prim(const void* x, int xdt, void* out, int64_t n, int mode, ct_s
     const int64_t units = cdiv64(n, 8);
     CT_REQUIRE(cdiv64(units, kBlock) < ((int64_t)1 << 31), "%s: tensor too large for one launch", what);
     dim3 grid((unsigned)cdiv64(units, kBlock));
-#define CT_FP4P(DT) do { if (mode == 0) hipLaunchKernelGGL((fp4_prim_kernel<DT, 0>), grid, dim3(kBlock), 0, as_stream(stream), x, out, n); \
-                         else hipLaunchKernelGGL((fp4_prim_kernel<DT, 1>), grid, dim3(kBlock), 0, as_stream(stream), x, out, n); } while (0)
-    switch (xdt) {
-        case CT_BF16: CT_FP4P(CT_BF16); break;
-        case CT_F16: CT_FP4P(CT_F16); break;
-        default: CT_FP4P(CT_F32); break;
-    }
-#undef CT_FP4P
+    for_dt(xdt, [&](auto DT) {
+        if (mode == 0) hipLaunchKernelGGL((fp4_prim_kernel<DT(), 0>), grid, dim3(kBlock), 0, as_stream(stream), x, out, n);
+        else hipLaunchKernelGGL((fp4_prim_kernel<DT(), 1>), grid, dim3(kBlock), 0, as_stream(stream), x, out, n); });
     CT_LAUNCH_CHECK(what);
 }
 
@@ -936,11 +895,7 @@ int ct_fp4_unpack(const uint8_t* packed, int64_t n, void* out, int odt, ct_strea
     const int64_t units = cdiv64(n, 8);
     CT_REQUIRE(cdiv64(units, kBlock) < ((int64_t)1 << 31), "ct_fp4_unpack: tensor too large for one launch");
     dim3 grid((unsigned)cdiv64(units, kBlock));
-    switch (odt) {
-        case CT_BF16: hipLaunchKernelGGL((fp4_unpack_kernel<CT_BF16>), grid, dim3(kBlock), 0, as_stream(stream), packed, out, n); break;
-        case CT_F16: hipLaunchKernelGGL((fp4_unpack_kernel<CT_F16>), grid, dim3(kBlock), 0, as_stream(stream), packed, out, n); break;
-        default: hipLaunchKernelGGL((fp4_unpack_kernel<CT_F32>), grid, dim3(kBlock), 0, as_stream(stream), packed, out, n); break;
-    }
+    for_dt(odt, [&](auto DT) { hipLaunchKernelGGL((fp4_unpack_kernel<DT()>), grid, dim3(kBlock), 0, as_stream(stream), packed, out, n); });
     CT_LAUNCH_CHECK("ct_fp4_unpack");
 }
 
@@ -965,52 +920,33 @@ int ct_rtn_mxfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, 
     const int64_t lanes = rows * (cols / 32);
     CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     dim3 grid((unsigned)cdiv64(lanes, kBlock));
-    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_mxfp4_kernel<CT_BF16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes,
-                                           reinterpret_cast<u32x4*>(packed), scale_e8m0, scale_out);
-    else hipLaunchKernelGGL((rtn_mxfp4_kernel<CT_F16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes,
-                            reinterpret_cast<u32x4*>(packed), scale_e8m0, scale_out);
+    for_dt16(xdt, [&](auto DT) {
+        hipLaunchKernelGGL((rtn_mxfp4_kernel<DT()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, reinterpret_cast<u32x4*>(packed), scale_e8m0,
+                           scale_out); });
     CT_LAUNCH_CHECK("ct_rtn_mxfp4_quant_pack");
 }
 
-int64_t ct_rtn_mxfp4_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_mxfp4_batch_plan: bad arguments");
+static int64_t rtn_mxfp4_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    // the conditions of ct_rtn_mxfp4_quant_pack, per item
+    const bool ok = it.rows > 0 && it.cols > 0 && it.group == 32 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && aligned16(it.src) && aligned16(it.dst) &&
+                    aligned_to<2>(it.scale);
+    if (!ok) {
+        set_error("ct_rtn_mxfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass MXFP4 compress "
+                  "(needs group 32, cols %% 32 == 0, 16-byte aligned src / dst, the E8M0 output in zp_packed)", i, (long long)it.rows, (long long)it.cols,
+                  (long long)it.group);
         return -1;
     }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        // the conditions of ct_rtn_mxfp4_quant_pack, per item
-        const bool ok = it.rows > 0 && it.cols > 0 && it.group == 32 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && aligned16(it.src) && aligned16(it.dst) &&
-                        (reinterpret_cast<uintptr_t>(it.scale) & 1u) == 0;
-        if (!ok) {
-            set_error("ct_rtn_mxfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass MXFP4 compress "
-                      "(needs group 32, cols %% 32 == 0, 16-byte aligned src / dst, the E8M0 output in zp_packed)", i, (long long)it.rows, (long long)it.cols,
-                      (long long)it.group);
-            return -1;
-        }
-        it.units = it.rows * (it.cols / 8);
-        it.upg = 4;
-        it.upg_shift = 2;
-        it.first_block = blocks;
-        it.main_blocks = cdiv64(it.units / 4, kBlock);
-        it.g_magic = 0;
-        it.g_shift = 0;
-        blocks += it.main_blocks;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_mxfp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, 4, 2, first_block, cdiv64(units / 4, kBlock));
+    return it.main_blocks;
 }
+
+int64_t ct_rtn_mxfp4_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_rtn_mxfp4_batch_plan", items, n, rtn_mxfp4_plan_item); }
 
 int ct_rtn_mxfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass MXFP4 compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    else hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_BATCH_ARGS(n, total_blocks);
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_rtn_mxfp4_quant_pack_batch");
 }
 
@@ -1019,67 +955,49 @@ int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, 
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "the one-pass NVFP4 compress takes 16-bit float weights, got dtype %d", xdt);
     CT_REQUIRE(rows >= 0 && cols >= 0 && cols % 32 == 0, "columns (%lld) must be a multiple of 32 (two groups of 16 per lane)", (long long)cols);
     CT_REQUIRE(global_scale != nullptr && scale_f8 != nullptr, "the global scale and the scale output are required");
-    CT_REQUIRE(aligned16(x) && aligned16(packed) && (reinterpret_cast<uintptr_t>(scale_f8) & 1u) == 0, "misaligned buffers");
+    CT_REQUIRE(aligned16(x) && aligned16(packed) && aligned_to<2>(scale_f8), "misaligned buffers");
     if (rows == 0 || cols == 0) return CT_OK;
     const int64_t lanes = rows * (cols / 32);
     CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     dim3 grid((unsigned)cdiv64(lanes, kBlock));
-    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_nvfp4_kernel<CT_BF16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, global_scale,
-                                           reinterpret_cast<u32x4*>(packed), reinterpret_cast<uint16_t*>(scale_f8), scale_out);
-    else hipLaunchKernelGGL((rtn_nvfp4_kernel<CT_F16>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, global_scale,
-                            reinterpret_cast<u32x4*>(packed), reinterpret_cast<uint16_t*>(scale_f8), scale_out);
+    for_dt16(xdt, [&](auto DT) {
+        hipLaunchKernelGGL((rtn_nvfp4_kernel<DT()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, global_scale,
+                           reinterpret_cast<u32x4*>(packed), reinterpret_cast<uint16_t*>(scale_f8), scale_out); });
     CT_LAUNCH_CHECK("ct_rtn_nvfp4_quant_pack");
 }
 
+static int64_t rtn_nvfp4_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    // the conditions of ct_rtn_nvfp4_quant_pack, per item, and the two words of the table form
+    const bool ok = it.rows > 0 && it.cols > 0 && it.group == 16 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && it.zp && it.scale && aligned16(it.src) &&
+                    aligned16(it.dst) && aligned_to<2>(it.zp_packed) && aligned_to<4>(it.zp) && aligned_to<4>(it.scale);
+    if (!ok) {
+        set_error("ct_rtn_nvfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass NVFP4 compress "
+                  "(needs group 16, cols %% 32 == 0, 16-byte aligned src / dst, the float8 output in zp_packed, the 4-byte aligned amax key in zp and "
+                  "global-scale output in scale)", i, (long long)it.rows, (long long)it.cols, (long long)it.group);
+        return -1;
+    }
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, 2, 1, first_block, cdiv64(units / 4, kBlock));
+    return it.main_blocks;
+}
+
 int64_t ct_rtn_nvfp4_batch_plan(ct_w4_item* items, int n) {
-    if (n <= 0 || items == nullptr) {
-        set_error("ct_rtn_nvfp4_batch_plan: bad arguments (a table of %d items)", n);
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        // the conditions of ct_rtn_nvfp4_quant_pack, per item, and the two words of the table form
-        const bool ok = it.rows > 0 && it.cols > 0 && it.group == 16 && it.cols % 32 == 0 && it.src && it.dst && it.zp_packed && it.zp && it.scale && aligned16(it.src) &&
-                        aligned16(it.dst) && (reinterpret_cast<uintptr_t>(it.zp_packed) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.zp) & 3u) == 0 &&
-                        (reinterpret_cast<uintptr_t>(it.scale) & 3u) == 0;
-        if (!ok) {
-            set_error("ct_rtn_nvfp4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass NVFP4 compress "
-                      "(needs group 16, cols %% 32 == 0, 16-byte aligned src / dst, the float8 output in zp_packed, the 4-byte aligned amax key in zp and "
-                      "global-scale output in scale)", i, (long long)it.rows, (long long)it.cols, (long long)it.group);
-            return -1;
-        }
-        it.units = it.rows * (it.cols / 8);
-        it.upg = 2;
-        it.upg_shift = 1;
-        it.first_block = blocks;
-        it.main_blocks = cdiv64(it.units / 4, kBlock);
-        it.g_magic = 0;
-        it.g_shift = 0;
-        blocks += it.main_blocks;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_nvfp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    PlanRules rules;
+    rules.empty_is_error = "%s: bad arguments (a table of %d items)";
+    return plan_table("ct_rtn_nvfp4_batch_plan", items, n, rtn_nvfp4_plan_item, rules);
 }
 
 int ct_rtn_nvfp4_amax_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass NVFP4 compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_nvfp4_amax_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    else hipLaunchKernelGGL((rtn_nvfp4_amax_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_BATCH_ARGS(n, total_blocks);
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((rtn_nvfp4_amax_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_rtn_nvfp4_amax_batch");
 }
 
 int ct_rtn_nvfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass NVFP4 compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-    if (xdt == CT_BF16) hipLaunchKernelGGL((rtn_nvfp4_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    else hipLaunchKernelGGL((rtn_nvfp4_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_BATCH_ARGS(n, total_blocks);
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((rtn_nvfp4_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_rtn_nvfp4_quant_pack_batch");
 }
 

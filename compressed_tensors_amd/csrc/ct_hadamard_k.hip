@@ -427,7 +427,7 @@ static int check_hadk(const void* x, const void* out, int dt, int64_t numel, int
     if (k > 1 && form_of(dt, n, k, acc64) == HADK_VALU && n / k > kHadKRunsMaxM)
         CT_UNSUPPORTED("the vector form takes runs of up to %d elements, got %lld", kHadKRunsMaxM, (long long)(n / k));
     if (!aligned16(x) || !aligned16(out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned tensors");
-    if (signs != nullptr && (reinterpret_cast<uintptr_t>(signs) & 7u)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
+    if (!aligned_to<8>(signs)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
     return CT_OK;
 }
 

@@ -342,7 +342,7 @@ static int check_hadp(const void* x, const void* out, int dt, int64_t numel, int
                                                                (long long)n, (long long)(acc64 ? kHadPMaxF64 : kHadPMaxF32), acc64 ? "float64" : "float32");
     if (!aligned16(x) || !aligned16(out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned tensors");
     if (!aligned16(gather_in) || !aligned16(gather_out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned gather tables");
-    if (signs != nullptr && (reinterpret_cast<uintptr_t>(signs) & 7u)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
+    if (!aligned_to<8>(signs)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
     return CT_OK;
 }
 

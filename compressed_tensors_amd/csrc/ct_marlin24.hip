@@ -1037,7 +1037,7 @@ int ct_marlin24_quant_compress(const void* w, int wdt, const void* scale, int sd
     CT_REQUIRE(m >= 0 && k >= 0 && m % 64 == 0 && k % 16 == 0, "marlin-24 needs rows %% 64 == 0 and cols %% 16 == 0, got (%lld, %lld)", (long long)m,
                (long long)k);
     CT_REQUIRE(cdiv >= 16 && (cdiv % 16 == 0 || cdiv >= k), "group size %lld must be a multiple of 16", (long long)cdiv);
-    CT_REQUIRE(aligned16(w) && (reinterpret_cast<uintptr_t>(comp) & 7u) == 0 && bad != nullptr, "misaligned buffers");
+    CT_REQUIRE(aligned16(w) && aligned_to<8>(comp) && bad != nullptr, "misaligned buffers");
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), as_stream(stream));
     if (e != hipSuccess) return hip_check(e, "ct_marlin24_quant_compress memset");
     if (m == 0 || k == 0) return CT_OK;
@@ -1046,22 +1046,16 @@ int ct_marlin24_quant_compress(const void* w, int wdt, const void* scale, int sd
     const float qmax = (float)((1 << bits) / 2 - 1), qmin = -(float)((1 << bits) / 2);
     const int64_t total = m * (k / 16);
     const unsigned grid = (unsigned)(cdiv64(total, kBlock) < ((int64_t)1 << 30) ? cdiv64(total, kBlock) : ((int64_t)1 << 30));
-    if (k % 256 == 0 && (reinterpret_cast<uintptr_t>(meta) & 7u) == 0 && (m / 64) * (k / 256) < ((int64_t)1 << 31)) {
+    if (k % 256 == 0 && aligned_to<8>(meta) && (m / 64) * (k / 256) < ((int64_t)1 << 31)) {
         const unsigned tg = (unsigned)((m / 64) * (k / 256));
-        if (wdt == CT_BF16)
-            hipLaunchKernelGGL((marlin24_quant_compress_tiled_kernel<CT_BF16>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c,
-                               scale_cols, qmin, qmax, comp, reinterpret_cast<uint16_t*>(meta), bad);
-        else
-            hipLaunchKernelGGL((marlin24_quant_compress_tiled_kernel<CT_F16>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c,
-                               scale_cols, qmin, qmax, comp, reinterpret_cast<uint16_t*>(meta), bad);
+        for_dt16(wdt, [&](auto DT) {
+            hipLaunchKernelGGL((marlin24_quant_compress_tiled_kernel<DT()>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, scale_cols,
+                               qmin, qmax, comp, reinterpret_cast<uint16_t*>(meta), bad); });
         CT_LAUNCH_CHECK("ct_marlin24_quant_compress[tiled]");
     }
-    if (wdt == CT_BF16)
-        hipLaunchKernelGGL((marlin24_quant_compress_kernel<CT_BF16>), dim3(grid), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, scale_cols,
-                           qmin, qmax, comp, reinterpret_cast<uint16_t*>(meta), bad);
-    else
-        hipLaunchKernelGGL((marlin24_quant_compress_kernel<CT_F16>), dim3(grid), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, scale_cols,
-                           qmin, qmax, comp, reinterpret_cast<uint16_t*>(meta), bad);
+    for_dt16(wdt, [&](auto DT) {
+        hipLaunchKernelGGL((marlin24_quant_compress_kernel<DT()>), dim3(grid), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, scale_cols, qmin,
+                           qmax, comp, reinterpret_cast<uint16_t*>(meta), bad); });
     CT_LAUNCH_CHECK("ct_marlin24_quant_compress");
 }
 
@@ -1075,7 +1069,7 @@ static int marlin24_compress_w4_impl(const void* w, int wdt, const void* scale, 
     CT_REQUIRE(m >= 0 && k >= 0 && m % 64 == 0 && k % 256 == 0, "the fused marlin-24 path needs rows %% 64 == 0 and cols %% 256 == 0, got (%lld, %lld)",
                (long long)m, (long long)k);
     CT_REQUIRE(cdiv >= 16 && (cdiv % 16 == 0 || cdiv >= k), "group size %lld must be a multiple of 16", (long long)cdiv);
-    CT_REQUIRE(aligned16(w) && (reinterpret_cast<uintptr_t>(meta) & 7u) == 0 && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0 && bad != nullptr,
+    CT_REQUIRE(aligned16(w) && aligned_to<8>(meta) && aligned_to<4>(packed) && bad != nullptr,
                "misaligned buffers");
     CT_REQUIRE((m / 64) * (k / 256) < ((int64_t)1 << 31), "tensor too large for one launch");
     unsigned int* tickets = nullptr;
@@ -1102,24 +1096,18 @@ static int marlin24_compress_w4_impl(const void* w, int wdt, const void* scale, 
     // (the lean kernel forms its lane offsets in 32 bits: sides below 2^24; anything larger takes the general fused kernel)
     const bool lean = (sdt == CT_F16 || sdt == CT_BF16) && (zp == nullptr || zdt == CT_I8) && m < kM24LeanMaxDim && k < kM24LeanMaxDim;
     if (lean) {
-#define CT_M24_LEAN(X, S)                                                                                                                      \
-    hipLaunchKernelGGL((marlin24_fused_w4_lean_kernel<X, S>), dim3(tg), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(w), \
-                       static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), m, k, c, k / c, packed, reinterpret_cast<uint16_t*>(meta), bad, \
-                       static_cast<uint16_t*>(scale_packed), scale_single, xcd_rows, tickets, verdict_word, tc_magic)
         const int xcd_rows = (m / 64) % 8 == 0 ? 1 : 0;  // the row blocks divide evenly over the eight XCDs
         const uint32_t tc_magic = k / 256 == 1 ? 0xffffffffu : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)(k / 256));
-        if (wdt == CT_BF16 && sdt == CT_BF16) CT_M24_LEAN(CT_BF16, CT_BF16);
-        else if (wdt == CT_BF16) CT_M24_LEAN(CT_BF16, CT_F16);
-        else if (sdt == CT_BF16) CT_M24_LEAN(CT_F16, CT_BF16);
-        else CT_M24_LEAN(CT_F16, CT_F16);
-#undef CT_M24_LEAN
+        for_dt16(wdt, [&](auto X) { for_dt16(sdt, [&](auto S) {
+            hipLaunchKernelGGL((marlin24_fused_w4_lean_kernel<X(), S()>), dim3(tg), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(w),
+                               static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), m, k, c, k / c, packed, reinterpret_cast<uint16_t*>(meta), bad,
+                               static_cast<uint16_t*>(scale_packed), scale_single, xcd_rows, tickets, verdict_word, tc_magic); }); });
         if (fused_scales) *fused_scales = scale_packed != nullptr;
-    } else if (wdt == CT_BF16)
-        hipLaunchKernelGGL((marlin24_fused_w4_kernel<CT_BF16>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, k / c, packed,
-                           reinterpret_cast<uint16_t*>(meta), bad);
-    else
-        hipLaunchKernelGGL((marlin24_fused_w4_kernel<CT_F16>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, k / c, packed,
-                           reinterpret_cast<uint16_t*>(meta), bad);
+    } else {
+        for_dt16(wdt, [&](auto DT) {
+            hipLaunchKernelGGL((marlin24_fused_w4_kernel<DT()>), dim3(tg), dim3(kBlock), 0, as_stream(stream), w, scale, sdt, zp, zdt, m, k, c, k / c, packed,
+                               reinterpret_cast<uint16_t*>(meta), bad); });
+    }
     CT_LAUNCH_CHECK("ct_marlin24_compress_w4");
 }
 
@@ -1138,12 +1126,9 @@ int ct_marlin24_compress_w4_full(const void* w, int wdt, const void* scale, int 
     const int64_t c = cdiv > k ? k : cdiv;
     const int64_t groups = k / c;
     CT_REQUIRE((m * groups) % 64 == 0, "scale count must be a multiple of 64");
-    if (sdt == CT_BF16)
-        hipLaunchKernelGGL(marlin24_pack_scales_kernel<true>, dim3(grid_1d(m * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale), m,
-                           groups, group_perm ? 0 : 1, static_cast<uint16_t*>(scale_packed));
-    else
-        hipLaunchKernelGGL(marlin24_pack_scales_kernel<false>, dim3(grid_1d(m * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale), m,
-                           groups, group_perm ? 0 : 1, static_cast<uint16_t*>(scale_packed));
+    for_bool(sdt == CT_BF16, [&](auto BF) {
+        hipLaunchKernelGGL(marlin24_pack_scales_kernel<BF()>, dim3(grid_1d(m * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale), m, groups,
+                           group_perm ? 0 : 1, static_cast<uint16_t*>(scale_packed)); });
     CT_LAUNCH_CHECK("ct_marlin24_compress_w4_full");
 }
 
@@ -1151,8 +1136,8 @@ int ct_marlin24_compress_w4_verdict(const void* w, int wdt, const void* scale, i
                                     int group_perm, int32_t* packed, int16_t* meta, void* scale_packed, int64_t* verdict_word, void* workspace,
                                     int clear_workspace, ct_stream_t stream) {
     CT_REQUIRE(sdt == CT_F16 || sdt == CT_BF16, "marlin-24 scales must be 16-bit floats, got dtype %d", sdt);
-    CT_REQUIRE(scale_packed != nullptr && verdict_word != nullptr && (reinterpret_cast<uintptr_t>(verdict_word) & 7u) == 0, "scale_packed / verdict_word NULL or misaligned");
-    CT_REQUIRE(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 127u) == 0, "workspace NULL or not 128-byte aligned (CT_M24_VERDICT_WORKSPACE_BYTES of device memory)");
+    CT_REQUIRE(scale_packed != nullptr && verdict_word != nullptr && aligned_to<8>(verdict_word), "scale_packed / verdict_word NULL or misaligned");
+    CT_REQUIRE(workspace != nullptr && aligned_to<128>(workspace), "workspace NULL or not 128-byte aligned (CT_M24_VERDICT_WORKSPACE_BYTES of device memory)");
     static int unused_flag;  // the kernel's `bad` argument is not touched in verdict mode; the shared argument check wants a non-null pointer
     return marlin24_compress_w4_impl(w, wdt, scale, sdt, zp, zdt, m, k, cdiv, packed, meta, &unused_flag, false, scale_packed, group_perm ? 0 : 1, nullptr, stream,
                                      reinterpret_cast<long long*>(verdict_word), workspace, clear_workspace != 0);
@@ -1204,12 +1189,9 @@ int ct_marlin24_pack_scales_f16(const void* scale, int dt, int64_t size_n, int64
     CT_REQUIRE(dt == CT_F16 || dt == CT_BF16, "marlin-24 scales must be 16-bit floats, got dtype %d", dt);
     CT_REQUIRE(size_n >= 0 && groups >= 0 && (size_n * groups) % 64 == 0, "scale count must be a multiple of 64");
     if (size_n == 0 || groups == 0) return CT_OK;
-    if (dt == CT_BF16)
-        hipLaunchKernelGGL(marlin24_pack_scales_kernel<true>, dim3(grid_1d(size_n * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale),
-                           size_n, groups, single, static_cast<uint16_t*>(out));
-    else
-        hipLaunchKernelGGL(marlin24_pack_scales_kernel<false>, dim3(grid_1d(size_n * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale),
-                           size_n, groups, single, static_cast<uint16_t*>(out));
+    for_bool(dt == CT_BF16, [&](auto BF) {
+        hipLaunchKernelGGL(marlin24_pack_scales_kernel<BF()>, dim3(grid_1d(size_n * groups)), dim3(kBlock), 0, as_stream(stream), static_cast<const uint16_t*>(scale),
+                           size_n, groups, single, static_cast<uint16_t*>(out)); });
     CT_LAUNCH_CHECK("ct_marlin24_pack_scales_f16");
 }
 

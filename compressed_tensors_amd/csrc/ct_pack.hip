@@ -7,6 +7,7 @@
 // 32 elements <-> B int32 words.  One 32-element group per lane: all bit positions are
 // compile-time constants after unrolling, every word is written exactly once, no atomics.
 #include "ct_common.h"
+#include "ct_plan.h"
 
 namespace ct {
 
@@ -365,7 +366,7 @@ int ct_pack_int32(const int8_t* q, int64_t rows, int64_t cols, int bits, int32_t
                            reinterpret_cast<u32x4*>(out));
         CT_LAUNCH_CHECK("ct_pack_int32[flat8]");
     }
-    if (bits == 4 && cols % 32 == 0 && out_row_stride == packed_cols && aligned16(q) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0) {
+    if (bits == 4 && cols % 32 == 0 && out_row_stride == packed_cols && aligned16(q) && aligned_to<8>(out)) {
         constexpr int U = 2;
         const int64_t items = rows * cols / 16;
         const int64_t g = cdiv64(items, (int64_t)kBlock * U);
@@ -405,28 +406,18 @@ int ct_unpack_int32(const int32_t* p, int64_t rows, int64_t words, int64_t p_row
     CT_LAUNCH_CHECK("ct_unpack_int32");
 }
 
-int64_t ct_zp4_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_zp4_batch_plan: bad arguments");
+// units and first_block are derived: the kernel takes src / dst / rows / cols as given
+static int64_t zp4_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    if (!(it.rows > 0 && it.cols > 0 && it.src && it.dst)) {
+        set_error("ct_zp4_batch_plan: item %d has an empty shape or a NULL pointer", i);
         return -1;
     }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        if (!(it.rows > 0 && it.cols > 0 && it.src && it.dst)) {
-            set_error("ct_zp4_batch_plan: item %d has an empty shape or a NULL pointer", i);
-            return -1;
-        }
-        it.units = cdiv64(it.rows, 32) * it.cols;  // one lane per (32-row group, column)
-        it.first_block = blocks;
-        blocks += cdiv64(it.units, kBlock);
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_zp4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    it.units = cdiv64(it.rows, 32) * it.cols;  // one lane per (32-row group, column)
+    it.first_block = first_block;
+    return cdiv64(it.units, kBlock);
 }
+
+int64_t ct_zp4_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_zp4_batch_plan", items, n, zp4_plan_item); }
 
 int ct_zp4_pack_dim0_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int direction, ct_stream_t stream) {
     CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31) && (direction == 0 || direction == 1), "bad batch arguments");

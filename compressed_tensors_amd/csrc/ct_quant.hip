@@ -14,6 +14,7 @@
 #include "ct_quant_lean.h"
 #include "ct_minmax.h"
 #include "ct_w4_variant.h"
+#include "ct_plan.h"
 
 #include <cstdlib>
 
@@ -2198,16 +2199,10 @@ static W4Params make_w4(const void* x, const void* scale, const void* zp, int zd
         p.upg_shift = 62;
     }
     if (!p.flat_scale && p.units < ((int64_t)1 << 31) && p.upr >= 1 && rdiv >= 1 && rdiv < ((int64_t)1 << 31) && p.upg >= 1) {
-        // Granlund-Montgomery with N = 31: magic = ceil(2^(31 + L) / d), L = ceil(log2 d), magic < 2^32, exact for n < 2^31
-        auto magic31 = [](int64_t d, uint32_t& magic, int& shift) {
-            int L = 0;
-            while (((int64_t)1 << L) < d) ++L;
-            shift = 31 + L;
-            magic = (uint32_t)((((uint64_t)1 << shift) + (uint64_t)(d - 1)) / (uint64_t)d);
-        };
-        magic31(p.upr, p.upr_magic, p.upr_shift);
-        magic31(rdiv, p.rdiv_magic, p.rdiv_shift);
-        magic31(p.upg, p.upg_magic, p.upg_mshift);
+        // the three divisors are below 2^31: magic_div never refuses
+        magic_div(p.upr, &p.upr_magic, &p.upr_shift);
+        magic_div(rdiv, &p.rdiv_magic, &p.rdiv_shift);
+        magic_div(p.upg, &p.upg_magic, &p.upg_mshift);
         p.nf_fast = 1;
     }
     return p;
@@ -2262,14 +2257,12 @@ static int launch_w4_gidx(const W4Params& w, int dt, const void* zp, const int32
     dim3 g((unsigned)(cdiv64(rows, kGidxRows) * chunks));
     // the LDS tables are sized for 128 / 256 / 512 / 1024 groups per row (round 6: rows of 28672 columns — 224 groups — ran on the 1024-group tables at
     // 3-5 workgroups per CU)
-#define CT_GIDXR_G(DT, ZP, MAXG_) hipLaunchKernelGGL((w4_gidx_rows_kernel<DT, ZP, COMPRESS, kGidxRows, (COMPRESS ? kGidxCompressUnits : kGidxDecompressUnits), MAXG_>), \
-                                                     g, dim3(kBlock), 0, as_stream(stream), w, col_group, chunks, rows)
-#define CT_GIDXR(DT, ZP) do { if (w.scale_cols <= kGidxSmallGroups) CT_GIDXR_G(DT, ZP, kGidxSmallGroups); else if (w.scale_cols <= 256) CT_GIDXR_G(DT, ZP, 256); \
-                              else if (w.scale_cols <= 512) CT_GIDXR_G(DT, ZP, 512); else CT_GIDXR_G(DT, ZP, kGidxMaxGroups); } while (0)
-    if (dt == CT_BF16) { if (zp) CT_GIDXR(CT_BF16, true); else CT_GIDXR(CT_BF16, false); }
-    else { if (zp) CT_GIDXR(CT_F16, true); else CT_GIDXR(CT_F16, false); }
+#define CT_GIDXR(MAXG_) hipLaunchKernelGGL((w4_gidx_rows_kernel<DT(), ZP(), COMPRESS, kGidxRows, (COMPRESS ? kGidxCompressUnits : kGidxDecompressUnits), MAXG_>), \
+                                           g, dim3(kBlock), 0, as_stream(stream), w, col_group, chunks, rows)
+    for_dt16(dt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+        if (w.scale_cols <= kGidxSmallGroups) CT_GIDXR(kGidxSmallGroups); else if (w.scale_cols <= 256) CT_GIDXR(256);
+        else if (w.scale_cols <= 512) CT_GIDXR(512); else CT_GIDXR(kGidxMaxGroups); }); });
 #undef CT_GIDXR
-#undef CT_GIDXR_G
     return hip_check(hipGetLastError(), what);
 }
 
@@ -2277,7 +2270,7 @@ static int launch_w4_gidx(const W4Params& w, int dt, const void* zp, const int32
 // 4-byte aligned code side
 static bool f32_quads_ok(int64_t rows, int64_t cols, int64_t cdiv, const int32_t* col_group, const void* floats, const void* codes) {
     return !col_group && rows > 0 && cols > 0 && cols % 8 == 0 && (cdiv % 8 == 0 || cdiv >= cols) && aligned16(floats) &&
-           (codes == nullptr || (reinterpret_cast<uintptr_t>(codes) & 3u) == 0) && rows * (cols / 8) < ((int64_t)1 << 38);
+           (codes == nullptr || aligned_to<4>(codes)) && rows * (cols / 8) < ((int64_t)1 << 38);
 }
 template <int MODE>
 static int launch_f32_quads(const W4Params& w, const void* zp, int sdt, float qmin, float qmax, ct_stream_t stream, const char* what, uint32_t xoff = 0u) {
@@ -2316,7 +2309,7 @@ static int quantize_impl(const void* x, int xdt, const void* scale, int sdt, con
     if (rows == 0 || cols == 0) return CT_OK;
     if (!gscale && fkind == 0 && xdt == CT_F32 && tdt == CT_F32 && odt == CT_I8 && is_float_dt(sdt) && f32_quads_ok(rows, cols, cdiv, col_group, x, out)) {
         W4Params w = make_w4(x, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
-        if ((reinterpret_cast<uintptr_t>(out) & 7u) == 0) {
+        if (aligned_to<8>(out)) {
             dim3 g(w4_grid(w.units, 2));
             if (zp) hipLaunchKernelGGL((f32_quant_units_kernel<true>), g, dim3(kBlock), 0, as_stream(stream), w, sdt, p.qmin, p.qmax);
             else hipLaunchKernelGGL((f32_quant_units_kernel<false>), g, dim3(kBlock), 0, as_stream(stream), w, sdt, p.qmin, p.qmax);
@@ -2325,7 +2318,7 @@ static int quantize_impl(const void* x, int xdt, const void* scale, int sdt, con
         return launch_f32_quads<F32_Q>(w, zp, sdt, p.qmin, p.qmax, stream, "ct_quantize[f32]");
     }
     if (!gscale && fkind == 1 && xdt == CT_F32 && tdt == CT_F32 && odt == CT_F8E4M3 && is_float_dt(sdt) && f32_quads_ok(rows, cols, cdiv, col_group, x, out) &&
-        (reinterpret_cast<uintptr_t>(out) & 7u) == 0) {
+        aligned_to<8>(out)) {
         W4Params w = make_w4(x, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
         dim3 g(w4_grid(w.units, 2));
         if (zp) hipLaunchKernelGGL((f32_quant_units_kernel<true, true>), g, dim3(kBlock), 0, as_stream(stream), w, sdt, p.qmin, p.qmax);
@@ -2337,16 +2330,9 @@ static int quantize_impl(const void* x, int xdt, const void* scale, int sdt, con
         const bool shared = (cdiv % 16 == 0) || cdiv >= cols;
         dim3 g8(w4_grid(w.units / 2, 1));
         const int qmin = -(1 << (bits - 1)), qmax = (1 << (bits - 1)) - 1;
-#define CT_Q8Q(DT, ZP, SH) do { if (fkind) hipLaunchKernelGGL((f8_quant_kernel<DT, ZP, SH>), g8, dim3(kBlock), 0, as_stream(stream), w); \
-                                else hipLaunchKernelGGL((q8_quant_kernel<DT, ZP, SH, 0>), g8, dim3(kBlock), 0, as_stream(stream), w, qmin, qmax); } while (0)
-        if (xdt == CT_BF16) {
-            if (zp) { if (shared) CT_Q8Q(CT_BF16, true, true); else CT_Q8Q(CT_BF16, true, false); }
-            else { if (shared) CT_Q8Q(CT_BF16, false, true); else CT_Q8Q(CT_BF16, false, false); }
-        } else {
-            if (zp) { if (shared) CT_Q8Q(CT_F16, true, true); else CT_Q8Q(CT_F16, true, false); }
-            else { if (shared) CT_Q8Q(CT_F16, false, true); else CT_Q8Q(CT_F16, false, false); }
-        }
-#undef CT_Q8Q
+        for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) { for_bool(shared, [&](auto SH) {
+            if (fkind) hipLaunchKernelGGL((f8_quant_kernel<DT(), ZP(), SH()>), g8, dim3(kBlock), 0, as_stream(stream), w);
+            else hipLaunchKernelGGL((q8_quant_kernel<DT(), ZP(), SH(), 0>), g8, dim3(kBlock), 0, as_stream(stream), w, qmin, qmax); }); }); });
         CT_LAUNCH_CHECK("ct_quantize[flat8]");
     }
     dim3 grid = grid_2d(rows, cdiv64(cols, 8));
@@ -2376,18 +2362,14 @@ static int fake_quantize_impl(const void* x, int xdt, const void* scale, int sdt
         constexpr int U = 2;
         if (p.fkind == 0 && w.flat_scale && w.upg_shift >= 0 && (!zp || zdt == CT_I8) && w.units < ((int64_t)1 << 38)) {
             dim3 gl((unsigned)cdiv64(w.units, (int64_t)kBlock * 2));
-#define CT_FQL(DT, ZP) hipLaunchKernelGGL((fq16_lean_kernel<DT, ZP>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), \
-                                           static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), static_cast<u32x4*>(out), w.units, w.upg_shift, p.qmin, p.qmax)
-            if (xdt == CT_BF16) { if (zp) CT_FQL(CT_BF16, true); else CT_FQL(CT_BF16, false); }
-            else { if (zp) CT_FQL(CT_F16, true); else CT_FQL(CT_F16, false); }
-#undef CT_FQL
+            for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+                hipLaunchKernelGGL((fq16_lean_kernel<DT(), ZP()>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), static_cast<const uint16_t*>(scale),
+                                   static_cast<const int8_t*>(zp), static_cast<u32x4*>(out), w.units, w.upg_shift, p.qmin, p.qmax); }); });
             CT_LAUNCH_CHECK("ct_fake_quantize[fq16 lean]");
         }
         dim3 gf(w4_grid(w.units, U));
-#define CT_FQ(DT, ZP) hipLaunchKernelGGL((fq16_kernel<DT, U, ZP>), gf, dim3(kBlock), 0, as_stream(stream), w, p.qmin, p.qmax, p.fkind)
-        if (xdt == CT_BF16) { if (zp) CT_FQ(CT_BF16, true); else CT_FQ(CT_BF16, false); }
-        else { if (zp) CT_FQ(CT_F16, true); else CT_FQ(CT_F16, false); }
-#undef CT_FQ
+        for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+            hipLaunchKernelGGL((fq16_kernel<DT(), U, ZP()>), gf, dim3(kBlock), 0, as_stream(stream), w, p.qmin, p.qmax, p.fkind); }); });
         CT_LAUNCH_CHECK("ct_fake_quantize[fq16]");
     }
     dim3 grid = grid_2d(rows, cdiv64(cols, 8));
@@ -2458,7 +2440,7 @@ static int dequantize_impl(const void* xq, int qdt, const void* scale, int sdt, 
     int rc = fill_qparams(p, xq, qdt, scale, sdt, zp, zdt, rows, cols, rdiv, cdiv, scale_cols, col_group, 8, out, odt);
     if (rc) return rc;
     if (rows == 0 || cols == 0) return CT_OK;
-    p.vec = (cols % 8 == 0) && aligned16(out) && ((reinterpret_cast<uintptr_t>(xq) & 7u) == 0);
+    p.vec = (cols % 8 == 0) && aligned16(out) && (aligned_to<8>(xq));
     set_float_kind(p, 0, gscale);
     if (!gscale && qdt == CT_I8 && sdt == CT_F32 && odt == CT_F32 && f32_quads_ok(rows, cols, cdiv, col_group, out, xq)) {
         W4Params w = make_w4(xq, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
@@ -2472,15 +2454,13 @@ static int dequantize_impl(const void* xq, int qdt, const void* scale, int sdt, 
         CT_LAUNCH_CHECK("ct_dequantize[fp8 -> f32]");
     }
     if (!gscale && (qdt == CT_I8 || qdt == CT_F8E4M3) && !col_group && (sdt == CT_BF16 || sdt == CT_F16) && odt == sdt && rows > 0 && cols % 8 == 0 &&
-        (cdiv % 8 == 0 || cdiv >= cols) && aligned16(out) && (reinterpret_cast<uintptr_t>(xq) & 7u) == 0) {
+        (cdiv % 8 == 0 || cdiv >= cols) && aligned16(out) && aligned_to<8>(xq)) {
         W4Params w = make_w4(xq, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
         const int unroll = decomp_unroll(w.units, rdiv == 1 && cdiv < cols, zp != nullptr);
         dim3 g8(w4_grid(w.units, unroll));
-#define CT_Q8D(DT, ZP) CT_FOR_UNROLL(unroll, if (qdt == CT_F8E4M3) hipLaunchKernelGGL((f8_dequant_kernel<DT, U, ZP>), g8, dim3(kBlock), 0, as_stream(stream), w); \
-                                             else hipLaunchKernelGGL((q8_dequant_kernel<DT, U, ZP, 0>), g8, dim3(kBlock), 0, as_stream(stream), w))
-        if (sdt == CT_BF16) { if (zp) CT_Q8D(CT_BF16, true); else CT_Q8D(CT_BF16, false); }
-        else { if (zp) CT_Q8D(CT_F16, true); else CT_Q8D(CT_F16, false); }
-#undef CT_Q8D
+        for_dt16(sdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+            CT_FOR_UNROLL(unroll, if (qdt == CT_F8E4M3) hipLaunchKernelGGL((f8_dequant_kernel<DT(), U, ZP()>), g8, dim3(kBlock), 0, as_stream(stream), w);
+                                  else hipLaunchKernelGGL((q8_dequant_kernel<DT(), U, ZP(), 0>), g8, dim3(kBlock), 0, as_stream(stream), w)); }); });
         CT_LAUNCH_CHECK("ct_dequantize[flat8]");
     }
     dim3 grid = grid_2d(rows, cdiv64(cols, 8));
@@ -2518,23 +2498,15 @@ int ct_quant_pack(const void* x, int xdt, const void* scale, int sdt, const void
 #endif
             const int variant = w4_compress_variant(forced, groups, reinterpret_cast<uintptr_t>(x));
             CT_REQUIRE(variant != kW4CompressBad, "CT_W4_COMPRESS must be plain, lds or auto, got '%s'", forced);
-#define CT_W4L(DT, ZP) do { if (variant == kW4CompressLds) CT_W4L_(w4_quant_pack_lds_kernel, DT, ZP); else CT_W4L_(w4_quant_pack_lean_kernel, DT, ZP); } while (0)
-#define CT_W4L_(K, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), reinterpret_cast<u32x4*>(packed), groups, gshift)
-            if (xdt == CT_BF16) { if (zp) CT_W4L(CT_BF16, true); else CT_W4L(CT_BF16, false); }
-            else { if (zp) CT_W4L(CT_F16, true); else CT_W4L(CT_F16, false); }
+#define CT_W4L(K) hipLaunchKernelGGL((K<DT(), ZP()>), gl, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), static_cast<const uint16_t*>(scale), \
+                                     static_cast<const int8_t*>(zp), reinterpret_cast<u32x4*>(packed), groups, gshift)
+            for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+                if (variant == kW4CompressLds) CT_W4L(w4_quant_pack_lds_kernel); else CT_W4L(w4_quant_pack_lean_kernel); }); });
 #undef CT_W4L
-#undef CT_W4L_
             CT_LAUNCH_CHECK("ct_quant_pack[w4 lean]");
         }
-#define CT_W4Q(DT, ZP, SH) hipLaunchKernelGGL((w4_quant_pack_kernel<DT, ZP, SH>), grid, dim3(kBlock), 0, as_stream(stream), w)
-        if (xdt == CT_BF16) {
-            if (zp) { if (shared) CT_W4Q(CT_BF16, true, true); else CT_W4Q(CT_BF16, true, false); }
-            else { if (shared) CT_W4Q(CT_BF16, false, true); else CT_W4Q(CT_BF16, false, false); }
-        } else {
-            if (zp) { if (shared) CT_W4Q(CT_F16, true, true); else CT_W4Q(CT_F16, true, false); }
-            else { if (shared) CT_W4Q(CT_F16, false, true); else CT_W4Q(CT_F16, false, false); }
-        }
-#undef CT_W4Q
+        for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) { for_bool(shared, [&](auto SH) {
+            hipLaunchKernelGGL((w4_quant_pack_kernel<DT(), ZP(), SH()>), grid, dim3(kBlock), 0, as_stream(stream), w); }); }); });
         CT_LAUNCH_CHECK("ct_quant_pack[w4]");
     }
     if (bits == 8 && xdt == CT_F32 && tdt == CT_F32 && is_float_dt(sdt) && f32_quads_ok(rows, cols, cdiv, col_group, x, packed)) {
@@ -2546,13 +2518,11 @@ int ct_quant_pack(const void* x, int xdt, const void* scale, int sdt, const void
         return launch_w4_gidx<true>(w, xdt, zp, col_group, rows, stream, "ct_quant_pack[w4 g_idx]");
     }
     if (bits == 4 && tdt == CT_F32 && is_float_dt(xdt) && !col_group && is_float_dt(sdt) && cols % 8 == 0 && cdiv % 8 == 0 && aligned16(x) &&
-        (reinterpret_cast<uintptr_t>(packed) & 3u) == 0 && rows * (cols / 8) < ((int64_t)1 << 38)) {
+        aligned_to<4>(packed) && rows * (cols / 8) < ((int64_t)1 << 38)) {
         W4Params w = make_w4(x, scale, zp, zdt, packed, rows, cols, rdiv, cdiv, scale_cols);
         dim3 gf(w4_grid(w.units, 2));
-#define CT_W4F(X) do { if (zp) hipLaunchKernelGGL((w4_quant_pack_f32_kernel<X, true>), gf, dim3(kBlock), 0, as_stream(stream), w, sdt); \
-                       else hipLaunchKernelGGL((w4_quant_pack_f32_kernel<X, false>), gf, dim3(kBlock), 0, as_stream(stream), w, sdt); } while (0)
-        if (xdt == CT_F32) CT_W4F(CT_F32); else if (xdt == CT_BF16) CT_W4F(CT_BF16); else CT_W4F(CT_F16);
-#undef CT_W4F
+        for_dt(xdt, [&](auto X) { for_bool(zp != nullptr, [&](auto ZP) {
+            hipLaunchKernelGGL((w4_quant_pack_f32_kernel<X(), ZP()>), gf, dim3(kBlock), 0, as_stream(stream), w, sdt); }); });
         CT_LAUNCH_CHECK("ct_quant_pack[w4 f32]");
     }
     if (bits == 8 && cols % 32 == 0 && q8_eligible(xdt, sdt, tdt, rows, cols, cdiv, col_group, x, packed)) {
@@ -2560,15 +2530,8 @@ int ct_quant_pack(const void* x, int xdt, const void* scale, int sdt, const void
         W4Params w = make_w4(x, scale, zp, zdt, packed, rows, cols, rdiv, cdiv, scale_cols);
         const bool shared = (cdiv % 16 == 0) || cdiv >= cols;
         dim3 g8(w4_grid(w.units / 2, 1));
-#define CT_Q8P(DT, ZP, SH) hipLaunchKernelGGL((q8_quant_kernel<DT, ZP, SH, 128>), g8, dim3(kBlock), 0, as_stream(stream), w, -128, 127)
-        if (xdt == CT_BF16) {
-            if (zp) { if (shared) CT_Q8P(CT_BF16, true, true); else CT_Q8P(CT_BF16, true, false); }
-            else { if (shared) CT_Q8P(CT_BF16, false, true); else CT_Q8P(CT_BF16, false, false); }
-        } else {
-            if (zp) { if (shared) CT_Q8P(CT_F16, true, true); else CT_Q8P(CT_F16, true, false); }
-            else { if (shared) CT_Q8P(CT_F16, false, true); else CT_Q8P(CT_F16, false, false); }
-        }
-#undef CT_Q8P
+        for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) { for_bool(shared, [&](auto SH) {
+            hipLaunchKernelGGL((q8_quant_kernel<DT(), ZP(), SH(), 128>), g8, dim3(kBlock), 0, as_stream(stream), w, -128, 127); }); }); });
         CT_LAUNCH_CHECK("ct_quant_pack[w8]");
     }
     // round 6: the widths next to 4 and 8 in the common checkpoint layout (ct_quant_wb.hip)
@@ -2593,11 +2556,9 @@ int ct_rtn_quant_pack_w4(const void* x, int xdt, int64_t rows, int64_t cols, int
     const int lpg = (int)(group / 32);
     CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     dim3 grid((unsigned)cdiv64(lanes, kBlock));
-#define CT_RTN4(DT, SY) hipLaunchKernelGGL((rtn_w4_kernel<DT, SY>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, lpg, \
-                                           reinterpret_cast<u32x4*>(packed), scale_out, zp_out)
-    if (xdt == CT_BF16) { if (symmetric) CT_RTN4(CT_BF16, true); else CT_RTN4(CT_BF16, false); }
-    else { if (symmetric) CT_RTN4(CT_F16, true); else CT_RTN4(CT_F16, false); }
-#undef CT_RTN4
+    for_dt16(xdt, [&](auto DT) { for_bool(symmetric, [&](auto SY) {
+        hipLaunchKernelGGL((rtn_w4_kernel<DT(), SY()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, lpg,
+                           reinterpret_cast<u32x4*>(packed), scale_out, zp_out); }); });
     CT_LAUNCH_CHECK("ct_rtn_quant_pack_w4");
 }
 
@@ -2615,7 +2576,7 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
     CT_REQUIRE(rows >= 0 && cols >= 0 && cols % 8 == 0 && cols <= kChannel8MaxCols,
                "columns (%lld) must be a multiple of 8 and at most CT_RTN_CHANNEL8_MAX_COLS = %lld", (long long)cols, (long long)kChannel8MaxCols);
     CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
-    CT_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && scale_out != nullptr, "misaligned buffers");
+    CT_REQUIRE(aligned16(x) && aligned_to<8>(out) && scale_out != nullptr, "misaligned buffers");
     CT_REQUIRE(symmetric || zp_out != nullptr, "asymmetric quantization needs the zero-point output");
     if (rows == 0 || cols == 0) return CT_OK;
     const int upr = (int)(cols / 8);
@@ -2631,31 +2592,24 @@ int ct_rtn_quant_channel8(const void* x, int xdt, int64_t rows, int64_t cols, in
     if (form == kChannel8Wave && cdiv64(rows, kBlock / 64) < ((int64_t)1 << 31)) {
         const int needw = (upr + 63) / 64;
         const unsigned gw = (unsigned)cdiv64(rows, kBlock / 64);
-#define CT_RW8(DT, MU, F8) hipLaunchKernelGGL((rtn_channel8_wave_kernel<DT, MU, F8>), dim3(gw), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
-                                              symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
-#define CT_RW8_U(DT, F8) do { if (needw <= 2) CT_RW8(DT, 2, F8); else if (needw <= 4) CT_RW8(DT, 4, F8); else CT_RW8(DT, 16, F8); } while (0)
-        if (xdt == CT_BF16) { if (fp8) CT_RW8_U(CT_BF16, true); else CT_RW8_U(CT_BF16, false); }
-        else { if (fp8) CT_RW8_U(CT_F16, true); else CT_RW8_U(CT_F16, false); }
-#undef CT_RW8_U
+#define CT_RW8(MU) hipLaunchKernelGGL((rtn_channel8_wave_kernel<DT(), MU, F8()>), dim3(gw), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
+                                      symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
+        for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) { if (needw <= 2) CT_RW8(2); else if (needw <= 4) CT_RW8(4); else CT_RW8(16); }); });
 #undef CT_RW8
         CT_LAUNCH_CHECK("ct_rtn_quant_channel8[wave]");
     }
     const int need = (upr + kBlock - 1) / kBlock;
     const unsigned grid = (unsigned)(rows < ((int64_t)1 << 30) ? rows : ((int64_t)1 << 30));
     if (form == kChannel8Long) {  // beyond 8 units per thread: registers for the first 2048 units, the rest streamed twice
-#define CT_RL8(DT, F8) hipLaunchKernelGGL((rtn_channel8_long_kernel<DT, F8>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
-                                          symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
-        if (xdt == CT_BF16) { if (fp8) CT_RL8(CT_BF16, true); else CT_RL8(CT_BF16, false); }
-        else { if (fp8) CT_RL8(CT_F16, true); else CT_RL8(CT_F16, false); }
-#undef CT_RL8
+        for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+            hipLaunchKernelGGL((rtn_channel8_long_kernel<DT(), F8()>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr,
+                               symmetric, static_cast<u32x2*>(out), scale_out, zp_out); }); });
         CT_LAUNCH_CHECK("ct_rtn_quant_channel8[long]");
     }
-#define CT_RC8(DT, MU, F8) hipLaunchKernelGGL((rtn_channel8_kernel<DT, MU, F8>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
-                                              symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
-#define CT_RC8_U(DT, F8) do { if (need <= 1) CT_RC8(DT, 1, F8); else if (need <= 2) CT_RC8(DT, 2, F8); else if (need <= 4) CT_RC8(DT, 4, F8); else CT_RC8(DT, 8, F8); } while (0)
-    if (xdt == CT_BF16) { if (fp8) CT_RC8_U(CT_BF16, true); else CT_RC8_U(CT_BF16, false); }
-    else { if (fp8) CT_RC8_U(CT_F16, true); else CT_RC8_U(CT_F16, false); }
-#undef CT_RC8_U
+#define CT_RC8(MU) hipLaunchKernelGGL((rtn_channel8_kernel<DT(), MU, F8()>), dim3(grid), dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), rows, upr, \
+                                      symmetric, static_cast<u32x2*>(out), scale_out, zp_out)
+    for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        if (need <= 1) CT_RC8(1); else if (need <= 2) CT_RC8(2); else if (need <= 4) CT_RC8(4); else CT_RC8(8); }); });
 #undef CT_RC8
     CT_LAUNCH_CHECK("ct_rtn_quant_channel8");
 }
@@ -2675,43 +2629,19 @@ static int64_t channel8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
     const int64_t blocks = form == kChannel8Wave ? cdiv64(it.rows, kBlock / 64) : it.rows;
     if (blocks >= ((int64_t)1 << 31)) CT_C8_REFUSE("2^31 workgroups or more");
 #undef CT_C8_REFUSE
-    it.units = it.rows * upr;
-    it.upg = (int32_t)upr;
-    it.upg_shift = form;
-    it.main_blocks = blocks;
-    it.g_magic = 0;
-    it.g_shift = 0;
-    it.first_block = first_block;
+    fill_w4_item(it, it.rows * upr, (int32_t)upr, form, first_block, blocks);
     return blocks;
 }
 
-int64_t ct_rtn_channel8_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_channel8_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t b = channel8_plan_item(items[i], i, blocks);
-        if (b < 0) return -1;
-        blocks += b;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_channel8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
-}
+int64_t ct_rtn_channel8_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_rtn_channel8_batch_plan", items, n, channel8_plan_item); }
 
 int ct_rtn_quant_channel8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass channel-wise compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_BATCH_SIZE(n, total_blocks);
     CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
     if (n == 0 || total_blocks == 0) return CT_OK;
-#define CT_RC8B(DT, F8) hipLaunchKernelGGL((rtn_channel8_batch_kernel<DT, F8>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric)
-    if (xdt == CT_BF16) { if (fp8) CT_RC8B(CT_BF16, true); else CT_RC8B(CT_BF16, false); }
-    else { if (fp8) CT_RC8B(CT_F16, true); else CT_RC8B(CT_F16, false); }
-#undef CT_RC8B
+    for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        hipLaunchKernelGGL((rtn_channel8_batch_kernel<DT(), F8()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric); }); });
     CT_LAUNCH_CHECK("ct_rtn_quant_channel8_batch");
 }
 
@@ -2731,35 +2661,14 @@ static int64_t block8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
     const int64_t G = it.cols / bw, blocks = ((it.rows + bh - 1) / bh) * G;
     if (blocks >= ((int64_t)1 << 31)) CT_B8_REFUSE("2^31 blocks or more");
 #undef CT_B8_REFUSE
-    it.units = it.rows * (it.cols / 8);
-    it.upg = (int32_t)(bw / 8);
-    it.upg_shift = log2_exact(it.upg);
-    it.main_blocks = log2_exact(bh) + 1;
-    int L = 0;  // n / G as (n * magic) >> shift, exact for n < 2^31 (Granlund-Montgomery, N = 31)
-    while (((int64_t)1 << L) < G) ++L;
-    it.g_shift = 31 + L;
-    it.g_magic = (uint32_t)((((uint64_t)1 << it.g_shift) + (uint64_t)(G - 1)) / (uint64_t)G);
-    it.first_block = first_block;
+    uint32_t magic = 0;
+    int32_t shift = 0;
+    magic_div(G, &magic, &shift);  // 1 <= G <= blocks < 2^31: never refused
+    fill_w4_item(it, it.rows * (it.cols / 8), (int32_t)(bw / 8), log2_exact(bw / 8), first_block, log2_exact(bh) + 1, magic, shift);
     return blocks;
 }
 
-int64_t ct_rtn_block8_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_block8_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t b = block8_plan_item(items[i], i, blocks);
-        if (b < 0) return -1;
-        blocks += b;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_block8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
-}
+int64_t ct_rtn_block8_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_rtn_block8_batch_plan", items, n, block8_plan_item); }
 
 int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t block_h, int64_t block_w, int fp8, int symmetric, void* out,
                         void* scale_out, int8_t* zp_out, ct_stream_t stream) {
@@ -2775,24 +2684,20 @@ int ct_rtn_quant_block8(const void* x, int xdt, int64_t rows, int64_t cols, int6
     if (blocks < 0) return CT_ERR_INVALID_ARG;
     const int need = (int)((block_h * block_w / 8 + kBlock - 1) / kBlock);
     const dim3 grid((unsigned)blocks);
-#define CT_RB8(DT, MU, F8) hipLaunchKernelGGL((rtn_block8_kernel<DT, MU, F8>), grid, dim3(kBlock), 0, as_stream(stream), it, symmetric)
-#define CT_RB8_U(DT, F8) do { if (need <= 1) CT_RB8(DT, 1, F8); else if (need <= 2) CT_RB8(DT, 2, F8); else if (need <= 4) CT_RB8(DT, 4, F8); else CT_RB8(DT, 8, F8); } while (0)
-    if (xdt == CT_BF16) { if (fp8) CT_RB8_U(CT_BF16, true); else CT_RB8_U(CT_BF16, false); }
-    else { if (fp8) CT_RB8_U(CT_F16, true); else CT_RB8_U(CT_F16, false); }
-#undef CT_RB8_U
+#define CT_RB8(MU) hipLaunchKernelGGL((rtn_block8_kernel<DT(), MU, F8()>), grid, dim3(kBlock), 0, as_stream(stream), it, symmetric)
+    for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        if (need <= 1) CT_RB8(1); else if (need <= 2) CT_RB8(2); else if (need <= 4) CT_RB8(4); else CT_RB8(8); }); });
 #undef CT_RB8
     CT_LAUNCH_CHECK("ct_rtn_quant_block8");
 }
 
 int ct_rtn_quant_block8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int fp8, int symmetric, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass block-wise compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_BATCH_SIZE(n, total_blocks);
     CT_REQUIRE(!fp8 || symmetric, "FLOAT 8-bit round-to-nearest is symmetric");
     if (n == 0 || total_blocks == 0) return CT_OK;
-#define CT_RB8B(DT, F8) hipLaunchKernelGGL((rtn_block8_batch_kernel<DT, F8>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric)
-    if (xdt == CT_BF16) { if (fp8) CT_RB8B(CT_BF16, true); else CT_RB8B(CT_BF16, false); }
-    else { if (fp8) CT_RB8B(CT_F16, true); else CT_RB8B(CT_F16, false); }
-#undef CT_RB8B
+    for_dt16(xdt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        hipLaunchKernelGGL((rtn_block8_batch_kernel<DT(), F8()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, symmetric); }); });
     CT_LAUNCH_CHECK("ct_rtn_quant_block8_batch");
 }
 
@@ -2810,35 +2715,14 @@ static int64_t group8_plan_item(ct_w4_item& it, int i, int64_t first_block) {
     if (!it.src || !it.dst) CT_G8_REFUSE("the weights and the code output are required");
     if (!it.scale && !it.zp_packed) CT_G8_REFUSE("a scale output is required: scale, or the E8M0 codes in zp_packed");
     if (!aligned16(it.src) || !aligned16(it.dst)) CT_G8_REFUSE("misaligned pointer: src and dst must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(it.scale) & 1u) CT_G8_REFUSE("misaligned pointer: the scale output must be 2-byte aligned");
+    if (!aligned_to<2>(it.scale)) CT_G8_REFUSE("misaligned pointer: the scale output must be 2-byte aligned");
 #undef CT_G8_REFUSE
-    it.units = it.rows * (it.cols / 8);
-    it.upg = (int32_t)(g / 8);
-    it.upg_shift = log2_exact(it.upg);
-    it.first_block = first_block;
-    it.main_blocks = cdiv64(it.units / 2, kBlock);
-    it.g_magic = 0;
-    it.g_shift = 0;
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, (int32_t)(g / 8), log2_exact(g / 8), first_block, cdiv64(units / 2, kBlock));
     return it.main_blocks;
 }
 
-int64_t ct_rtn_group8_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_group8_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t b = group8_plan_item(items[i], i, blocks);
-        if (b < 0) return -1;
-        blocks += b;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_group8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
-}
+int64_t ct_rtn_group8_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_rtn_group8_batch_plan", items, n, group8_plan_item); }
 
 // kind / symmetric / words of the group entries, checked alike for one tensor and a table
 #define CT_G8_KIND_CHECK() do { \
@@ -2846,11 +2730,9 @@ int64_t ct_rtn_group8_batch_plan(ct_w4_item* items, int n) {
     CT_REQUIRE(kind == QP_INT || symmetric, "FLOAT 8-bit round-to-nearest is symmetric"); \
     CT_REQUIRE(kind == QP_INT || !words, "the (code + 128) word form is INT only"); } while (0)
 // KERNEL<DT, KIND, SYM> by the runtime dtype, kind and symmetry
-#define CT_G8_DISPATCH(LAUNCH) do { \
-    if (xdt == CT_BF16) { if (kind == QP_MXFP8) LAUNCH(CT_BF16, QP_MXFP8, true); else if (kind == QP_FP8) LAUNCH(CT_BF16, QP_FP8, true); \
-                          else if (symmetric) LAUNCH(CT_BF16, QP_INT, true); else LAUNCH(CT_BF16, QP_INT, false); } \
-    else { if (kind == QP_MXFP8) LAUNCH(CT_F16, QP_MXFP8, true); else if (kind == QP_FP8) LAUNCH(CT_F16, QP_FP8, true); \
-           else if (symmetric) LAUNCH(CT_F16, QP_INT, true); else LAUNCH(CT_F16, QP_INT, false); } } while (0)
+#define CT_G8_DISPATCH(LAUNCH) for_dt16(xdt, [&](auto DT) { \
+    if (kind == QP_MXFP8) LAUNCH(DT(), QP_MXFP8, true); else if (kind == QP_FP8) LAUNCH(DT(), QP_FP8, true); \
+    else if (symmetric) LAUNCH(DT(), QP_INT, true); else LAUNCH(DT(), QP_INT, false); })
 
 int ct_rtn_quant_group8(const void* x, int xdt, int64_t rows, int64_t cols, int64_t group, int kind, int symmetric, int words, void* out, void* scale_out,
                         int8_t* zp_out, uint8_t* e8m0_out, const uint8_t* code_table, ct_stream_t stream) {
@@ -2880,7 +2762,7 @@ int ct_rtn_quant_group8(const void* x, int xdt, int64_t rows, int64_t cols, int6
 int ct_rtn_quant_group8_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int xdt, int kind, int symmetric, int words, const uint8_t* code_table,
                               ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "batched one-pass group-wise compress: 16-bit weights only, got dtype %d", xdt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_BATCH_SIZE(n, total_blocks);
     CT_G8_KIND_CHECK();
     CT_REQUIRE(kind != QP_MXFP8 || code_table != nullptr, "MXFP8 needs the code table");
     if (n == 0 || total_blocks == 0) return CT_OK;
@@ -2903,7 +2785,7 @@ int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_
     if (rc) return rc;
     if (rows == 0 || cols == 0) return CT_OK;
     if (words == cols / 8 && w4_eligible(sdt, sdt, odt, bits, rows, cols, rdiv, cdiv, col_group, packed, out) &&
-        (reinterpret_cast<uintptr_t>(packed) & 3u) == 0) {
+        aligned_to<4>(packed)) {
         W4Params w = make_w4(packed, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
         // units per lane: decomp_unroll_grouped()
         const int unroll = decomp_unroll_grouped(w.units);
@@ -2916,13 +2798,11 @@ int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_
         // 29.85 -> 28.55 us at 8192^2 (71.0 -> 74.1 % of 8 TB/s), symmetric 28.6-29.2 -> 28.4; a tensor of ONE round is latency-bound and loses
         // with them (4096^2: 8.5 -> 10.2 us), so those keep the vector loads (tools/kbench/kbench_w4d.hip, profiles/r05_w4d_scale_modes.txt)
         const bool scalar = w.flat_scale && w.upg_shift == 4 && w.units % 64 == 0 && w.units > 8 * (int64_t)kCUs * 8 * kBlock && (!zp || zdt == CT_I8) &&
-                            (reinterpret_cast<uintptr_t>(scale) & 7u) == 0 && (reinterpret_cast<uintptr_t>(zp) & 3u) == 0;
-#define CT_W4D(DT, ZP) CT_FOR_UNROLL(unroll, if (scalar) hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT, U, ZP, kW4ScaleScalar>), grid, dim3(kBlock), 0, as_stream(stream), w); \
-                                             else if (rowlead) hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT, U, ZP, kW4ScaleRowLead>), grid, dim3(kBlock), 0, as_stream(stream), w); \
-                                             else hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT, U, ZP, kW4ScalePerLane>), grid, dim3(kBlock), 0, as_stream(stream), w))
-        if (sdt == CT_BF16) { if (zp) CT_W4D(CT_BF16, true); else CT_W4D(CT_BF16, false); }
-        else { if (zp) CT_W4D(CT_F16, true); else CT_W4D(CT_F16, false); }
-#undef CT_W4D
+                            aligned_to<8>(scale) && aligned_to<4>(zp);
+        for_dt16(sdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+            CT_FOR_UNROLL(unroll, if (scalar) hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT(), U, ZP(), kW4ScaleScalar>), grid, dim3(kBlock), 0, as_stream(stream), w);
+                                  else if (rowlead) hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT(), U, ZP(), kW4ScaleRowLead>), grid, dim3(kBlock), 0, as_stream(stream), w);
+                                  else hipLaunchKernelGGL((w4_unpack_dequant_kernel<DT(), U, ZP(), kW4ScalePerLane>), grid, dim3(kBlock), 0, as_stream(stream), w)); }); });
         CT_LAUNCH_CHECK("ct_unpack_dequant[w4]");
     }
     if (bits == 8 && words == cols / 4 && sdt == CT_F32 && odt == CT_F32 && f32_quads_ok(rows, cols, cdiv, col_group, out, packed)) {
@@ -2934,7 +2814,7 @@ int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_
         return launch_w4_gidx<false>(w, sdt, zp, col_group, rows, stream, "ct_unpack_dequant[w4 g_idx]");
     }
     if (bits == 4 && words == cols / 8 && sdt == CT_F32 && odt == CT_F32 && !col_group && cols % 8 == 0 && cdiv % 8 == 0 && aligned16(out) &&
-        (reinterpret_cast<uintptr_t>(packed) & 3u) == 0 && rows * (cols / 8) < ((int64_t)1 << 38)) {
+        aligned_to<4>(packed) && rows * (cols / 8) < ((int64_t)1 << 38)) {
         W4Params w = make_w4(packed, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
         dim3 gf(w4_grid(2 * w.units, 4));
         if (zp) hipLaunchKernelGGL((w4_unpack_dequant_f32_kernel<true>), gf, dim3(kBlock), 0, as_stream(stream), w);
@@ -2942,15 +2822,13 @@ int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_
         CT_LAUNCH_CHECK("ct_unpack_dequant[w4 f32]");
     }
     if (bits == 8 && words == cols / 4 && cols % 32 == 0 && !col_group && (sdt == CT_BF16 || sdt == CT_F16) && odt == sdt && rows > 0 &&
-        (cdiv % 8 == 0 || cdiv >= cols) && aligned16(out) && (reinterpret_cast<uintptr_t>(packed) & 7u) == 0) {
+        (cdiv % 8 == 0 || cdiv >= cols) && aligned16(out) && aligned_to<8>(packed)) {
         W4Params w = make_w4(packed, scale, zp, zdt, out, rows, cols, rdiv, cdiv, scale_cols);
         // units per lane: decomp_unroll_grouped() (at 8 units per lane this variant — it un-biases the packed bytes — needs 117 VGPRs)
         const int unroll = decomp_unroll_grouped(w.units);
         dim3 g8(w4_grid(w.units, unroll));
-#define CT_Q8U(DT, ZP) CT_FOR_UNROLL(unroll, hipLaunchKernelGGL((q8_dequant_kernel<DT, U, ZP, 128>), g8, dim3(kBlock), 0, as_stream(stream), w))
-        if (sdt == CT_BF16) { if (zp) CT_Q8U(CT_BF16, true); else CT_Q8U(CT_BF16, false); }
-        else { if (zp) CT_Q8U(CT_F16, true); else CT_Q8U(CT_F16, false); }
-#undef CT_Q8U
+        for_dt16(sdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+            CT_FOR_UNROLL(unroll, hipLaunchKernelGGL((q8_dequant_kernel<DT(), U, ZP(), 128>), g8, dim3(kBlock), 0, as_stream(stream), w)); }); });
         CT_LAUNCH_CHECK("ct_unpack_dequant[w8]");
     }
     if (words == (cols / 32) * bits && wb_layout_ok(sdt, sdt, odt, bits, zdt, zp, rows, cols, rdiv, cdiv, scale_cols, col_group, out, packed))
@@ -2971,26 +2849,23 @@ static int64_t w4_plan_item(ct_w4_item& it, int i, int direction, int64_t first_
                   (long long)it.cols, (long long)it.group);
         return -1;
     }
-    it.units = it.rows * (it.cols / 8);
-    it.upg = (int32_t)(g / 8);
-    it.upg_shift = log2_exact(it.upg);
-    it.first_block = first_block;
-    it.main_blocks = direction == 0 ? cdiv64(it.units / 4, kBlock) : cdiv64(it.units, (int64_t)kBlock * kBatchUnroll * kW4BatchIter);
-    // n / G as (n * magic) >> shift, exact for n < 2^31 (Granlund-Montgomery with N = 31: magic = ceil(2^(31 + L) / G), L = ceil(log2 G), magic < 2^32)
+    const int64_t units = it.rows * (it.cols / 8);
     const int64_t G = it.cols / g;
-    int L = 0;
-    while (((int64_t)1 << L) < G) ++L;
-    if (L > 31) {
+    uint32_t magic = it.g_magic;  // an item refused for its groups per row keeps the two words it came with
+    int32_t shift = it.g_shift;
+    const bool divides = magic_div(G, &magic, &shift);
+    const int32_t upg = (int32_t)(g / 8);
+    fill_w4_item(it, units, upg, log2_exact(upg), first_block,
+                 direction == 0 ? cdiv64(units / 4, kBlock) : cdiv64(units, (int64_t)kBlock * kBatchUnroll * kW4BatchIter), magic, shift);
+    if (!divides) {
         set_error("ct_w4_batch_plan: item %d has %lld groups per row", i, (long long)G);
         return -1;
     }
-    it.g_shift = 31 + L;
-    it.g_magic = (uint32_t)((((uint64_t)1 << it.g_shift) + (uint64_t)(G - 1)) / (uint64_t)G);  // 2^(31 + L) + G - 1 < 2^63
     int64_t tail = 0;
     if (it.zp_packed) {
         const bool fits = direction == 0
             ? it.zp != nullptr
-            : (g == 128 && it.cols % 512 == 0 && it.units < ((int64_t)1 << 31) && aligned16(it.zp_packed) && (reinterpret_cast<uintptr_t>(it.scale) & 7u) == 0);
+            : (g == 128 && it.cols % 512 == 0 && it.units < ((int64_t)1 << 31) && aligned16(it.zp_packed) && aligned_to<8>(it.scale));
         if (!fits) {
             set_error(direction == 0 ? "ct_w4_batch_plan: item %d asks for packed zero points (zp_packed) without giving the int8 zero points (zp)"
                                      : "ct_w4_batch_plan: item %d (rows %lld, cols %lld, group %lld) cannot read its zero points in packed form "
@@ -3005,36 +2880,23 @@ static int64_t w4_plan_item(ct_w4_item& it, int i, int direction, int64_t first_
 }
 
 int64_t ct_w4_batch_plan(ct_w4_item* items, int n, int direction) {
-    if (n < 0 || (n > 0 && items == nullptr) || (direction != 0 && direction != 1)) {
-        set_error("ct_w4_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t b = w4_plan_item(items[i], i, direction, blocks);
-        if (b < 0) return -1;
-        blocks += b;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_w4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    PlanRules rules;
+    rules.args_ok = direction == 0 || direction == 1;
+    return plan_table("ct_w4_batch_plan", items, n, [&](ct_w4_item& it, int i, int64_t first_block) { return w4_plan_item(it, i, direction, first_block); }, rules);
 }
 
 int ct_quant_pack_w4_zp(const void* x, int xdt, const void* scale, const int8_t* zp, int64_t rows, int64_t cols, int64_t group, int32_t* packed,
                         int32_t* zp_packed, ct_stream_t stream) {
     CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "ct_quant_pack_w4_zp: 16-bit weights only, got dtype %d", xdt);
     CT_REQUIRE(rows >= 0 && cols >= 0, "negative shape");
-    CT_REQUIRE(zp != nullptr && zp_packed != nullptr && (reinterpret_cast<uintptr_t>(zp_packed) & 3u) == 0, "zp / zp_packed NULL or misaligned");
+    CT_REQUIRE(zp != nullptr && zp_packed != nullptr && aligned_to<4>(zp_packed), "zp / zp_packed NULL or misaligned");
     if (rows == 0 || cols == 0) return CT_OK;
     ct_w4_item it{};
     it.src = x; it.scale = scale; it.zp = zp; it.dst = packed; it.rows = rows; it.cols = cols; it.group = group; it.zp_packed = zp_packed;
     const int64_t blocks = w4_plan_item(it, 0, 0, 0);
     if (blocks < 0) return CT_ERR_INVALID_ARG;
     CT_REQUIRE(blocks < ((int64_t)1 << 31), "tensor too large for one launch");
-    if (xdt == CT_BF16) hipLaunchKernelGGL((w4_quant_pack_one_kernel<CT_BF16>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it);
-    else hipLaunchKernelGGL((w4_quant_pack_one_kernel<CT_F16>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it);
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((w4_quant_pack_one_kernel<DT()>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it); });
     CT_LAUNCH_CHECK("ct_quant_pack_w4_zp");
 }
 
@@ -3044,7 +2906,7 @@ int ct_unpack_dequant_w4_zp(const int32_t* packed, const void* scale, int sdt, c
     CT_REQUIRE(rows >= 0 && cols >= 0, "negative shape");
     CT_REQUIRE(zp_packed != nullptr, "zp_packed is NULL");
     if (rows == 0 || cols == 0) return CT_OK;
-    if (!(group == 128 && cols % 512 == 0 && rows * (cols / 8) < ((int64_t)1 << 31) && aligned16(zp_packed) && (reinterpret_cast<uintptr_t>(scale) & 7u) == 0))
+    if (!(group == 128 && cols % 512 == 0 && rows * (cols / 8) < ((int64_t)1 << 31) && aligned16(zp_packed) && aligned_to<8>(scale)))
         CT_UNSUPPORTED("ct_unpack_dequant_w4_zp: needs group == 128, cols %% 512 == 0, rows * cols < 2^34, zp_packed 16-byte and scale 8-byte aligned "
                        "(unpack the zero points with ct_unpack_int32_dim0 and call ct_unpack_dequant)");
     ct_w4_item it{};
@@ -3054,112 +2916,75 @@ int ct_unpack_dequant_w4_zp(const int32_t* packed, const void* scale, int sdt, c
     if (blocks < 0) return CT_ERR_INVALID_ARG;
     CT_REQUIRE(blocks < ((int64_t)1 << 31), "tensor too large for one launch");
     const int64_t stride = (int64_t)kBlock * kBatchUnroll;
-    if (sdt == CT_BF16) hipLaunchKernelGGL((w4_unpack_dequant_one_kernel<CT_BF16>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it, stride);
-    else hipLaunchKernelGGL((w4_unpack_dequant_one_kernel<CT_F16>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it, stride);
+    for_dt16(sdt, [&](auto DT) { hipLaunchKernelGGL((w4_unpack_dequant_one_kernel<DT()>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), it, stride); });
     CT_LAUNCH_CHECK("ct_unpack_dequant_w4_zp");
 }
 
 int ct_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, ct_stream_t stream) {
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched W4 path: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-    if (dt == CT_BF16) hipLaunchKernelGGL((w4_quant_pack_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
-    else hipLaunchKernelGGL((w4_quant_pack_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_BATCH_ARGS(n, total_blocks);
+    for_dt16(dt, [&](auto DT) { hipLaunchKernelGGL((w4_quant_pack_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_quant_pack_batch");
 }
 
 int ct_unpack_dequant_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, ct_stream_t stream) {
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched W4 path: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     const int64_t stride = (int64_t)kBlock * kBatchUnroll;
-    if (dt == CT_BF16) hipLaunchKernelGGL((w4_unpack_dequant_batch_kernel<CT_BF16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, stride);
-    else hipLaunchKernelGGL((w4_unpack_dequant_batch_kernel<CT_F16>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, stride);
+    for_dt16(dt, [&](auto DT) {
+        hipLaunchKernelGGL((w4_unpack_dequant_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, stride); });
     CT_LAUNCH_CHECK("ct_unpack_dequant_batch");
 }
 
-int64_t ct_rtn_w4_batch_plan(ct_w4_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_w4_batch_plan: bad arguments");
+static int64_t rtn_w4_plan_item(ct_w4_item& it, int i, int64_t first_block) {
+    const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
+    // the conditions of ct_rtn_quant_pack_w4, per item
+    const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
+                    aligned16(it.src) && aligned16(it.dst);
+    if (!ok) {
+        set_error("ct_rtn_w4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W4 compress "
+                  "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, 16-byte aligned src / dst, the scale output)", i, (long long)it.rows,
+                  (long long)it.cols, (long long)it.group);
         return -1;
     }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
-        // the conditions of ct_rtn_quant_pack_w4, per item
-        const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
-                        aligned16(it.src) && aligned16(it.dst);
-        if (!ok) {
-            set_error("ct_rtn_w4_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W4 compress "
-                      "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, 16-byte aligned src / dst, the scale output)", i, (long long)it.rows,
-                      (long long)it.cols, (long long)it.group);
-            return -1;
-        }
-        if (it.zp_packed) {
-            set_error("ct_rtn_w4_batch_plan: item %d gives zp_packed; the stored zero points come from ct_zp4_pack_dim0_batch behind this launch", i);
-            return -1;
-        }
-        it.units = it.rows * (it.cols / 8);
-        it.upg = (int32_t)(g / 8);
-        it.upg_shift = log2_exact(it.upg);
-        it.first_block = blocks;
-        it.main_blocks = cdiv64(it.units / 4, kBlock);
-        it.g_magic = 0;
-        it.g_shift = 0;
-        blocks += it.main_blocks;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_w4_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
+    if (it.zp_packed) {
+        set_error("ct_rtn_w4_batch_plan: item %d gives zp_packed; the stored zero points come from ct_zp4_pack_dim0_batch behind this launch", i);
         return -1;
     }
-    return blocks;
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, (int32_t)(g / 8), log2_exact(g / 8), first_block, cdiv64(units / 4, kBlock));
+    return it.main_blocks;
 }
+
+int64_t ct_rtn_w4_batch_plan(ct_w4_item* items, int n) { return plan_table("ct_rtn_w4_batch_plan", items, n, rtn_w4_plan_item); }
 
 int ct_rtn_quant_pack_w4_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int symmetric, ct_stream_t stream) {
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched one-pass W4 compress: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-#define CT_RTN4B(DT, SY) hipLaunchKernelGGL((rtn_w4_batch_kernel<DT, SY>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n)
-    if (dt == CT_BF16) { if (symmetric) CT_RTN4B(CT_BF16, true); else CT_RTN4B(CT_BF16, false); }
-    else { if (symmetric) CT_RTN4B(CT_F16, true); else CT_RTN4B(CT_F16, false); }
-#undef CT_RTN4B
+    CT_BATCH_ARGS(n, total_blocks);
+    for_dt16(dt, [&](auto DT) { for_bool(symmetric, [&](auto SY) {
+        hipLaunchKernelGGL((rtn_w4_batch_kernel<DT(), SY()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); }); });
     CT_LAUNCH_CHECK("ct_rtn_quant_pack_w4_batch");
 }
 
-int64_t ct_q8_batch_plan(ct_w4_item* items, int n, int direction) {
-    if (n < 0 || (n > 0 && items == nullptr) || (direction != 0 && direction != 1)) {
-        set_error("ct_q8_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        const int64_t numel = it.rows * it.cols;
-        it.main_blocks = 0;
-        if (it.group < 0) {  // block strategy: -group = (rows per block << 24) | columns per block
-            const int64_t bh = (-it.group) >> 24, bw = (-it.group) & 0xffffff;
-            const bool okb = it.rows > 0 && it.cols > 0 && bh >= 1 && bw >= 16 && (bh & (bh - 1)) == 0 && (bw & (bw - 1)) == 0 && it.cols % bw == 0 && it.src && it.scale && it.dst &&
-                             aligned16(it.src) && aligned16(it.dst) && numel / 8 < ((int64_t)1 << 31);
-            if (!okb) {
-                set_error("ct_q8_batch_plan: item %d (rows %lld, cols %lld, block %lld x %lld) is not eligible for the batched 8-bit path (block sides must be powers of "
-                          "two, the width >= 16 and a divisor of cols, fewer than 2^34 elements, 16-byte aligned buffers)", i, (long long)it.rows, (long long)it.cols,
-                          (long long)bh, (long long)bw);
-                return -1;
-            }
-            it.units = numel / 8;
-            it.upg = (int32_t)(bw / 8);
-            it.upg_shift = log2_exact(it.upg);
-            it.main_blocks = log2_exact(bh) + 1;
-            const int64_t upr = it.cols / 8;  // n / upr as (n * magic) >> shift, exact for n < 2^31 (Granlund-Montgomery, N = 31)
-            int L = 0;
-            while (((int64_t)1 << L) < upr) ++L;
-            it.g_shift = 31 + L;
-            it.g_magic = (uint32_t)((((uint64_t)1 << it.g_shift) + (uint64_t)(upr - 1)) / (uint64_t)upr);
-            it.first_block = blocks;
-            blocks += direction == 0 ? cdiv64(it.units / 2, kBlock) : cdiv64(it.units, (int64_t)kBlock * kBatchUnroll * kBatchIter);
-            continue;
+// a group / channel / whole-tensor item, or (group < 0) a block item; it leaves g_magic / g_shift of the former as they came
+static int64_t q8_plan_item(ct_w4_item& it, int i, int direction, int64_t first_block) {
+    const int64_t numel = it.rows * it.cols;
+    it.main_blocks = 0;
+    if (it.group < 0) {  // block strategy: -group = (rows per block << 24) | columns per block
+        const int64_t bh = (-it.group) >> 24, bw = (-it.group) & 0xffffff;
+        const bool okb = it.rows > 0 && it.cols > 0 && bh >= 1 && bw >= 16 && (bh & (bh - 1)) == 0 && (bw & (bw - 1)) == 0 && it.cols % bw == 0 && it.src && it.scale && it.dst &&
+                         aligned16(it.src) && aligned16(it.dst) && numel / 8 < ((int64_t)1 << 31);
+        if (!okb) {
+            set_error("ct_q8_batch_plan: item %d (rows %lld, cols %lld, block %lld x %lld) is not eligible for the batched 8-bit path (block sides must be powers of "
+                      "two, the width >= 16 and a divisor of cols, fewer than 2^34 elements, 16-byte aligned buffers)", i, (long long)it.rows, (long long)it.cols,
+                      (long long)bh, (long long)bw);
+            return -1;
         }
+        uint32_t magic = 0;
+        int32_t shift = 0;
+        magic_div(it.cols / 8, &magic, &shift);  // a unit's row from its index; units per row <= numel / 8 < 2^31: never refused
+        fill_w4_item(it, numel / 8, (int32_t)(bw / 8), log2_exact(bw / 8), first_block, log2_exact(bh) + 1, magic, shift);
+    } else {
         const bool whole = it.rows > 0 && it.cols > 0 && it.group >= numel;  // per tensor
         const int64_t g = whole ? numel : ((it.group <= 0 || it.group > it.cols) ? it.cols : it.group);
         const bool ok = it.rows > 0 && it.cols > 0 && it.cols % 16 == 0 && g % 16 == 0 && (whole || it.cols % g == 0) && it.src && it.scale && it.dst &&
@@ -3179,19 +3004,20 @@ int64_t ct_q8_batch_plan(ct_w4_item* items, int n, int direction) {
             it.upg = (int32_t)(g / 8);
             it.upg_shift = log2_exact(it.upg);
         }
-        it.first_block = blocks;
-        blocks += direction == 0 ? cdiv64(it.units / 2, kBlock) : cdiv64(it.units, (int64_t)kBlock * kBatchUnroll * kBatchIter);
+        it.first_block = first_block;
     }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_q8_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    return direction == 0 ? cdiv64(it.units / 2, kBlock) : cdiv64(it.units, (int64_t)kBlock * kBatchUnroll * kBatchIter);
+}
+
+int64_t ct_q8_batch_plan(ct_w4_item* items, int n, int direction) {
+    PlanRules rules;
+    rules.args_ok = direction == 0 || direction == 1;
+    return plan_table("ct_q8_batch_plan", items, n, [&](ct_w4_item& it, int i, int64_t first_block) { return q8_plan_item(it, i, direction, first_block); }, rules);
 }
 
 int ct_q8_quant_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int fp8, int bits, ct_stream_t stream) {
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched 8-bit path: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
+    CT_BATCH_SIZE(n, total_blocks);
     CT_REQUIRE((fp8 == 1 || fp8 == 2) || (bits >= 1 && bits <= 8), "num_bits must be in [1, 8], got %d", bits);
     if (n == 0 || total_blocks == 0) return CT_OK;
     const bool f8codes = fp8 == 1 || fp8 == 2;
@@ -3201,40 +3027,27 @@ int ct_q8_quant_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, 
     const dim3 grid((unsigned)total_blocks);
     if (fp8 == 3) {  // pack-quantized 8-bit (pack_to_int32 of 8-bit codes, helpers.py:39-75): dst = int32 (rows, cols / 4)
         CT_REQUIRE(bits == 8, "packed 8-bit words need num_bits == 8, got %d", bits);
-        if (dt == CT_BF16) hipLaunchKernelGGL((q8_quant_batch_kernel<CT_BF16, false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
-        else hipLaunchKernelGGL((q8_quant_batch_kernel<CT_F16, false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
+        for_dt16(dt, [&](auto DT) { hipLaunchKernelGGL((q8_quant_batch_kernel<DT(), false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt); });
         CT_LAUNCH_CHECK("ct_q8_quant_batch[packed]");
     }
-    if (dt == CT_BF16) {
-        if (fp8) hipLaunchKernelGGL((q8_quant_batch_kernel<CT_BF16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
-        else hipLaunchKernelGGL((q8_quant_batch_kernel<CT_BF16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
-    } else {
-        if (fp8) hipLaunchKernelGGL((q8_quant_batch_kernel<CT_F16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
-        else hipLaunchKernelGGL((q8_quant_batch_kernel<CT_F16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt);
-    }
+    for_dt16(dt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        hipLaunchKernelGGL((q8_quant_batch_kernel<DT(), F8()>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, qmin, qmax, zdt); }); });
     CT_LAUNCH_CHECK("ct_q8_quant_batch");
 }
 
 int ct_q8_dequant_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int fp8, ct_stream_t stream) {
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched 8-bit path: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     const int64_t stride = (int64_t)kBlock * kBatchUnroll;
     CT_REQUIRE(fp8 >= 0 && fp8 <= 3, "fp8 must be 0, 1, 2 (float8 codes with float8 zero points) or 3 (int8 codes + 128 in int32 words), got %d", fp8);
     const int zdt = fp8 == 2 ? CT_F8E4M3 : CT_I8;
     const dim3 grid((unsigned)total_blocks);
     if (fp8 == 3) {
-        if (dt == CT_BF16) hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_BF16, false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
-        else hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_F16, false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
+        for_dt16(dt, [&](auto DT) { hipLaunchKernelGGL((q8_dequant_batch_kernel<DT(), false, 128>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt); });
         CT_LAUNCH_CHECK("ct_q8_dequant_batch[packed]");
     }
-    if (dt == CT_BF16) {
-        if (fp8) hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_BF16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
-        else hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_BF16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
-    } else {
-        if (fp8) hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_F16, true>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
-        else hipLaunchKernelGGL((q8_dequant_batch_kernel<CT_F16, false>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt);
-    }
+    for_dt16(dt, [&](auto DT) { for_bool(fp8, [&](auto F8) {
+        hipLaunchKernelGGL((q8_dequant_batch_kernel<DT(), F8()>), grid, dim3(kBlock), 0, as_stream(stream), items_dev, n, stride, zdt); }); });
     CT_LAUNCH_CHECK("ct_q8_dequant_batch");
 }
 

@@ -22,6 +22,7 @@
 // Zero points of an asymmetric scheme travel as int8 here (their stored form for b != 4 is made by ct_pack_int32_dim0).
 #include "ct_minmax.h"
 #include "ct_quant_lean.h"
+#include "ct_plan.h"
 
 namespace ct {
 
@@ -231,6 +232,8 @@ static int log2_exact64(int64_t v) {
     return l;
 }
 
+// the widths of the lean kernels (1..7 without 4); CT_RTN_WB_BITS below is not this switch: the one-pass kernels have no 1-bit instantiation and
+// their entries have refused every other width before they reach it, where this one answers -1 and the caller falls through
 #define CT_WB_BITS(bits, ...)                                \
     switch (bits) {                                          \
         case 1: { constexpr int B = 1; __VA_ARGS__; } break; \
@@ -253,7 +256,7 @@ bool wb_layout_ok(int dt, int sdt, int other_dt, int bits, int zdt, const void* 
     const int64_t c = cdiv > cols ? cols : cdiv;
     if (c % 32 || cols % c || scale_cols != cols / c) return false;
     if (rows * (cols / 32) >= ((int64_t)1 << 38)) return false;
-    return aligned16(wide) && (reinterpret_cast<uintptr_t>(words) & 3u) == 0;
+    return aligned16(wide) && aligned_to<4>(words);
 }
 
 // returns -1 when the width has no lean kernel (the caller falls through to the any-layout kernels)
@@ -263,11 +266,9 @@ int launch_wb_quant_pack(const void* x, int xdt, const void* scale, const void* 
     const int64_t groups = rows * (cols / 32), gpg = c / 32;
     const int gshift = log2_exact64(gpg);
     const dim3 grid((unsigned)cdiv64(groups, kBlock));
-#define CT_WBQ(DT, ZP) CT_WB_BITS(bits, hipLaunchKernelGGL((wb_quant_pack_lean_kernel<DT, B, ZP>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), \
-                                                          static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), reinterpret_cast<uint32_t*>(packed), groups, gshift, gpg))
-    if (xdt == CT_BF16) { if (zp) { CT_WBQ(CT_BF16, true); } else { CT_WBQ(CT_BF16, false); } }
-    else { if (zp) { CT_WBQ(CT_F16, true); } else { CT_WBQ(CT_F16, false); } }
-#undef CT_WBQ
+    CT_WB_BITS(bits, for_dt16(xdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+        hipLaunchKernelGGL((wb_quant_pack_lean_kernel<DT(), B, ZP()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x),
+                           static_cast<const uint16_t*>(scale), static_cast<const int8_t*>(zp), reinterpret_cast<uint32_t*>(packed), groups, gshift, gpg); }); }));
     CT_LAUNCH_CHECK("ct_quant_pack[lean, any width]");
 }
 
@@ -278,15 +279,12 @@ int launch_wb_unpack_dequant(const int32_t* packed, const void* scale, int sdt, 
     const int upg_shift = log2_exact64(upg);
     constexpr int U = 2;
     const dim3 grid((unsigned)cdiv64(units, (int64_t)kBlock * U));
-    const bool scalar = upg == 16 && units % 64 == 0 && (reinterpret_cast<uintptr_t>(scale) & 7u) == 0 && (reinterpret_cast<uintptr_t>(zp) & 3u) == 0;
-#define CT_WBD(DT, ZP)                                                                                                                                                           \
-    CT_WB_BITS(bits, if (scalar) hipLaunchKernelGGL((wb_unpack_dequant_kernel<DT, B, U, ZP, kWbScaleScalar>), grid, dim3(kBlock), 0, as_stream(stream),                         \
-                                                    reinterpret_cast<const uint32_t*>(packed), scale, static_cast<const int8_t*>(zp), out, units, total_words, upg_shift, upg); \
-                     else hipLaunchKernelGGL((wb_unpack_dequant_kernel<DT, B, U, ZP, kWbScalePerLane>), grid, dim3(kBlock), 0, as_stream(stream),                               \
-                                             reinterpret_cast<const uint32_t*>(packed), scale, static_cast<const int8_t*>(zp), out, units, total_words, upg_shift, upg))
-    if (sdt == CT_BF16) { if (zp) { CT_WBD(CT_BF16, true); } else { CT_WBD(CT_BF16, false); } }
-    else { if (zp) { CT_WBD(CT_F16, true); } else { CT_WBD(CT_F16, false); } }
-#undef CT_WBD
+    const bool scalar = upg == 16 && units % 64 == 0 && aligned_to<8>(scale) && aligned_to<4>(zp);
+    CT_WB_BITS(bits, for_dt16(sdt, [&](auto DT) { for_bool(zp != nullptr, [&](auto ZP) {
+        if (scalar) hipLaunchKernelGGL((wb_unpack_dequant_kernel<DT(), B, U, ZP(), kWbScaleScalar>), grid, dim3(kBlock), 0, as_stream(stream),
+                                       reinterpret_cast<const uint32_t*>(packed), scale, static_cast<const int8_t*>(zp), out, units, total_words, upg_shift, upg);
+        else hipLaunchKernelGGL((wb_unpack_dequant_kernel<DT(), B, U, ZP(), kWbScalePerLane>), grid, dim3(kBlock), 0, as_stream(stream),
+                                reinterpret_cast<const uint32_t*>(packed), scale, static_cast<const int8_t*>(zp), out, units, total_words, upg_shift, upg); }); }));
     CT_LAUNCH_CHECK("ct_unpack_dequant[lean, any width]");
 }
 
@@ -420,7 +418,7 @@ int ct_rtn_quant_pack_wb(const void* x, int xdt, int64_t rows, int64_t cols, int
     CT_REQUIRE(group % 32 == 0 && group <= 2048 && log2_exact(group / 32) >= 0, "group size must be 32 * 2^k <= 2048, got %lld", (long long)group);
     CT_REQUIRE(cols % group == 0, "columns (%lld) must be a multiple of the group size %lld", (long long)cols, (long long)group);
     CT_REQUIRE(aligned16(x), "the weights must be 16-byte aligned");
-    CT_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 3u) == 0, "the packed words must be 4-byte aligned");
+    CT_REQUIRE(aligned_to<4>(packed), "the packed words must be 4-byte aligned");
     CT_REQUIRE(scale_out && zp_out, "scale and zero-point outputs are required");
     if (rows == 0 || cols == 0) return CT_OK;
     CT_REQUIRE(x && packed, "x and packed are required");
@@ -428,63 +426,44 @@ int ct_rtn_quant_pack_wb(const void* x, int xdt, int64_t rows, int64_t cols, int
     const int lpg = (int)(group / 32);
     CT_REQUIRE(cdiv64(lanes, kBlock) < ((int64_t)1 << 31), "tensor too large for one launch");
     const dim3 grid((unsigned)cdiv64(lanes, kBlock));
-#define CT_RTNWB(DT, SY) CT_RTN_WB_BITS(bits, hipLaunchKernelGGL((rtn_wb_kernel<DT, B, SY>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), \
-                                                                 lanes, lpg, reinterpret_cast<uint32_t*>(packed), scale_out, zp_out))
-    if (xdt == CT_BF16) { if (symmetric) { CT_RTNWB(CT_BF16, true); } else { CT_RTNWB(CT_BF16, false); } }
-    else { if (symmetric) { CT_RTNWB(CT_F16, true); } else { CT_RTNWB(CT_F16, false); } }
-#undef CT_RTNWB
+    CT_RTN_WB_BITS(bits, for_dt16(xdt, [&](auto DT) { for_bool(symmetric, [&](auto SY) {
+        hipLaunchKernelGGL((rtn_wb_kernel<DT(), B, SY()>), grid, dim3(kBlock), 0, as_stream(stream), static_cast<const u32x4*>(x), lanes, lpg,
+                           reinterpret_cast<uint32_t*>(packed), scale_out, zp_out); }); }));
     CT_LAUNCH_CHECK("ct_rtn_quant_pack_wb");
+}
+
+static int64_t rtn_wb_plan_item(ct_w4_item& it, int i, int bits, int64_t first_block) {
+    const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
+    // the conditions of ct_rtn_quant_pack_wb, per item
+    const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
+                    aligned16(it.src) && aligned_to<4>(it.dst);
+    if (!ok) {
+        set_error("ct_rtn_wb_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W%d compress "
+                  "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, a 16-byte aligned src, a 4-byte aligned dst, the scale output)", i,
+                  (long long)it.rows, (long long)it.cols, (long long)it.group, bits);
+        return -1;
+    }
+    if (it.zp_packed) {
+        set_error("ct_rtn_wb_batch_plan: item %d gives zp_packed; the stored zero points come from ct_pack_int32_dim0 behind this launch", i);
+        return -1;
+    }
+    const int64_t units = it.rows * (it.cols / 8);
+    fill_w4_item(it, units, (int32_t)(g / 8), log2_exact(g / 8), first_block, cdiv64(units / 4, kBlock));
+    return it.main_blocks;
 }
 
 int64_t ct_rtn_wb_batch_plan(ct_w4_item* items, int n, int bits) {
     if (!rtn_wb_bits_ok("ct_rtn_wb_batch_plan", bits)) return -1;
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_rtn_wb_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        ct_w4_item& it = items[i];
-        const int64_t g = (it.group <= 0 || it.group >= it.cols) ? it.cols : it.group;
-        // the conditions of ct_rtn_quant_pack_wb, per item
-        const bool ok = it.rows > 0 && it.cols > 0 && g % 32 == 0 && g <= 2048 && log2_exact(g / 32) >= 0 && it.cols % g == 0 && it.src && it.dst && it.scale &&
-                        aligned16(it.src) && (reinterpret_cast<uintptr_t>(it.dst) & 3u) == 0;
-        if (!ok) {
-            set_error("ct_rtn_wb_batch_plan: item %d (rows %lld, cols %lld, group %lld) is not eligible for the batched one-pass W%d compress "
-                      "(needs a group of 32 * 2^k <= 2048 elements, cols %% group == 0, a 16-byte aligned src, a 4-byte aligned dst, the scale output)", i,
-                      (long long)it.rows, (long long)it.cols, (long long)it.group, bits);
-            return -1;
-        }
-        if (it.zp_packed) {
-            set_error("ct_rtn_wb_batch_plan: item %d gives zp_packed; the stored zero points come from ct_pack_int32_dim0 behind this launch", i);
-            return -1;
-        }
-        it.units = it.rows * (it.cols / 8);
-        it.upg = (int32_t)(g / 8);
-        it.upg_shift = log2_exact(it.upg);
-        it.first_block = blocks;
-        it.main_blocks = cdiv64(it.units / 4, kBlock);
-        it.g_magic = 0;
-        it.g_shift = 0;
-        blocks += it.main_blocks;
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_rtn_wb_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    return plan_table("ct_rtn_wb_batch_plan", items, n, [&](ct_w4_item& it, int i, int64_t first_block) { return rtn_wb_plan_item(it, i, bits, first_block); });
 }
 
 int ct_rtn_quant_pack_wb_batch(const ct_w4_item* items_dev, int n, int64_t total_blocks, int dt, int bits, int symmetric, ct_stream_t stream) {
     if (!rtn_wb_bits_ok("ct_rtn_quant_pack_wb_batch", bits)) return CT_ERR_UNSUPPORTED;
     CT_REQUIRE(dt == CT_BF16 || dt == CT_F16, "batched one-pass compress: 16-bit weights only, got dtype %d", dt);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     CT_REQUIRE(items_dev != nullptr, "the table is required");
-#define CT_RTNWBB(DT, SY) CT_RTN_WB_BITS(bits, hipLaunchKernelGGL((rtn_wb_batch_kernel<DT, B, SY>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n))
-    if (dt == CT_BF16) { if (symmetric) { CT_RTNWBB(CT_BF16, true); } else { CT_RTNWBB(CT_BF16, false); } }
-    else { if (symmetric) { CT_RTNWBB(CT_F16, true); } else { CT_RTNWBB(CT_F16, false); } }
-#undef CT_RTNWBB
+    CT_RTN_WB_BITS(bits, for_dt16(dt, [&](auto DT) { for_bool(symmetric, [&](auto SY) {
+        hipLaunchKernelGGL((rtn_wb_batch_kernel<DT(), B, SY()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); }); }));
     CT_LAUNCH_CHECK("ct_rtn_quant_pack_wb_batch");
 }
 

@@ -15,6 +15,7 @@
 // buffer so that the value side is ONE contiguous run per super-chunk moved with aligned
 // 16-byte vectors (scalar head/tail); only LDS sees the 2-byte scattered accesses.
 #include "ct_common.h"
+#include "ct_plan.h"
 
 #include <atomic>
 #include <chrono>
@@ -2123,7 +2124,7 @@ int ct_bitmask_compress(const void* x, int dt, int64_t rows, int64_t cols, void*
     const int64_t need = ct_bitmask_compress_workspace_bytes(rows, cols);
     CT_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
                (long long)need);
-    CT_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "workspace must be 8-byte aligned");
+    CT_REQUIRE(aligned_to<8>(workspace), "workspace must be 8-byte aligned");
     CT_REQUIRE(aligned16(values), "values buffer must be 16-byte aligned");
     // 16- and 32-bit elements (the latter as pairs of halves): the resident form (x read once).  CT_BITMASK_RESIDENT=0 selects the two kernels
     // below for 16-bit elements (x read twice; 32-bit ones then take the generic path), which
@@ -2207,7 +2208,7 @@ int ct_bitmask_compress(const void* x, int dt, int64_t rows, int64_t cols, void*
                 const int64_t cu = (units - u0) < cw * kWT ? (units - u0) : cw * kWT;
                 const int64_t nwg = cdiv64(cw, wg_wts);
                 uint8_t* bm0 = bitmask + (es == 4 ? u0 / 2 : (es == 1 ? u0 * 2 : u0));  // a mask byte covers one 16-bit unit, two 32-bit units or half an 8-bit unit
-                const int mask_dwords = (es == 4 || cu % 4 == 0) && ((reinterpret_cast<uintptr_t>(bm0) & 3u) == 0);
+                const int mask_dwords = (es == 4 || cu % 4 == 0) && aligned_to<4>(bm0);
                 // the chunk's running total: straight into *total for the last chunk, else into one of two alternating workspace words
                 unsigned long long* run_out = k + 1 == nchunks ? reinterpret_cast<unsigned long long*>(total) : ctl + 2 + (k & 1);
                 // stagger (see the kernel): only when the launch is at least two full residency rounds (two workgroups per CU each) — with a
@@ -2253,7 +2254,7 @@ int ct_bitmask_compress(const void* x, int dt, int64_t rows, int64_t cols, void*
         const Flat16Plan p = flat16_plan(rows, cols);
         int64_t* block_tot = static_cast<int64_t*>(workspace);
         int32_t* span_tot = reinterpret_cast<int32_t*>(block_tot + p.nblocks);
-        const int mask_dwords = (p.units % 4 == 0) && ((reinterpret_cast<uintptr_t>(bitmask) & 3u) == 0);
+        const int mask_dwords = (p.units % 4 == 0) && aligned_to<4>(bitmask);
         // One chunk.  (Walking the tensor in cache-sized chunks — count chunk k, scatter chunk k, ... — so that the scatter's re-read
         // of x hits a cache was measured in round 2: 64 / 32 / 16 / 8 MB chunks -> 80 / 102 / 155 / 280 us against 66; the loop below
         // still carries a running total from chunk to chunk, and is exercised with one chunk.)
@@ -2287,13 +2288,11 @@ int ct_bitmask_compress(const void* x, int dt, int64_t rows, int64_t cols, void*
 }
 
 int64_t ct_bitmask_batch_plan(ct_bitmask_item* items, int n, int64_t* workspace_bytes) {
-    if (n < 0 || (n > 0 && items == nullptr) || workspace_bytes == nullptr) {
-        set_error("ct_bitmask_batch_plan: bad arguments");
-        return -1;
-    }
+    // the pre-pass runs before plan_table has looked at (items, n): of a table that will be refused it reads nothing
+    const int count = items ? n : 0;
     const int cus = device_cus();
-    int64_t blocks = 0, slots = 0;
-    const int es0 = n > 0 ? dt_size(items[0].dt) : 2;
+    int64_t slots = 0;
+    const int es0 = count > 0 ? dt_size(items[0].dt) : 2;
     auto tag_of = [](uint32_t c) { return 0x80000000u | (c % 0x7ffffffeu); };
     const uint32_t gen0 = resident_generation().fetch_add((uint32_t)(n > 0 ? n : 1)) + 1u;
     // wave-tiles per wave.  A single tensor spreads thin (fewer tiles per wave) so that every CU gets a workgroup; a TABLE fills the chip with its
@@ -2301,14 +2300,15 @@ int64_t ct_bitmask_batch_plan(ct_bitmask_item* items, int n, int64_t* workspace_
     // ~8-12 us whatever it carries): with 1-2 tiles per wave (the single-tensor rule on 1-23 MB tensors) 154 tensors ran at 3.4 TB/s.  If the whole
     // table still makes at least two residency rounds with full registers, every item takes kResKeep tiles per wave.
     int64_t all_wts = 0;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < count; ++i)
         if (items[i].rows > 0 && items[i].cols > 0) all_wts += cdiv64(items[i].rows * (items[i].cols * dt_size(items[i].dt) / 16), kWT);
     const bool full_tiles = all_wts >= (int64_t)2 * 2 * cus * kResWaves * kResKeep;
-    for (int i = 0; i < n; ++i) {
-        ct_bitmask_item& it = items[i];
+    PlanRules rules;
+    rules.args_ok = workspace_bytes != nullptr;
+    const int64_t blocks = plan_table("ct_bitmask_batch_plan", items, n, [&](ct_bitmask_item& it, int i, int64_t first_block) -> int64_t {
         const int es = dt_size(it.dt);
         const bool ok = (es == 1 || es == 2 || es == 4) && es == es0 && it.rows > 0 && it.cols > 0 && it.cols % (es == 1 ? 16 : 8) == 0 && it.x && it.values && it.bitmask && it.row_offsets && it.total &&
-                        aligned16(it.x) && aligned16(it.values) && it.values_capacity >= 0 && (reinterpret_cast<uintptr_t>(it.total) & 7u) == 0;
+                        aligned16(it.x) && aligned16(it.values) && it.values_capacity >= 0 && aligned_to<8>(it.total);
         if (!ok) {
             set_error("ct_bitmask_batch_plan: item %d (rows %lld, cols %lld, dtype %d) is not eligible for the batched sparse-bitmask compress (8-, 16- or 32-bit "
                       "payloads of ONE element size per table, cols x element size %% 16 == 0, non-empty, x / values 16-byte aligned, no NULL pointer)", i, (long long)it.rows,
@@ -2329,27 +2329,22 @@ int64_t ct_bitmask_batch_plan(ct_bitmask_item* items, int n, int64_t* workspace_
         }
         it.tpw = (int32_t)tpw;
         it.nwg = (int32_t)nwg;
-        it.mask_dwords = ((es == 4 || it.units % 4 == 0) && ((reinterpret_cast<uintptr_t>(it.bitmask) & 3u) == 0)) ? 1 : 0;
+        it.mask_dwords = ((es == 4 || it.units % 4 == 0) && aligned_to<4>(it.bitmask)) ? 1 : 0;
         it.gen = tag_of(gen0 + (uint32_t)i);
-        it.first_block = blocks;
+        it.first_block = first_block;
         it.slots_offset = slots;
-        blocks += nwg;
         slots += (nwg + 15) / 16 * 16;  // 128-byte lines: two tensors never share one
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_bitmask_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    *workspace_bytes = slots * 8 + 16;
+        return nwg;
+    }, rules);
+    if (blocks >= 0) *workspace_bytes = slots * 8 + 16;
     return blocks;
 }
 
 int ct_bitmask_compress_batch(const ct_bitmask_item* items_dev, int n, int64_t total_blocks, int element_size, void* workspace, int64_t workspace_bytes,
                               ct_stream_t stream) {
     CT_REQUIRE(element_size == 1 || element_size == 2 || element_size == 4, "batched sparse-bitmask compress: 8-, 16- or 32-bit payloads, got element size %d", element_size);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
-    CT_REQUIRE(items_dev != nullptr && workspace != nullptr && workspace_bytes >= 16 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "table / workspace NULL or misaligned");
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr && workspace != nullptr && workspace_bytes >= 16 && aligned_to<8>(workspace), "table / workspace NULL or misaligned");
     constexpr unsigned long long wait_ticks = 2000ull * 100ull;  // 100 MHz ticks: 2 ms, then self-help (as the single-tensor launch)
     if (element_size == 1)
         hipLaunchKernelGGL((flat16_resident_batch_kernel<1>), dim3((unsigned)total_blocks), dim3(kResWaves * 64), 0, as_stream(stream), items_dev, n,
@@ -2364,17 +2359,11 @@ int ct_bitmask_compress_batch(const ct_bitmask_item* items_dev, int n, int64_t t
 }
 
 int64_t ct_bitmask_decompress_batch_plan(ct_bitmask_ditem* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_bitmask_decompress_batch_plan: bad arguments");
-        return -1;
-    }
-    int64_t blocks = 0;
-    const int es0 = n > 0 ? dt_size(items[0].dt) : 2;
-    for (int i = 0; i < n; ++i) {
-        ct_bitmask_ditem& it = items[i];
+    const int es0 = (items && n > 0) ? dt_size(items[0].dt) : 2;  // one element size per table: the first item's
+    return plan_table("ct_bitmask_decompress_batch_plan", items, n, [&](ct_bitmask_ditem& it, int i, int64_t first_block) -> int64_t {
         const int es = dt_size(it.dt);
         const bool ok = (es == 2 || es == 4) && es == es0 && it.rows > 0 && it.cols > 0 && (it.cols * es / 2) % 32 == 0 && it.values_len >= 0 && it.bitmask && it.row_offsets && it.out &&
-                        (it.values != nullptr || it.values_len == 0) && aligned16(it.values) && aligned16(it.out) && (reinterpret_cast<uintptr_t>(it.bitmask) & 3u) == 0;
+                        (it.values != nullptr || it.values_len == 0) && aligned16(it.values) && aligned16(it.out) && aligned_to<4>(it.bitmask);
         if (!ok) {
             set_error("ct_bitmask_decompress_batch_plan: item %d (rows %lld, cols %lld, dtype %d) is not eligible for the batched sparse-bitmask decompress (16- or 32-bit "
                       "payloads of ONE element size per table, cols x element size %% 64 == 0, row_offsets given, values / out 16-byte and bitmask 4-byte aligned)", i,
@@ -2384,50 +2373,33 @@ int64_t ct_bitmask_decompress_batch_plan(ct_bitmask_ditem* items, int n) {
         const int64_t hcols = it.cols * es / 2;  // the row in 16-bit items
         // the tile form (the kernel's dispatch): rows of several tiles / the row is one tile / 16-bit rows shorter than a tile: flat tiles
         it.single = (es == 2 && hcols % kTile16 != 0) ? kDecFlat : (hcols > kTile16 ? kDecRows : kDecSingle);  // as the single-tensor launch
-        it.first_block = blocks;
-        blocks += it.single == kDecFlat ? cdiv64(it.rows * (hcols / 8), kTile16 / 8) : it.rows * cdiv64(hcols, kTile16);
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_bitmask_decompress_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+        it.first_block = first_block;
+        return it.single == kDecFlat ? cdiv64(it.rows * (hcols / 8), kTile16 / 8) : it.rows * cdiv64(hcols, kTile16);
+    });
 }
 
 int ct_bitmask_decompress_batch(const ct_bitmask_ditem* items_dev, int n, int64_t total_blocks, int element_size, ct_stream_t stream) {
     CT_REQUIRE(element_size == 2 || element_size == 4, "batched sparse-bitmask decompress: 16- or 32-bit payloads, got element size %d", element_size);
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     CT_REQUIRE(items_dev != nullptr, "table is NULL");
     if (element_size == 4) hipLaunchKernelGGL((bitmask_decompress16_batch_kernel<4>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
     else hipLaunchKernelGGL((bitmask_decompress16_batch_kernel<2>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
     CT_LAUNCH_CHECK("ct_bitmask_decompress_batch");
 }
 
-int64_t ct_copy_batch_plan(ct_copy_item* items, int n) {
-    if (n < 0 || (n > 0 && items == nullptr)) {
-        set_error("ct_copy_batch_plan: bad arguments");
+static int64_t copy_plan_item(ct_copy_item& it, int i, int64_t first_block) {
+    if (it.bytes < 0 || (it.bytes > 0 && (!it.src || !it.dst))) {
+        set_error("ct_copy_batch_plan: item %d has a negative size or a NULL pointer", i);
         return -1;
     }
-    int64_t blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        if (items[i].bytes < 0 || (items[i].bytes > 0 && (!items[i].src || !items[i].dst))) {
-            set_error("ct_copy_batch_plan: item %d has a negative size or a NULL pointer", i);
-            return -1;
-        }
-        items[i].first_block = blocks;
-        blocks += cdiv64(items[i].bytes, (int64_t)kBlock * 64);
-    }
-    if (blocks >= ((int64_t)1 << 31)) {
-        set_error("ct_copy_batch_plan: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-        return -1;
-    }
-    return blocks;
+    it.first_block = first_block;
+    return cdiv64(it.bytes, (int64_t)kBlock * 64);
 }
 
+int64_t ct_copy_batch_plan(ct_copy_item* items, int n) { return plan_table("ct_copy_batch_plan", items, n, copy_plan_item); }
+
 int ct_copy_batch(const ct_copy_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream) {
-    CT_REQUIRE(n >= 0 && total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), "bad batch size");
-    if (n == 0 || total_blocks == 0) return CT_OK;
+    CT_BATCH_ARGS(n, total_blocks);
     CT_REQUIRE(items_dev != nullptr, "table is NULL");
     hipLaunchKernelGGL(copy_batch_kernel, dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
     CT_LAUNCH_CHECK("ct_copy_batch");
@@ -2446,7 +2418,7 @@ int ct_bitmask_decompress(const void* values, int64_t values_len, const uint8_t*
     // cross values_len are read element-wise in the kernel
     const int vec_in = aligned16(values);
     // (2:4-regular rows of 16-bit payloads measure the same on this kernel as on the general kernel's local-expand path: 33.9 / 34.8 us)
-    if ((es == 2 || es == 4) && (cols * es / 2) % 32 == 0 && vec_out && vec_in && (reinterpret_cast<uintptr_t>(bitmask) & 3u) == 0 &&
+    if ((es == 2 || es == 4) && (cols * es / 2) % 32 == 0 && vec_out && vec_in && aligned_to<4>(bitmask) &&
         values_len < ((int64_t)1 << 61)) {
         const int64_t hcols = cols * es / 2;  // the row in 16-bit items
         const int64_t tiles = rows * cdiv64(hcols, kTile16);
@@ -2468,7 +2440,7 @@ int ct_bitmask_decompress(const void* values, int64_t values_len, const uint8_t*
     }
     // 8-bit payloads: the byte-granular LDS-window kernel, for the unstructured codec (row offsets) and the 2:4 codec (fixed_row_nnz) alike — the
     // general kernel's 2:4-regular row path ran 8192^2 int8 at 33.4 us HBM-cold, this one at 22.2-23.0.
-    if (es == 1 && cols % 16 == 0 && (cols <= 16384 || cols % 64 == 0) && vec_out && vec_in && (reinterpret_cast<uintptr_t>(bitmask) & 3u) == 0 &&
+    if (es == 1 && cols % 16 == 0 && (cols <= 16384 || cols % 64 == 0) && vec_out && vec_in && aligned_to<4>(bitmask) &&
         values_len < ((int64_t)1 << 61)) {
 #define CT_DEC8(SINGLE_, UPL_, FLAT_, GRID_)                                                                                                                     \
     hipLaunchKernelGGL((bitmask_decompress8_kernel<SINGLE_, UPL_, FLAT_>), dim3(GRID_), dim3(kBlock), 0, as_stream(stream), static_cast<const uint8_t*>(values), \
@@ -2507,7 +2479,7 @@ int ct_sparse24_compress(const void* x, int dt, int64_t rows, int64_t cols, void
     const int64_t units = rows * (cols / 8);
     CT_REQUIRE(aligned16(values), "values buffer must be 16-byte aligned");
     const int vec = aligned16(x);
-    if (vec && (es == 1 || es == 2) && units % 2 == 0 && (reinterpret_cast<uintptr_t>(bitmask) & 1u) == 0 && units / 2 < ((int64_t)1 << 38)) {
+    if (vec && (es == 1 || es == 2) && units % 2 == 0 && aligned_to<2>(bitmask) && units / 2 < ((int64_t)1 << 38)) {
         const int64_t pairs = units / 2;
         dim3 g((unsigned)cdiv64(pairs, kBlock));
         if (es == 2) hipLaunchKernelGGL((sparse24_pair_kernel<2>), g, dim3(kBlock), 0, as_stream(stream), x, float_kind(dt), pairs, values, bitmask);
