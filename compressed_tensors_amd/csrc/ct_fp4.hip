@@ -117,7 +117,10 @@ __device__ __forceinline__ uint32_t fp4_quant_unit(const uint32_t (&ws)[4], floa
         fp4_unpack_pair<XDT>(ws[j], x0, x1);
         float q0 = x0 / s_eff, q1 = x1 / s_eff;
         if (in_dtype) { q0 = round_to<XDT>(q0); q1 = round_to<XDT>(q1); }  // the quotient stays in x.dtype
-        t[2 * j] = q0; t[2 * j + 1] = q1;
+        // a NaN quotient (a NaN element, a NaN scale, inf / inf: only this path sees them — a NaN or inf scale fails both range tests above) has the
+        // magnitude 0 upstream: cast_to_fp4's comparisons leave the NaN alone and pack_fp4_to_uint8's int8 cast makes it 0, where the hardware
+        // conversion would saturate it to the code of 6.  Its sign bit is the sign of a NaN, which nothing compares
+        t[2 * j] = q0 != q0 ? 0.0f : q0; t[2 * j + 1] = q1 != q1 ? 0.0f : q1;
     }
     return fp4_word(t);
 }
@@ -275,6 +278,10 @@ __global__ __launch_bounds__(kBlock) void fp4_quant_pack_batch_kernel(const ct_w
 // (calculate_qparams' MX branch: compute_qparams_float) -> x / scale -> cast_to_fp4 -> 16 bytes of nibbles + one
 // exponent byte.  2 + 0.5 + 1/32 B per element instead of (2 + 2/32) + (2 + 0.5 + 2/32); bit-identical to
 // ct_minmax_qparams_float(kind 3) + ct_fp4_quant_pack + compress_mx_scale by construction (same helpers).
+// compress_mx_scale(inf): the float -> int32 cast of log2(inf) = inf gives 0x80000000 on the x86 hosts the reference's fixtures come from, and
+// 127 + that, as uint8, is 127 (tests/test_gpu_nonfinite_rtn.py holds it against the table ct_mx_scale_compress reads)
+constexpr uint32_t kE8M0OfInf = 127u;
+
 template <int XDT>
 __device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0, void* __restrict__ scale_out,
                                                int64_t l) {
@@ -286,9 +293,11 @@ __device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32
     for (int i = 0; i < 4; ++i) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
     const MinMax m = absmax_finish<XDT>(acc);
     const float s = compute_qparams_float<XDT>(m, QP_MXFP4, 1.0f);
-    // compress_mx_scale: 127 + floor(log2(s)); s is a power of two (2^-127, the only subnormal one, is code 0), or inf / NaN
+    // compress_mx_scale: 127 + floor(log2(s)); s is a power of two (2^-127, the only subnormal one, is code 0) or inf — the scale of a group that holds
+    // an inf or a NaN (the MX rule turns a NaN amax into +inf: s is never NaN).  The byte of inf is not its exponent field 255: upstream's
+    // `127 + floor(log2(inf)).to(int32)` wraps to kE8M0OfInf, the entry codec._mx_code_table holds for inf
     const uint32_t ef = (f_bits(s) >> 23) & 0xffu;
-    e8m0[l] = (uint8_t)((s != s) ? 0u : ef);  // inf: 255 = its exponent field; the int cast of NaN is 0 upstream
+    e8m0[l] = (uint8_t)(ef == 0xffu ? kE8M0OfInf : ef);
     if (scale_out) store1<XDT>(scale_out, l, s);
     uint32_t w[4];
 #pragma unroll
