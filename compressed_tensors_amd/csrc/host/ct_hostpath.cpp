@@ -1,28 +1,42 @@
-// ct_hostpath.cpp — the per-module host loop of the batched W4A16 module paths, in C++ (CPython extension `_hostpath`).
+// ct_hostpath.cpp — the per-module host loops of compress_modules / decompress_modules, in C++ (CPython extension `_hostpath`), for every format that has
+// a table launch: pack-quantized W4 (w4_*), the plain 8-bit codecs (q8_*), mxfp8 (mx8_*), pack-quantized W8 (w8_*, finished by the W4 functions), NVFP4 /
+// MXFP4 (fp4_*) — and, launching per module by address, pack-quantized in the other word widths and with activation ordering (wb_*).
 //
 // Why: compress_model / decompress_model of a 154-module checkpoint spend 20 us of interpreter time per module and direction in
 // PackedQuantizationCompressor.compress_modules / decompress_modules (dictionary look-ups, ~25 tensor attribute calls, torch.empty,
 // nn.Parameter, dictionary surgery) next to two kernels of 0.42 ms each (bench.py `tinyllama_checkpoint.api`).  The same steps here
 // cost ~5 us.  Nothing in this file computes on tensor data: it reads the modules' own `_parameters`, validates layouts, allocates
-// outputs with ATen, fills the `struct ct_w4_item` table (include/ct_hip.h) that ct_quant_pack_batch / ct_unpack_dequant_batch
-// consume, and — after the Python side has planned, uploaded and LAUNCHED the table — rewrites the modules' parameter
+// outputs with ATen, fills the `struct ct_w4_item` table (include/ct_hip.h) that the `ct_*_batch` launches consume, and — after the Python side
+// (compressors/base.py:run_planned) has planned, uploaded and LAUNCHED the table — rewrites the modules' parameter
 // dictionaries under the running kernel, exactly as compressed_tensors_amd/utils/module.py:swap_direct_entries does
 // (reference: compressors/base.py:95-131, utils/module.py:33-65, compressors/pack_quantized/base.py:62-163).
+//
+// How the loops are laid out: ONE driver walks the modules (`each_plain_module`: the `infos`, the plain-class test, the module's
+// dictionaries, the hand-back in `rest`), ONE plan driver on top of it collects tables (`plan_modules`: the batch map, its way back to Python), ONE row builder
+// fills a table row by the struct's field names (`item_row`), ONE finish driver walks the jobs (`finish_jobs`).  A scheme supplies a TAKE function
+// `(module, info, Entries&, Sink&) -> bool` — is the module this scheme's plain case?  then allocate, hand the sink the row(s) and the job — and the
+// dictionary surgery of its finish.  Tests a loop shares with the others are named functions (`dense_source`, `stored_shape`, `Sink::at`, `drop_mask_names`);
+// what a loop asks beyond them stands next to the shared call.
 //
 // Also here (second half of the file): the host side of the two plug-in calls that wait for the device before they return — the
 // sparse-bitmask compress and the default mode of the marlin-24 compress — where the interpreter's 15-20 us sat in series with a
 // 30-42 us kernel.
 //
 // A module that is anything but the plain case (a buffer among its entries, a trainable parameter that stays, a class with its own
-// __setattr__, activation arguments, activation ordering, an unusual layout) is handed back untouched in `rest`; the Python path,
+// __setattr__, activation arguments, an unusual layout) is handed back untouched in `rest`; the Python path,
 // which covers every case, takes it.  The Python path is also what runs when this extension has not been built.
+#include "ct_hip.h"  // struct ct_w4_item: the table row (the build passes -I include)
+
 #include <torch/csrc/autograd/python_variable.h>
 #include <torch/extension.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
+#include <optional>
 #include <pybind11/stl.h>
 #include <stdexcept>
 #include <string>
@@ -173,17 +187,65 @@ struct Entries {
     bool has(PyObject* name) const { return PyDict_GetItem(params, name) != nullptr; }
 };
 
-inline bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15u) == 0; }
-inline bool half_type(at::ScalarType t) { return t == at::kBFloat16 || t == at::kHalf; }
+PyObject* g_input_zero_point = nullptr;   // entry names beyond `Names` (interned at import)
+PyObject* g_output_zero_point = nullptr;
+PyObject* g_weight_global_scale = nullptr;
 
-// every parameter that stays must already be a non-trainable Parameter (else the generic path re-wraps it); no buffers at all
-bool staying_entries_are_final(const Entries& e, std::initializer_list<PyObject*> leaving) {
+inline bool aligned(const at::Tensor& t, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & (bytes - 1)) == 0; }
+inline bool aligned16(const at::Tensor& t) { return aligned(t, 16); }
+inline bool half_type(at::ScalarType t) { return t == at::kBFloat16 || t == at::kHalf; }
+inline int half_code(at::ScalarType t) { return t == at::kHalf ? 1 : 2; }  // _lib.F16 / _lib.BF16
+
+// C ABI element code of a tensor's dtype (include/ct_hip.h enum ct_dtype), -1 for a type the ABI has no code for
+int dtype_code(at::ScalarType t) {
+    switch (t) {
+        case at::kFloat: return CT_F32;
+        case at::kHalf: return CT_F16;
+        case at::kBFloat16: return CT_BF16;
+        case at::kChar: return CT_I8;
+        case at::kInt: return CT_I32;
+        case at::kByte: case at::kBool: return CT_U8;
+        case at::kShort: return CT_I16;
+        case at::kLong: return CT_I64;
+        default: return -1;
+    }
+}
+
+// the dense-source test every loop makes of the tensor its launch streams (weights, codes or packed words): two-dimensional, contiguous, on a GPU — on
+// GPU `device_index` where the loop launches on one device — and aligned to what the kernel loads at once
+inline bool dense_source(const at::Tensor& t, uintptr_t align = 16, int device_index = -1) {
+    return ((t.is_cuda() && (device_index < 0 || t.device().index() == device_index)) || g_allow_cpu) && t.is_contiguous() && aligned(t, align) && t.dim() == 2;
+}
+
+// an optional entry as the loops want it: a tensor (`t`, what Entries::tensor found under `name`) or not there at all — not None, not another object
+inline bool tensor_or_absent(const Entries& e, const at::Tensor* t, PyObject* name) { return t != nullptr || !e.has(name); }
+
+inline const void* data_or_null(const at::Tensor* t) { return t ? t->data_ptr() : nullptr; }
+
+// the stored `weight_shape` of a pack-quantized module as upstream writes it (int64, CPU, two elements: pack_quantized/base.py:105): its rows and
+// columns, or false for anything else
+bool stored_shape(const at::Tensor* shape_t, int64_t& rows, int64_t& cols) {
+    if (!shape_t || !shape_t->device().is_cpu() || shape_t->scalar_type() != at::kLong || shape_t->numel() != 2 || !shape_t->is_contiguous()) return false;
+    rows = shape_t->data_ptr<int64_t>()[0];
+    cols = shape_t->data_ptr<int64_t>()[1];
+    return rows > 0 && cols > 0;
+}
+
+// the drop mask of the `infos` encodings: the zero points a symmetric scheme does not store (compressors/base.py: zp_drop_mask), bit k = name k
+inline std::array<PyObject*, 3> drop_mask_names() { return {N.weight_zero_point, g_input_zero_point, g_output_zero_point}; }
+
+// every parameter that stays must already be a non-trainable Parameter (else the generic path re-wraps it); no buffers at all.  Leaving: the names in
+// `leaving` and the zero points of `dropmask`
+bool staying_entries_are_final(const Entries& e, std::initializer_list<PyObject*> leaving, int dropmask = 0) {
     if (PyDict_Size(e.buffers) != 0) return false;
+    const auto dropped = drop_mask_names();
     PyObject *key, *value;
     Py_ssize_t pos = 0;
     while (PyDict_Next(e.params, &pos, &key, &value)) {
         bool leaves = false;
         for (PyObject* l : leaving) leaves = leaves || key == l || PyObject_RichCompareBool(key, l, Py_EQ) == 1;
+        for (int k = 0; k < 3; ++k)
+            if ((dropmask >> k) & 1) leaves = leaves || key == dropped[k] || PyObject_RichCompareBool(key, dropped[k], Py_EQ) == 1;
         if (leaves || value == Py_None) continue;
         if (!THPVariable_Check(value) || THPVariable_Unpack(value).requires_grad()) return false;
     }
@@ -197,8 +259,16 @@ py::object make_parameter(const at::Tensor& t) {  // == torch.nn.Parameter(t, re
     return py::reinterpret_steal<py::object>(r);
 }
 
+void set_entry(const Entries& e, PyObject* name, const at::Tensor& t) { PyDict_SetItem(e.params, name, make_parameter(t).ptr()); }  // in place when the key exists
+
 void drop(PyObject* dict, PyObject* name) {  // del dict[name] if present
     if (PyDict_GetItem(dict, name) && PyDict_DelItem(dict, name) != 0) PyErr_Clear();
+}
+
+void drop_zero_points(const Entries& e, long dropmask) {
+    const auto names = drop_mask_names();
+    for (int k = 0; k < 3; ++k)
+        if ((dropmask >> k) & 1) drop(e.params, names[k]);
 }
 
 void set_status(PyObject* module, PyObject* status) {
@@ -212,14 +282,54 @@ bool dict_has(PyObject* module, PyObject* name) {
     return dictptr && *dictptr && PyDict_GetItem(*dictptr, name) != nullptr;
 }
 
-constexpr int kItemWords = 13;  // struct ct_w4_item of include/ct_hip.h in 64-bit words; word 10 = zp_packed, 11-12 derived (as 7-9)
+inline py::object borrowed(PyObject* o) { return py::reinterpret_borrow<py::object>(o); }
+inline py::object wrap(const at::Tensor& t) { return py::reinterpret_steal<py::object>(THPVariable_Wrap(t)); }
+// a module's own entry object, for a job: it keeps the tensor alive until the launch has been issued (the table holds raw pointers); None when absent
+inline py::object entry_ref(const Entries& e, PyObject* name) {
+    PyObject* o = PyDict_GetItem(e.params, name);
+    return o ? borrowed(o) : py::none();
+}
+
+// ------------------------------------------------------------------------------------------
+// The table, its row builder and the drivers
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(ct_w4_item) % sizeof(int64_t) == 0, "a table row is a whole number of 64-bit words");
+constexpr int kItemWords = sizeof(ct_w4_item) / sizeof(int64_t);  // the Python side reads the same struct (codec._ITEM_WORDS, codec.item_row)
+
+// one row of a table, by the struct's field names; everything else (the fields ct_*_batch_plan derives) zero.  What the fields MEAN is the launch's
+// business (include/ct_hip.h: every `ct_*_batch` entry says how it reads struct ct_w4_item).
+ct_w4_item item_row(const void* src, const void* scale, const void* zp, void* dst, int64_t rows, int64_t cols, int64_t group, void* zp_packed = nullptr) {
+    ct_w4_item it{};
+    it.src = src;
+    it.scale = scale;
+    it.zp = zp;
+    it.dst = dst;
+    it.rows = rows;
+    it.cols = cols;
+    it.group = group;
+    it.zp_packed = zp_packed;
+    return it;
+}
 
 struct Batch {
-    std::vector<int64_t> words;     // kItemWords per item: struct ct_w4_item
-    std::vector<int64_t> zp_words;  // the same layout, one item per ASYMMETRIC module whose zero points the weights' launch cannot take in packed
-                                    // form (decompress of a layout outside groups of 128 / cols % 512 == 0): through ct_zp4_pack_dim0_batch
+    std::vector<int64_t> words;      // kItemWords per item: struct ct_w4_item
+    std::vector<int64_t> aux_words;  // the same layout: the table of the launch that goes with the weights' — the zero points of ASYMMETRIC W4 modules whose
+                                     // weights' launch cannot take them in packed form (ct_zp4_pack_dim0_batch), the scales of mxfp8 (ct_mx_scale_batch)
     py::list jobs;
-    int n = 0, zp_n = 0;
+    int n = 0, aux_n = 0;
+    static void append(std::vector<int64_t>& to, const ct_w4_item& it) {
+        to.resize(to.size() + kItemWords);
+        std::memcpy(to.data() + to.size() - kItemWords, &it, sizeof(it));
+    }
+    void row(const ct_w4_item& it) { append(words, it), n += 1; }
+    void aux_row(const ct_w4_item& it) { append(aux_words, it), aux_n += 1; }
+};
+
+// where a take function puts what it planned: one Batch per (device index or -1 for the tests' CPU tensors, the launch's code — what the code encodes is
+// between the take function and its Python launcher).  std::map: the batches leave in key order, which is launch order.
+struct Sink {
+    std::map<std::pair<int, int>, Batch> batches;
+    Batch& at(const at::Tensor& t, int code) { return batches[{t.is_cuda() ? (int)t.device().index() : -1, code}]; }
 };
 
 at::Tensor words_tensor(const std::vector<int64_t>& v) {
@@ -228,190 +338,160 @@ at::Tensor words_tensor(const std::vector<int64_t>& v) {
     return t;
 }
 
-py::dict batches_to_python(std::map<std::pair<int, int>, Batch>& batches) {
+py::dict batches_to_python(const Sink& sink) {  // {(device, code): (words, n, jobs, aux words, aux n)}: what compressors/base.py:run_planned iterates
     py::dict out;
-    for (auto& kv : batches) {
+    for (auto& kv : sink.batches) {
         const Batch& b = kv.second;
-        out[py::make_tuple(kv.first.first, kv.first.second)] = py::make_tuple(words_tensor(b.words), b.n, b.jobs, words_tensor(b.zp_words), b.zp_n);
+        out[py::make_tuple(kv.first.first, kv.first.second)] = py::make_tuple(words_tensor(b.words), b.n, b.jobs, words_tensor(b.aux_words), b.aux_n);
     }
     return out;
 }
 
-// infos[i]: group size of module i's scheme (0 = channel-wise), + kAsymmetric when the scheme stores packed zero points
-// (pack_to_int32(zp, 4, packed_dim=0), pack_quantized/base.py:107-110), or < 0 when the scheme is not an int4 group / channel scheme
-constexpr int64_t kAsymmetric = int64_t(1) << 40;
-
-py::tuple w4_plan_compress(py::list modules, py::object infos_arg) {
+// The loop head and the refusal tail of every module loop.  `infos` (nullptr: the loop has none, every module's info is 1) as `Infos` reads it;
+// `body(module, info, entries) -> bool` sees a module of a plain class with its dictionaries open and answers whether it took it.  Every other module —
+// in module order — is the list returned: the Python path's.
+template <class Body>
+py::list each_plain_module(const py::list& modules, PyObject* infos_arg, Body body) {
     touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;  // (device index, dtype code 1 = fp16 / 2 = bf16) -> table
     py::list rest;
-    Infos infos(infos_arg.ptr());
+    std::optional<Infos> infos;
+    if (infos_arg) infos.emplace(infos_arg);
     const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
     for (Py_ssize_t i = 0; i < n; ++i) {
         PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        const bool asym = info >= kAsymmetric;
-        const int64_t ginfo = asym ? info - kAsymmetric : info;
+        const int64_t info = infos ? infos->of(m, i) : 1;
         Entries e;
-        bool ok = ginfo >= 0 && plain_type(m) && e.open(m) && !dict_has(m, N.weight_packed) && !dict_has(m, N.weight_shape);
-        const at::Tensor *w = nullptr, *scale = nullptr, *zp = nullptr;
-        int64_t rows = 0, cols = 0, group = 0;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            ok = w && scale && !e.has(N.weight_g_idx) && (zp != nullptr || !e.has(N.weight_zero_point)) && w->dim() == 2 && half_type(w->scalar_type()) &&
-                 scale->scalar_type() == w->scalar_type() && (w->is_cuda() || g_allow_cpu) && w->is_contiguous() && aligned16(*w) && scale->is_contiguous() &&
-                 aligned16(*scale) && scale->device() == w->device();
-        }
-        if (ok) {
-            rows = w->size(0);
-            cols = w->size(1);
-            group = ginfo == 0 ? cols : ginfo;
-            ok = rows > 0 && cols % 32 == 0 && group % 32 == 0 && cols % group == 0 && scale->dim() == 2 && scale->size(0) == rows &&
-                 scale->size(1) == cols / group;
-            if (ok && zp)
-                ok = zp->scalar_type() == at::kChar && zp->sizes() == scale->sizes() && zp->is_contiguous() && aligned16(*zp) && zp->device() == w->device();
-            ok = ok && (zp || !asym) && staying_entries_are_final(e, {N.weight, N.weight_zero_point});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor packed = at::empty({rows, cols / 8}, w->options().dtype(at::kInt));
-        Batch& b = batches[{w->is_cuda() ? (int)w->device().index() : -1, w->scalar_type() == at::kHalf ? 1 : 2}];
-        py::object zp_packed = py::none(), zp_ref = py::none();
-        int64_t zpp_ptr = 0;
-        if (asym) {  // int8 (R, G) -> int32 (ceil(R / 8), G): written by tail workgroups of the weights' own launch (round 6: ct_w4_item.zp_packed)
-            at::Tensor zpp = at::empty({(rows * 4 + 31) / 32, zp->size(1)}, w->options().dtype(at::kInt));
-            zpp_ptr = (int64_t)(uintptr_t)zpp.data_ptr();
-            zp_packed = py::reinterpret_steal<py::object>(THPVariable_Wrap(zpp));
-            zp_ref = py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_zero_point));
-        }
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)w->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp ? (int64_t)(uintptr_t)zp->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)packed.data_ptr(), rows, cols, group, 0, 0, 0, zpp_ptr, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        // the job keeps the inputs alive until the launch has been issued (the table holds raw pointers)
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(packed)), rows, cols,
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)), zp_packed, zp_ref));
+        if (!(plain_type(m) && e.open(m) && body(m, info, e))) rest.append(borrowed(m));
     }
-    return py::make_tuple(batches_to_python(batches), rest);
+    return rest;
 }
 
-// after the launch: `weight` (and the zero point a symmetric scheme does not store) leave, `weight_packed` and `weight_shape` arrive, an asymmetric
-// scheme's zero point is replaced by its packed form
-void w4_finish_compress(py::list jobs, py::object status) {
+// The plan driver.  `take(module, info, entries, sink) -> bool`: false = not this scheme's plain case, and then NOTHING was put into the sink; true = the
+// outputs are allocated and the sink's batch for the module holds its row (rows) and its job — a tuple that starts with the module, carries what the
+// scheme's finish needs, and holds a reference to every INPUT the rows point at.  Returns (batches for Python, rest).
+template <class Take>
+py::tuple plan_modules(const py::list& modules, PyObject* infos_arg, Take take) {
+    Sink sink;
+    py::list rest = each_plain_module(modules, infos_arg, [&](PyObject* m, int64_t info, Entries& e) { return take(m, info, e, sink); });
+    return py::make_tuple(batches_to_python(sink), rest);
+}
+
+// The finish driver, after the launch: `rewrite(job, entries)` is the dictionary surgery of one module (job[0]), then the module's status.
+template <class Rewrite>
+void finish_jobs(const py::list& jobs, PyObject* status, Rewrite rewrite) {
     touch_tls();
     const Py_ssize_t n = PyList_GET_SIZE(jobs.ptr());
     for (Py_ssize_t i = 0; i < n; ++i) {
         PyObject* job = PyList_GET_ITEM(jobs.ptr(), i);
         PyObject* m = PyTuple_GET_ITEM(job, 0);
-        const at::Tensor& packed = THPVariable_Unpack(PyTuple_GET_ITEM(job, 1));
-        const int64_t rows = PyLong_AsLongLong(PyTuple_GET_ITEM(job, 2)), cols = PyLong_AsLongLong(PyTuple_GET_ITEM(job, 3));
         Entries e;
         if (!e.open(m)) throw std::runtime_error("module lost its _parameters");
+        rewrite(job, e);
+        set_status(m, status);
+    }
+}
+
+inline const at::Tensor& job_tensor(PyObject* job, int k) { return THPVariable_Unpack(PyTuple_GET_ITEM(job, k)); }
+
+at::Tensor shape_tensor(int64_t rows, int64_t cols) {  // `weight_shape`: int64, CPU, as upstream (pack_quantized/base.py:105)
+    at::Tensor shape = at::empty({2}, at::TensorOptions().dtype(at::kLong));
+    shape.data_ptr<int64_t>()[0] = rows;
+    shape.data_ptr<int64_t>()[1] = cols;
+    return shape;
+}
+
+// ------------------------------------------------------------------------------------------
+// pack-quantized W4 (int4, 16-bit weights and scales of one dtype; ct_quant_pack_batch / ct_unpack_dequant_batch).  batch key code: the dtype code.
+// compress infos[i]: group size of module i's scheme (0 = channel-wise), + kAsymmetric when the scheme stores packed zero points
+// (pack_to_int32(zp, 4, packed_dim=0), pack_quantized/base.py:107-110), or < 0 when the scheme is not an int4 group / channel scheme
+// ------------------------------------------------------------------------------------------
+constexpr int64_t kAsymmetric = int64_t(1) << 40;
+
+bool w4_take_compress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    const bool asym = info >= kAsymmetric;
+    const int64_t ginfo = asym ? info - kAsymmetric : info;
+    if (ginfo < 0 || dict_has(m, N.weight_packed) || dict_has(m, N.weight_shape)) return false;
+    const at::Tensor *w = e.tensor(N.weight), *scale = e.tensor(N.weight_scale), *zp = e.tensor(N.weight_zero_point);
+    // (the kernel loads scales and zero points in 16-byte units too: both aligned, unlike the per-module launches of the wb loop)
+    if (!(w && scale && !e.has(N.weight_g_idx) && tensor_or_absent(e, zp, N.weight_zero_point) && dense_source(*w) && half_type(w->scalar_type()) &&
+          scale->scalar_type() == w->scalar_type() && scale->is_contiguous() && aligned16(*scale) && scale->device() == w->device()))
+        return false;
+    const int64_t rows = w->size(0), cols = w->size(1), group = ginfo == 0 ? cols : ginfo;
+    if (!(rows > 0 && cols % 32 == 0 && group % 32 == 0 && cols % group == 0 && scale->dim() == 2 && scale->size(0) == rows && scale->size(1) == cols / group)) return false;
+    if (zp && !(zp->scalar_type() == at::kChar && zp->sizes() == scale->sizes() && zp->is_contiguous() && aligned16(*zp) && zp->device() == w->device())) return false;
+    if (!((zp || !asym) && staying_entries_are_final(e, {N.weight, N.weight_zero_point}))) return false;
+    at::Tensor packed = at::empty({rows, cols / 8}, w->options().dtype(at::kInt));
+    at::Tensor zpp;  // int8 (R, G) -> int32 (ceil(R / 8), G): written by tail workgroups of the weights' own launch (ct_w4_item.zp_packed)
+    if (asym) zpp = at::empty({(rows * 4 + 31) / 32, zp->size(1)}, w->options().dtype(at::kInt));
+    Batch& b = sink.at(*w, half_code(w->scalar_type()));
+    b.row(item_row(w->data_ptr(), scale->data_ptr(), data_or_null(zp), packed.data_ptr(), rows, cols, group, asym ? zpp.data_ptr() : nullptr));
+    // (module, packed, rows, cols, keep-alive weight, zp_packed or None, keep-alive zero point or None)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(packed), rows, cols, entry_ref(e, N.weight), asym ? wrap(zpp) : py::none(),
+                                 asym ? entry_ref(e, N.weight_zero_point) : py::none()));
+    return true;
+}
+
+// `weight` (and the zero point a symmetric scheme does not store) leave, `weight_packed` and `weight_shape` arrive, an asymmetric
+// scheme's zero point is replaced by its packed form
+void w4_finish_compress(py::list jobs, py::object status) {
+    finish_jobs(jobs, status.ptr(), [](PyObject* job, Entries& e) {
+        const int64_t rows = PyLong_AsLongLong(PyTuple_GET_ITEM(job, 2)), cols = PyLong_AsLongLong(PyTuple_GET_ITEM(job, 3));
         PyObject* zp_packed = PyTuple_GET_ITEM(job, 5);
         drop(e.params, N.weight);
         if (zp_packed == Py_None) drop(e.params, N.weight_zero_point);  // a symmetric scheme stores none (compressors/base.py: symmetric_zp_keys)
-        at::Tensor shape = at::empty({2}, at::TensorOptions().dtype(at::kLong));  // int64, CPU: as upstream (pack_quantized/base.py:105)
-        shape.data_ptr<int64_t>()[0] = rows;
-        shape.data_ptr<int64_t>()[1] = cols;
-        PyDict_SetItem(e.params, N.weight_packed, make_parameter(packed).ptr());
-        PyDict_SetItem(e.params, N.weight_shape, make_parameter(shape).ptr());
-        if (zp_packed != Py_None) PyDict_SetItem(e.params, N.weight_zero_point, make_parameter(THPVariable_Unpack(zp_packed)).ptr());  // in place: same position
-        set_status(m, status.ptr());
-    }
+        set_entry(e, N.weight_packed, job_tensor(job, 1));
+        set_entry(e, N.weight_shape, shape_tensor(rows, cols));
+        if (zp_packed != Py_None) set_entry(e, N.weight_zero_point, THPVariable_Unpack(zp_packed));  // in place: same position
+    });
 }
 
-// infos[i]: 1 when module i's scheme is a symmetric int4 scheme (the strategy is inferred from the scale's shape, as `dequantize` does), 2 when it is
-// an asymmetric int4 group / channel scheme (zero points stored packed along rows), else 0
-py::tuple w4_plan_decompress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        const bool scheme_ok = info == 1 || info == 2, asym = info == 2;
-        Entries e;
-        bool ok = scheme_ok && plain_type(m) && e.open(m) && !dict_has(m, N.weight);
-        const at::Tensor *packed = nullptr, *scale = nullptr, *shape_t = nullptr, *zpp = nullptr;
-        int64_t rows = 0, cols = 0, group = 0;
-        if (ok) {
-            packed = e.tensor(N.weight_packed);
-            scale = e.tensor(N.weight_scale);
-            shape_t = e.tensor(N.weight_shape);
-            zpp = e.tensor(N.weight_zero_point);
-            ok = packed && scale && shape_t && !e.has(N.weight_g_idx) && (asym ? zpp != nullptr : !e.has(N.weight_zero_point)) && !e.has(N.weight) &&
-                 (packed->is_cuda() || g_allow_cpu) &&
-                 packed->is_contiguous() && packed->scalar_type() == at::kInt && aligned16(*packed) && packed->dim() == 2 && scale->dim() == 2 &&
-                 half_type(scale->scalar_type()) && scale->is_contiguous() && aligned16(*scale) && scale->device() == packed->device() &&
-                 shape_t->device().is_cpu() && shape_t->scalar_type() == at::kLong && shape_t->numel() == 2 && shape_t->is_contiguous();
+// decompress infos[i]: 1 when module i's scheme is a symmetric int4 scheme (the strategy is inferred from the scale's shape, as `dequantize` does), 2 when
+// it is an asymmetric int4 group / channel scheme (zero points stored packed along rows), else 0
+bool w4_take_decompress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    const bool asym = info == 2;
+    if (!(info == 1 || info == 2) || dict_has(m, N.weight)) return false;
+    const at::Tensor *packed = e.tensor(N.weight_packed), *scale = e.tensor(N.weight_scale), *zpp = e.tensor(N.weight_zero_point);
+    int64_t rows = 0, cols = 0;
+    if (!(packed && scale && !e.has(N.weight_g_idx) && (asym ? zpp != nullptr : !e.has(N.weight_zero_point)) && !e.has(N.weight) && dense_source(*packed) &&
+          packed->scalar_type() == at::kInt && scale->dim() == 2 && half_type(scale->scalar_type()) && scale->is_contiguous() && aligned16(*scale) &&
+          scale->device() == packed->device() && stored_shape(e.tensor(N.weight_shape), rows, cols)))
+        return false;
+    if (!(scale->size(1) > 0 && cols % scale->size(1) == 0)) return false;
+    const int64_t group = scale->size(1) == 1 ? cols : cols / scale->size(1);  // (R, 1): channel; (R, G): group (forward.py:99-130)
+    if (!(cols % 32 == 0 && group % 32 == 0 && cols % group == 0 && scale->size(0) == rows && scale->size(1) == cols / group && packed->size(0) == rows &&
+          packed->size(1) == cols / 8 && staying_entries_are_final(e, {N.weight_packed, N.weight_zero_point})))
+        return false;
+    if (asym && !(zpp->scalar_type() == at::kInt && zpp->dim() == 2 && zpp->size(0) == (rows * 4 + 31) / 32 && zpp->size(1) == scale->size(1) && zpp->is_contiguous() &&
+                  zpp->device() == packed->device()))
+        return false;
+    at::Tensor out = at::empty({rows, cols}, scale->options());
+    Batch& b = sink.at(*packed, half_code(scale->scalar_type()));
+    at::Tensor zp;
+    void* zpp_in = nullptr;
+    if (asym) {
+        zp = at::empty({rows, scale->size(1)}, packed->options().dtype(at::kChar));
+        if (group == 128 && cols % 512 == 0 && rows * (cols / 8) < (int64_t(1) << 31) && aligned16(*zpp)) {
+            // the weights' launch reads the zero points in their stored form and its tail workgroups write the int8 form back
+            // (include/ct_hip.h, ct_w4_item.zp_packed) — no launch in front of it
+            zpp_in = zpp->data_ptr();
+        } else {  // int32 (ceil(R / 8), G) -> int8 (R, G): unpacked by the launch that runs BEFORE the weights' (the table below points at it)
+            b.aux_row(item_row(zpp->data_ptr(), nullptr, nullptr, zp.data_ptr(), rows, scale->size(1), 0));
         }
-        if (ok) {
-            rows = shape_t->data_ptr<int64_t>()[0];
-            cols = shape_t->data_ptr<int64_t>()[1];
-            ok = rows > 0 && cols > 0 && scale->size(1) > 0 && cols % scale->size(1) == 0;
-        }
-        if (ok) {
-            group = scale->size(1) == 1 ? cols : cols / scale->size(1);  // (R, 1): channel; (R, G): group (forward.py:99-130)
-            ok = cols % 32 == 0 && group % 32 == 0 && cols % group == 0 && scale->size(0) == rows && scale->size(1) == cols / group && packed->size(0) == rows &&
-                 packed->size(1) == cols / 8 && staying_entries_are_final(e, {N.weight_packed, N.weight_zero_point});
-            if (ok && asym)
-                ok = zpp->scalar_type() == at::kInt && zpp->dim() == 2 && zpp->size(0) == (rows * 4 + 31) / 32 && zpp->size(1) == scale->size(1) &&
-                     zpp->is_contiguous() && zpp->device() == packed->device();
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor out = at::empty({rows, cols}, scale->options());
-        Batch& b = batches[{packed->is_cuda() ? (int)packed->device().index() : -1, scale->scalar_type() == at::kHalf ? 1 : 2}];
-        py::object zp_obj = py::none(), zpp_ref = py::none();
-        int64_t zp_ptr = 0, zpp_ptr = 0;
-        if (asym) {
-            at::Tensor zp = at::empty({rows, scale->size(1)}, packed->options().dtype(at::kChar));
-            zp_ptr = (int64_t)(uintptr_t)zp.data_ptr();
-            if (group == 128 && cols % 512 == 0 && rows * (cols / 8) < (int64_t(1) << 31) && aligned16(*zpp)) {
-                // round 6: the weights' launch reads the zero points in their stored form and its tail workgroups write the int8 form back
-                // (include/ct_hip.h, ct_w4_item.zp_packed) — no launch in front of it
-                zpp_ptr = (int64_t)(uintptr_t)zpp->data_ptr();
-            } else {  // int32 (ceil(R / 8), G) -> int8 (R, G): unpacked by the launch that runs BEFORE the weights' (the table below points at it)
-                const int64_t zitem[kItemWords] = {(int64_t)(uintptr_t)zpp->data_ptr(), 0, 0, (int64_t)(uintptr_t)zp.data_ptr(), rows, scale->size(1), 0, 0, 0, 0, 0, 0, 0};
-                b.zp_words.insert(b.zp_words.end(), zitem, zitem + kItemWords);
-                b.zp_n += 1;
-            }
-            zp_obj = py::reinterpret_steal<py::object>(THPVariable_Wrap(zp));
-            zpp_ref = py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_zero_point));
-        }
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)packed->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp_ptr, (int64_t)(uintptr_t)out.data_ptr(), rows, cols,
-                                          group, 0, 0, 0, zpp_ptr, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_packed)), zp_obj, zpp_ref));
     }
-    return py::make_tuple(batches_to_python(batches), rest);
+    b.row(item_row(packed->data_ptr(), scale->data_ptr(), asym ? zp.data_ptr() : nullptr, out.data_ptr(), rows, cols, group, zpp_in));
+    // (module, out, keep-alive packed, unpacked zero points or None, keep-alive packed zero points or None)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), entry_ref(e, N.weight_packed), asym ? wrap(zp) : py::none(),
+                                 asym ? entry_ref(e, N.weight_zero_point) : py::none()));
+    return true;
 }
 
 void w4_finish_decompress(py::list jobs, py::object status) {
-    touch_tls();
-    const Py_ssize_t n = PyList_GET_SIZE(jobs.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* job = PyList_GET_ITEM(jobs.ptr(), i);
-        PyObject* m = PyTuple_GET_ITEM(job, 0);
-        const at::Tensor& out = THPVariable_Unpack(PyTuple_GET_ITEM(job, 1));
-        Entries e;
-        if (!e.open(m)) throw std::runtime_error("module lost its _parameters");
+    finish_jobs(jobs, status.ptr(), [](PyObject* job, Entries& e) {
         PyObject* zp = PyTuple_GET_ITEM(job, 3);
         drop(e.params, N.weight_packed);
-        PyDict_SetItem(e.params, N.weight, make_parameter(out).ptr());
-        if (zp != Py_None) PyDict_SetItem(e.params, N.weight_zero_point, make_parameter(THPVariable_Unpack(zp)).ptr());  // unpacked, int8, in place
-        set_status(m, status.ptr());
-    }
+        set_entry(e, N.weight, job_tensor(job, 1));
+        if (zp != Py_None) set_entry(e, N.weight_zero_point, THPVariable_Unpack(zp));  // unpacked, int8, in place
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -420,12 +500,10 @@ void w4_finish_decompress(py::list jobs, py::object status) {
 // NaiveQuantizationCompressor._batch_compress / _batch_decompress and codec.q8_batch_group (the Python loop: 7-9 us per module and direction, which a
 // 1B-parameter FP8 checkpoint's modules do not hide).
 // compress infos[i]: group_size (bits 0-19; 0 = none; the block width of a block scheme) | num_bits << 20 | FLOAT << 24 | strategy << 25 (0 tensor, 1 channel,
-//                    2 group, 3 block) | drop mask << 27 (bit 0 weight_zero_point, 1 input_zero_point, 2 output_zero_point: the zero points a symmetric scheme does
-//                    not store) | block height << 30, or < 0
-// batch key: (device index, dtype code | kind << 4 | num_bits << 8), kind 0 int8, 1 fp8, 2 fp8 with float8 zero points
+//                    2 group, 3 block) | drop mask << 27 (`drop_mask_names`) | block height << 30, or < 0
+// batch key code: dtype code | kind << 4 | num_bits << 8, kind 0 int8, 1 fp8, 2 fp8 with float8 zero points, 3 int8 packed four to a word (w8_*)
 // ------------------------------------------------------------------------------------------
-PyObject* g_input_zero_point = nullptr;
-PyObject* g_output_zero_point = nullptr;
+inline int q8_code(at::ScalarType dt, int kind, int bits) { return half_code(dt) | (kind << 4) | (bits << 8); }
 
 // codec.q8_batch_group: elements per scale, or 0.  strategy < 0: inferred from the scale's shape (forward.py:99-130)
 int64_t q8_group(int64_t rows, int64_t cols, const at::Tensor& scale, const at::Tensor* zp, at::ScalarType wdt, const at::Device& dev, int strategy, int64_t group_size,
@@ -456,125 +534,65 @@ int64_t q8_group(int64_t rows, int64_t cols, const at::Tensor& scale, const at::
     return group;
 }
 
-py::tuple q8_plan_compress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        const int64_t group_size = info & 0xfffff;
-        const int bits = (int)((info >> 20) & 15), strategy = (int)((info >> 25) & 3), dropmask = (int)((info >> 27) & 7);
-        const int64_t block_rows = (info >> 30) & 0xfffff;
-        const bool is_float = ((info >> 24) & 1) != 0;
-        Entries e;
-        bool ok = info >= 0 && plain_type(m) && e.open(m);
-        const at::Tensor *w = nullptr, *scale = nullptr, *zp = nullptr;
-        int64_t group = 0;
-        bool f8z = false;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            ok = w && scale && !e.has(N.weight_g_idx) && (zp != nullptr || !e.has(N.weight_zero_point)) && w->dim() == 2 && (w->is_cuda() || g_allow_cpu) &&
-                 w->is_contiguous() && aligned16(*w) && bits >= 1 && bits <= 8 && (!is_float || bits == 8);
-        }
-        if (ok) {
-            f8z = is_float && zp && zp->scalar_type() == at::kFloat8_e4m3fn;
-            ok = !(is_float && zp && !f8z);
-            if (ok) group = q8_group(w->size(0), w->size(1), *scale, zp, w->scalar_type(), w->device(), strategy, group_size, f8z, block_rows);
-            ok = ok && group != 0 &&
-                 staying_entries_are_final(e, {N.weight, (dropmask & 1) ? N.weight_zero_point : N.weight, (dropmask & 2) ? g_input_zero_point : N.weight,
-                                               (dropmask & 4) ? g_output_zero_point : N.weight});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        const int64_t rows = w->size(0), cols = w->size(1);
-        at::Tensor out = at::empty({rows, cols}, w->options().dtype(is_float ? at::kFloat8_e4m3fn : at::kChar));
-        const int kind = is_float ? (f8z ? 2 : 1) : 0;
-        Batch& b = batches[{w->is_cuda() ? (int)w->device().index() : -1, (w->scalar_type() == at::kHalf ? 1 : 2) | (kind << 4) | (bits << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)w->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp ? (int64_t)(uintptr_t)zp->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)out.data_ptr(), rows, cols, group, 0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        // the job keeps the inputs alive until the launch has been issued (the table holds raw pointers)
-        PyObject* zp_obj = zp ? PyDict_GetItem(e.params, N.weight_zero_point) : Py_None;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)), dropmask,
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)), py::reinterpret_borrow<py::object>(zp_obj)));
+// the entries the 8-bit loops (q8, mx8, w8 compress) read the same way: a dense `weight`, a scale, a zero point or none, no activation ordering
+struct Q8Entries {
+    const at::Tensor *w, *scale, *zp;
+    bool ok;
+    explicit Q8Entries(const Entries& e) : w(e.tensor(N.weight)), scale(e.tensor(N.weight_scale)), zp(e.tensor(N.weight_zero_point)) {
+        ok = w && scale && !e.has(N.weight_g_idx) && tensor_or_absent(e, zp, N.weight_zero_point) && dense_source(*w);
     }
-    return py::make_tuple(batches_to_python(batches), rest);
+};
+
+bool q8_take_compress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    const int64_t group_size = info & 0xfffff, block_rows = (info >> 30) & 0xfffff;
+    const int bits = (int)((info >> 20) & 15), strategy = (int)((info >> 25) & 3), dropmask = (int)((info >> 27) & 7);
+    const bool is_float = ((info >> 24) & 1) != 0;
+    if (info < 0) return false;
+    const Q8Entries q(e);
+    if (!(q.ok && bits >= 1 && bits <= 8 && (!is_float || bits == 8))) return false;
+    const at::Tensor *w = q.w, *zp = q.zp;
+    const bool f8z = is_float && zp && zp->scalar_type() == at::kFloat8_e4m3fn;
+    if (is_float && zp && !f8z) return false;
+    const int64_t rows = w->size(0), cols = w->size(1);
+    const int64_t group = q8_group(rows, cols, *q.scale, zp, w->scalar_type(), w->device(), strategy, group_size, f8z, block_rows);
+    if (group == 0 || !staying_entries_are_final(e, {N.weight}, dropmask)) return false;
+    at::Tensor out = at::empty({rows, cols}, w->options().dtype(is_float ? at::kFloat8_e4m3fn : at::kChar));
+    Batch& b = sink.at(*w, q8_code(w->scalar_type(), is_float ? (f8z ? 2 : 1) : 0, bits));
+    b.row(item_row(w->data_ptr(), q.scale->data_ptr(), data_or_null(zp), out.data_ptr(), rows, cols, group));
+    // (module, codes, drop mask, keep-alive weight, keep-alive zero point or None)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), dropmask, entry_ref(e, N.weight), zp ? entry_ref(e, N.weight_zero_point) : py::none()));
+    return true;
 }
 
-// after the launch: the codes replace `weight` (re-added last, as swap_direct_entries with `weight` among the removed names), a symmetric scheme's zero points leave
+// the codes replace `weight` (re-added last, as swap_direct_entries with `weight` among the removed names), a symmetric scheme's zero points leave
 void q8_finish(py::list jobs, py::object status) {
-    touch_tls();
-    const Py_ssize_t n = PyList_GET_SIZE(jobs.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* job = PyList_GET_ITEM(jobs.ptr(), i);
-        PyObject* m = PyTuple_GET_ITEM(job, 0);
-        const at::Tensor& out = THPVariable_Unpack(PyTuple_GET_ITEM(job, 1));
-        const long dropmask = PyLong_AsLong(PyTuple_GET_ITEM(job, 2));
-        Entries e;
-        if (!e.open(m)) throw std::runtime_error("module lost its _parameters");
-        if (dropmask & 1) drop(e.params, N.weight_zero_point);
-        if (dropmask & 2) drop(e.params, g_input_zero_point);
-        if (dropmask & 4) drop(e.params, g_output_zero_point);
+    finish_jobs(jobs, status.ptr(), [](PyObject* job, Entries& e) {
+        drop_zero_points(e, PyLong_AsLong(PyTuple_GET_ITEM(job, 2)));
         drop(e.params, N.weight);  // `compress` / `decompress` pop `weight` and add the result last (naive_quantized/base.py:62-126): it ends up behind the entries that stay
-        PyDict_SetItem(e.params, N.weight, make_parameter(out).ptr());
-        set_status(m, status.ptr());
-    }
+        set_entry(e, N.weight, job_tensor(job, 1));
+    });
 }
 
-// infos[i]: > 0 when the module's codec is the plain 8-bit one (the layout is read off the stored tensors, as `dequantize` does), else 0
-py::tuple q8_plan_decompress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        Entries e;
-        bool ok = info > 0 && plain_type(m) && e.open(m);
-        const at::Tensor *q = nullptr, *scale = nullptr, *zp = nullptr;
-        int64_t group = 0;
-        int kind = -1;
-        if (ok) {
-            q = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            ok = q && scale && !e.has(N.weight_g_idx) && (zp != nullptr || !e.has(N.weight_zero_point)) && q->dim() == 2 && (q->is_cuda() || g_allow_cpu) &&
-                 q->is_contiguous() && aligned16(*q);
-        }
-        if (ok) {
-            kind = q->scalar_type() == at::kChar ? 0 : q->scalar_type() == at::kFloat8_e4m3fn ? 1 : -1;
-            const bool f8z = kind == 1 && zp && zp->scalar_type() == at::kFloat8_e4m3fn;
-            ok = kind >= 0 && !(kind == 1 && zp && !f8z);
-            if (f8z) kind = 2;
-            if (ok) group = q8_group(q->size(0), q->size(1), *scale, zp, scale->scalar_type(), q->device(), -1, 0, f8z);
-            ok = ok && group != 0 && staying_entries_are_final(e, {N.weight});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        const int64_t rows = q->size(0), cols = q->size(1);
-        at::Tensor out = at::empty({rows, cols}, scale->options());
-        Batch& b = batches[{q->is_cuda() ? (int)q->device().index() : -1, (scale->scalar_type() == at::kHalf ? 1 : 2) | (kind << 4) | (8 << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)q->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp ? (int64_t)(uintptr_t)zp->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)out.data_ptr(), rows, cols, group, 0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)), 0,
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)), py::none()));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+// decompress infos[i]: > 0 when the module's codec is the plain 8-bit one (the layout is read off the stored tensors, as `dequantize` does), else 0
+bool q8_take_decompress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    if (info <= 0) return false;
+    const Q8Entries q(e);
+    if (!q.ok) return false;
+    const at::Tensor *codes = q.w, *scale = q.scale, *zp = q.zp;
+    int kind = codes->scalar_type() == at::kChar ? 0 : codes->scalar_type() == at::kFloat8_e4m3fn ? 1 : -1;
+    const bool f8z = kind == 1 && zp && zp->scalar_type() == at::kFloat8_e4m3fn;
+    if (kind < 0 || (kind == 1 && zp && !f8z)) return false;
+    if (f8z) kind = 2;
+    const int64_t rows = codes->size(0), cols = codes->size(1);
+    const int64_t group = q8_group(rows, cols, *scale, zp, scale->scalar_type(), codes->device(), -1, 0, f8z);
+    if (group == 0 || !staying_entries_are_final(e, {N.weight})) return false;
+    at::Tensor out = at::empty({rows, cols}, scale->options());
+    Batch& b = sink.at(*codes, q8_code(scale->scalar_type(), kind, 8));
+    b.row(item_row(codes->data_ptr(), scale->data_ptr(), data_or_null(zp), out.data_ptr(), rows, cols, group));
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), 0, entry_ref(e, N.weight), py::none()));  // q8_finish's job: nothing to drop
+    return true;
 }
+
 
 // the quantized modules of a model in `named_modules(remove_duplicate=True)` order (pre-order over `_modules`, every module once):
 // model_compressor.py:152-164,191-195 with is_module_quantized (quantization/utils/helpers.py:229-250: a scheme with at least one of
@@ -1043,24 +1061,11 @@ py::tuple marlin24_w4_full(const at::Tensor& weight, int wdt, const at::Tensor& 
 }
 
 
-// C ABI element code of a tensor's dtype (include/ct_hip.h enum ct_dtype), -1 for a type the ABI has no code for
-int dtype_code(at::ScalarType t) {
-    switch (t) {
-        case at::kFloat: return 0;
-        case at::kHalf: return 1;
-        case at::kBFloat16: return 2;
-        case at::kChar: return 3;
-        case at::kInt: return 4;
-        case at::kByte: case at::kBool: return 5;
-        case at::kShort: return 6;
-        case at::kLong: return 7;
-        default: return -1;
-    }
-}
-
 // pack-quantized with the other word widths (2 / 3 / 5 / 6 / 7 bits) and, for EVERY width, modules with activation ordering (a `weight_g_idx` entry; symmetric
 // weights-only group / channel schemes): no table form exists for them, so this loop launches `ct_quant_pack` / `ct_unpack_dequant` per module BY ADDRESS on `stream` of device `device_index` (which the caller has
 // made current) and rewrites the dictionary right behind each launch — the interpreter's 22-33 us per module become ~7.  Entries as the W4 loop leaves them.
+// The loop head and the hand-back are `each_plain_module`'s; there is no table, so no plan driver and no finish.  A refused launch hands the module back too:
+// the Python path repeats it and reports the library's message.
 // infos[i]: group_size | ASYMMETRIC << 24 (the scheme stores its zero points packed along rows, pack_quantized/base.py:107-110: one more launch,
 // ct_pack_int32_dim0 / ct_unpack_int32_dim0) | strategy << 25 (1 channel, 2 group) | num_bits << 28, or < 0.
 using quant_pack_fn = int (*)(const void*, int, const void*, int, const void*, int, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t*, int, int, int32_t*, void*);
@@ -1095,369 +1100,190 @@ at::Tensor col_group_of(const at::Tensor& g_idx, const at::Tensor& like, int64_t
     return cg;
 }
 
-inline int half_code(at::ScalarType t) { return t == at::kHalf ? 1 : 2; }  // _lib.F16 / _lib.BF16
+// which modules the per-module loop is for: every one with activation ordering, and without it the widths that have no table (4 and — symmetric — 8 ride theirs)
+inline bool wb_is_mine(const Entries& e, const at::Tensor* gidx, int bits, bool asym) {
+    return gidx != nullptr || (!e.has(N.weight_g_idx) && bits != 4 && (bits != 8 || asym));
+}
 
 py::list wb_compress_modules(py::list modules, py::object infos_arg, int device_index, uintptr_t stream, py::object status) {
-    touch_tls();
     if (!g_quant_pack) throw std::runtime_error("wb_compress_modules: bind_pack has not been called");
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
+    return each_plain_module(modules, infos_arg.ptr(), [&](PyObject* m, int64_t info, Entries& e) {
         const int bits = (int)((info >> 28) & 15), strategy = (int)((info >> 25) & 3);
         const bool asym = ((info >> 24) & 1) != 0;
-        Entries e;
-        bool ok = info >= 0 && bits >= 1 && bits <= 8 && plain_type(m) && e.open(m) && !dict_has(m, N.weight_packed) && !dict_has(m, N.weight_shape);
-        const at::Tensor *w = nullptr, *scale = nullptr, *zp = nullptr, *gidx = nullptr;
-        int64_t rows = 0, cols = 0, group = 0;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            gidx = e.tensor(N.weight_g_idx);
-            // (the widths 4 and — symmetric — 8 without activation ordering ride their tables: handed back)
-            ok = w && scale && (gidx != nullptr || (!e.has(N.weight_g_idx) && bits != 4 && (bits != 8 || asym))) && (zp != nullptr || !e.has(N.weight_zero_point)) &&
-                 (!asym || (zp != nullptr && g_pack_dim0 != nullptr)) &&
-                 !e.has(N.weight_packed) && w->dim() == 2 && half_type(w->scalar_type()) && ((w->is_cuda() && w->device().index() == device_index) || g_allow_cpu) &&
-                 w->is_contiguous() && aligned16(*w) && scale->scalar_type() == w->scalar_type() && scale->device() == w->device() && scale->is_contiguous() &&
-                 scale->dim() == 2 && (gidx == nullptr || strategy == 2);
-        }
-        if (ok) {
-            rows = w->size(0);
-            cols = w->size(1);
-            group = strategy == 1 ? cols : (info & 0xfffff);
-            ok = rows > 0 && cols > 0 && group > 0 && cols % group == 0 && scale->size(0) == rows && scale->size(1) == cols / group;
-            if (ok && zp) ok = zp->scalar_type() == at::kChar && zp->sizes() == scale->sizes() && zp->is_contiguous() && zp->device() == w->device();
-            ok = ok && staying_entries_are_final(e, {N.weight, N.weight_zero_point});
-        }
+        if (!(info >= 0 && bits >= 1 && bits <= 8) || dict_has(m, N.weight_packed) || dict_has(m, N.weight_shape)) return false;
+        const at::Tensor *w = e.tensor(N.weight), *scale = e.tensor(N.weight_scale), *zp = e.tensor(N.weight_zero_point), *gidx = e.tensor(N.weight_g_idx);
+        // (scales and zero points need no alignment here, unlike the W4 table: ct_quant_pack reads them by element)
+        if (!(w && scale && wb_is_mine(e, gidx, bits, asym) && tensor_or_absent(e, zp, N.weight_zero_point) && (!asym || (zp != nullptr && g_pack_dim0 != nullptr)) &&
+              !e.has(N.weight_packed) && dense_source(*w, 16, device_index) && half_type(w->scalar_type()) && scale->scalar_type() == w->scalar_type() &&
+              scale->device() == w->device() && scale->is_contiguous() && scale->dim() == 2 && (gidx == nullptr || strategy == 2)))
+            return false;
+        const int64_t rows = w->size(0), cols = w->size(1), group = strategy == 1 ? cols : (info & 0xfffff);
+        if (!(rows > 0 && cols > 0 && group > 0 && cols % group == 0 && scale->size(0) == rows && scale->size(1) == cols / group)) return false;
+        if (zp && !(zp->scalar_type() == at::kChar && zp->sizes() == scale->sizes() && zp->is_contiguous() && zp->device() == w->device())) return false;
+        if (!staying_entries_are_final(e, {N.weight, N.weight_zero_point})) return false;
         at::Tensor cg;
-        if (ok && gidx) {
+        if (gidx) {
             cg = col_group_of(*gidx, *w, cols, group, stream);
-            ok = cg.defined();
+            if (!cg.defined()) return false;
         }
-        if (ok) {
-            const int64_t words = (cols * bits + 31) / 32;
-            at::Tensor packed = at::empty({rows, words}, w->options().dtype(at::kInt));
-            const int dt = half_code(w->scalar_type());
-            const int rc = w->is_cpu() ? 0
-                                       : g_quant_pack(w->data_ptr(), dt, scale->data_ptr(), dt, zp ? zp->data_ptr() : nullptr, zp ? 3 /* _lib.I8 */ : -1, rows, cols, 1, group,
-                                                      cols / group, cg.defined() ? static_cast<const int32_t*>(cg.data_ptr()) : nullptr, bits, dt,
-                                                      static_cast<int32_t*>(packed.data_ptr()), reinterpret_cast<void*>(stream));
-            at::Tensor zpp;
-            int rc2 = 0;
-            if (rc == 0 && asym) {  // pack_to_int32(zp, num_bits, packed_dim=0)
-                zpp = at::empty({(rows * bits + 31) / 32, zp->size(1)}, w->options().dtype(at::kInt));
-                rc2 = w->is_cpu() ? 0
-                                  : g_pack_dim0(static_cast<const int8_t*>(zp->data_ptr()), rows, zp->size(1), bits, static_cast<int32_t*>(zpp.data_ptr()), reinterpret_cast<void*>(stream));
-            }
-            if (rc == 0 && rc2 == 0) {
-                drop(e.params, N.weight);
-                if (asym) PyDict_SetItem(e.params, N.weight_zero_point, make_parameter(zpp).ptr());  // in place: same position
-                else drop(e.params, N.weight_zero_point);  // a symmetric scheme stores none (compressors/base.py: symmetric_zp_keys)
-                at::Tensor shape = at::empty({2}, at::TensorOptions().dtype(at::kLong));
-                shape.data_ptr<int64_t>()[0] = rows;
-                shape.data_ptr<int64_t>()[1] = cols;
-                PyDict_SetItem(e.params, N.weight_packed, make_parameter(packed).ptr());
-                PyDict_SetItem(e.params, N.weight_shape, make_parameter(shape).ptr());
-                set_status(m, status.ptr());
-                continue;
-            }
+        at::Tensor packed = at::empty({rows, (cols * bits + 31) / 32}, w->options().dtype(at::kInt));
+        const int dt = half_code(w->scalar_type());
+        if (!w->is_cpu() && g_quant_pack(w->data_ptr(), dt, scale->data_ptr(), dt, data_or_null(zp), zp ? CT_I8 : -1, rows, cols, 1, group, cols / group,
+                                         cg.defined() ? static_cast<const int32_t*>(cg.data_ptr()) : nullptr, bits, dt, static_cast<int32_t*>(packed.data_ptr()),
+                                         reinterpret_cast<void*>(stream)) != 0)
+            return false;
+        at::Tensor zpp;
+        if (asym) {  // pack_to_int32(zp, num_bits, packed_dim=0)
+            zpp = at::empty({(rows * bits + 31) / 32, zp->size(1)}, w->options().dtype(at::kInt));
+            if (!w->is_cpu() && g_pack_dim0(static_cast<const int8_t*>(zp->data_ptr()), rows, zp->size(1), bits, static_cast<int32_t*>(zpp.data_ptr()), reinterpret_cast<void*>(stream)) != 0)
+                return false;
         }
-        rest.append(py::reinterpret_borrow<py::object>(m));  // (a refused launch too: the Python path repeats it and reports the library's message)
-    }
-    return rest;
+        drop(e.params, N.weight);
+        if (asym) set_entry(e, N.weight_zero_point, zpp);  // in place: same position
+        else drop(e.params, N.weight_zero_point);  // a symmetric scheme stores none (compressors/base.py: symmetric_zp_keys)
+        set_entry(e, N.weight_packed, packed);
+        set_entry(e, N.weight_shape, shape_tensor(rows, cols));
+        set_status(m, status.ptr());
+        return true;
+    });
 }
 
 py::list wb_decompress_modules(py::list modules, py::object infos_arg, int device_index, uintptr_t stream, py::object status) {
-    touch_tls();
     if (!g_unpack_dequant) throw std::runtime_error("wb_decompress_modules: bind_pack has not been called");
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
+    return each_plain_module(modules, infos_arg.ptr(), [&](PyObject* m, int64_t info, Entries& e) {
         const int bits = (int)((info >> 28) & 15);
         const bool asym = ((info >> 24) & 1) != 0;
-        Entries e;
-        bool ok = info >= 0 && bits >= 1 && bits <= 8 && plain_type(m) && e.open(m) && !dict_has(m, N.weight);
-        const at::Tensor *packed = nullptr, *scale = nullptr, *shape_t = nullptr, *gidx = nullptr, *zpp = nullptr;
-        int64_t rows = 0, cols = 0, group = 0;
-        if (ok) {
-            packed = e.tensor(N.weight_packed);
-            scale = e.tensor(N.weight_scale);
-            shape_t = e.tensor(N.weight_shape);
-            gidx = e.tensor(N.weight_g_idx);
-            zpp = e.tensor(N.weight_zero_point);
-            ok = packed && scale && shape_t && (gidx != nullptr || (!e.has(N.weight_g_idx) && bits != 4 && (bits != 8 || asym))) &&
-                 (asym ? (zpp != nullptr && g_unpack_dim0 != nullptr) : !e.has(N.weight_zero_point)) && !e.has(N.weight) &&
-                 ((packed->is_cuda() && packed->device().index() == device_index) || g_allow_cpu) && packed->is_contiguous() && packed->scalar_type() == at::kInt &&
-                 aligned16(*packed) && packed->dim() == 2 && scale->dim() == 2 && half_type(scale->scalar_type()) && scale->is_contiguous() &&
-                 scale->device() == packed->device() && shape_t->device().is_cpu() && shape_t->scalar_type() == at::kLong && shape_t->numel() == 2 && shape_t->is_contiguous();
-        }
-        if (ok) {
-            rows = shape_t->data_ptr<int64_t>()[0];
-            cols = shape_t->data_ptr<int64_t>()[1];
-            // (R, 1): channel; (R, G): groups of cols / G — the layout upstream's argument-free dequantize infers (forward.py:99-130)
-            ok = rows > 0 && cols > 0 && scale->size(0) == rows && scale->size(1) > 0 && cols % scale->size(1) == 0 && packed->size(0) == rows &&
-                 packed->size(1) == (cols * bits + 31) / 32 && staying_entries_are_final(e, {N.weight_packed, N.weight_zero_point});
-            group = ok ? cols / scale->size(1) : 0;
-            if (ok && asym)
-                ok = zpp->scalar_type() == at::kInt && zpp->dim() == 2 && zpp->size(0) == (rows * bits + 31) / 32 && zpp->size(1) == scale->size(1) && zpp->is_contiguous() &&
-                     zpp->device() == packed->device();
-        }
+        if (!(info >= 0 && bits >= 1 && bits <= 8) || dict_has(m, N.weight)) return false;
+        const at::Tensor *packed = e.tensor(N.weight_packed), *scale = e.tensor(N.weight_scale), *gidx = e.tensor(N.weight_g_idx), *zpp = e.tensor(N.weight_zero_point);
+        int64_t rows = 0, cols = 0;
+        if (!(packed && scale && wb_is_mine(e, gidx, bits, asym) && (asym ? (zpp != nullptr && g_unpack_dim0 != nullptr) : !e.has(N.weight_zero_point)) && !e.has(N.weight) &&
+              dense_source(*packed, 16, device_index) && packed->scalar_type() == at::kInt && scale->dim() == 2 && half_type(scale->scalar_type()) && scale->is_contiguous() &&
+              scale->device() == packed->device() && stored_shape(e.tensor(N.weight_shape), rows, cols)))
+            return false;
+        // (R, 1): channel; (R, G): groups of cols / G — the layout upstream's argument-free dequantize infers (forward.py:99-130)
+        if (!(scale->size(0) == rows && scale->size(1) > 0 && cols % scale->size(1) == 0 && packed->size(0) == rows && packed->size(1) == (cols * bits + 31) / 32 &&
+              staying_entries_are_final(e, {N.weight_packed, N.weight_zero_point})))
+            return false;
+        const int64_t group = cols / scale->size(1);
+        if (asym && !(zpp->scalar_type() == at::kInt && zpp->dim() == 2 && zpp->size(0) == (rows * bits + 31) / 32 && zpp->size(1) == scale->size(1) && zpp->is_contiguous() &&
+                      zpp->device() == packed->device()))
+            return false;
         at::Tensor cg;
-        if (ok && gidx) {
+        if (gidx) {
             cg = col_group_of(*gidx, *packed, cols, group, stream);
-            ok = cg.defined();
+            if (!cg.defined()) return false;
         }
-        if (ok) {
-            at::Tensor out = at::empty({rows, cols}, scale->options());
-            const int dt = half_code(scale->scalar_type());
-            at::Tensor zp8;
-            int rc0 = 0;
-            if (asym) {  // unpack_from_int32(zp, num_bits, (rows, G), packed_dim=0): in front of the weights' launch, which reads it
-                zp8 = at::empty({rows, scale->size(1)}, packed->options().dtype(at::kChar));
-                rc0 = packed->is_cpu() ? 0
-                                       : g_unpack_dim0(static_cast<const int32_t*>(zpp->data_ptr()), zpp->size(0), zpp->size(1), rows, bits, static_cast<int8_t*>(zp8.data_ptr()),
-                                                       reinterpret_cast<void*>(stream));
-            }
-            const int rc = rc0 != 0 || packed->is_cpu() ? rc0
-                                            : g_unpack_dequant(static_cast<const int32_t*>(packed->data_ptr()), rows, packed->size(1), cols, bits, scale->data_ptr(), dt,
-                                                               asym ? zp8.data_ptr() : nullptr, asym ? 3 : -1, 1,
-                                                               group, cols / group, cg.defined() ? static_cast<const int32_t*>(cg.data_ptr()) : nullptr, out.data_ptr(), dt,
-                                                               reinterpret_cast<void*>(stream));
-            if (rc == 0) {
-                drop(e.params, N.weight_packed);
-                if (asym) PyDict_SetItem(e.params, N.weight_zero_point, make_parameter(zp8).ptr());  // unpacked, int8, in place
-                PyDict_SetItem(e.params, N.weight, make_parameter(out).ptr());
-                set_status(m, status.ptr());
-                continue;
-            }
+        at::Tensor out = at::empty({rows, cols}, scale->options());
+        const int dt = half_code(scale->scalar_type());
+        at::Tensor zp8;
+        if (asym) {  // unpack_from_int32(zp, num_bits, (rows, G), packed_dim=0): in front of the weights' launch, which reads it
+            zp8 = at::empty({rows, scale->size(1)}, packed->options().dtype(at::kChar));
+            if (!packed->is_cpu() && g_unpack_dim0(static_cast<const int32_t*>(zpp->data_ptr()), zpp->size(0), zpp->size(1), rows, bits, static_cast<int8_t*>(zp8.data_ptr()),
+                                                   reinterpret_cast<void*>(stream)) != 0)
+                return false;
         }
-        rest.append(py::reinterpret_borrow<py::object>(m));
-    }
-    return rest;
+        if (!packed->is_cpu() && g_unpack_dequant(static_cast<const int32_t*>(packed->data_ptr()), rows, packed->size(1), cols, bits, scale->data_ptr(), dt,
+                                                  asym ? zp8.data_ptr() : nullptr, asym ? CT_I8 : -1, 1, group, cols / group,
+                                                  cg.defined() ? static_cast<const int32_t*>(cg.data_ptr()) : nullptr, out.data_ptr(), dt, reinterpret_cast<void*>(stream)) != 0)
+            return false;
+        drop(e.params, N.weight_packed);
+        if (asym) set_entry(e, N.weight_zero_point, zp8);  // unpacked, int8, in place
+        set_entry(e, N.weight, out);
+        set_status(m, status.ptr());
+        return true;
+    });
 }
 
 // mxfp8-quantized (reference compressors/mxfp8/base.py:29-118): float8 weights in groups of 32 — rows of the 8-bit tables, kind fp8 / fp8z — under 16-bit
-// power-of-two scales that are STORED as E8M0 codes: a second table (`zp_words` of the batch; ct_mx_scale_batch) converts the scales, float -> code on the way
+// power-of-two scales that are STORED as E8M0 codes: a second table (the batch's aux rows; ct_mx_scale_batch) converts the scales, float -> code on the way
 // in, code -> bfloat16 on the way back (launched BEFORE the weights' table, which reads the bfloat16 scales).  infos[i] (compress): 1 | drop mask << 1, or 0.
-py::tuple mx8_plan_compress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        const int dropmask = (int)((info >> 1) & 7);
-        Entries e;
-        bool ok = info > 0 && (info & 1) && plain_type(m) && e.open(m);
-        const at::Tensor *w = nullptr, *scale = nullptr, *zp = nullptr;
-        int64_t group = 0;
-        bool f8z = false;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            ok = w && scale && !e.has(N.weight_g_idx) && (zp != nullptr || !e.has(N.weight_zero_point)) && w->dim() == 2 && (w->is_cuda() || g_allow_cpu) &&
-                 w->is_contiguous() && aligned16(*w);
-        }
-        if (ok) {
-            f8z = zp && zp->scalar_type() == at::kFloat8_e4m3fn;
-            ok = !(zp && !f8z);
-            if (ok) group = q8_group(w->size(0), w->size(1), *scale, zp, w->scalar_type(), w->device(), 2, 32, f8z);
-            ok = ok && group == 32 &&
-                 staying_entries_are_final(e, {N.weight, N.weight_scale, (dropmask & 1) ? N.weight_zero_point : N.weight, (dropmask & 2) ? g_input_zero_point : N.weight,
-                                               (dropmask & 4) ? g_output_zero_point : N.weight});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        const int64_t rows = w->size(0), cols = w->size(1);
-        at::Tensor out = at::empty({rows, cols}, w->options().dtype(at::kFloat8_e4m3fn));
-        at::Tensor codes = at::empty(scale->sizes(), scale->options().dtype(at::kByte));
-        Batch& b = batches[{w->is_cuda() ? (int)w->device().index() : -1, (w->scalar_type() == at::kHalf ? 1 : 2) | ((f8z ? 2 : 1) << 4) | (8 << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)w->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp ? (int64_t)(uintptr_t)zp->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)out.data_ptr(), rows, cols, group, 0, 0, 0, 0, 0, 0};
-        const int64_t sitem[kItemWords] = {(int64_t)(uintptr_t)scale->data_ptr(), 0, 0, (int64_t)(uintptr_t)codes.data_ptr(), scale->numel(), 1, 0, 0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.zp_words.insert(b.zp_words.end(), sitem, sitem + kItemWords);
-        b.n += 1;
-        b.zp_n += 1;
-        PyObject* zp_obj = zp ? PyDict_GetItem(e.params, N.weight_zero_point) : Py_None;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)),
-                                     py::reinterpret_steal<py::object>(THPVariable_Wrap(codes)), dropmask, py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_scale)), py::reinterpret_borrow<py::object>(zp_obj)));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+bool mx8_take_compress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    const int dropmask = (int)((info >> 1) & 7);
+    if (!(info > 0 && (info & 1))) return false;
+    const Q8Entries q(e);
+    if (!q.ok) return false;
+    const at::Tensor *w = q.w, *scale = q.scale, *zp = q.zp;
+    const bool f8z = zp && zp->scalar_type() == at::kFloat8_e4m3fn;
+    if (zp && !f8z) return false;
+    const int64_t rows = w->size(0), cols = w->size(1);
+    const int64_t group = q8_group(rows, cols, *scale, zp, w->scalar_type(), w->device(), 2, 32, f8z);
+    if (group != 32 || !staying_entries_are_final(e, {N.weight, N.weight_scale}, dropmask)) return false;
+    at::Tensor out = at::empty({rows, cols}, w->options().dtype(at::kFloat8_e4m3fn));
+    at::Tensor codes = at::empty(scale->sizes(), scale->options().dtype(at::kByte));
+    Batch& b = sink.at(*w, q8_code(w->scalar_type(), f8z ? 2 : 1, 8));
+    b.row(item_row(w->data_ptr(), scale->data_ptr(), data_or_null(zp), out.data_ptr(), rows, cols, group));
+    b.aux_row(item_row(scale->data_ptr(), nullptr, nullptr, codes.data_ptr(), scale->numel(), 1, 0));
+    // (module, codes, scale codes, drop mask, keep-alive weight, keep-alive scale, keep-alive zero point or None)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), wrap(codes), dropmask, entry_ref(e, N.weight), entry_ref(e, N.weight_scale),
+                                 zp ? entry_ref(e, N.weight_zero_point) : py::none()));
+    return true;
 }
 
-py::tuple mx8_plan_decompress(py::list modules) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        Entries e;
-        bool ok = plain_type(m) && e.open(m);
-        const at::Tensor *q = nullptr, *codes = nullptr;
-        int64_t rows = 0, cols = 0;
-        if (ok) {
-            q = e.tensor(N.weight);
-            codes = e.tensor(N.weight_scale);
-            ok = q && codes && !e.has(N.weight_g_idx) && !e.has(N.weight_zero_point) && q->dim() == 2 && q->scalar_type() == at::kFloat8_e4m3fn &&
-                 (q->is_cuda() || g_allow_cpu) && q->is_contiguous() && aligned16(*q) && codes->scalar_type() == at::kByte && codes->device() == q->device() &&
-                 codes->is_contiguous() && codes->dim() == 2;
-        }
-        if (ok) {
-            rows = q->size(0);
-            cols = q->size(1);
-            ok = rows > 0 && cols % 32 == 0 && codes->size(0) == rows && codes->size(1) == cols / 32 && cols / 32 > 1 && staying_entries_are_final(e, {N.weight, N.weight_scale});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor scale = at::empty(codes->sizes(), codes->options().dtype(at::kBFloat16));  // decompress_mx_scale: bfloat16, and so is the weight (mxfp8/base.py:74-101)
-        at::Tensor out = at::empty({rows, cols}, scale.options());
-        Batch& b = batches[{q->is_cuda() ? (int)q->device().index() : -1, 2 | (1 << 4) | (8 << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)q->data_ptr(), (int64_t)(uintptr_t)scale.data_ptr(), 0, (int64_t)(uintptr_t)out.data_ptr(), rows, cols, 32,
-                                          0, 0, 0, 0, 0, 0};
-        const int64_t sitem[kItemWords] = {(int64_t)(uintptr_t)codes->data_ptr(), 0, 0, (int64_t)(uintptr_t)scale.data_ptr(), codes->numel(), 1, 0, 0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.zp_words.insert(b.zp_words.end(), sitem, sitem + kItemWords);
-        b.n += 1;
-        b.zp_n += 1;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)),
-                                     py::reinterpret_steal<py::object>(THPVariable_Wrap(scale)), 0, py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_scale)), py::none()));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+bool mx8_take_decompress(PyObject* m, int64_t, Entries& e, Sink& sink) {
+    const at::Tensor *q = e.tensor(N.weight), *codes = e.tensor(N.weight_scale);
+    if (!(q && codes && !e.has(N.weight_g_idx) && !e.has(N.weight_zero_point) && dense_source(*q) && q->scalar_type() == at::kFloat8_e4m3fn &&
+          codes->scalar_type() == at::kByte && codes->device() == q->device() && codes->is_contiguous() && codes->dim() == 2))
+        return false;
+    const int64_t rows = q->size(0), cols = q->size(1);
+    // (cols / 32 > 1: only this loop asks it — a single group per row is left to the Python path)
+    if (!(rows > 0 && cols % 32 == 0 && codes->size(0) == rows && codes->size(1) == cols / 32 && cols / 32 > 1 && staying_entries_are_final(e, {N.weight, N.weight_scale})))
+        return false;
+    at::Tensor scale = at::empty(codes->sizes(), codes->options().dtype(at::kBFloat16));  // decompress_mx_scale: bfloat16, and so is the weight (mxfp8/base.py:74-101)
+    at::Tensor out = at::empty({rows, cols}, scale.options());
+    Batch& b = sink.at(*q, q8_code(at::kBFloat16, 1, 8));
+    b.row(item_row(q->data_ptr(), scale.data_ptr(), nullptr, out.data_ptr(), rows, cols, 32));
+    b.aux_row(item_row(codes->data_ptr(), nullptr, nullptr, scale.data_ptr(), codes->numel(), 1, 0));
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), wrap(scale), 0, entry_ref(e, N.weight), entry_ref(e, N.weight_scale), py::none()));
+    return true;
 }
 
 // the scale is replaced where it is, `weight` is re-added last (mxfp8/base.py: the naive codec pops and re-adds it, the scale is assigned to its existing key)
 void mx8_finish(py::list jobs, py::object status) {
-    touch_tls();
-    const Py_ssize_t n = PyList_GET_SIZE(jobs.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* job = PyList_GET_ITEM(jobs.ptr(), i);
-        PyObject* m = PyTuple_GET_ITEM(job, 0);
-        const at::Tensor& out = THPVariable_Unpack(PyTuple_GET_ITEM(job, 1));
-        const at::Tensor& sc = THPVariable_Unpack(PyTuple_GET_ITEM(job, 2));
-        const long dropmask = PyLong_AsLong(PyTuple_GET_ITEM(job, 3));
-        Entries e;
-        if (!e.open(m)) throw std::runtime_error("module lost its _parameters");
-        if (dropmask & 1) drop(e.params, N.weight_zero_point);
-        if (dropmask & 2) drop(e.params, g_input_zero_point);
-        if (dropmask & 4) drop(e.params, g_output_zero_point);
-        PyDict_SetItem(e.params, N.weight_scale, make_parameter(sc).ptr());
+    finish_jobs(jobs, status.ptr(), [](PyObject* job, Entries& e) {
+        drop_zero_points(e, PyLong_AsLong(PyTuple_GET_ITEM(job, 3)));
+        set_entry(e, N.weight_scale, job_tensor(job, 2));
         drop(e.params, N.weight);
-        PyDict_SetItem(e.params, N.weight, make_parameter(out).ptr());
-        set_status(m, status.ptr());
-    }
+        set_entry(e, N.weight, job_tensor(job, 1));
+    });
 }
 
 // pack-quantized with num_bits = 8 and a symmetric weights-only scheme (the W8A16 preset; reference compressors/pack_quantized/base.py:62-163): the codes are
 // the 8-bit tables' kind 3 (int8 + 128, four to an int32 word = pack_to_int32), the entries are the W4 ones (weight -> weight_packed + weight_shape), so the
-// jobs go to w4_finish_compress / w4_finish_decompress.  infos[i]: group_size | strategy << 25 (0 tensor, 1 channel, 2 group), or < 0.
-// batch key: (device index, dtype code | 3 << 4 | 8 << 8), as the 8-bit tables.
-py::tuple w8_plan_compress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        Entries e;
-        bool ok = info >= 0 && plain_type(m) && e.open(m) && !dict_has(m, N.weight_packed) && !dict_has(m, N.weight_shape);
-        const at::Tensor *w = nullptr, *scale = nullptr, *zp = nullptr;
-        int64_t group = 0;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            zp = e.tensor(N.weight_zero_point);
-            // (a `weight_shape` left by an earlier decompress is overwritten in place, as in the W4 loop)
-            ok = w && scale && !e.has(N.weight_g_idx) && (zp != nullptr || !e.has(N.weight_zero_point)) && !e.has(N.weight_packed) && w->dim() == 2 &&
-                 (w->is_cuda() || g_allow_cpu) && w->is_contiguous() && aligned16(*w) && w->size(1) % 32 == 0;
-        }
-        if (ok) {
-            group = q8_group(w->size(0), w->size(1), *scale, zp, w->scalar_type(), w->device(), (int)((info >> 25) & 3), info & 0xfffff, false);
-            ok = group > 0 && staying_entries_are_final(e, {N.weight, N.weight_zero_point});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        const int64_t rows = w->size(0), cols = w->size(1);
-        at::Tensor packed = at::empty({rows, cols / 4}, w->options().dtype(at::kInt));
-        Batch& b = batches[{w->is_cuda() ? (int)w->device().index() : -1, (w->scalar_type() == at::kHalf ? 1 : 2) | (3 << 4) | (8 << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)w->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), zp ? (int64_t)(uintptr_t)zp->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)packed.data_ptr(), rows, cols, group, 0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        PyObject* zp_obj = zp ? PyDict_GetItem(e.params, N.weight_zero_point) : Py_None;
-        // w4_finish_compress's job: (module, packed, rows, cols, keep-alive weight, zp_packed = None: the symmetric scheme's zero point is dropped, keep-alive zp)
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(packed)), rows, cols,
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)), py::none(), py::reinterpret_borrow<py::object>(zp_obj)));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+// jobs have the W4 jobs' layout and go to w4_finish_compress / w4_finish_decompress.  infos[i]: group_size | strategy << 25 (0 tensor, 1 channel, 2 group), or < 0.
+bool w8_take_compress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    if (info < 0 || dict_has(m, N.weight_packed) || dict_has(m, N.weight_shape)) return false;
+    const Q8Entries q(e);
+    // (a `weight_shape` left by an earlier decompress is overwritten in place, as in the W4 loop)
+    if (!(q.ok && !e.has(N.weight_packed) && q.w->size(1) % 32 == 0)) return false;
+    const at::Tensor *w = q.w, *zp = q.zp;
+    const int64_t rows = w->size(0), cols = w->size(1);
+    const int64_t group = q8_group(rows, cols, *q.scale, zp, w->scalar_type(), w->device(), (int)((info >> 25) & 3), info & 0xfffff, false);
+    if (!(group > 0 && staying_entries_are_final(e, {N.weight, N.weight_zero_point}))) return false;
+    at::Tensor packed = at::empty({rows, cols / 4}, w->options().dtype(at::kInt));
+    Batch& b = sink.at(*w, q8_code(w->scalar_type(), 3, 8));
+    b.row(item_row(w->data_ptr(), q.scale->data_ptr(), data_or_null(zp), packed.data_ptr(), rows, cols, group));
+    // w4_finish_compress's job: (module, packed, rows, cols, keep-alive weight, zp_packed = None: the symmetric scheme's zero point is dropped, keep-alive zp)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(packed), rows, cols, entry_ref(e, N.weight), py::none(), zp ? entry_ref(e, N.weight_zero_point) : py::none()));
+    return true;
 }
 
-py::tuple w8_plan_decompress(py::list modules, py::object infos_arg) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        Entries e;
-        bool ok = info >= 0 && plain_type(m) && e.open(m) && !dict_has(m, N.weight);
-        const at::Tensor *packed = nullptr, *scale = nullptr, *shape_t = nullptr;
-        int64_t rows = 0, cols = 0, group = 0;
-        if (ok) {
-            packed = e.tensor(N.weight_packed);
-            scale = e.tensor(N.weight_scale);
-            shape_t = e.tensor(N.weight_shape);
-            ok = packed && scale && shape_t && !e.has(N.weight_g_idx) && !e.has(N.weight_zero_point) && !e.has(N.weight) && (packed->is_cuda() || g_allow_cpu) &&
-                 packed->is_contiguous() && packed->scalar_type() == at::kInt && aligned16(*packed) && packed->dim() == 2 && shape_t->device().is_cpu() &&
-                 shape_t->scalar_type() == at::kLong && shape_t->numel() == 2 && shape_t->is_contiguous();
-        }
-        if (ok) {
-            rows = shape_t->data_ptr<int64_t>()[0];
-            cols = shape_t->data_ptr<int64_t>()[1];
-            ok = rows > 0 && cols > 0 && cols % 32 == 0 && packed->size(0) == rows && packed->size(1) == cols / 4;
-        }
-        if (ok) {
-            // the layout is read off the scale's shape, as upstream's argument-free dequantize call does (pack_quantized/base.py:156-161, forward.py:99-130)
-            group = q8_group(rows, cols, *scale, nullptr, scale->scalar_type(), packed->device(), -1, 0, false);
-            ok = group != 0 && staying_entries_are_final(e, {N.weight_packed});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor out = at::empty({rows, cols}, scale->options());
-        Batch& b = batches[{packed->is_cuda() ? (int)packed->device().index() : -1, (scale->scalar_type() == at::kHalf ? 1 : 2) | (3 << 4) | (8 << 8)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)packed->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), 0, (int64_t)(uintptr_t)out.data_ptr(), rows, cols, group,
-                                          0, 0, 0, 0, 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        // w4_finish_decompress's job: (module, out, keep-alive packed, zp = None, -)
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_packed)), py::none(), py::none()));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+bool w8_take_decompress(PyObject* m, int64_t info, Entries& e, Sink& sink) {
+    if (info < 0 || dict_has(m, N.weight)) return false;
+    const at::Tensor *packed = e.tensor(N.weight_packed), *scale = e.tensor(N.weight_scale);
+    int64_t rows = 0, cols = 0;
+    if (!(packed && scale && !e.has(N.weight_g_idx) && !e.has(N.weight_zero_point) && !e.has(N.weight) && dense_source(*packed) && packed->scalar_type() == at::kInt &&
+          stored_shape(e.tensor(N.weight_shape), rows, cols)))
+        return false;
+    if (!(cols % 32 == 0 && packed->size(0) == rows && packed->size(1) == cols / 4)) return false;
+    // the layout is read off the scale's shape, as upstream's argument-free dequantize call does (pack_quantized/base.py:156-161, forward.py:99-130)
+    const int64_t group = q8_group(rows, cols, *scale, nullptr, scale->scalar_type(), packed->device(), -1, 0, false);
+    if (group == 0 || !staying_entries_are_final(e, {N.weight_packed})) return false;
+    at::Tensor out = at::empty({rows, cols}, scale->options());
+    Batch& b = sink.at(*packed, q8_code(scale->scalar_type(), 3, 8));
+    b.row(item_row(packed->data_ptr(), scale->data_ptr(), nullptr, out.data_ptr(), rows, cols, group));
+    // w4_finish_decompress's job: (module, out, keep-alive packed, zp = None, -)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), entry_ref(e, N.weight_packed), py::none(), py::none()));
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1468,140 +1294,91 @@ py::tuple w8_plan_decompress(py::list modules, py::object infos_arg) {
 // weight_scale (and a symmetric scheme's zero points) leave, weight_packed and the stored weight_scale arrive — resp. the other way round.  The interpreter
 // spent 14 us per module and direction on this with one launch per module (a TinyLlama-shaped NVFP4 tree ran at 0.13 of the HBM peak, an 8B-shaped one at 0.58).
 // compress infos[i]: 1 | drop mask << 1 (weight / input / output zero point of a symmetric scheme) when the scheme stores its scale in the format's usual
-// dtype; else 0.  batch key: (device index, weights' dtype code | scales' dtype code << 4) — dtype codes as `dtype_code` below.
+// dtype; else 0.  batch key code: weights' dtype code | scales' dtype code << 4 (`dtype_code`); 0 on the way back (the outputs are bfloat16).
 // ------------------------------------------------------------------------------------------
-PyObject* g_weight_global_scale = nullptr;
-
 // the global scale as the kernel takes it: one float32 on the tensor's device (codec._gs_fast's no-op case)
-inline bool plain_gs(const at::Tensor& g, const at::Device& dev) {
-    return g.scalar_type() == at::kFloat && g.numel() == 1 && g.device() == dev && (reinterpret_cast<uintptr_t>(g.data_ptr()) & 3u) == 0;
+inline bool plain_gs(const at::Tensor& g, const at::Device& dev) { return g.scalar_type() == at::kFloat && g.numel() == 1 && g.device() == dev && aligned(g, 4); }
+
+// NVFP4 (group 16) has a global scale entry and it is the plain one; MXFP4 has none at all
+inline bool fp4_global_scale_ok(const Entries& e, const at::Tensor* gs, int64_t group, const at::Device& dev) {
+    return (gs != nullptr) == (group == 16) && tensor_or_absent(e, gs, g_weight_global_scale) && (!gs || plain_gs(*gs, dev));
 }
 
-py::tuple fp4_plan_compress(py::list modules, py::object infos_arg, int64_t group) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    Infos infos(infos_arg.ptr());
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        const int64_t info = infos.of(m, i);
-        const int dropmask = (int)((info >> 1) & 7);
-        Entries e;
-        bool ok = info > 0 && (info & 1) && plain_type(m) && e.open(m) && !dict_has(m, N.weight_packed);
-        const at::Tensor *w = nullptr, *scale = nullptr, *gs = nullptr;
-        if (ok) {
-            w = e.tensor(N.weight);
-            scale = e.tensor(N.weight_scale);
-            gs = e.tensor(g_weight_global_scale);
-            // (a zero point entry: dropped for a symmetric scheme; present under an asymmetric one the Python path raises)
-            ok = w && scale && (gs != nullptr) == (group == 16) && (gs != nullptr || !e.has(g_weight_global_scale)) && !e.has(N.weight_packed) && w->dim() == 2 &&
-                 half_type(w->scalar_type()) && (w->is_cuda() || g_allow_cpu) && w->is_contiguous() && aligned16(*w) && scale->device() == w->device() &&
-                 scale->is_contiguous() && (reinterpret_cast<uintptr_t>(scale->data_ptr()) & 7u) == 0 &&
-                 (half_type(scale->scalar_type()) || (group == 16 && scale->scalar_type() == at::kFloat)) && (!gs || plain_gs(*gs, w->device())) &&
-                 (e.tensor(N.weight_zero_point) == nullptr || (dropmask & 1));
-        }
-        int64_t rows = 0, cols = 0;
-        if (ok) {
-            rows = w->size(0);
-            cols = w->size(1);
-            ok = rows > 0 && cols % group == 0 && (rows * cols) % 32 == 0 && scale->dim() == 2 && scale->size(0) == rows && scale->size(1) == cols / group &&
-                 staying_entries_are_final(e, {N.weight, N.weight_scale, (dropmask & 1) ? N.weight_zero_point : N.weight, (dropmask & 2) ? g_input_zero_point : N.weight,
-                                               (dropmask & 4) ? g_output_zero_point : N.weight});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor packed = at::empty({rows, cols / 2}, w->options().dtype(at::kByte));
-        at::Tensor stored = at::empty({rows, cols / group}, w->options().dtype(group == 16 ? at::kFloat8_e4m3fn : at::kByte));
-        const int wcode = w->scalar_type() == at::kHalf ? 1 : 2, scode = scale->scalar_type() == at::kFloat ? 0 : scale->scalar_type() == at::kHalf ? 1 : 2;
-        Batch& b = batches[{w->is_cuda() ? (int)w->device().index() : -1, wcode | (scode << 4)}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)w->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), gs ? (int64_t)(uintptr_t)gs->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)packed.data_ptr(), rows, cols, group, 0, 0, 0, (int64_t)(uintptr_t)stored.data_ptr(), 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        // the job keeps the inputs alive until the launch has been issued (the table holds raw pointers)
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(packed)),
-                                     py::reinterpret_steal<py::object>(THPVariable_Wrap(stored)), dropmask, py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_scale))));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+bool fp4_take_compress(PyObject* m, int64_t info, Entries& e, Sink& sink, int64_t group) {
+    const int dropmask = (int)((info >> 1) & 7);
+    if (!(info > 0 && (info & 1)) || dict_has(m, N.weight_packed)) return false;
+    const at::Tensor *w = e.tensor(N.weight), *scale = e.tensor(N.weight_scale), *gs = e.tensor(g_weight_global_scale);
+    // (the kernel loads four 16-bit / two float32 scales at once: 8-byte aligned, not 16.  A zero point entry: dropped for a symmetric scheme; present under
+    // an asymmetric one the Python path raises)
+    if (!(w && scale && !e.has(N.weight_packed) && dense_source(*w) && half_type(w->scalar_type()) && fp4_global_scale_ok(e, gs, group, w->device()) &&
+          scale->device() == w->device() && scale->is_contiguous() && aligned(*scale, 8) &&
+          (half_type(scale->scalar_type()) || (group == 16 && scale->scalar_type() == at::kFloat)) && (e.tensor(N.weight_zero_point) == nullptr || (dropmask & 1))))
+        return false;
+    const int64_t rows = w->size(0), cols = w->size(1);
+    if (!(rows > 0 && cols % group == 0 && (rows * cols) % 32 == 0 && scale->dim() == 2 && scale->size(0) == rows && scale->size(1) == cols / group &&
+          staying_entries_are_final(e, {N.weight, N.weight_scale}, dropmask)))
+        return false;
+    at::Tensor packed = at::empty({rows, cols / 2}, w->options().dtype(at::kByte));
+    at::Tensor stored = at::empty({rows, cols / group}, w->options().dtype(group == 16 ? at::kFloat8_e4m3fn : at::kByte));
+    Batch& b = sink.at(*w, half_code(w->scalar_type()) | (dtype_code(scale->scalar_type()) << 4));
+    b.row(item_row(w->data_ptr(), scale->data_ptr(), data_or_null(gs), packed.data_ptr(), rows, cols, group, stored.data_ptr()));
+    // (module, packed bytes, stored scale, drop mask, keep-alive weight, keep-alive scale)
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(packed), wrap(stored), dropmask, entry_ref(e, N.weight), entry_ref(e, N.weight_scale)));
+    return true;
 }
 
-py::tuple fp4_plan_decompress(py::list modules, int64_t group) {
-    touch_tls();
-    std::map<std::pair<int, int>, Batch> batches;
-    py::list rest;
-    const Py_ssize_t n = PyList_GET_SIZE(modules.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* m = PyList_GET_ITEM(modules.ptr(), i);
-        Entries e;
-        bool ok = plain_type(m) && e.open(m) && !dict_has(m, N.weight);
-        const at::Tensor *packed = nullptr, *scale = nullptr, *gs = nullptr;
-        if (ok) {
-            packed = e.tensor(N.weight_packed);
-            scale = e.tensor(N.weight_scale);
-            gs = e.tensor(g_weight_global_scale);
-            ok = packed && scale && (gs != nullptr) == (group == 16) && (gs != nullptr || !e.has(g_weight_global_scale)) && !e.has(N.weight) &&
-                 packed->scalar_type() == at::kByte && packed->dim() == 2 && (packed->is_cuda() || g_allow_cpu) && packed->is_contiguous() &&
-                 (reinterpret_cast<uintptr_t>(packed->data_ptr()) & 3u) == 0 && scale->device() == packed->device() && scale->is_contiguous() &&
-                 scale->scalar_type() == (group == 16 ? at::kFloat8_e4m3fn : at::kByte) && (!gs || plain_gs(*gs, packed->device()));
-        }
-        int64_t rows = 0, cols = 0;
-        if (ok) {
-            rows = packed->size(0);
-            cols = packed->size(1) * 2;
-            ok = rows > 0 && cols > 0 && cols % group == 0 && (rows * cols) % 32 == 0 && scale->dim() == 2 && scale->size(0) == rows && scale->size(1) == cols / group &&
-                 staying_entries_are_final(e, {N.weight_packed, N.weight_scale});
-        }
-        if (!ok) {
-            rest.append(py::reinterpret_borrow<py::object>(m));
-            continue;
-        }
-        at::Tensor out = at::empty({rows, cols}, packed->options().dtype(at::kBFloat16));  // unpack_fp4_from_uint8's default dtype (nvfp4/base.py:118-131)
-        at::Tensor sout = at::empty({rows, cols / group}, packed->options().dtype(at::kBFloat16));
-        Batch& b = batches[{packed->is_cuda() ? (int)packed->device().index() : -1, 0}];
-        const int64_t item[kItemWords] = {(int64_t)(uintptr_t)packed->data_ptr(), (int64_t)(uintptr_t)scale->data_ptr(), gs ? (int64_t)(uintptr_t)gs->data_ptr() : 0,
-                                          (int64_t)(uintptr_t)out.data_ptr(), rows, cols, group, 0, 0, 0, (int64_t)(uintptr_t)sout.data_ptr(), 0, 0};
-        b.words.insert(b.words.end(), item, item + kItemWords);
-        b.n += 1;
-        b.jobs.append(py::make_tuple(py::reinterpret_borrow<py::object>(m), py::reinterpret_steal<py::object>(THPVariable_Wrap(out)),
-                                     py::reinterpret_steal<py::object>(THPVariable_Wrap(sout)), 0, py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_packed)),
-                                     py::reinterpret_borrow<py::object>(PyDict_GetItem(e.params, N.weight_scale))));
-    }
-    return py::make_tuple(batches_to_python(batches), rest);
+bool fp4_take_decompress(PyObject* m, int64_t, Entries& e, Sink& sink, int64_t group) {
+    if (dict_has(m, N.weight)) return false;
+    const at::Tensor *packed = e.tensor(N.weight_packed), *scale = e.tensor(N.weight_scale), *gs = e.tensor(g_weight_global_scale);
+    // (packed bytes: the kernel loads 4-byte words of them, not 16-byte units)
+    if (!(packed && scale && !e.has(N.weight) && dense_source(*packed, 4) && packed->scalar_type() == at::kByte && fp4_global_scale_ok(e, gs, group, packed->device()) &&
+          scale->device() == packed->device() && scale->is_contiguous() && scale->scalar_type() == (group == 16 ? at::kFloat8_e4m3fn : at::kByte)))
+        return false;
+    const int64_t rows = packed->size(0), cols = packed->size(1) * 2;
+    if (!(rows > 0 && cols > 0 && cols % group == 0 && (rows * cols) % 32 == 0 && scale->dim() == 2 && scale->size(0) == rows && scale->size(1) == cols / group &&
+          staying_entries_are_final(e, {N.weight_packed, N.weight_scale})))
+        return false;
+    at::Tensor out = at::empty({rows, cols}, packed->options().dtype(at::kBFloat16));  // unpack_fp4_from_uint8's default dtype (nvfp4/base.py:118-131)
+    at::Tensor sout = at::empty({rows, cols / group}, packed->options().dtype(at::kBFloat16));
+    Batch& b = sink.at(*packed, 0);
+    b.row(item_row(packed->data_ptr(), scale->data_ptr(), data_or_null(gs), out.data_ptr(), rows, cols, group, sout.data_ptr()));
+    b.jobs.append(py::make_tuple(borrowed(m), wrap(out), wrap(sout), 0, entry_ref(e, N.weight_packed), entry_ref(e, N.weight_scale)));
+    return true;
 }
 
-// after the launch; the entries arrive in the order swap_direct_entries leaves them: (weight_packed, weight_scale) resp. (weight_scale, weight)
+// the entries arrive in the order swap_direct_entries leaves them: (weight_packed, weight_scale) resp. (weight_scale, weight)
 void fp4_finish(py::list jobs, py::object status, bool compress) {
-    touch_tls();
-    const Py_ssize_t n = PyList_GET_SIZE(jobs.ptr());
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject* job = PyList_GET_ITEM(jobs.ptr(), i);
-        PyObject* m = PyTuple_GET_ITEM(job, 0);
-        const at::Tensor& a = THPVariable_Unpack(PyTuple_GET_ITEM(job, 1));  // packed bytes / dense weight
-        const at::Tensor& sc = THPVariable_Unpack(PyTuple_GET_ITEM(job, 2));
-        const long dropmask = PyLong_AsLong(PyTuple_GET_ITEM(job, 3));
-        Entries e;
-        if (!e.open(m)) throw std::runtime_error("module lost its _parameters");
+    finish_jobs(jobs, status.ptr(), [compress](PyObject* job, Entries& e) {
+        const at::Tensor &a = job_tensor(job, 1), &sc = job_tensor(job, 2);  // a: packed bytes / dense weight
+        drop(e.params, compress ? N.weight : N.weight_packed);
+        drop(e.params, N.weight_scale);
         if (compress) {
-            drop(e.params, N.weight);
-            drop(e.params, N.weight_scale);
-            if (dropmask & 1) drop(e.params, N.weight_zero_point);
-            if (dropmask & 2) drop(e.params, g_input_zero_point);
-            if (dropmask & 4) drop(e.params, g_output_zero_point);
-            PyDict_SetItem(e.params, N.weight_packed, make_parameter(a).ptr());
-            PyDict_SetItem(e.params, N.weight_scale, make_parameter(sc).ptr());
+            drop_zero_points(e, PyLong_AsLong(PyTuple_GET_ITEM(job, 3)));
+            set_entry(e, N.weight_packed, a);
+            set_entry(e, N.weight_scale, sc);
         } else {
-            drop(e.params, N.weight_packed);
-            drop(e.params, N.weight_scale);
-            PyDict_SetItem(e.params, N.weight_scale, make_parameter(sc).ptr());
-            PyDict_SetItem(e.params, N.weight, make_parameter(a).ptr());
+            set_entry(e, N.weight_scale, sc);
+            set_entry(e, N.weight, a);
         }
-        set_status(m, status.ptr());
-    }
+    });
 }
+
+// the Python-visible plan entries: names, arguments and return shapes as the compressors call them (compressors/*/base.py through run_planned)
+py::tuple w4_plan_compress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), w4_take_compress); }
+py::tuple w4_plan_decompress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), w4_take_decompress); }
+py::tuple q8_plan_compress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), q8_take_compress); }
+py::tuple q8_plan_decompress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), q8_take_decompress); }
+py::tuple mx8_plan_compress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), mx8_take_compress); }
+py::tuple mx8_plan_decompress(py::list modules) { return plan_modules(modules, nullptr, mx8_take_decompress); }
+py::tuple w8_plan_compress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), w8_take_compress); }
+py::tuple w8_plan_decompress(py::list modules, py::object infos) { return plan_modules(modules, infos.ptr(), w8_take_decompress); }
+py::tuple fp4_plan_compress(py::list modules, py::object infos, int64_t group) {
+    return plan_modules(modules, infos.ptr(), [group](PyObject* m, int64_t info, Entries& e, Sink& sink) { return fp4_take_compress(m, info, e, sink, group); });
+}
+py::tuple fp4_plan_decompress(py::list modules, int64_t group) {
+    return plan_modules(modules, nullptr, [group](PyObject* m, int64_t info, Entries& e, Sink& sink) { return fp4_take_decompress(m, info, e, sink, group); });
+}
+
 
 // Marlin24Compressor.compress for an int4 scheme outside a deferred-check context, from the popped state-dict entries on: the layout tests
 // of the one-launch path (compressors/sparse/marlin_24.py, same conditions), then marlin24_w4_full.  `group_size`: the scheme's, 0 for a
@@ -1633,6 +1410,9 @@ py::object marlin24_compress_default(const at::Tensor& weight, const at::Tensor&
 PYBIND11_MODULE(_hostpath, mod) {
     touch_tls();
     N.init();
+    g_input_zero_point = PyUnicode_InternFromString("input_zero_point");
+    g_output_zero_point = PyUnicode_InternFromString("output_zero_point");
+    g_weight_global_scale = PyUnicode_InternFromString("weight_global_scale");
     py::module_ torch_mod = py::module_::import("torch");
     g_make_subclass = py::object(torch_mod.attr("Tensor").attr("_make_subclass")).release().ptr();
     g_parameter_cls = py::object(torch_mod.attr("nn").attr("Parameter")).release().ptr();
@@ -1642,9 +1422,6 @@ PYBIND11_MODULE(_hostpath, mod) {
     mod.def("w4_finish_compress", &w4_finish_compress);
     mod.def("w4_plan_decompress", &w4_plan_decompress);
     mod.def("w4_finish_decompress", &w4_finish_decompress);
-    g_input_zero_point = PyUnicode_InternFromString("input_zero_point");
-    g_output_zero_point = PyUnicode_InternFromString("output_zero_point");
-    g_weight_global_scale = PyUnicode_InternFromString("weight_global_scale");
     mod.def("fp4_plan_compress", &fp4_plan_compress);
     mod.def("fp4_plan_decompress", &fp4_plan_decompress);
     mod.def("fp4_finish", &fp4_finish);
@@ -1670,3 +1447,4 @@ PYBIND11_MODULE(_hostpath, mod) {
     mod.def("set_wait_mode", [](int v) { g_wait_mode = v; });
     mod.attr("ITEM_WORDS") = kItemWords;
 }
+
