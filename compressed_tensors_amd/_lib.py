@@ -146,6 +146,8 @@ _PROTOTYPES = {
     "ct_awq_repack_batch": ([_P, _I, _L, _S], _I),
     "ct_fp8block_dequant_plan": ([_P, _I], _L),
     "ct_fp8block_dequant_batch": ([_P, _I, _L, _I, _S], _I),
+    "ct_fp8block_mxfp4_plan": ([_P, _I], _L),
+    "ct_fp8block_mxfp4_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_bitmask_row_popcount": ([_P, _L, _L, _P, _S], _I),
     "ct_sparse24_compress": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_sparse24_mask": ([_P, _I, _L, _P, _S], _I),
@@ -202,6 +204,16 @@ class Fp8BlockItem(ctypes.Structure):
     _fields_ = [("w", _P), ("scale", _P), ("out", _P), ("rows", _L), ("cols", _L), ("block_h", _L), ("block_w", _L),
                 ("scale_shape", _L * 2), ("sdt", _c.c_int32), ("fast", _c.c_int32), ("scale_stride", _L * 2), ("units_per_row", _L),
                 ("first_block", _L)]
+
+
+class Fp8BlockMxItem(ctypes.Structure):
+    """struct ct_fp8block_mx_item of include/ct_hip.h (a row of ct_fp8block_mxfp4_batch's table)"""
+    _fields_ = [("w", _P), ("scale", _P), ("packed", _P), ("e8m0", _P), ("rows", _L), ("cols", _L), ("block_h", _L), ("block_w", _L),
+                ("scale_shape", _L * 2), ("sdt", _c.c_int32), ("reserved", _c.c_int32), ("scale_stride", _L * 2), ("units_per_row", _L),
+                ("units", _L), ("first_block", _L)]
+
+
+FP8BLOCK_MX_GROUPS_PER_BLOCK = 512  # CT_FP8BLOCK_MX_GROUPS_PER_BLOCK of include/ct_hip.h
 
 
 class AttnTensor(ctypes.Structure):

@@ -140,6 +140,9 @@ __all__ = [
     "rtn_block8_launch",
     "rtn_group8_launch",
     "rtn_channel8_launch",
+    "rtn_mxfp4_outputs",
+    "rtn_mxfp4_launch",
+    "fp8block_to_mxfp4",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -1926,6 +1929,26 @@ def rtn_mxfp4_quantize_and_pack(x: torch.Tensor, *, return_scale: bool = False):
     return _home(packed, x), _home(code, x)
 
 
+def fp8block_to_mxfp4(weight: torch.Tensor, weight_scale_inv: torch.Tensor, *, weight_block_size=(128, 128), dtype: torch.dtype = torch.bfloat16):
+    """An FP8 block-quantized weight (float8_e4m3fn (R, C), `weight_scale_inv` per block of `weight_block_size` or a torch broadcast of it) straight to
+    MXFP4: (packed uint8 (R, C / 2), E8M0 codes uint8 (R, C / 32)), byte for byte `rtn_mxfp4_quantize_and_pack` of the weight dequantized to `dtype`
+    (bfloat16 or float16), which is never materialised (`ct_fp8block_mxfp4_batch`; a block width that is no multiple of 32 takes the two launches).
+    Host tensors in, host tensors out; device tensors stay on their device."""
+    from .entrypoints.convert import fp8block_mxfp4 as fx
+
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"fp8block_to_mxfp4: dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    block = fx._block_size("fp8block_to_mxfp4", weight_block_size)
+    fx._check_module("weight", weight, weight_scale_inv)
+    if weight.shape[1] % 32 != 0:
+        raise ValueError(f"tensor column shape must be divisble by the given group_size 32 but got {weight.shape[1]}")
+    on_device = weight.device.type == "cuda"
+    got = fx.ReadyDict()
+    fx.transcode(got, ["w"], [(weight, weight_scale_inv)], block, dtype, weight.device if on_device else _lib.require_device(), True, to_host=not on_device)
+    got.wait()
+    return got["w.weight_packed"], got["w.weight_scale"]
+
+
 def rtn_nvfp4_quantize_and_pack(x: torch.Tensor, global_scale: Optional[torch.Tensor] = None, *, return_scale: bool = False):
     """Round-to-nearest NVFP4 compress (groups of 16): generate_gparam of the weight unless `global_scale` is given, then ONE
     pass: min-max observer + calculate_qparams (float8 scales under the global scale) + quantize + cast_to_fp4 + pack.
@@ -2396,6 +2419,11 @@ def rtn_channel8_launch(dtype: torch.dtype, fp8: bool, symmetric: bool) -> tuple
     return "rtn_channel8", 0, (DT[dtype], int(bool(fp8)), int(bool(symmetric)))
 
 
+def rtn_mxfp4_launch(dtype: torch.dtype) -> tuple:
+    """`rtn_w4_launch` for the one-pass MXFP4 table"""
+    return "rtn_mxfp4", 0, (DT[dtype],)
+
+
 def _launch_rtn(words, n: int, device, launch, *args):
     """one launch of a one-pass table under `launch(*args)`'s (kind, d, scalars); an empty table returns None before anything about it is looked at"""
     if not n:
@@ -2510,6 +2538,11 @@ def rtn_group8_outputs(rows: int, cols: int, dtype, group: int, qtype: str = "in
     if with_zp and not fp8:
         out.append(("zp", grid, torch.int8))
     return out + [("zp_packed", grid, torch.uint8)] if mx else out
+
+
+def rtn_mxfp4_outputs(rows: int, cols: int) -> list:
+    """the one-pass MXFP4 table: packed nibbles uint8 (R, C / 2) and, in the row's `zp_packed`, the E8M0 codes uint8 (R, C / 32)"""
+    return [("dst", (rows, cols // 2), torch.uint8), ("zp_packed", (rows, cols // 32), torch.uint8)]
 
 
 def _rtn_item(x, group: int, entries, fields=("dst", "scale", "zp")) -> tuple:

@@ -18,6 +18,7 @@
 // +-6) and v_cvt_scalef32_pk_f32_fp4 back; both are checked against the oracle over every bf16 input on the device
 // (tests/test_gpu_parity.py).  -0.0 inputs are folded to +0.0 with one add before the conversion.
 #include "ct_common.h"
+#include "ct_fp8block.h"
 #include "ct_minmax.h"
 #include "ct_plan.h"
 
@@ -324,6 +325,116 @@ __global__ __launch_bounds__(kBlock) void rtn_mxfp4_batch_kernel(const ct_w4_ite
     const int64_t l = ((int64_t)blockIdx.x - it.first_block) * kBlock + threadIdx.x;
     if (l >= (it.units >> 2)) return;
     rtn_mxfp4_lane<XDT>(static_cast<const u32x4*>(it.src), static_cast<u32x4*>(it.dst), static_cast<uint8_t*>(it.zp_packed), const_cast<void*>(it.scale), l);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// FP8 block-quantized weights -> MXFP4 in ONE pass over a table (ct_fp8block_mxfp4_batch): the element of ct_fp8block.hip, rounded to the dense
+// dtype XDT in registers, then rtn_mxfp4_lane's arithmetic on those bits — byte for byte the two launches, 1 + 0.5 + 1/32 B per element instead of
+// (1 + 2) + (2 + 0.5 + 1/32).
+// Work unit: one MX group (32 codes of one row; cols % 32 == 0, so group g is the elements 32 g .. 32 g + 31 of the flat tensor, and block_w % 32 == 0,
+// so it lies under one scale).  A lane that owned a whole group would read 32 bytes at a 32-byte stride; here TWO neighbouring lanes share a group,
+// 16 codes each: one 16-byte load (a wave reads 1 KiB contiguous), max |d| of the two halves joined by one cross-lane exchange (xor 1), one 8-byte
+// non-temporal nibble store (a wave writes 512 B contiguous), the exponent byte from the even lane.  Lane t takes half t % 2 of the groups
+// wg_g0 + t / 2 + 128 k, k = 0..3, all loads before the arithmetic as in fp8b_fast.
+constexpr int kFp8bMxSteps = 4;                                  // groups per lane pair
+constexpr int kFp8bMxStride = kBlock / 2;                        // groups between a lane's steps
+constexpr int64_t kFp8bMxGroupsPerBlock = int64_t(kFp8bMxStride) * kFp8bMxSteps;
+static_assert(kFp8bMxGroupsPerBlock == CT_FP8BLOCK_MX_GROUPS_PER_BLOCK, "include/ct_hip.h states the workgroup's share");
+
+// two products -> one word of two XDT values, rounded as store8 rounds them
+template <int XDT>
+__device__ __forceinline__ uint32_t fp8b_mx_pair(float a, float b) {
+    if constexpr (XDT == CT_BF16) {
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        typedef bf16_t b2 __attribute__((ext_vector_type(2)));
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
+    } else {
+        return f_to_f16_bits(a) | (f_to_f16_bits(b) << 16);
+    }
+}
+
+// half a group: 16 codes under the scale s -> max |d| joined with the neighbour's, the group's MX scale, 8 bytes of nibbles
+template <int XDT>
+__device__ __forceinline__ void fp8b_mx_half(const ct_fp8block_mx_item& it, int64_t g, int half, float s, const u32x4 q) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const uint32_t words[4] = {q.x, q.y, q.z, q.w};
+    uint32_t d[8];  // the 16 dense values, as the dequantize would have stored them
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)words[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)words[i], true);
+        d[2 * i] = fp8b_mx_pair<XDT>(fp8b_mul(lo.x, s), fp8b_mul(lo.y, s));
+        d[2 * i + 1] = fp8b_mx_pair<XDT>(fp8b_mul(hi.x, s), fp8b_mul(hi.y, s));
+    }
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = absmax_acc(acc, d[i]);
+    acc = absmax_group_reduce(acc, 2);  // both lanes of a pair are here together: they share g
+    const float sc = compute_qparams_float<XDT>(absmax_finish<XDT>(acc), QP_MXFP4, 1.0f);
+    const uint32_t ef = (f_bits(sc) >> 23) & 0xffu;  // as rtn_mxfp4_lane
+    if (half == 0) it.e8m0[g] = (uint8_t)(ef == 0xffu ? kE8M0OfInf : ef);
+    const uint32_t lo4[4] = {d[0], d[1], d[2], d[3]}, hi4[4] = {d[4], d[5], d[6], d[7]};
+    const uint32_t w0 = fp4_quant_unit<XDT, false>(lo4, sc, 1.0f, true), w1 = fp4_quant_unit<XDT, false>(hi4, sc, 1.0f, true);
+    stream_store8(it.packed + 16 * g + 8 * half, u32x2{w0, w1});
+}
+
+template <int XDT, int SDT>
+__device__ __forceinline__ void fp8b_mx_groups(const ct_fp8block_mx_item& it, int64_t wg_g0) {
+    const int half = threadIdx.x & 1;
+    const int64_t g0 = wg_g0 + (threadIdx.x >> 1), units = it.units;
+    if (g0 >= units) return;  // no barriers below; a pair leaves together
+    const int64_t upr = it.units_per_row;
+    int64_t r = g0 / upr, c = g0 - r * upr;
+    const int64_t dq = kFp8bMxStride / upr, dr = kFp8bMxStride - dq * upr;
+    uint32_t rs[kFp8bMxSteps], cs[kFp8bMxSteps];
+#pragma unroll
+    for (int k = 0; k < kFp8bMxSteps; ++k) {
+        rs[k] = (uint32_t)r;
+        cs[k] = (uint32_t)c;
+        r += dq;
+        c += dr;
+        if (c >= upr) {
+            c -= upr;
+            ++r;
+        }
+    }
+    const auto src = fp8b_global<u32x4>(it.w);
+    const auto scale_of = [&](int k) {
+        return fp8b_scale<SDT>(it.scale, (int64_t)(rs[k] / (uint32_t)it.block_h) * it.scale_stride[0] +
+                                             (int64_t)((32u * cs[k]) / (uint32_t)it.block_w) * it.scale_stride[1]);
+    };
+    const auto group = [&](int k) { return g0 + (int64_t)kFp8bMxStride * k; };
+    if (group(kFp8bMxSteps - 1) < units) {
+        // every step exists: the four 16-byte code loads and the four scale loads in flight, with no condition the compiler could sink them into
+        u32x4 q[kFp8bMxSteps];
+        float s[kFp8bMxSteps];
+#pragma unroll
+        for (int k = 0; k < kFp8bMxSteps; ++k) {
+            q[k] = src[2 * group(k) + half];
+            s[k] = scale_of(k);
+        }
+#pragma unroll
+        for (int k = 0; k < kFp8bMxSteps; ++k) fp8b_mx_half<XDT>(it, group(k), half, s[k], q[k]);
+    } else {
+        // the item's last workgroup
+        for (int k = 0; k < kFp8bMxSteps && group(k) < units; ++k) fp8b_mx_half<XDT>(it, group(k), half, scale_of(k), src[2 * group(k) + half]);
+    }
+}
+
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void fp8block_mxfp4_kernel(const ct_fp8block_mx_item* __restrict__ items, int n) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].first_block <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const ct_fp8block_mx_item it = items[lo];
+    const int64_t wg_g0 = ((int64_t)blockIdx.x - it.first_block) * kFp8bMxGroupsPerBlock;
+    // one straight-line body per scale dtype: a branch on the dtype between the loads would make each wait for the last
+    switch (it.sdt) {
+        case CT_F32: fp8b_mx_groups<XDT, CT_F32>(it, wg_g0); break;
+        case CT_BF16: fp8b_mx_groups<XDT, CT_BF16>(it, wg_g0); break;
+        default: fp8b_mx_groups<XDT, CT_F16>(it, wg_g0); break;
+    }
 }
 
 // The NVFP4 counterpart: a lane owns two groups of 16; the global scale (generate_gparam: a tensor-wide amax, i.e. one
@@ -957,6 +1068,68 @@ int ct_rtn_mxfp4_quant_pack_batch(const ct_w4_item* items_dev, int n, int64_t to
     CT_BATCH_ARGS(n, total_blocks);
     for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((rtn_mxfp4_batch_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_rtn_mxfp4_quant_pack_batch");
+}
+
+static int64_t fp8b_mx_plan_item(ct_fp8block_mx_item& it, int i, int64_t first_block) {
+    constexpr int64_t kDimMax = int64_t(1) << 31;  // as ct_fp8block_dequant_plan: the kernel divides rows and columns as 32-bit numbers
+    const char* const name = "ct_fp8block_mxfp4_plan";
+    if (!(it.w && it.scale && it.packed && it.e8m0)) {
+        set_error("%s: item %d has a NULL pointer", name, i);
+        return -1;
+    }
+    if (!(it.rows > 0 && it.cols > 0 && it.rows < kDimMax && it.cols < kDimMax)) {
+        set_error("%s: item %d has shape (%lld, %lld) (need positive sizes below 2^31)", name, i, (long long)it.rows, (long long)it.cols);
+        return -1;
+    }
+    if (!(it.block_h > 0 && it.block_w > 0 && it.block_h < kDimMax && it.block_w < kDimMax)) {
+        set_error("%s: item %d has block size (%lld, %lld) (need positive sizes below 2^31)", name, i, (long long)it.block_h, (long long)it.block_w);
+        return -1;
+    }
+    if (it.sdt != CT_F32 && it.sdt != CT_BF16 && it.sdt != CT_F16) {
+        set_error("%s: item %d: weight_scale_inv must be float32, bfloat16 or float16 (dtype code %d)", name, i, it.sdt);
+        return -1;
+    }
+    if (it.cols % 32 != 0) {
+        set_error("%s: item %d: columns (%lld) must be a multiple of the MX group size 32", name, i, (long long)it.cols);
+        return -1;
+    }
+    if (it.block_w % 32 != 0) {
+        set_error("%s: item %d: block width %lld is not a multiple of 32 (an MX group would straddle two scale blocks)", name, i, (long long)it.block_w);
+        return -1;
+    }
+    const int64_t nrb = cdiv64(it.rows, it.block_h), ncb = cdiv64(it.cols, it.block_w);
+    const int64_t s0 = it.scale_shape[0], s1 = it.scale_shape[1];
+    if (!((s0 == nrb || s0 == 1) && (s1 == ncb || s1 == 1))) {
+        set_error("%s: item %d: weight_scale_inv of shape (%lld, %lld) for a (%lld, %lld) weight in (%lld, %lld) blocks, expected (%lld, %lld) or a "
+                  "broadcast of it", name, i, (long long)s0, (long long)s1, (long long)it.rows, (long long)it.cols, (long long)it.block_h,
+                  (long long)it.block_w, (long long)nrb, (long long)ncb);
+        return -1;
+    }
+    if (!aligned16(it.w)) {
+        set_error("%s: item %d: weight is not 16-byte aligned", name, i);
+        return -1;
+    }
+    if (!aligned16(it.packed)) {
+        set_error("%s: item %d: weight_packed is not 16-byte aligned", name, i);
+        return -1;
+    }
+    it.reserved = 0;
+    it.scale_stride[0] = s0 == 1 ? 0 : s1;
+    it.scale_stride[1] = s1 == 1 ? 0 : 1;
+    it.units_per_row = it.cols / 32;
+    it.units = it.rows * it.units_per_row;
+    it.first_block = first_block;
+    return cdiv64(it.units, kFp8bMxGroupsPerBlock);
+}
+
+int64_t ct_fp8block_mxfp4_plan(ct_fp8block_mx_item* items, int n) { return plan_table("ct_fp8block_mxfp4_plan", items, n, fp8b_mx_plan_item); }
+
+int ct_fp8block_mxfp4_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "ct_fp8block_mxfp4_batch: the dense dtype must be bfloat16 or float16 (dtype code %d)", xdt);
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr, "ct_fp8block_mxfp4_batch: table is NULL");
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((fp8block_mxfp4_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
+    CT_LAUNCH_CHECK("ct_fp8block_mxfp4_batch");
 }
 
 int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, const float* global_scale, uint8_t* packed, uint8_t* scale_f8,

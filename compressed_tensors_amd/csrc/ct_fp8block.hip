@@ -18,6 +18,7 @@
 // (v_cvt_pk_bf16_f32 / v_cvt_f16_f32).  The product is pinned in a register before a cast to half, as in mul_round_to: this
 // keeps clang from selecting v_fma_mixlo_f16 a, b, +0, which loses the sign of a zero product.
 #include "ct_common.h"
+#include "ct_fp8block.h"
 
 namespace ct {
 
@@ -28,33 +29,6 @@ constexpr int kFp8bUnitsPerLane = 4;
 constexpr int64_t kFp8bUnitsPerBlock = int64_t(kBlock) * kFp8bUnitsPerLane;
 constexpr int64_t kFp8bMaxBlocks = (int64_t(1) << 24) - 1;     // one launch: workgroups x 256 lanes < 2^32
 constexpr int64_t kFp8bDimMax = int64_t(1) << 31;
-
-// the table's pointers are generic ones: as flat accesses their loads would count against both wait counters and be waited for one
-// by one, so the fast path reads through global-address-space views of them
-template <typename T>
-__device__ __forceinline__ const __attribute__((address_space(1))) T* fp8b_global(const void* p) {
-    return (const __attribute__((address_space(1))) T*)p;
-}
-
-// one scale of sdt CT_F32 / CT_BF16 / CT_F16, widened exactly
-template <int SDT>
-__device__ __forceinline__ float fp8b_scale(const void* p, int64_t i) {
-    if constexpr (SDT == CT_F32) return fp8b_global<float>(p)[i];
-    else if constexpr (SDT == CT_BF16) return bf16_bits_to_f(fp8b_global<uint16_t>(p)[i]);
-    else return f16_bits_to_f(fp8b_global<uint16_t>(p)[i]);
-}
-
-__device__ __forceinline__ float fp8b_scale(const void* p, int sdt, int64_t i) {
-    if (sdt == CT_F32) return static_cast<const float*>(p)[i];
-    const uint32_t h = static_cast<const uint16_t*>(p)[i];
-    return sdt == CT_BF16 ? bf16_bits_to_f(h) : f16_bits_to_f(h);
-}
-
-__device__ __forceinline__ float fp8b_mul(float q, float s) {
-    float p = q * s;
-    asm("" : "+v"(p));
-    return p;
-}
 
 // eight codes at element e of the flat tensor: one 8-byte load's worth, one scale, one 16-byte store (two for float32)
 template <int ODT>

@@ -1,13 +1,15 @@
 """Dense checkpoints -> compressed-tensors checkpoints of the data-free presets (no reference counterpart: the reference produces such checkpoints
 through calibration-free `compress_model`; the bits are those of calculate_qparams over each block's, group's or output channel's min / max followed by
-`quantize` and the format's packing): `FP8BlockQuantizer` (FP8_BLOCK, `float-quantized`), `MXFP8Quantizer` (`mxfp8-quantized`), `FP8DynamicQuantizer`
-(FP8_DYNAMIC, `float-quantized`), `W8A8Quantizer` (INT8_W8A8, `int-quantized`) and `PackQuantizedQuantizer` (W4A16, W4A16_ASYM, W2A16 ... W7A16 and their
-channel-wise forms, `pack-quantized`).  One body, `_DenseQuantizer`, serves all five; `CompressedTensorsDequantizer` reads every one of them back."""
+`quantize` and the format's packing): `FP8BlockQuantizer` (FP8_BLOCK, `float-quantized`), `MXFP8Quantizer` (`mxfp8-quantized`), `MXFP4Quantizer`
+(MXFP4A16 / MXFP4, `mxfp4-pack-quantized`), `FP8DynamicQuantizer` (FP8_DYNAMIC, `float-quantized`), `W8A8Quantizer` (INT8_W8A8, `int-quantized`) and
+`PackQuantizedQuantizer` (W4A16, W4A16_ASYM, W2A16 ... W7A16 and their channel-wise forms, `pack-quantized`).  One body, `_DenseQuantizer`, serves all
+six; `CompressedTensorsDequantizer` reads every one of them back."""
 from typing import Dict, Iterable, List, Set
 
 import torch
 
 from ... import _lib, codec
+from ...compressors.fp4.base import MXFP4PackedCompressor
 from ...compressors.mxfp8.base import MXFP8QuantizationCompressor
 from ...compressors.naive_quantized.base import FloatQuantizationCompressor, IntQuantizationCompressor
 from ...compressors.pack_quantized.base import PackedQuantizationCompressor
@@ -16,7 +18,7 @@ from .converters import Converter, _ConfigDict, match_quantizable_tensors
 from .fp8block import _block_size
 from .staging import ReadyDict, device_outputs, launch_tables, return_to_host, settle, stage_inputs, table_calls
 
-__all__ = ["FP8BlockQuantizer", "MXFP8Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer", "PackQuantizedQuantizer"]
+__all__ = ["FP8BlockQuantizer", "MXFP8Quantizer", "MXFP4Quantizer", "FP8DynamicQuantizer", "W8A8Quantizer", "PackQuantizedQuantizer"]
 
 _DENSE_DTYPES = (torch.bfloat16, torch.float16)
 _DEFAULT_IGNORE = ("lm_head", "re:.*embed_tokens$")
@@ -27,6 +29,12 @@ def _preset(**changed) -> dict:
     static symmetric float8 codes under one min-max scale per output channel"""
     return {"num_bits": 8, "type": "float", "symmetric": True, "group_size": None, "strategy": "channel", "block_structure": None, "dynamic": False,
             "actorder": None, "scale_dtype": None, "zp_dtype": None, "observer": "memoryless_minmax", "observer_kwargs": {}, **changed}
+
+
+def mxfp4_preset_args(activations: bool):
+    """(weights, input_activations) of the reference's MXFP4A16 preset, or of MXFP4 with `activations` (quant_scheme.py:204-238)"""
+    mx = dict(num_bits=4, strategy="group", group_size=32, scale_dtype="torch.uint8")  # (a symmetric scheme dumps no zp_dtype)
+    return _preset(**mx), (_preset(dynamic=True, observer=None, **mx) if activations else None)
 
 
 class _DenseQuantizer(Converter):
@@ -256,6 +264,45 @@ class MXFP8Quantizer(_DenseQuantizer):
 
     def _launch(self, dtype, dev):
         return codec.rtn_group8_launch(dtype, dev, codec._QP_MXFP8)
+
+
+class MXFP4Quantizer(_DenseQuantizer):
+    """Quantize a dense checkpoint to the MXFP4A16 scheme (weights E2M1 nibbles in groups of 32, round-to-nearest under each group's E8M0 min-max
+    scale; with `activations` the MXFP4 scheme: dynamic MXFP4 input activations as well) in the compressed-tensors `mxfp4-pack-quantized` format: per
+    targeted module `weight_packed` (uint8, (rows, cols / 2)) where the weight was and `weight_scale` (uint8 exponents, (rows, cols / 32)).  Columns
+    that are no whole groups of 32 raise the reference's ValueError."""
+
+    format = "mxfp4-pack-quantized"
+    entry_of = {"dst": "weight_packed", "zp_packed": "weight_scale"}  # the stored scale is the E8M0 code output
+
+    def __init__(self, ignore: Iterable[str] = _DEFAULT_IGNORE, targets: Iterable[str] = tuple(), activations: bool = False, *, device=None):
+        super().__init__(ignore, targets, device=device)
+        self.activations = bool(activations)
+
+    def _preset_args(self):
+        return mxfp4_preset_args(self.activations)
+
+    def _scheme(self):
+        mx = dict(num_bits=4, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8, zp_dtype=torch.uint8)
+        return QuantizationScheme(targets=["Linear"], weights=QuantizationArgs(dynamic=False, **mx),
+                                  input_activations=QuantizationArgs(dynamic=True, **mx) if self.activations else None)
+
+    def _compressor(self):
+        return MXFP4PackedCompressor
+
+    def _outputs(self, rows, cols, dtype):
+        return codec.rtn_mxfp4_outputs(rows, cols)
+
+    def _group(self, shape):
+        return 32  # (`_entries` has refused every other shape)
+
+    def _launch(self, dtype, dev):
+        return codec.rtn_mxfp4_launch(dtype)
+
+    def _entries(self, m, w):
+        if w.shape[1] % 32:
+            raise ValueError(f"{m}: tensor column shape must be divisble by the given group_size 32 but got {w.shape[1]}")
+        return super()._entries(m, w)
 
 
 class _Channel8Quantizer(_DenseQuantizer):

@@ -805,6 +805,32 @@ typedef struct ct_fp8block_item {
 int64_t ct_fp8block_dequant_plan(ct_fp8block_item* items_host, int n);
 int ct_fp8block_dequant_batch(const ct_fp8block_item* items_dev, int n, int64_t total_blocks, int odt, ct_stream_t stream);
 
+/* FP8 block-quantized weights straight to mxfp4-pack-quantized for a TABLE of modules in ONE launch: the bytes of ct_fp8block_dequant_batch
+ * (odt = xdt) followed by ct_rtn_mxfp4_quant_pack_batch, without the dense weight in between.  Per MX group (32 consecutive elements of a row):
+ *   d[i] = rnd_xdt( f32(w[r, c + i]) * f32(scale[r / block_h, (c + i) / block_w]) ),  s = the MX scale of max |d| (calculate_qparams' MX branch),
+ *   e8m0 = the stored exponent byte of s,  packed = the E2M1 nibbles of d / s (low nibble first).
+ * w is float8_e4m3fn (rows, cols) row-major, packed uint8 (rows, cols / 2), e8m0 uint8 (rows, cols / 32); xdt (CT_BF16 or CT_F16: one per launch) is
+ * the dense dtype that is never materialised.  The plan admits an item with cols % 32 == 0, block_w % 32 == 0 (no group straddles a scale block),
+ * 16-byte aligned w and packed, and the scale shapes and dtypes of ct_fp8block_dequant_plan; anything else returns -1 with ct_last_error naming the
+ * item.  A workgroup owns CT_FP8BLOCK_MX_GROUPS_PER_BLOCK consecutive groups of one item.  Protocol as the other batches. */
+#define CT_FP8BLOCK_MX_GROUPS_PER_BLOCK 512
+typedef struct ct_fp8block_mx_item {
+    const uint8_t* w;
+    const void* scale;
+    uint8_t* packed;
+    uint8_t* e8m0;
+    int64_t rows, cols, block_h, block_w;
+    int64_t scale_shape[2];    /* as found; the plan checks it */
+    int32_t sdt;
+    int32_t reserved;          /* derived: 0 */
+    int64_t scale_stride[2];   /* derived: in elements, 0 along a broadcast dimension */
+    int64_t units_per_row;     /* derived: cols / 32, the MX groups of a row */
+    int64_t units;             /* derived: rows * units_per_row */
+    int64_t first_block;       /* derived */
+} ct_fp8block_mx_item;         /* 16 64-bit words */
+int64_t ct_fp8block_mxfp4_plan(ct_fp8block_mx_item* items_host, int n);
+int ct_fp8block_mxfp4_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
+
 /* sparse-bitmask decompress: out = zeros; out[mask] = values.  row_offsets may be NULL only if
  * fixed_row_nnz >= 0 (every row holds exactly that many values: the 2:4 codec).  16-bit payloads with
  * cols % 32 == 0 and 32-bit payloads with cols % 16 == 0 (as pairs of halves) take the LDS-window
