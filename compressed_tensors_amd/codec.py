@@ -1483,7 +1483,7 @@ def dynamic_qdq(x: torch.Tensor, *, kind: str, segs: int, seg_len: int, num_bits
     return out, scale, zp
 
 
-HADAMARD_MAX_SIZE = {torch.float32: 16384, torch.float64: 16384}  # kHadMaxF32 / kHadMaxF64 of csrc/ct_hadamard.hip
+HADAMARD_MAX_SIZE = {torch.float32: 16384, torch.float64: 16384}  # kHadMaxF32 / kHadMaxF64 of csrc/ct_hadamard.h
 
 
 class HadamardPlan(NamedTuple):
@@ -1496,20 +1496,19 @@ class HadamardPlan(NamedTuple):
     rows: int
     cols: int
 
+    @property
+    def is_cols(self) -> bool:
+        """the column form (HadamardKPlan answers the same question)"""
+        return self.form == "cols"
 
-def plan_hadamard(shape, dtype, size: int, dim: int = -1, precision=torch.float32, *, device_type: str = "cuda", contiguous: bool = True) -> HadamardPlan:
-    """The host-side decision of `hadamard_transform`, from shapes and dtypes alone (no tensor data is touched): the form, the
-    block count and the accumulator — or upstream's ValueError (transform/utils/hadamard.py:37-42, transform/utils/matrix.py:41-45)
-    for a size that is not a positive power of two or does not divide the dimension, or NotImplementedError for what the
-    kernels decline (a caller such as install() hands those to the reference)."""
-    size = int(size)
-    if size <= 0:
-        raise ValueError("Cannot construct deterministic hadamard of size <= 0")
-    if size & (size - 1):
-        raise ValueError("Cannot construct deterministic hadamard of size != 2^n")
-    shape = tuple(int(d) for d in shape)
+
+def _plan_rotation_dims(what: str, shape, dtype, size: int, dim: int, precision, device_type: str, contiguous: bool):
+    """What plan_hadamard and plan_hadamard_k share behind their own errors for `size`, in the order both raise: upstream's ValueError for a size that
+    does not divide the dimension (transform/utils/matrix.py:41-45), then NotImplementedError for the precisions, dtypes, devices and layouts no
+    rotation kernel takes.  Returns the shape as a tuple, the normalised dim, and outer, inner, numel around it."""
+    shape = tuple(map(int, shape))
     if not shape:
-        raise ValueError("hadamard_transform of a 0-dim tensor")
+        raise ValueError(f"{what} of a 0-dim tensor")
     if not -len(shape) <= dim < len(shape):
         raise IndexError(f"dim {dim} out of range for a {len(shape)}-dim tensor")
     dim %= len(shape)
@@ -1525,16 +1524,57 @@ def plan_hadamard(shape, dtype, size: int, dim: int = -1, precision=torch.float3
         raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {device_type} tensor")
     if not contiguous:
         raise NotImplementedError("the hadamard kernels take contiguous tensors")
-    if size > HADAMARD_MAX_SIZE[precision]:
-        raise NotImplementedError(f"hadamard size {size} exceeds the supported maximum {HADAMARD_MAX_SIZE[precision]} at precision {precision}")
     outer, inner = math.prod(shape[:dim]), math.prod(shape[dim + 1:])
-    acc64 = precision is torch.float64
-    if inner == 1 or size == 1:  # the transformed dimension is contiguous (a bias column (n, 1) included)
-        numel = outer * shape[dim] * inner
-        return HadamardPlan("rows", size, numel // size, acc64, numel // max(shape[dim], 1), shape[dim])
+    return shape, dim, outer, inner, outer * shape[dim] * inner
+
+
+def _rotation_rows_or_cols(shape, dim: int, size: int, outer: int, inner: int, numel: int) -> tuple:
+    """("rows" or "cols", blocks, rows, cols) of a rotation along `dim`: the row form when the transformed dimension is contiguous (a bias
+    column (n, 1) included), the column form along dim 0 of one matrix"""
+    if inner == 1 or size == 1:
+        return "rows", numel // size, numel // max(shape[dim], 1), shape[dim]
     if outer != 1:
         raise NotImplementedError(f"the column form takes one matrix: dim {dim} of shape {shape} is neither the first nor the last dimension")
-    return HadamardPlan("cols", size, (shape[dim] // size) * inner, acc64, shape[dim], inner)
+    return "cols", (shape[dim] // size) * inner, shape[dim], inner
+
+
+def plan_hadamard(shape, dtype, size: int, dim: int = -1, precision=torch.float32, *, device_type: str = "cuda", contiguous: bool = True) -> HadamardPlan:
+    """The host-side decision of `hadamard_transform`, from shapes and dtypes alone (no tensor data is touched): the form, the
+    block count and the accumulator — or upstream's ValueError (transform/utils/hadamard.py:37-42, transform/utils/matrix.py:41-45)
+    for a size that is not a positive power of two or does not divide the dimension, or NotImplementedError for what the
+    kernels decline (a caller such as install() hands those to the reference)."""
+    size = int(size)
+    if size <= 0:
+        raise ValueError("Cannot construct deterministic hadamard of size <= 0")
+    if size & (size - 1):
+        raise ValueError("Cannot construct deterministic hadamard of size != 2^n")
+    shape, dim, outer, inner, numel = _plan_rotation_dims("hadamard_transform", shape, dtype, size, dim, precision, device_type, contiguous)
+    if size > HADAMARD_MAX_SIZE[precision]:
+        raise NotImplementedError(f"hadamard size {size} exceeds the supported maximum {HADAMARD_MAX_SIZE[precision]} at precision {precision}")
+    form, blocks, rows, cols = _rotation_rows_or_cols(shape, dim, size, outer, inner, numel)
+    return HadamardPlan(form, size, blocks, precision is torch.float64, rows, cols)
+
+
+def _rotation_launch(x: torch.Tensor, had_k=None, k: int = 1, signs=None, n: int = 0, gathers=()):
+    """What the three launch functions do between the plan and the call, in the order all three raise: the int8 tables `had_k` (k, k) and
+    `signs` (n,) are what they must be (ValueError), a GPU is there and x is on it, the tables are on x's device (ValueError), x and the 16-bit
+    `gathers` are 16-byte and signs 8-byte aligned (NotImplementedError).  Returns (out, launch): the empty output, and False for an empty x."""
+    tables = () if had_k is None and signs is None else (("had_k", had_k, (k, k)), ("signs", signs, (n,)))
+    for name, t, shape in tables:
+        if t is not None and (t.dtype is not torch.int8 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int8 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device()
+    if not x.is_cuda:
+        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
+    for name, t, _ in tables:
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{name} is on {t.device}, the value on {x.device}")
+    misaligned = x.data_ptr() % 16 or (signs is not None and signs.data_ptr() % 8)
+    for g in gathers:
+        misaligned = misaligned or g.data_ptr() % 16
+    if misaligned:
+        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
+    return torch.empty_like(x), x.numel() != 0
 
 
 def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=torch.float32, perm: Optional["HadamardPermTables"] = None,
@@ -1549,13 +1589,8 @@ def hadamard_transform(x: torch.Tensor, size: int, *, dim: int = -1, precision=t
     if perm is not None:
         return _hadamard_perm_transform(x, size, None, None, dim, precision, False, perm, form)
     plan = plan_hadamard(x.shape, x.dtype, size, dim, precision, contiguous=x.is_contiguous())
-    _lib.require_device()
-    if not x.is_cuda:
-        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
-    if x.data_ptr() % 16:
-        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
-    out = torch.empty_like(x)
-    if x.numel() == 0:
+    out, launch = _rotation_launch(x)
+    if not launch:
         return out
     if plan.form == "rows":
         call("ct_hadamard_rows", ptr(x), ptr(out), DT[x.dtype], x.numel(), plan.size, int(plan.acc64), stream_of(x))
@@ -1586,6 +1621,11 @@ class HadamardKPlan(NamedTuple):
     cols: int
     workspace: int
 
+    @property
+    def is_cols(self) -> bool:
+        """the column form (HadamardPlan answers the same question)"""
+        return self.entry == "cols"
+
 
 def plan_hadamard_k(shape, dtype, size: int, k: int = 1, dim: int = -1, precision=torch.float32, *, device_type: str = "cuda",
                     contiguous: bool = True) -> HadamardKPlan:
@@ -1596,24 +1636,7 @@ def plan_hadamard_k(shape, dtype, size: int, k: int = 1, dim: int = -1, precisio
     size, k = int(size), int(k)
     if size <= 0 or k <= 0 or size % k or (size // k) & (size // k - 1):
         raise ValueError(f"Cannot construct random hadamard matrix of size {size}")
-    shape = tuple(int(d) for d in shape)
-    if not shape:
-        raise ValueError("hadamard_k_transform of a 0-dim tensor")
-    if not -len(shape) <= dim < len(shape):
-        raise IndexError(f"dim {dim} out of range for a {len(shape)}-dim tensor")
-    dim %= len(shape)
-    if shape[dim] % size != 0:
-        raise ValueError(f"{size} must divide {shape[dim]} (dim {dim} of shape {shape})")
-    if precision in (torch.bfloat16, torch.float16):
-        raise NotImplementedError(f"precision {precision}: upstream would run its GEMM in that dtype, which no kernel here reproduces")
-    if precision not in HADAMARD_MAX_SIZE:
-        raise NotImplementedError(f"precision must be torch.float32 or torch.float64, got {precision}")
-    if dtype not in _FLOATS:
-        raise NotImplementedError(f"the hadamard kernels take bfloat16, float16 and float32 tensors, got {dtype}")
-    if device_type != "cuda":
-        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {device_type} tensor")
-    if not contiguous:
-        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    shape, dim, outer, inner, numel = _plan_rotation_dims("hadamard_k_transform", shape, dtype, size, dim, precision, device_type, contiguous)
     m, acc64 = size // k, precision is torch.float64
     if k == 1:
         form = "butterfly"
@@ -1628,15 +1651,11 @@ def plan_hadamard_k(shape, dtype, size: int, k: int = 1, dim: int = -1, precisio
         form = "mfma" if dtype is not torch.float32 and not acc64 and 8 <= m <= 128 and lds <= _HADAMARD_K_MAX_LDS else "valu"
         if form == "valu" and m > HADAMARD_K_MAX_RUN:
             raise NotImplementedError(f"the vector form of the hadamard mix takes runs of up to {HADAMARD_K_MAX_RUN} elements, got {m}")
-    outer, inner = math.prod(shape[:dim]), math.prod(shape[dim + 1:])
-    numel = outer * shape[dim] * inner
-    acc_bytes = numel * (8 if acc64 else 4) if form == "valu" else 0
-    if inner == 1 or size == 1:
-        return HadamardKPlan("rows", form, size, k, m, numel // size, acc64, numel // max(shape[dim], 1), shape[dim], acc_bytes)
-    if outer != 1:
-        raise NotImplementedError(f"the column form takes one matrix: dim {dim} of shape {shape} is neither the first nor the last dimension")
-    itemsize = 4 if dtype is torch.float32 else 2
-    return HadamardKPlan("cols", form, size, k, m, (shape[dim] // size) * inner, acc64, shape[dim], inner, ((numel * itemsize + 15) & ~15) + acc_bytes)
+    entry, blocks, rows, cols = _rotation_rows_or_cols(shape, dim, size, outer, inner, numel)
+    workspace = numel * (8 if acc64 else 4) if form == "valu" else 0  # the accumulators of the vector form
+    if entry == "cols":  # in front of them, the transposed tensor
+        workspace += (numel * (4 if dtype is torch.float32 else 2) + 15) & ~15
+    return HadamardKPlan(entry, form, size, k, m, blocks, acc64, rows, cols, workspace)
 
 
 def hadamard_k_transform(x: torch.Tensor, n: int, had_k: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None, *, dim: int = -1,
@@ -1654,19 +1673,8 @@ def hadamard_k_transform(x: torch.Tensor, n: int, had_k: Optional[torch.Tensor] 
         return _hadamard_perm_transform(x, n, had_k, signs, dim, precision, transposed, perm, form)
     k = 1 if had_k is None else int(had_k.shape[0])
     plan = plan_hadamard_k(x.shape, x.dtype, n, k, dim, precision, device_type=x.device.type, contiguous=x.is_contiguous())
-    for name, t, shape in (("had_k", had_k, (k, k)), ("signs", signs, (plan.size,))):
-        if t is not None and (t.dtype is not torch.int8 or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous int8 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
-    _lib.require_device()
-    if not x.is_cuda:
-        raise NotImplementedError(f"the hadamard kernels take GPU tensors, got a {x.device.type} tensor")
-    for name, t in (("had_k", had_k), ("signs", signs)):
-        if t is not None and t.device != x.device:
-            raise ValueError(f"{name} is on {t.device}, the value on {x.device}")
-    if x.data_ptr() % 16 or (signs is not None and signs.data_ptr() % 8):
-        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
-    out = torch.empty_like(x)
-    if x.numel() == 0:
+    out, launch = _rotation_launch(x, had_k, k, signs, plan.size)
+    if not launch:
         return out
     ws = torch.empty(plan.workspace, dtype=torch.uint8, device=x.device) if plan.workspace else None
     tail = (plan.size, plan.k, ptr(had_k), ptr(signs), int(bool(transposed)), int(plan.acc64), ptr(ws), stream_of(x))
@@ -1738,11 +1746,9 @@ class HadamardPermPlan(NamedTuple):
     reason: Optional[str]
 
     def launches(self) -> int:
-        cols = (self.base.form if isinstance(self.base, HadamardPlan) else self.base.entry) == "cols"
         if self.form == "fused":
-            return 3 if cols else 1
-        inner = 1 if isinstance(self.base, HadamardPlan) or self.base.form != "valu" else 2
-        return 2 + inner + (2 if cols else 0)
+            return 3 if self.base.is_cols else 1
+        return 2 + (2 if self.base.form == "valu" else 1) + (2 if self.base.is_cols else 0)
 
 
 def plan_hadamard_perm(shape, dtype, size: int, dim: int = -1, precision=torch.float32, *, k: int = 1, random: bool = False,
@@ -1754,19 +1760,18 @@ def plan_hadamard_perm(shape, dtype, size: int, dim: int = -1, precision=torch.f
     unpermuted plan is.  `form`: "fused" / "composed" force a form ("fused" raises NotImplementedError where no fused launch exists)."""
     if form not in (None, "fused", "composed"):
         raise ValueError(f"form must be None, 'fused' or 'composed', got {form!r}")
-    if random or int(k) != 1:
+    k = int(k)
+    if random or k != 1:
         base = plan_hadamard_k(shape, dtype, size, k, dim, precision, device_type=device_type, contiguous=contiguous)
-        cols = base.entry == "cols"
     else:
         base = plan_hadamard(shape, dtype, size, dim, precision, device_type=device_type, contiguous=contiguous)
-        cols = base.form == "cols"
     key, reason = None, None
-    if isinstance(base, HadamardKPlan) and base.k != 1:
-        reason = f"k = {base.k} > 1: the mix has no permuted launch"
+    if k != 1:
+        reason = f"k = {k} > 1: the mix has no permuted launch"
     elif base.size > HADAMARD_PERM_MAX_SIZE[precision]:
         reason = f"hadamard size {base.size} exceeds the maximum {HADAMARD_PERM_MAX_SIZE[precision]} of the permuted launch at precision {precision}"
     else:
-        key = "cols" if cols else ("group" if base.size <= 512 else "block") + ("_f64" if base.acc64 else "")
+        key = "cols" if base.is_cols else ("group" if base.size <= 512 else "block") + ("_f64" if base.acc64 else "")
     if form == "fused" and key is None:
         raise NotImplementedError(f"no fused permuted launch: {reason}")
     if key is not None and form is None and not HADAMARD_PERM_MEASURED_FASTER[key]:
@@ -1792,15 +1797,8 @@ def _hadamard_perm_transform(x, n, had_k, signs, dim, precision, transposed, per
         y = hadamard_k_transform(g, n, had_k, signs, dim=dim, precision=precision, transposed=transposed) if random \
             else hadamard_transform(g, n, dim=dim, precision=precision)
         return y.unflatten(d, (-1, perm.n)).index_select(d + 1, perm.index_out).flatten(d, d + 1)
-    if signs is not None and (signs.dtype is not torch.int8 or tuple(signs.shape) != (perm.n,) or not signs.is_contiguous()):
-        raise ValueError(f"signs must be a contiguous int8 tensor of shape {(perm.n,)}, got {signs.dtype} {tuple(signs.shape)}")
-    _lib.require_device()
-    if signs is not None and signs.device != x.device:
-        raise ValueError(f"signs is on {signs.device}, the value on {x.device}")
-    if x.data_ptr() % 16 or (signs is not None and signs.data_ptr() % 8) or perm.gather_in.data_ptr() % 16 or perm.gather_out.data_ptr() % 16:
-        raise NotImplementedError("the hadamard kernels take 16-byte aligned tensors")
-    out = torch.empty_like(x)
-    if x.numel() == 0:
+    out, launch = _rotation_launch(x, None, 1, signs, perm.n, (perm.gather_in, perm.gather_out))
+    if not launch:
         return out
     base = plan.base
     tail = (base.size, int(base.acc64), ptr(perm.gather_in), ptr(perm.gather_out), ptr(signs), int(bool(transposed)), stream_of(x))

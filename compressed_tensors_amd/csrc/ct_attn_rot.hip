@@ -91,10 +91,7 @@ extern "C" int ct_attn_rot_qdq(const ct_attn_tensor* tensors, int n, int rot_siz
         if (((rot_mask >> i) & 1) && t.D % (uint32_t)rot_size) CT_UNSUPPORTED("tensor %d: hadamard size %d does not divide rows of %u elements", i, rot_size, t.D);
     }
     if (blocks == 0) return CT_OK;
-    HadScale<float> sn;  // launch_rows' of csrc/ct_hadamard.hip
-    sn.sn = (float)__builtin_sqrt((double)rot_size);
-    sn.rn = 1.0f / sn.sn;
-    sn.mode = log2_exact(rot_size) % 2 == 0 ? HAD_MUL : HAD_FAST;
+    const HadScale<float> sn = make_had_scale<float>(rot_size);  // ct_hadamard_rows'
     const dim3 grid((unsigned)blocks);
     CT_ATTN_DISPATCH_FQ_Q(mode, xdt, tdt, hipLaunchKernelGGL((attn_rot_kernel<X, T, M>), grid, dim3(kBlock), 0, as_stream(stream), p, rot_size, rot_mask, sn));
     CT_LAUNCH_CHECK("ct_attn_rot_qdq");

@@ -16,7 +16,8 @@
 //
 // Kernels
 //   had_group_kernel  n <= 512: n / 8 lanes own a block (n < 8: one lane owns 8 / n blocks), several blocks per wave
-//   had_block_kernel  n = 1024 .. 16384: one workgroup of WAVES waves per block, U units per thread
+//   had_block_kernel  n = 1024 .. 16384: one workgroup of WAVES waves per block, U units per thread; the stages between its loads and its
+//                     stores are ct_hadamard_block.inc, shared with the block kernels of ct_hadamard_k.hip, ct_hadamard_perm.hip and ct_rotated.hip
 //   transpose_kernel  the column form (transformed dimension is dim 0 of a rows x cols matrix): transpose into the workspace,
 //                     row form in place, transpose back — 3 x the traffic of the row form, the same arithmetic
 #include "ct_hadamard.h"
@@ -24,8 +25,6 @@
 namespace ct {
 
 // ---- n <= 512: lpb = max(n / 8, 1) lanes per block, U units per lane kBlock apart ------------------------------------------------
-constexpr int kHadGroupUnits = 2;
-
 template <int XDT, typename A>
 __global__ __launch_bounds__(kBlock) void had_group_kernel(const void* x, void* out, int64_t numel, int n, HadScale<A> sn) {
     constexpr int U = kHadGroupUnits;
@@ -63,7 +62,6 @@ __global__ __launch_bounds__(64 * WAVES) void had_block_kernel(const void* x, vo
     constexpr int T = 64 * WAVES, N = T * U * 8;
     constexpr int CH = 16 / (int)sizeof(A), CPU = 8 / CH;  // elements of a 16-byte chunk, chunks per unit
     typedef A chunk_t __attribute__((ext_vector_type(CH)));
-    // chunk c of unit u of thread t at ((u * CPU + c) * T + t): consecutive lanes 16 bytes apart, for the writes and for the reads
     __shared__ chunk_t lds[WAVES > 1 ? N / CH : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
@@ -71,57 +69,7 @@ __global__ __launch_bounds__(64 * WAVES) void had_block_kernel(const void* x, vo
         A v[U][8];
 #pragma unroll
         for (int u = 0; u < U; ++u) had_load<XDT, A>(x, e0 + ((int64_t)u * T + tid) * 8, e0 + N, v[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            unit_stages(v[u], 8);
-            lane_stages(v[u], 64, lane);
-            if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);  // one unit's exchanges at a time: 64 values per thread leave no room for more
-        }
-#pragma unroll
-        for (int h = 1; h < U; h <<= 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!(u & h)) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const A a = v[u][k], c = v[u | h][k];
-                        v[u][k] = a + c;
-                        v[u | h][k] = a - c;
-                    }
-                }
-            }
-        }
-        if constexpr (WAVES > 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t w;
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) w[e] = v[u][c * CH + e];
-                    lds[(u * CPU + c) * T + tid] = w;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t r = lds[(u * CPU + c) * T + lane];  // wave 0: sign + for every reader
-#pragma unroll
-                    for (int w = 1; w < WAVES; ++w) {
-                        const chunk_t p = lds[(u * CPU + c) * T + w * 64 + lane];
-                        const A sign = (__builtin_popcount(w & wave) & 1) ? (A)-1 : (A)1;  // wave-uniform
-#pragma unroll
-                        for (int e = 0; e < CH; ++e) r[e] = fma_t(p[e], sign, r[e]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) v[u][c * CH + e] = r[e];
-                    if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();  // lds is rewritten by the next block
-        }
+#include "ct_hadamard_block.inc"
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             had_store<XDT, A>(out, e0 + ((int64_t)u * T + tid) * 8, e0 + N, v[u], sn);
@@ -149,55 +97,33 @@ __global__ __launch_bounds__(kBlock) void transpose_kernel(const E* __restrict__
     }
 }
 
-template <int XDT, typename A, int U, int WAVES>
-static void launch_block(const void* x, void* out, int64_t blocks, HadScale<A> sn, hipStream_t s) {
-    const int64_t g = blocks < kMaxGridX ? blocks : kMaxGridX;
-    hipLaunchKernelGGL((had_block_kernel<XDT, A, U, WAVES>), dim3((unsigned)g), dim3(64 * WAVES), 0, s, x, out, blocks, sn);
-}
-
-constexpr int64_t kHadMaxF32 = 16384, kHadMaxF64 = 16384;  // 64 values per thread at 4 waves; the forms tried for 32768 (8 x 8 waves, 16 x 4) spill
-
+// ---- host: the launch path of ct_hadamard.h around this file's two kernels -----------------------------------------------------------------
 template <int XDT, typename A>
 static int launch_rows(const void* x, void* out, int64_t numel, int64_t n, hipStream_t s) {
-    HadScale<A> sn;
-    sn.sn = (A)__builtin_sqrt((double)n);  // float32(sqrt(float64(n))), as the reference's `/ self._scale` in float32
-    sn.rn = (A)1 / sn.sn;
-    sn.mode = log2_exact(n) % 2 == 0 ? HAD_MUL : (sizeof(A) == 4 ? HAD_FAST : HAD_IEEE);
-    if (n <= 512) {
-        const int64_t g = cdiv64(cdiv64(numel, 8), (int64_t)kBlock * kHadGroupUnits);
-        CT_REQUIRE(g < ((int64_t)1 << 31), "tensor too large for one launch");
-        hipLaunchKernelGGL((had_group_kernel<XDT, A>), dim3((unsigned)g), dim3(kBlock), 0, s, x, out, numel, (int)n, sn);
-        return CT_OK;
-    }
-    const int64_t blocks = numel / n;
-    switch (n) {
-        case 1024: launch_block<XDT, A, 2, 1>(x, out, blocks, sn, s); break;
-        case 2048: launch_block<XDT, A, 4, 1>(x, out, blocks, sn, s); break;
-        case 4096: launch_block<XDT, A, 4, 2>(x, out, blocks, sn, s); break;
-        case 8192: launch_block<XDT, A, 4, 4>(x, out, blocks, sn, s); break;
-        case 16384: launch_block<XDT, A, 8, 4>(x, out, blocks, sn, s); break;
-        default: break;  // unreachable: check_had
-    }
-    return CT_OK;
+    return launch_had_rows<A>(
+        numel, n, [&](dim3 grid, HadScale<A> sn) { hipLaunchKernelGGL((had_group_kernel<XDT, A>), grid, dim3(kBlock), 0, s, x, out, numel, (int)n, sn); },
+        [&](auto U, auto W, dim3 grid, int64_t blocks, HadScale<A> sn) {
+            hipLaunchKernelGGL((had_block_kernel<XDT, A, U(), W()>), grid, dim3(64 * W()), 0, s, x, out, blocks, sn);
+        });
 }
 
 static int check_had(const void* x, const void* out, int dt, int64_t numel, int64_t n, int acc64) {
-    CT_REQUIRE(is_float_dt(dt), "dtype code %d is not a float type", dt);
-    CT_REQUIRE(n >= 1 && log2_exact(n) >= 0, "Cannot construct deterministic hadamard of size != 2^n");
-    CT_REQUIRE(numel >= 0 && numel % n == 0, "hadamard size %lld does not divide %lld elements", (long long)n, (long long)numel);
-    CT_REQUIRE(acc64 == 0 || acc64 == 1, "accumulator selector must be 0 (float32) or 1 (float64), got %d", acc64);
-    if (n > (acc64 ? kHadMaxF64 : kHadMaxF32)) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %lld of the %s accumulator", (long long)n,
-                                                             (long long)(acc64 ? kHadMaxF64 : kHadMaxF32), acc64 ? "float64" : "float32");
-    if (!aligned16(x) || !aligned16(out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned tensors");
-    return CT_OK;
+    return check_had_common(
+        x, out, dt, numel, n, acc64, 0,
+        [&]() -> int {
+            CT_REQUIRE(n >= 1 && log2_exact(n) >= 0, "Cannot construct deterministic hadamard of size != 2^n");
+            return CT_OK;
+        },
+        [&]() -> int {
+            if (n > (acc64 ? kHadMaxF64 : kHadMaxF32)) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %lld of the %s accumulator", (long long)n,
+                                                                     (long long)(acc64 ? kHadMaxF64 : kHadMaxF32), acc64 ? "float64" : "float32");
+            return CT_OK;
+        });
 }
 
 static int dispatch_rows(const void* x, void* out, int dt, int64_t numel, int64_t n, int acc64, hipStream_t s) {
     if (numel == 0) return CT_OK;
-#define CT_HAD_ROWS(X) (acc64 ? launch_rows<X, double>(x, out, numel, n, s) : launch_rows<X, float>(x, out, numel, n, s))
-    const int rc = dt == CT_BF16 ? CT_HAD_ROWS(CT_BF16) : dt == CT_F16 ? CT_HAD_ROWS(CT_F16) : CT_HAD_ROWS(CT_F32);
-#undef CT_HAD_ROWS
-    return rc;
+    return for_had_types(dt, acc64, [&](auto X, auto a) { return launch_rows<X(), decltype(a)>(x, out, numel, n, s); });
 }
 
 template <typename E>
@@ -226,24 +152,10 @@ int ct_hadamard_rows(const void* x, void* out, int dt, int64_t numel, int64_t n,
 }
 
 int ct_hadamard_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64, ct_stream_t stream) {
-    CT_REQUIRE(rows >= 0 && cols >= 0, "bad matrix shape (%lld, %lld)", (long long)rows, (long long)cols);
-    int rc = check_had(x, out, dt, rows, n, acc64);  // n divides the ROWS
-    if (rc) return rc;
-    CT_REQUIRE(workspace != nullptr && aligned16(workspace), "ct_hadamard_cols needs a 16-byte aligned workspace of rows * cols elements");
-    if (rows == 0 || cols == 0) return CT_OK;
-    CT_REQUIRE(cdiv64(rows, 64) * cdiv64(cols, 64) < ((int64_t)1 << 31), "matrix too large for one launch");
     hipStream_t s = as_stream(stream);
-    if (dt == CT_F32) launch_transpose<uint32_t>(x, workspace, rows, cols, s);
-    else launch_transpose<uint16_t>(x, workspace, rows, cols, s);
-    rc = hip_check(hipGetLastError(), "ct_hadamard_cols[transpose]");
-    if (rc) return rc;
-    rc = dispatch_rows(workspace, workspace, dt, rows * cols, n, acc64, s);  // in place: every element is read and written by one thread
-    if (rc) return rc;
-    rc = hip_check(hipGetLastError(), "ct_hadamard_cols[rows]");
-    if (rc) return rc;
-    if (dt == CT_F32) launch_transpose<uint32_t>(workspace, out, cols, rows, s);
-    else launch_transpose<uint16_t>(workspace, out, cols, rows, s);
-    CT_LAUNCH_CHECK("ct_hadamard_cols[transpose back]");
+    return had_cols_form(
+        "ct_hadamard_cols", "of rows * cols elements", x, out, workspace, dt, rows, cols, s, [&] { return check_had(x, out, dt, rows, n, acc64); },  // n divides the ROWS
+        [&](void* w, int64_t numel) { return dispatch_rows(w, w, dt, numel, n, acc64, s); });  // in place: every element is read and written by one thread
 }
 
 }  // extern "C"

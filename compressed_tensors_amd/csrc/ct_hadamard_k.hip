@@ -80,12 +80,10 @@ __device__ __forceinline__ u32x4 flip8(u32x4 v, const int8_t* __restrict__ signs
 }
 
 // ---- (a) n <= 512: had_group_kernel with signs ------------------------------------------------------------------------------------------
-constexpr int kHadKGroupUnits = 2;
-
 template <int XDT, typename A>
 __global__ __launch_bounds__(kBlock) void hadk_group_kernel(const void* x, void* out, int64_t numel, int n, const int8_t* __restrict__ signs,
                                                             int transposed, HadScale<A> sn) {
-    constexpr int U = kHadKGroupUnits;
+    constexpr int U = kHadGroupUnits;
     const int64_t units = (numel + 7) >> 3;
     const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
     const int lpb = n >> 3, lane = threadIdx.x & 63;
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void hadk_group_kernel(const void* x, void*
     }
 }
 
-// ---- (a) n = 64 * WAVES * U * 8: had_block_kernel with signs ----------------------------------------------------------------------------
+// ---- (a) n = 64 * WAVES * U * 8: had_block_kernel with signs (the same ct_hadamard_block.inc between the loads and the stores) ------------
 template <int XDT, typename A, int U, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void hadk_block_kernel(const void* x, void* out, int64_t blocks, const int8_t* __restrict__ signs,
                                                                 int transposed, HadScale<A> sn) {
@@ -130,57 +128,7 @@ __global__ __launch_bounds__(64 * WAVES) void hadk_block_kernel(const void* x, v
         for (int u = 0; u < U; ++u) {
             hadk_load<XDT, A>(x, e0 + ((int64_t)u * T + tid) * 8, e0 + N, v[u], transposed ? nullptr : signs, (int64_t)(u * T + tid) * 8, N - 1);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            unit_stages(v[u], 8);
-            lane_stages(v[u], 64, lane);
-            if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int h = 1; h < U; h <<= 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!(u & h)) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const A a = v[u][k], c = v[u | h][k];
-                        v[u][k] = a + c;
-                        v[u | h][k] = a - c;
-                    }
-                }
-            }
-        }
-        if constexpr (WAVES > 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t w;
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) w[e] = v[u][c * CH + e];
-                    lds[(u * CPU + c) * T + tid] = w;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t r = lds[(u * CPU + c) * T + lane];
-#pragma unroll
-                    for (int w = 1; w < WAVES; ++w) {
-                        const chunk_t p = lds[(u * CPU + c) * T + w * 64 + lane];
-                        const A sign = (__builtin_popcount(w & wave) & 1) ? (A)-1 : (A)1;
-#pragma unroll
-                        for (int e = 0; e < CH; ++e) r[e] = fma_t(p[e], sign, r[e]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) v[u][c * CH + e] = r[e];
-                    if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();
-        }
+#include "ct_hadamard_block.inc"
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             hadk_store<XDT, A>(out, e0 + ((int64_t)u * T + tid) * 8, e0 + N, v[u], sn, transposed ? signs : nullptr, (int64_t)(u * T + tid) * 8, N - 1);
@@ -415,50 +363,35 @@ static int form_of(int dt, int64_t n, int64_t k, int acc64) {
 
 static int check_hadk(const void* x, const void* out, int dt, int64_t numel, int64_t n, int64_t k, const int8_t* had_k, const int8_t* signs, int transposed,
                       int acc64) {
-    CT_REQUIRE(is_float_dt(dt), "dtype code %d is not a float type", dt);
-    CT_REQUIRE(n >= 1 && k >= 1 && n % k == 0 && log2_exact(n / k) >= 0, "hadamard size %lld is not %lld * 2^m", (long long)n, (long long)k);
-    CT_REQUIRE(numel >= 0 && numel % n == 0, "hadamard size %lld does not divide %lld elements", (long long)n, (long long)numel);
-    CT_REQUIRE(acc64 == 0 || acc64 == 1, "accumulator selector must be 0 (float32) or 1 (float64), got %d", acc64);
-    CT_REQUIRE(transposed == 0 || transposed == 1, "transposed must be 0 or 1, got %d", transposed);
-    CT_REQUIRE((k == 1) == (had_k == nullptr), "had_k is the k x k mix for k > 1 and null for k == 1");
-    if (k == 1 && n > 16384) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum 16384 of the butterfly", (long long)n);
-    if (k > kHadKMaxK) CT_UNSUPPORTED("the mix takes k <= %d, got %lld", kHadKMaxK, (long long)k);
-    if (k > 1 && n > kHadKMfmaMaxN) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %d of the mixed forms", (long long)n, kHadKMfmaMaxN);
-    if (k > 1 && form_of(dt, n, k, acc64) == HADK_VALU && n / k > kHadKRunsMaxM)
-        CT_UNSUPPORTED("the vector form takes runs of up to %d elements, got %lld", kHadKRunsMaxM, (long long)(n / k));
-    if (!aligned16(x) || !aligned16(out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned tensors");
+    const int rc = check_had_common(
+        x, out, dt, numel, n, acc64, transposed,
+        [&]() -> int {
+            CT_REQUIRE(n >= 1 && k >= 1 && n % k == 0 && log2_exact(n / k) >= 0, "hadamard size %lld is not %lld * 2^m", (long long)n, (long long)k);
+            return CT_OK;
+        },
+        [&]() -> int {
+            CT_REQUIRE((k == 1) == (had_k == nullptr), "had_k is the k x k mix for k > 1 and null for k == 1");
+            if (k == 1 && n > kHadMaxF32) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %lld of the butterfly", (long long)n, (long long)kHadMaxF32);
+            if (k > kHadKMaxK) CT_UNSUPPORTED("the mix takes k <= %d, got %lld", kHadKMaxK, (long long)k);
+            if (k > 1 && n > kHadKMfmaMaxN) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %d of the mixed forms", (long long)n, kHadKMfmaMaxN);
+            if (k > 1 && form_of(dt, n, k, acc64) == HADK_VALU && n / k > kHadKRunsMaxM)
+                CT_UNSUPPORTED("the vector form takes runs of up to %d elements, got %lld", kHadKRunsMaxM, (long long)(n / k));
+            return CT_OK;
+        });
+    if (rc) return rc;
     if (!aligned_to<8>(signs)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
     return CT_OK;
 }
 
-template <int XDT, typename A, int U, int WAVES>
-static void launch_kblock(const void* x, void* out, int64_t blocks, const int8_t* signs, int transposed, HadScale<A> sn, hipStream_t s) {
-    const int64_t g = blocks < kMaxGridX ? blocks : kMaxGridX;
-    hipLaunchKernelGGL((hadk_block_kernel<XDT, A, U, WAVES>), dim3((unsigned)g), dim3(64 * WAVES), 0, s, x, out, blocks, signs, transposed, sn);
-}
-
+// form (a) with float32 accumulation: the launch path of ct_hadamard.h around hadk_group_kernel / hadk_block_kernel
 template <int XDT, typename A>
 static int launch_butterfly(const void* x, void* out, int64_t numel, int64_t n, const int8_t* signs, int transposed, hipStream_t s) {
-    HadScale<A> sn;
-    sn.sn = (A)__builtin_sqrt((double)n);
-    sn.rn = (A)1 / sn.sn;
-    sn.mode = log2_exact(n) % 2 == 0 ? HAD_MUL : (sizeof(A) == 4 ? HAD_FAST : HAD_IEEE);  // n is a power of two: the divisors HadScale was proven for
-    if (n <= 512) {
-        const int64_t g = cdiv64(cdiv64(numel, 8), (int64_t)kBlock * kHadKGroupUnits);
-        CT_REQUIRE(g < ((int64_t)1 << 31), "tensor too large for one launch");
-        hipLaunchKernelGGL((hadk_group_kernel<XDT, A>), dim3((unsigned)g), dim3(kBlock), 0, s, x, out, numel, (int)n, signs, transposed, sn);
-        return CT_OK;
-    }
-    const int64_t blocks = numel / n;
-    switch (n) {
-        case 1024: launch_kblock<XDT, A, 2, 1>(x, out, blocks, signs, transposed, sn, s); break;
-        case 2048: launch_kblock<XDT, A, 4, 1>(x, out, blocks, signs, transposed, sn, s); break;
-        case 4096: launch_kblock<XDT, A, 4, 2>(x, out, blocks, signs, transposed, sn, s); break;
-        case 8192: launch_kblock<XDT, A, 4, 4>(x, out, blocks, signs, transposed, sn, s); break;
-        case 16384: launch_kblock<XDT, A, 8, 4>(x, out, blocks, signs, transposed, sn, s); break;
-        default: break;  // unreachable: check_hadk
-    }
-    return CT_OK;
+    return launch_had_rows<A>(
+        numel, n,
+        [&](dim3 grid, HadScale<A> sn) { hipLaunchKernelGGL((hadk_group_kernel<XDT, A>), grid, dim3(kBlock), 0, s, x, out, numel, (int)n, signs, transposed, sn); },
+        [&](auto U, auto W, dim3 grid, int64_t blocks, HadScale<A> sn) {
+            hipLaunchKernelGGL((hadk_block_kernel<XDT, A, U(), W()>), grid, dim3(64 * W()), 0, s, x, out, blocks, signs, transposed, sn);
+        });
 }
 
 template <int XDT>
@@ -519,9 +452,9 @@ static int dispatch_k_rows(const void* x, void* out, int dt, int64_t numel, int6
                            int acc64, void* workspace, hipStream_t s) {
     if (numel == 0) return CT_OK;
     if (k == 1 && signs == nullptr) return ct_hadamard_rows(x, out, dt, numel, n, acc64, reinterpret_cast<ct_stream_t>(s));  // the Sylvester rotation itself
-    if (dt == CT_BF16) return dispatch_dt<CT_BF16>(x, out, numel, n, k, had_k, signs, transposed, acc64, workspace, s);
-    if (dt == CT_F16) return dispatch_dt<CT_F16>(x, out, numel, n, k, had_k, signs, transposed, acc64, workspace, s);
-    return dispatch_dt<CT_F32>(x, out, numel, n, k, had_k, signs, transposed, acc64, workspace, s);
+    int rc = CT_OK;
+    for_dt(dt, [&](auto X) { rc = dispatch_dt<X()>(x, out, numel, n, k, had_k, signs, transposed, acc64, workspace, s); });
+    return rc;
 }
 
 }  // namespace ct
@@ -541,24 +474,14 @@ int ct_hadamard_k_rows(const void* x, void* out, int dt, int64_t numel, int64_t 
 
 int ct_hadamard_k_cols(const void* x, void* out, int dt, int64_t rows, int64_t cols, int64_t n, int64_t k, const int8_t* had_k, const int8_t* signs,
                        int transposed, int acc64, void* workspace, ct_stream_t stream) {
-    CT_REQUIRE(rows >= 0 && cols >= 0, "bad matrix shape (%lld, %lld)", (long long)rows, (long long)cols);
-    int rc = check_hadk(x, out, dt, rows, n, k, had_k, signs, transposed, acc64);  // n divides the ROWS
-    if (rc) return rc;
-    CT_REQUIRE(workspace != nullptr && aligned16(workspace), "ct_hadamard_k_cols needs a 16-byte aligned workspace (ct_hadamard_k_workspace_bytes)");
-    if (rows == 0 || cols == 0) return CT_OK;
-    CT_REQUIRE(cdiv64(rows, 64) * cdiv64(cols, 64) < ((int64_t)1 << 31), "matrix too large for one launch");
     hipStream_t s = as_stream(stream);
-    const int64_t numel = rows * cols, tbytes = (numel * dt_size(dt) + 15) & ~(int64_t)15;
-    void* rest = static_cast<char*>(workspace) + tbytes;  // the accumulators of the vector form
-    launch_transpose_words(x, workspace, dt_size(dt), rows, cols, s);
-    rc = hip_check(hipGetLastError(), "ct_hadamard_k_cols[transpose]");
-    if (rc) return rc;
-    rc = dispatch_k_rows(workspace, workspace, dt, numel, n, k, had_k, signs, transposed, acc64, rest, s);  // in place: a block is read whole before it is written
-    if (rc) return rc;
-    rc = hip_check(hipGetLastError(), "ct_hadamard_k_cols[rows]");
-    if (rc) return rc;
-    launch_transpose_words(workspace, out, dt_size(dt), cols, rows, s);
-    CT_LAUNCH_CHECK("ct_hadamard_k_cols[transpose back]");
+    return had_cols_form(
+        "ct_hadamard_k_cols", "(ct_hadamard_k_workspace_bytes)", x, out, workspace, dt, rows, cols, s,
+        [&] { return check_hadk(x, out, dt, rows, n, k, had_k, signs, transposed, acc64); },  // n divides the ROWS
+        [&](void* w, int64_t numel) {  // in place: a block is read whole before it is written; behind the transposed tensor, the accumulators of the vector form
+            void* rest = static_cast<char*>(w) + ((numel * dt_size(dt) + 15) & ~(int64_t)15);
+            return dispatch_k_rows(w, w, dt, numel, n, k, had_k, signs, transposed, acc64, rest, s);
+        });
 }
 
 int64_t ct_hadamard_k_workspace_bytes(int dt, int64_t numel, int64_t n, int64_t k, int acc64, int cols_form) {

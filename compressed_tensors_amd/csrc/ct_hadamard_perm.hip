@@ -7,8 +7,8 @@
 // Both gathers go through LDS; global access stays contiguous (16-byte loads and stores):
 //   load    the raw 2- or 4-byte words of a block are written to LDS in the tensor's order; element k of a unit is then
 //           the word at q[k] & (n - 1) of its block: one aligned 16-byte read of the table per unit, 8 scattered LDS reads
-//   core    unit stages, lane stages, the U stages, the wave exchange with its fma signs, one division, one rounding — the stage
-//           order of had_group_kernel / had_block_kernel exactly, so the launch computes the bits of the composition
+//   core    unit stages, lane stages, the U stages, the wave exchange with its fma signs (ct_hadamard_block.inc), one division, one
+//           rounding — the stage order of had_group_kernel / had_block_kernel exactly, so the launch computes the bits of the composition
 //           index_select(q) -> ct_hadamard_rows -> index_select(p)
 //   store   the ROUNDED words go to LDS in natural order; output element j is the word at p[j] & (n - 1)
 // The mask keeps every index inside the block whatever the table holds: the host validates the permutation once, the mask is what
@@ -149,14 +149,12 @@ __device__ __forceinline__ void hadp_wave_sync() {
 }
 
 // ---- n <= 512: had_group_kernel between two wave-private gathers ------------------------------------------------------------------------
-constexpr int kHadPGroupUnits = 2;  // kHadGroupUnits
-
 template <int XDT, typename A>
 __global__ __launch_bounds__(kBlock) void hadp_group_kernel(const void* x, void* out, int64_t numel, int n, const uint16_t* __restrict__ gather_in,
                                                             const uint16_t* __restrict__ gather_out, const int8_t* __restrict__ signs, int transposed,
                                                             HadScale<A> sn) {
     typedef typename HadpWord<XDT>::type E;
-    constexpr int U = kHadPGroupUnits;
+    constexpr int U = kHadGroupUnits;
     // image[i][wave]: the 512 words the wave holds in unit slot i, in the tensor's order
     __shared__ __attribute__((aligned(16))) E image[U][kBlock / 64][512];
     const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
@@ -222,57 +220,7 @@ __global__ __launch_bounds__(64 * WAVES) void hadp_block_kernel(const void* x, v
             if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);  // one unit's gather at a time, as the stages below
         }
         __syncthreads();  // the image is read: the exchange and the output image overwrite it
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            unit_stages(v[u], 8);
-            lane_stages(v[u], 64, lane);
-            if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int h = 1; h < U; h <<= 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!(u & h)) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const A a = v[u][k], c = v[u | h][k];
-                        v[u][k] = a + c;
-                        v[u | h][k] = a - c;
-                    }
-                }
-            }
-        }
-        if constexpr (WAVES > 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t w;
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) w[e] = v[u][c * CH + e];
-                    lds[(u * CPU + c) * T + tid] = w;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < CPU; ++c) {
-                    chunk_t r = lds[(u * CPU + c) * T + lane];  // wave 0: sign + for every reader
-#pragma unroll
-                    for (int w = 1; w < WAVES; ++w) {
-                        const chunk_t p = lds[(u * CPU + c) * T + w * 64 + lane];
-                        const A sign = (__builtin_popcount(w & wave) & 1) ? (A)-1 : (A)1;  // wave-uniform
-#pragma unroll
-                        for (int e = 0; e < CH; ++e) r[e] = fma_t(p[e], sign, r[e]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) v[u][c * CH + e] = r[e];
-                    if constexpr (U >= 8) __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();  // the exchange is read: the output image overwrites it
-        }
+#include "ct_hadamard_block.inc"  // WAVES > 1: its last barrier stands between the reads of the exchange and the output image laid over it
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             uint32_t w[8];
@@ -295,52 +243,36 @@ __global__ __launch_bounds__(64 * WAVES) void hadp_block_kernel(const void* x, v
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 constexpr int64_t kHadPMaxF32 = 16384, kHadPMaxF64 = 8192;  // float64 at 16384 spills here (it does not in the parent): the composition takes it
 
-template <int XDT, typename A, int U, int WAVES>
-static void launch_pblock(const void* x, void* out, int64_t blocks, const uint16_t* q, const uint16_t* p, const int8_t* signs, int transposed, HadScale<A> sn,
-                          hipStream_t s) {
-    const int64_t g = blocks < kMaxGridX ? blocks : kMaxGridX;
-    hipLaunchKernelGGL((hadp_block_kernel<XDT, A, U, WAVES>), dim3((unsigned)g), dim3(64 * WAVES), 0, s, x, out, blocks, q, p, signs, transposed, sn);
-}
-
+// the launch path of ct_hadamard.h around this file's two kernels
 template <int XDT, typename A>
 static int launch_prows(const void* x, void* out, int64_t numel, int64_t n, const uint16_t* q, const uint16_t* p, const int8_t* signs, int transposed,
                         hipStream_t s) {
-    HadScale<A> sn;
-    sn.sn = (A)__builtin_sqrt((double)n);
-    sn.rn = (A)1 / sn.sn;
-    sn.mode = log2_exact(n) % 2 == 0 ? HAD_MUL : (sizeof(A) == 4 ? HAD_FAST : HAD_IEEE);
-    if (n <= 512) {
-        const int64_t g = cdiv64(cdiv64(numel, 8), (int64_t)kBlock * kHadPGroupUnits);
-        CT_REQUIRE(g < ((int64_t)1 << 31), "tensor too large for one launch");
-        hipLaunchKernelGGL((hadp_group_kernel<XDT, A>), dim3((unsigned)g), dim3(kBlock), 0, s, x, out, numel, (int)n, q, p, signs, transposed, sn);
-        return CT_OK;
-    }
-    const int64_t blocks = numel / n;
-    switch (n) {
-        case 1024: launch_pblock<XDT, A, 2, 1>(x, out, blocks, q, p, signs, transposed, sn, s); break;
-        case 2048: launch_pblock<XDT, A, 4, 1>(x, out, blocks, q, p, signs, transposed, sn, s); break;
-        case 4096: launch_pblock<XDT, A, 4, 2>(x, out, blocks, q, p, signs, transposed, sn, s); break;
-        case 8192: launch_pblock<XDT, A, 4, 4>(x, out, blocks, q, p, signs, transposed, sn, s); break;
-        case 16384:
-            // 64 float64 accumulators per thread beside the gathers spill (the compiler's resource report): declined in check_hadp
-            if constexpr (sizeof(A) == 4) launch_pblock<XDT, A, 8, 4>(x, out, blocks, q, p, signs, transposed, sn, s);
-            break;
-        default: break;  // unreachable: check_hadp
-    }
-    return CT_OK;
+    return launch_had_rows<A>(
+        numel, n,
+        [&](dim3 grid, HadScale<A> sn) { hipLaunchKernelGGL((hadp_group_kernel<XDT, A>), grid, dim3(kBlock), 0, s, x, out, numel, (int)n, q, p, signs, transposed, sn); },
+        [&](auto U, auto W, dim3 grid, int64_t blocks, HadScale<A> sn) {
+            // n = 16384: 64 float64 accumulators per thread beside the gathers spill (the compiler's resource report): declined in check_hadp
+            if constexpr (U() < 8 || sizeof(A) == 4)
+                hipLaunchKernelGGL((hadp_block_kernel<XDT, A, U(), W()>), grid, dim3(64 * W()), 0, s, x, out, blocks, q, p, signs, transposed, sn);
+        });
 }
 
 static int check_hadp(const void* x, const void* out, int dt, int64_t numel, int64_t n, int acc64, const void* gather_in, const void* gather_out,
                       const int8_t* signs, int transposed) {
-    CT_REQUIRE(is_float_dt(dt), "dtype code %d is not a float type", dt);
-    CT_REQUIRE(n >= 1 && log2_exact(n) >= 0, "Cannot construct deterministic hadamard of size != 2^n");
-    CT_REQUIRE(numel >= 0 && numel % n == 0, "hadamard size %lld does not divide %lld elements", (long long)n, (long long)numel);
-    CT_REQUIRE(acc64 == 0 || acc64 == 1, "accumulator selector must be 0 (float32) or 1 (float64), got %d", acc64);
-    CT_REQUIRE(transposed == 0 || transposed == 1, "transposed must be 0 or 1, got %d", transposed);
-    CT_REQUIRE(gather_in != nullptr && gather_out != nullptr, "the permuted rotation needs both gather tables");
-    if (n > (acc64 ? kHadPMaxF64 : kHadPMaxF32)) CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %lld of the permuted rotation with the %s accumulator",
-                                                               (long long)n, (long long)(acc64 ? kHadPMaxF64 : kHadPMaxF32), acc64 ? "float64" : "float32");
-    if (!aligned16(x) || !aligned16(out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned tensors");
+    const int rc = check_had_common(
+        x, out, dt, numel, n, acc64, transposed,
+        [&]() -> int {
+            CT_REQUIRE(n >= 1 && log2_exact(n) >= 0, "Cannot construct deterministic hadamard of size != 2^n");
+            return CT_OK;
+        },
+        [&]() -> int {
+            CT_REQUIRE(gather_in != nullptr && gather_out != nullptr, "the permuted rotation needs both gather tables");
+            if (n > (acc64 ? kHadPMaxF64 : kHadPMaxF32))
+                CT_UNSUPPORTED("hadamard size %lld exceeds the supported maximum %lld of the permuted rotation with the %s accumulator", (long long)n,
+                               (long long)(acc64 ? kHadPMaxF64 : kHadPMaxF32), acc64 ? "float64" : "float32");
+            return CT_OK;
+        });
+    if (rc) return rc;
     if (!aligned16(gather_in) || !aligned16(gather_out)) CT_UNSUPPORTED("the hadamard kernels take 16-byte aligned gather tables");
     if (!aligned_to<8>(signs)) CT_UNSUPPORTED("the hadamard kernels take 8-byte aligned signs");
     return CT_OK;
@@ -351,11 +283,7 @@ static int dispatch_prows(const void* x, void* out, int dt, int64_t numel, int64
     if (numel == 0) return CT_OK;
     const uint16_t* q = static_cast<const uint16_t*>(gather_in);
     const uint16_t* p = static_cast<const uint16_t*>(gather_out);
-#define CT_HADP_ROWS(X) \
-    (acc64 ? launch_prows<X, double>(x, out, numel, n, q, p, signs, transposed, s) : launch_prows<X, float>(x, out, numel, n, q, p, signs, transposed, s))
-    const int rc = dt == CT_BF16 ? CT_HADP_ROWS(CT_BF16) : dt == CT_F16 ? CT_HADP_ROWS(CT_F16) : CT_HADP_ROWS(CT_F32);
-#undef CT_HADP_ROWS
-    return rc;
+    return for_had_types(dt, acc64, [&](auto X, auto a) { return launch_prows<X(), decltype(a)>(x, out, numel, n, q, p, signs, transposed, s); });
 }
 
 }  // namespace ct
@@ -375,22 +303,12 @@ int ct_hadamard_perm_rows(const void* x, void* out, int dt, int64_t numel, int64
 
 int ct_hadamard_perm_cols(const void* x, void* out, void* workspace, int dt, int64_t rows, int64_t cols, int64_t n, int acc64, const void* gather_in,
                           const void* gather_out, const int8_t* signs, int transposed, ct_stream_t stream) {
-    CT_REQUIRE(rows >= 0 && cols >= 0, "bad matrix shape (%lld, %lld)", (long long)rows, (long long)cols);
-    int rc = check_hadp(x, out, dt, rows, n, acc64, gather_in, gather_out, signs, transposed);  // n divides the ROWS
-    if (rc) return rc;
-    CT_REQUIRE(workspace != nullptr && aligned16(workspace), "ct_hadamard_perm_cols needs a 16-byte aligned workspace of rows * cols elements");
-    if (rows == 0 || cols == 0) return CT_OK;
-    CT_REQUIRE(cdiv64(rows, 64) * cdiv64(cols, 64) < ((int64_t)1 << 31), "matrix too large for one launch");
     hipStream_t s = as_stream(stream);
-    launch_transpose_words(x, workspace, dt_size(dt), rows, cols, s);
-    rc = hip_check(hipGetLastError(), "ct_hadamard_perm_cols[transpose]");
-    if (rc) return rc;
-    rc = dispatch_prows(workspace, workspace, dt, rows * cols, n, acc64, gather_in, gather_out, signs, transposed, s);  // in place: a block is in LDS before it is written
-    if (rc) return rc;
-    rc = hip_check(hipGetLastError(), "ct_hadamard_perm_cols[rows]");
-    if (rc) return rc;
-    launch_transpose_words(workspace, out, dt_size(dt), cols, rows, s);
-    CT_LAUNCH_CHECK("ct_hadamard_perm_cols[transpose back]");
+    // had_cols_form of ct_hadamard.h: launch_transpose_words, the row form in place (a block is in LDS before it is written), launch_transpose_words
+    return had_cols_form(
+        "ct_hadamard_perm_cols", "of rows * cols elements", x, out, workspace, dt, rows, cols, s,
+        [&] { return check_hadp(x, out, dt, rows, n, acc64, gather_in, gather_out, signs, transposed); },  // n divides the ROWS
+        [&](void* w, int64_t numel) { return dispatch_prows(w, w, dt, numel, n, acc64, gather_in, gather_out, signs, transposed, s); });
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@
 // Kernels (n the rotation block, L the segment; both runs of the contiguous last dimension)
 //   rot_group_kernel  n <= 512, L = 8 * 2^k <= 512: had_group_kernel's stages, then dyn_group_kernel's in-wave reduction and
 //                     QDQ on the same registers (both parents use units kBlock apart, U = 2)
-//   rot_block_kernel  n = 1024 .. 8192, one workgroup per block (had_block_kernel's stages incl. the LDS exchange); consecutive
+//   rot_block_kernel  n = 1024 .. 8192, one workgroup per block (had_block_kernel's stages incl. the LDS exchange: ct_hadamard_block.inc); consecutive
 //                     units sit in consecutive lanes, so L <= 512 is reduced inside the wave; L = n (the block is a token row)
 //                     is finished across the waves through LDS as dyn_seg_kernel does
 //   rot_seg_kernel    n <= 512 < L, n divides L: dyn_seg_kernel's staged form (a token row of up to 32768 elements held as raw
@@ -46,11 +46,9 @@ __device__ __forceinline__ void raw_pack(const float (&v)[8], RawUnit<XDT>& r) {
 }
 
 // ---- n <= 512 and L <= 512: lpb lanes per rotation block, lpg lanes per segment, U units per lane kBlock apart ---------------------
-constexpr int kRotGroupUnits = 2;  // kHadGroupUnits of ct_hadamard.hip and the U of ct_dynamic_qdq's group launch
-
 template <int XDT, bool GS>
 __global__ __launch_bounds__(kBlock) void rot_group_kernel(DynParams p, void* rotated, int64_t units, int n, int lpg, HadScale<float> sn) {
-    constexpr int U = kRotGroupUnits;
+    constexpr int U = kHadGroupUnits;
     const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
     const int lpb = n >> 3, lane = threadIdx.x & 63;
     float v[U][8];
@@ -102,10 +100,10 @@ __global__ __launch_bounds__(kBlock) void rot_group_kernel(DynParams p, void* ro
 // ---- n = 64 * WAVES * U * 8: one workgroup per rotation block; lpg lanes per segment, or the block is the segment (lpg == 0) ---------
 template <int XDT, bool GS, int U, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void rot_block_kernel(DynParams p, void* rotated, int64_t blocks, int lpg, HadScale<float> sn) {
-    constexpr int T = 64 * WAVES, N = T * U * 8;
-    typedef float chunk_t __attribute__((ext_vector_type(4)));
-    // chunk c of unit u of thread t at ((u * 2 + c) * T + t), as in had_block_kernel
-    __shared__ chunk_t lds[WAVES > 1 ? N / 4 : 1];
+    typedef float A;  // the names ct_hadamard_block.inc expects: float32 accumulation, two 16-byte chunks per unit
+    constexpr int T = 64 * WAVES, N = T * U * 8, CH = 4, CPU = 2;
+    typedef A chunk_t __attribute__((ext_vector_type(CH)));
+    __shared__ chunk_t lds[WAVES > 1 ? N / CH : 1];
     __shared__ MinMax red[WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
@@ -113,50 +111,7 @@ __global__ __launch_bounds__(64 * WAVES) void rot_block_kernel(DynParams p, void
         float v[U][8];
 #pragma unroll
         for (int u = 0; u < U; ++u) load8<XDT>(p.x, (u0 + u * T + tid) << 3, v[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            unit_stages(v[u], 8);
-            lane_stages(v[u], 64, lane);
-        }
-#pragma unroll
-        for (int h = 1; h < U; h <<= 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!(u & h)) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const float a = v[u][k], c = v[u | h][k];
-                        v[u][k] = a + c;
-                        v[u | h][k] = a - c;
-                    }
-                }
-            }
-        }
-        if constexpr (WAVES > 1) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c) lds[(u * 2 + c) * T + tid] = chunk_t{v[u][4 * c], v[u][4 * c + 1], v[u][4 * c + 2], v[u][4 * c + 3]};
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    chunk_t r = lds[(u * 2 + c) * T + lane];  // wave 0: sign + for every reader
-#pragma unroll
-                    for (int w = 1; w < WAVES; ++w) {
-                        const chunk_t q = lds[(u * 2 + c) * T + w * 64 + lane];
-                        const float sign = (__builtin_popcount(w & wave) & 1) ? -1.0f : 1.0f;  // wave-uniform
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) r[e] = fma_t(q[e], sign, r[e]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[u][4 * c + e] = r[e];
-                }
-            }
-            __syncthreads();  // lds is rewritten by the next block
-        }
+#include "ct_hadamard_block.inc"
         MinMax m[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -265,8 +220,7 @@ __global__ __launch_bounds__(kSegMaxThreads) void rot_seg_kernel(DynParams p, vo
 
 template <int XDT, bool GS, int U, int WAVES>
 static void launch_rot_block(const DynParams& p, void* rotated, int64_t blocks, int lpg, HadScale<float> sn, hipStream_t s) {
-    const int64_t g = blocks < kMaxGridX ? blocks : kMaxGridX;
-    hipLaunchKernelGGL((rot_block_kernel<XDT, GS, U, WAVES>), dim3((unsigned)g), dim3(64 * WAVES), 0, s, p, rotated, blocks, lpg, sn);
+    hipLaunchKernelGGL((rot_block_kernel<XDT, GS, U, WAVES>), capped_grid(blocks), dim3(64 * WAVES), 0, s, p, rotated, blocks, lpg, sn);
 }
 
 // n = 16384 (<8, 4>: 64 values per thread, 284 VGPRs + 28 AGPRs, one wave per SIMD) was built without scratch and MEASURED slower than the two
@@ -291,16 +245,13 @@ int ct_hadamard_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, in
     if (numel == 0) return CT_OK;
     if (!aligned16(x) || (out && !aligned16(out)) || (rotated_out && !aligned16(rotated_out))) CT_UNSUPPORTED("the fused rotation takes 16-byte aligned tensors");
     if (L % 8) CT_UNSUPPORTED("segments of %lld elements are not whole 16-byte units", (long long)L);
-    HadScale<float> sn;
-    sn.sn = (float)__builtin_sqrt((double)n);
-    sn.rn = 1.0f / sn.sn;
-    sn.mode = log2_exact(n) % 2 == 0 ? HAD_MUL : HAD_FAST;
+    const HadScale<float> sn = make_had_scale<float>(n);
     hipStream_t s = as_stream(stream);
     const int64_t upr = L / 8;
     const bool in_wave = upr <= 64 && log2_exact(upr) >= 0;  // dyn_group_kernel's segments
     if (n <= 512 && in_wave) {
         const int64_t units = numel / 8;
-        const int64_t g = cdiv64(units, (int64_t)kBlock * kRotGroupUnits);
+        const int64_t g = cdiv64(units, (int64_t)kBlock * kHadGroupUnits);
         CT_REQUIRE(g < ((int64_t)1 << 31), "activation too large for one launch");
         CT_DYN_DISPATCH(xdt, global_scale, hipLaunchKernelGGL((rot_group_kernel<X, G>), dim3((unsigned)g), dim3(kBlock), 0, s, p, rotated_out, units, (int)n, (int)upr, sn));
         CT_LAUNCH_CHECK("ct_hadamard_dynamic_qdq[group]");
@@ -311,8 +262,7 @@ int ct_hadamard_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, in
         int64_t nt = cdiv64(cdiv64(upr, kSegUnits), 64) * 64;
         if (nt > kSegMaxThreads) nt = kSegMaxThreads;
         if (upr > nt * kSegUnits) CT_UNSUPPORTED("rows of %lld elements exceed the staged form (%d)", (long long)L, kSegMaxThreads * kSegUnits * 8);
-        const int64_t g = segs < kMaxGridX ? segs : kMaxGridX;
-        CT_DYN_DISPATCH(xdt, global_scale, hipLaunchKernelGGL((rot_seg_kernel<X, G>), dim3((unsigned)g), dim3((unsigned)nt), 0, s, p, rotated_out, (int)n, sn));
+        CT_DYN_DISPATCH(xdt, global_scale, hipLaunchKernelGGL((rot_seg_kernel<X, G>), capped_grid(segs), dim3((unsigned)nt), 0, s, p, rotated_out, (int)n, sn));
         CT_LAUNCH_CHECK("ct_hadamard_dynamic_qdq[row]");
     }
     if (n > kRotMaxBlock) CT_UNSUPPORTED("hadamard size %lld exceeds the fused maximum %lld", (long long)n, (long long)kRotMaxBlock);
