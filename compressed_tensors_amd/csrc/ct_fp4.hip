@@ -107,8 +107,10 @@ __device__ __forceinline__ uint32_t fp4_quant_unit(const uint32_t (&ws)[4], floa
         for (int j = 0; j < 4; ++j) {
             float x0, x1;
             fp4_unpack_pair<XDT>(ws[j], x0, x1);
-            t[2 * j] = fp4_fast_quotient(x0, s_eff, r, lim);
-            t[2 * j + 1] = fp4_fast_quotient(x1, s_eff, r, lim);
+            // a NaN element under a scale inside the range: the clamp (v_med3_f32) would hand back +-lim and the code of 6, where upstream's NaN
+            // quotient has the magnitude 0 (see below)
+            t[2 * j] = x0 != x0 ? 0.0f : fp4_fast_quotient(x0, s_eff, r, lim);
+            t[2 * j + 1] = x1 != x1 ? 0.0f : fp4_fast_quotient(x1, s_eff, r, lim);
         }
         return fp4_word_signbit(t);
     }
@@ -118,7 +120,7 @@ __device__ __forceinline__ uint32_t fp4_quant_unit(const uint32_t (&ws)[4], floa
         fp4_unpack_pair<XDT>(ws[j], x0, x1);
         float q0 = x0 / s_eff, q1 = x1 / s_eff;
         if (in_dtype) { q0 = round_to<XDT>(q0); q1 = round_to<XDT>(q1); }  // the quotient stays in x.dtype
-        // a NaN quotient (a NaN element, a NaN scale, inf / inf: only this path sees them — a NaN or inf scale fails both range tests above) has the
+        // a NaN quotient (a NaN scale, inf / inf: only this path sees them — a NaN or inf scale fails both range tests above; a NaN element) has the
         // magnitude 0 upstream: cast_to_fp4's comparisons leave the NaN alone and pack_fp4_to_uint8's int8 cast makes it 0, where the hardware
         // conversion would saturate it to the code of 6.  Its sign bit is the sign of a NaN, which nothing compares
         t[2 * j] = q0 != q0 ? 0.0f : q0; t[2 * j + 1] = q1 != q1 ? 0.0f : q1;

@@ -1195,7 +1195,9 @@ __global__ __launch_bounds__(kBlock) void q8_dequant_kernel(W4Params p) {
 // on the raw pairs (f8_f16_unit_ok): every element finite (inf / NaN: the Newton correction would turn inf into NaN), and zero or at least 2^-13 |s| in
 // magnitude — below that the shortcut's quotient may differ from the IEEE one in the last fp16-subnormal place (ct_selftest_f16_div), i.e. be -0 where the
 // divide gives -2^-24, and `+ zero_point` turns the first into +0 and leaves the second negative.  A -0 weight needs no care HERE (the Newton step returns +0
-// for it, and -0 + z == +0 + z); WITHOUT a zero point the sign of a zero result is the weight's, so a unit that holds a -0 takes the scalar form too.
+// for it, and -0 + z == +0 + z) — unless the zero point is itself -0 (a float8 zero point may be: byte 0x80), under which -0 + z is -0 and +0 + z is +0:
+// f8_quant_words keeps such a group on the scalar form.  WITHOUT a zero point the sign of a zero result is the weight's, so a unit that holds a -0 takes the
+// scalar form too.
 template <bool ZP>
 __device__ __forceinline__ bool f8_f16_unit_ok(const u32x4& raw, float s) {
     // |x| >= thr  <=>  bits(|x|) >= bits(thr) for non-negative fp16; thr = 2^-13 |s| rounded to fp16 and moved one place up
@@ -1239,7 +1241,7 @@ __device__ __forceinline__ void f8_quant_words_f16(const u32x4& raw, float s, fl
 template <int DT, bool FAST, bool ZP>
 __device__ __forceinline__ void f8_quant_words(const u32x4& raw, float s, float rs, float z, uint32_t& lo, uint32_t& hi) {
     if constexpr (DT == CT_F16 && FAST) {
-        if (f8_f16_unit_ok<ZP>(raw, s)) {  // lanes almost always agree
+        if (!(ZP && f_bits(z) == 0x80000000u) && f8_f16_unit_ok<ZP>(raw, s)) {  // lanes almost always agree
             f8_quant_words_f16<ZP>(raw, s, rs, z, lo, hi);
             return;
         }
