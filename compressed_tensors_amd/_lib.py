@@ -148,6 +148,11 @@ _PROTOTYPES = {
     "ct_fp8block_dequant_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_fp8block_mxfp4_plan": ([_P, _I], _L),
     "ct_fp8block_mxfp4_batch": ([_P, _I, _L, _I, _S], _I),
+    "ct_fp8block_mxfp8_plan": ([_P, _I], _L),
+    "ct_fp8block_mxfp8_batch": ([_P, _I, _L, _I, _P, _S], _I),
+    "ct_fp8block_nvfp4_plan": ([_P, _I], _L),
+    "ct_fp8block_nvfp4_amax_batch": ([_P, _I, _L, _I, _S], _I),
+    "ct_fp8block_nvfp4_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_bitmask_row_popcount": ([_P, _L, _L, _P, _S], _I),
     "ct_sparse24_compress": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_sparse24_mask": ([_P, _I, _L, _P, _S], _I),
@@ -213,7 +218,16 @@ class Fp8BlockMxItem(ctypes.Structure):
                 ("units", _L), ("first_block", _L)]
 
 
+class Fp8BlockNvItem(ctypes.Structure):
+    """struct ct_fp8block_nv_item of include/ct_hip.h (a row of ct_fp8block_nvfp4_amax_batch's and ct_fp8block_nvfp4_batch's table)"""
+    _fields_ = [("w", _P), ("scale", _P), ("packed", _P), ("scale_f8", _P), ("key", _P), ("global_scale", _P), ("rows", _L), ("cols", _L),
+                ("block_h", _L), ("block_w", _L), ("scale_shape", _L * 2), ("sdt", _c.c_int32), ("reserved", _c.c_int32), ("scale_stride", _L * 2),
+                ("units_per_row", _L), ("units", _L), ("first_block", _L)]
+
+
 FP8BLOCK_MX_GROUPS_PER_BLOCK = 512  # CT_FP8BLOCK_MX_GROUPS_PER_BLOCK of include/ct_hip.h
+FP8BLOCK_MXFP8_GROUPS_PER_BLOCK = 512  # CT_FP8BLOCK_MXFP8_GROUPS_PER_BLOCK
+FP8BLOCK_NV_GROUPS_PER_BLOCK = 1024  # CT_FP8BLOCK_NV_GROUPS_PER_BLOCK
 
 
 class AttnTensor(ctypes.Structure):

@@ -143,6 +143,8 @@ __all__ = [
     "rtn_mxfp4_outputs",
     "rtn_mxfp4_launch",
     "fp8block_to_mxfp4",
+    "fp8block_to_mxfp8",
+    "fp8block_to_nvfp4",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -1932,19 +1934,27 @@ def fp8block_to_mxfp4(weight: torch.Tensor, weight_scale_inv: torch.Tensor, *, w
     MXFP4: (packed uint8 (R, C / 2), E8M0 codes uint8 (R, C / 32)), byte for byte `rtn_mxfp4_quantize_and_pack` of the weight dequantized to `dtype`
     (bfloat16 or float16), which is never materialised (`ct_fp8block_mxfp4_batch`; a block width that is no multiple of 32 takes the two launches).
     Host tensors in, host tensors out; device tensors stay on their device."""
-    from .entrypoints.convert import fp8block_mxfp4 as fx
+    from .entrypoints.convert import fp8block_transcode as ft
 
-    if dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"fp8block_to_mxfp4: dtype must be torch.bfloat16 or torch.float16, got {dtype}")
-    block = fx._block_size("fp8block_to_mxfp4", weight_block_size)
-    fx._check_module("weight", weight, weight_scale_inv)
-    if weight.shape[1] % 32 != 0:
-        raise ValueError(f"tensor column shape must be divisble by the given group_size 32 but got {weight.shape[1]}")
-    on_device = weight.device.type == "cuda"
-    got = fx.ReadyDict()
-    fx.transcode(got, ["w"], [(weight, weight_scale_inv)], block, dtype, weight.device if on_device else _lib.require_device(), True, to_host=not on_device)
-    got.wait()
-    return got["w.weight_packed"], got["w.weight_scale"]
+    return ft.transcode_one(ft.MXFP4, "fp8block_to_mxfp4", weight, weight_scale_inv, weight_block_size, dtype)
+
+
+def fp8block_to_mxfp8(weight: torch.Tensor, weight_scale_inv: torch.Tensor, *, weight_block_size=(128, 128), dtype: torch.dtype = torch.bfloat16):
+    """`fp8block_to_mxfp4` for MXFP8: (float8_e4m3fn codes (R, C), E8M0 codes uint8 (R, C / 32)), byte for byte
+    `rtn_quantize_group8(..., group_size=32, qtype="float", mx=True)` of the weight dequantized to `dtype`, which is never materialised
+    (`ct_fp8block_mxfp8_batch`; a block width that is no multiple of 32 takes the two launches)."""
+    from .entrypoints.convert import fp8block_transcode as ft
+
+    return ft.transcode_one(ft.MXFP8, "fp8block_to_mxfp8", weight, weight_scale_inv, weight_block_size, dtype)
+
+
+def fp8block_to_nvfp4(weight: torch.Tensor, weight_scale_inv: torch.Tensor, *, weight_block_size=(128, 128), dtype: torch.dtype = torch.bfloat16):
+    """`fp8block_to_mxfp4` for NVFP4: (packed uint8 (R, C / 2), float8_e4m3fn scales (R, C / 16), float32 (1,) global scale), byte for byte
+    `rtn_nvfp4_quantize_and_pack` of the weight dequantized to `dtype`, which is never materialised (`ct_fp8block_nvfp4_amax_batch` and
+    `ct_fp8block_nvfp4_batch`; a block width that is no multiple of 16 takes the composition)."""
+    from .entrypoints.convert import fp8block_transcode as ft
+
+    return ft.transcode_one(ft.NVFP4, "fp8block_to_nvfp4", weight, weight_scale_inv, weight_block_size, dtype)
 
 
 def rtn_nvfp4_quantize_and_pack(x: torch.Tensor, global_scale: Optional[torch.Tensor] = None, *, return_scale: bool = False):

@@ -343,18 +343,6 @@ constexpr int kFp8bMxStride = kBlock / 2;                        // groups betwe
 constexpr int64_t kFp8bMxGroupsPerBlock = int64_t(kFp8bMxStride) * kFp8bMxSteps;
 static_assert(kFp8bMxGroupsPerBlock == CT_FP8BLOCK_MX_GROUPS_PER_BLOCK, "include/ct_hip.h states the workgroup's share");
 
-// two products -> one word of two XDT values, rounded as store8 rounds them
-template <int XDT>
-__device__ __forceinline__ uint32_t fp8b_mx_pair(float a, float b) {
-    if constexpr (XDT == CT_BF16) {
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        typedef bf16_t b2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{a, b}, b2));
-    } else {
-        return f_to_f16_bits(a) | (f_to_f16_bits(b) << 16);
-    }
-}
-
 // half a group: 16 codes under the scale s -> max |d| joined with the neighbour's, the group's MX scale, 8 bytes of nibbles
 template <int XDT>
 __device__ __forceinline__ void fp8b_mx_half(const ct_fp8block_mx_item& it, int64_t g, int half, float s, const u32x4 q) {
@@ -515,6 +503,96 @@ __global__ __launch_bounds__(kBlock) void rtn_nvfp4_batch_kernel(const ct_w4_ite
     const float gs = gparam_from_amax<XDT>(m.nan ? __builtin_nanf("") : m.mx);
     if (l == 0) static_cast<float*>(const_cast<void*>(it.scale))[0] = gs;
     rtn_nvfp4_lane<XDT>(static_cast<const u32x4*>(it.src), gs, static_cast<u32x4*>(it.dst), static_cast<uint16_t*>(it.zp_packed), nullptr, l);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// FP8 block-quantized weights -> NVFP4 over a table in TWO launches (ct_fp8block_nvfp4_amax_batch, ct_fp8block_nvfp4_batch): the element of
+// ct_fp8block.hip rounded to the dense dtype XDT in registers, then rtn_nvfp4_amax_batch_kernel's fold and rtn_nvfp4_batch_kernel's body on those
+// bits — byte for byte the three launches, 1 + (1 + 0.5 + 1/16) B per element instead of (1 + 2) + 2 + (2 + 0.5 + 1/16).
+// Work unit: one group of 16 codes of one row (cols % 16 == 0: group g is the elements 16 g .. 16 g + 15 of the flat tensor; block_w % 16 == 0: it
+// lies under one scale) — ONE 16-byte load, so a lane owns whole groups and nothing crosses lanes.  Lane t takes the groups wg_g0 + t + 256 k,
+// k = 0..3: every load instruction of a wave reads 1 KiB contiguous, every nibble store writes 512 B contiguous (8 bytes per lane), every scale
+// store 64 B; all loads before the arithmetic as in fp8b_mx_groups, the step-by-step loop in an item's last workgroup only.
+constexpr int kFp8bNvSteps = 4;                                  // groups per lane
+constexpr int64_t kFp8bNvGroupsPerBlock = int64_t(kBlock) * kFp8bNvSteps;
+static_assert(kFp8bNvGroupsPerBlock == CT_FP8BLOCK_NV_GROUPS_PER_BLOCK, "include/ct_hip.h states the workgroup's share");
+
+// body(group, its scale_inv, its 16 codes) for the lane's groups.  A lane past the item's end does nothing and stays: the fold reduces over the wave
+template <int SDT, typename Body>
+__device__ __forceinline__ void fp8b_nv_groups(const ct_fp8block_nv_item& it, int64_t wg_g0, Body&& body) {
+    const int64_t g0 = wg_g0 + threadIdx.x, units = it.units;
+    if (g0 >= units) return;
+    uint32_t rs[kFp8bNvSteps], cs[kFp8bNvSteps];
+    fp8b_step_coords<kFp8bNvSteps>(g0, it.units_per_row, kBlock, rs, cs);
+    const auto src = fp8b_global<u32x4>(it.w);
+    const auto scale_of = [&](int k) { return fp8b_unit_scale<SDT>(it, rs[k], 16u * cs[k]); };
+    const auto group = [&](int k) { return g0 + (int64_t)kBlock * k; };
+    if (group(kFp8bNvSteps - 1) < units) {
+        // every step exists: the four 16-byte code loads and the four scale loads in flight, with no condition the compiler could sink them into
+        u32x4 q[kFp8bNvSteps];
+        float s[kFp8bNvSteps];
+#pragma unroll
+        for (int k = 0; k < kFp8bNvSteps; ++k) {
+            q[k] = src[group(k)];
+            s[k] = scale_of(k);
+        }
+#pragma unroll
+        for (int k = 0; k < kFp8bNvSteps; ++k) body(group(k), s[k], q[k]);
+    } else {
+        // the item's last workgroup
+        for (int k = 0; k < kFp8bNvSteps && group(k) < units; ++k) body(group(k), scale_of(k), src[group(k)]);
+    }
+}
+
+// one straight-line body per scale dtype: a branch on the dtype between the loads would make each wait for the last
+template <typename Body>
+__device__ __forceinline__ void fp8b_nv_groups_of(const ct_fp8block_nv_item& it, int64_t wg_g0, Body&& body) {
+    switch (it.sdt) {
+        case CT_F32: fp8b_nv_groups<CT_F32>(it, wg_g0, body); break;
+        case CT_BF16: fp8b_nv_groups<CT_BF16>(it, wg_g0, body); break;
+        default: fp8b_nv_groups<CT_F16>(it, wg_g0, body); break;
+    }
+}
+
+// FOLD: max |d| of the item into its key, as rtn_nvfp4_amax_batch_kernel folds max |x|
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void fp8block_nvfp4_amax_kernel(const ct_fp8block_nv_item* __restrict__ items, int n) {
+    const ct_fp8block_nv_item it = fp8b_find(items, n, (int64_t)blockIdx.x);
+    const int64_t wg_g0 = ((int64_t)blockIdx.x - it.first_block) * kFp8bNvGroupsPerBlock;
+    uint32_t acc = 0;  // a lane past the end carries the identity through the reduction
+    fp8b_nv_groups_of(it, wg_g0, [&](int64_t, float s, const u32x4 q) {
+        uint32_t d[8];
+        fp8b_dense16<XDT>(q, s, d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = absmax_acc(acc, d[i]);
+    });
+    acc = absmax_group_reduce(acc, 64);
+    if ((threadIdx.x & 63u) == 0u) {
+        const uint32_t h = (acc & 0xffffu) > (acc >> 16) ? (acc & 0xffffu) : (acc >> 16);
+        if (h > __hip_atomic_load(it.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(it.key, h);
+    }
+}
+
+// QUANTIZE: rtn_nvfp4_lane's arithmetic, one group at a time, under the global scale of the item's key; the item's first lane stores it
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void fp8block_nvfp4_kernel(const ct_fp8block_nv_item* __restrict__ items, int n) {
+    const ct_fp8block_nv_item it = fp8b_find(items, n, (int64_t)blockIdx.x);
+    const int64_t wg_g0 = ((int64_t)blockIdx.x - it.first_block) * kFp8bNvGroupsPerBlock;
+    const MinMax m = absmax_finish<XDT>(it.key[0]);  // the key is one 16-bit magnitude: the high half is zero
+    const float gs = gparam_from_amax<XDT>(m.nan ? __builtin_nanf("") : m.mx);
+    if (wg_g0 == 0 && threadIdx.x == 0) it.global_scale[0] = gs;
+    fp8b_nv_groups_of(it, wg_g0, [&](int64_t g, float s, const u32x4 q) {
+        uint32_t d[8];
+        fp8b_dense16<XDT>(q, s, d);
+        uint32_t acc = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = absmax_acc(acc, d[i]);
+        const float sc = compute_qparams_float<XDT>(absmax_finish<XDT>(acc), QP_NVFP4, gs);
+        it.scale_f8[g] = (uint8_t)(f2_to_fp8x2(sc, sc) & 0xffu);  // scale.to(float8_e4m3fn): exact, the value is float8 already
+        const uint32_t lo4[4] = {d[0], d[1], d[2], d[3]}, hi4[4] = {d[4], d[5], d[6], d[7]};
+        const uint32_t w0 = fp4_quant_unit<XDT, true>(lo4, sc, gs, false), w1 = fp4_quant_unit<XDT, true>(hi4, sc, gs, false);
+        stream_store8(it.packed + 8 * g, u32x2{w0, w1});
+    });
 }
 
 // every mantissa of s in [1, 2) against every mantissa of x in [1, 2) (7 bits bf16, 10 bits fp16; `xbits` of them):
@@ -1132,6 +1210,40 @@ int ct_fp8block_mxfp4_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t
     CT_REQUIRE(items_dev != nullptr, "ct_fp8block_mxfp4_batch: table is NULL");
     for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((fp8block_mxfp4_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_fp8block_mxfp4_batch");
+}
+
+static int64_t fp8b_nv_plan_item(ct_fp8block_nv_item& it, int i, int64_t first_block) {
+    const char* const name = "ct_fp8block_nvfp4_plan";
+    if (!fp8b_plan_source(it, i, name, 16, "NVFP4", it.w && it.scale && it.packed && it.scale_f8 && it.key && it.global_scale)) return -1;
+    if (!aligned16(it.packed)) {
+        set_error("%s: item %d: weight_packed is not 16-byte aligned", name, i);
+        return -1;
+    }
+    if (!(aligned_to<4>(it.key) && aligned_to<4>(it.global_scale))) {
+        set_error("%s: item %d: the amax key and weight_global_scale must be 4-byte aligned", name, i);
+        return -1;
+    }
+    it.reserved = 0;
+    it.first_block = first_block;
+    return cdiv64(it.units, kFp8bNvGroupsPerBlock);
+}
+
+int64_t ct_fp8block_nvfp4_plan(ct_fp8block_nv_item* items, int n) { return plan_table("ct_fp8block_nvfp4_plan", items, n, fp8b_nv_plan_item); }
+
+int ct_fp8block_nvfp4_amax_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "ct_fp8block_nvfp4_amax_batch: the dense dtype must be bfloat16 or float16 (dtype code %d)", xdt);
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr, "ct_fp8block_nvfp4_amax_batch: table is NULL");
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((fp8block_nvfp4_amax_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
+    CT_LAUNCH_CHECK("ct_fp8block_nvfp4_amax_batch");
+}
+
+int ct_fp8block_nvfp4_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "ct_fp8block_nvfp4_batch: the dense dtype must be bfloat16 or float16 (dtype code %d)", xdt);
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr, "ct_fp8block_nvfp4_batch: table is NULL");
+    for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((fp8block_nvfp4_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
+    CT_LAUNCH_CHECK("ct_fp8block_nvfp4_batch");
 }
 
 int ct_rtn_nvfp4_quant_pack(const void* x, int xdt, int64_t rows, int64_t cols, const float* global_scale, uint8_t* packed, uint8_t* scale_f8,

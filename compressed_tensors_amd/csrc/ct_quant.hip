@@ -13,6 +13,7 @@
 #include "ct_quant_core.h"
 #include "ct_quant_lean.h"
 #include "ct_minmax.h"
+#include "ct_fp8block.h"
 #include "ct_w4_variant.h"
 #include "ct_plan.h"
 
@@ -1992,6 +1993,87 @@ __global__ __launch_bounds__(kBlock) void rtn_group8_batch_kernel(const ct_w4_it
                                    static_cast<int8_t*>(const_cast<void*>(it.zp)), static_cast<uint8_t*>(it.zp_packed), mx_table, flip, l);
 }
 
+// ------------------------------------------------------------------------------------------
+// FP8 block-quantized weights -> MXFP8 in ONE pass over a table (ct_fp8block_mxfp8_batch): the element of ct_fp8block.hip, rounded to the dense dtype
+// XDT in registers, then rtn_group8_lane<XDT, QP_MXFP8, true>'s arithmetic on those bits — byte for byte ct_fp8block_dequant_batch followed by the
+// one-pass MXFP8 table, 1 + 1 + 1/32 B per element instead of (1 + 2) + (2 + 1 + 1/32).
+// Work unit and lane layout: fp8b_mx_groups' (ct_fp4.hip), the measured shape.  One MX group is 32 codes of one row (cols % 32 == 0, block_w % 32 == 0:
+// one scale); TWO neighbouring lanes share it, 16 codes each: one 16-byte load, max |d| of the halves joined by one absmax_group_reduce(acc, 2), one
+// 16-byte non-temporal store of the lane's 16 output codes — a wave reads and writes 1 KiB contiguous each way —, the exponent byte from the even lane.
+// Lane t takes half t % 2 of the groups wg_g0 + t / 2 + 128 k, k = 0..3, all loads before the arithmetic.  The table row is ct_fp8block_mx_item with
+// `packed` = the float8 codes (rows, cols).
+constexpr int kFp8bMx8Steps = 4;                                 // groups per lane pair
+constexpr int kFp8bMx8Stride = kBlock / 2;                       // groups between a lane's steps
+constexpr int64_t kFp8bMx8GroupsPerBlock = int64_t(kFp8bMx8Stride) * kFp8bMx8Steps;
+static_assert(kFp8bMx8GroupsPerBlock == CT_FP8BLOCK_MXFP8_GROUPS_PER_BLOCK, "include/ct_hip.h states the workgroup's share");
+
+// half a group: 16 codes under the scale s -> max |d| joined with the neighbour's, the group's MX scale, 16 float8 codes
+template <int XDT>
+__device__ __forceinline__ void fp8b_mx8_half(const ct_fp8block_mx_item& it, int64_t g, int half, float s, const u32x4 q, const uint8_t* __restrict__ mx_table) {
+    uint32_t d[8];
+    fp8b_dense16<XDT>(q, s, d);
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = absmax_acc(acc, d[i]);
+    acc = absmax_group_reduce(acc, 2);  // both lanes of a pair are here together: they share g
+    const float sc = compute_qparams_float<XDT>(absmax_finish<XDT>(acc), QP_MXFP8, 1.0f);
+    if (half == 0) {
+        // as rtn_group8_lane: the exponent field of a finite scale, else the byte of the table ct_mx_scale_compress reads
+        const uint32_t ef = (f_bits(sc) >> 23) & 0xffu;
+        it.e8m0[g] = ef != 0xffu ? (uint8_t)ef : mx_table[XDT == CT_BF16 ? f_to_bf16_bits(sc) : f_to_f16_bits(sc)];
+    }
+    const float rs = 1.0f / sc;
+    const bool fast = fast_scale_ok<XDT>(sc);  // as rtn_group8_lane chooses the quotient
+    const u32x4 r[2] = {u32x4{d[0], d[1], d[2], d[3]}, u32x4{d[4], d[5], d[6], d[7]}};
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        // -0.0 + 0 = +0.0: the zero-point add is kept (f8_quant_lane)
+        if (fast) f8_quant_words<XDT, true, true>(r[i], sc, rs, 0.0f, w[2 * i], w[2 * i + 1]);
+        else f8_quant_words<XDT, false, true>(r[i], sc, rs, 0.0f, w[2 * i], w[2 * i + 1]);
+    }
+    stream_store16(it.packed + 32 * g + 16 * half, u32x4{w[0], w[1], w[2], w[3]});
+}
+
+template <int XDT, int SDT>
+__device__ __forceinline__ void fp8b_mx8_groups(const ct_fp8block_mx_item& it, int64_t wg_g0, const uint8_t* __restrict__ mx_table) {
+    const int half = threadIdx.x & 1;
+    const int64_t g0 = wg_g0 + (threadIdx.x >> 1), units = it.units;
+    if (g0 >= units) return;  // no barriers below; a pair leaves together
+    uint32_t rs[kFp8bMx8Steps], cs[kFp8bMx8Steps];
+    fp8b_step_coords<kFp8bMx8Steps>(g0, it.units_per_row, kFp8bMx8Stride, rs, cs);
+    const auto src = fp8b_global<u32x4>(it.w);
+    const auto scale_of = [&](int k) { return fp8b_unit_scale<SDT>(it, rs[k], 32u * cs[k]); };
+    const auto group = [&](int k) { return g0 + (int64_t)kFp8bMx8Stride * k; };
+    if (group(kFp8bMx8Steps - 1) < units) {
+        // every step exists: the four 16-byte code loads and the four scale loads in flight, with no condition the compiler could sink them into
+        u32x4 q[kFp8bMx8Steps];
+        float s[kFp8bMx8Steps];
+#pragma unroll
+        for (int k = 0; k < kFp8bMx8Steps; ++k) {
+            q[k] = src[2 * group(k) + half];
+            s[k] = scale_of(k);
+        }
+#pragma unroll
+        for (int k = 0; k < kFp8bMx8Steps; ++k) fp8b_mx8_half<XDT>(it, group(k), half, s[k], q[k], mx_table);
+    } else {
+        // the item's last workgroup
+        for (int k = 0; k < kFp8bMx8Steps && group(k) < units; ++k) fp8b_mx8_half<XDT>(it, group(k), half, scale_of(k), src[2 * group(k) + half], mx_table);
+    }
+}
+
+template <int XDT>
+__global__ __launch_bounds__(kBlock) void fp8block_mxfp8_kernel(const ct_fp8block_mx_item* __restrict__ items, int n, const uint8_t* __restrict__ mx_table) {
+    const ct_fp8block_mx_item it = fp8b_find(items, n, (int64_t)blockIdx.x);
+    const int64_t wg_g0 = ((int64_t)blockIdx.x - it.first_block) * kFp8bMx8GroupsPerBlock;
+    // one straight-line body per scale dtype: a branch on the dtype between the loads would make each wait for the last
+    switch (it.sdt) {
+        case CT_F32: fp8b_mx8_groups<XDT, CT_F32>(it, wg_g0, mx_table); break;
+        case CT_BF16: fp8b_mx8_groups<XDT, CT_BF16>(it, wg_g0, mx_table); break;
+        default: fp8b_mx8_groups<XDT, CT_F16>(it, wg_g0, mx_table); break;
+    }
+}
+
 // fake_quantize fast path (forward_helpers.py:180-215): x, scale and the result share one 16-bit dtype.
 // Same flat unit stream: lane = UNROLL units one block apart, 16 B in, 16 B out.
 template <int DT, int UNROLL, bool HAS_ZP>
@@ -2776,6 +2858,29 @@ int ct_rtn_quant_group8_batch(const ct_w4_item* items_dev, int n, int64_t total_
 }
 #undef CT_G8_DISPATCH
 #undef CT_G8_KIND_CHECK
+
+static int64_t fp8b_mx8_plan_item(ct_fp8block_mx_item& it, int i, int64_t first_block) {
+    const char* const name = "ct_fp8block_mxfp8_plan";
+    if (!fp8b_plan_source(it, i, name, 32, "MX", it.w && it.scale && it.packed && it.e8m0)) return -1;
+    if (!aligned16(it.packed)) {
+        set_error("%s: item %d: the float8 output is not 16-byte aligned", name, i);
+        return -1;
+    }
+    it.reserved = 0;
+    it.first_block = first_block;
+    return cdiv64(it.units, kFp8bMx8GroupsPerBlock);
+}
+
+int64_t ct_fp8block_mxfp8_plan(ct_fp8block_mx_item* items, int n) { return plan_table("ct_fp8block_mxfp8_plan", items, n, fp8b_mx8_plan_item); }
+
+int ct_fp8block_mxfp8_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t total_blocks, int xdt, const uint8_t* code_table, ct_stream_t stream) {
+    CT_REQUIRE(xdt == CT_BF16 || xdt == CT_F16, "ct_fp8block_mxfp8_batch: the dense dtype must be bfloat16 or float16 (dtype code %d)", xdt);
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr && code_table != nullptr, "ct_fp8block_mxfp8_batch: the table and the E8M0 code table are required");
+    for_dt16(xdt, [&](auto DT) {
+        hipLaunchKernelGGL((fp8block_mxfp8_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n, code_table); });
+    CT_LAUNCH_CHECK("ct_fp8block_mxfp8_batch");
+}
 
 int ct_unpack_dequant(const int32_t* packed, int64_t rows, int64_t words, int64_t cols, int bits,
                       const void* scale, int sdt, const void* zp, int zdt, int64_t rdiv, int64_t cdiv,

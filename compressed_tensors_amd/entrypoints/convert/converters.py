@@ -138,6 +138,11 @@ class CompressedTensorsDequantizer(Converter):
             raise ValueError("Model quantization config was found, but it does not match expected compressed-tensors quantization format")
         self.ignore = list(data.get("ignore") or []) + list(ignore)
         self.schemes: List[QuantizationScheme] = []
+        # `dynamic="local"` activations (the NVFP4 preset) are read as static below, so that a calibrated checkpoint's `input_global_scale` is a
+        # partner of its weight.  A data-free conversion (FP8BlockToNVFP4Converter) writes none: there the name is a partner only where the
+        # checkpoint holds it
+        self._local_inputs = [((group.get("input_activations") or {}).get("dynamic") == "local") for group in data["config_groups"].values()]
+        self._files, self._stored = files, None
         for group in data["config_groups"].values():
             scheme = QuantizationScheme(targets=list(group.get("targets", [])), weights=_args_from_dict(group.get("weights")),
                                         input_activations=_args_from_dict(group.get("input_activations")),
@@ -148,6 +153,21 @@ class CompressedTensorsDequantizer(Converter):
 
     def _compressor(self, scheme):
         return BaseCompressor.get_value_from_registry(scheme.format)
+
+    def _param_names(self, scheme, module_name: str, present) -> tuple:
+        """the compression params of a module under `scheme`, root first; `input_global_scale` of `dynamic="local"` activations only where
+        `present(key)` says the checkpoint has it"""
+        names = self._compressor(scheme).compression_param_names(scheme)
+        if self._local_inputs[self.schemes.index(scheme)]:
+            names = tuple(p for p in names if p != "input_global_scale" or present(f"{module_name}.{p}"))
+        return names
+
+    def _in_checkpoint(self, key: str) -> bool:
+        if self._stored is None:
+            from .safetensors_io import get_weight_map
+
+            self._stored = set(get_weight_map(self._files))
+        return key in self._stored
 
     def process(self, tensors: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         from ... import _lib
@@ -163,7 +183,7 @@ class CompressedTensorsDequantizer(Converter):
             for module_name, _ in match_quantizable_tensors(tensors, self.ignore, scheme.targets, param_targets=[names[0]]):
                 # weight_shape stays on the host (upstream keeps it a CPU int64 tensor)
                 modules.append(module_name)
-                state_dicts.append({p: tensors.pop(f"{module_name}.{p}") for p in names})
+                state_dicts.append({p: tensors.pop(f"{module_name}.{p}") for p in self._param_names(scheme, module_name, tensors.__contains__)})
             if not modules:
                 continue
             keep.append(_stage_to_device(state_dicts, dev, host_only=("weight_shape",)))
@@ -212,7 +232,7 @@ class CompressedTensorsDequantizer(Converter):
             names = self._compressor(scheme).compression_param_names(scheme)
             for module_name, _ in match_quantizable_tensors(tensors, self.ignore, scheme.targets, param_targets=[names[0]]):
                 matched.add(module_name)
-                for p in names:
+                for p in self._param_names(scheme, module_name, tensors.__contains__):
                     key = f"{module_name}.{p}"
                     if key not in tensors:
                         raise ValueError(f"Expected key {key} not found")
@@ -233,6 +253,6 @@ class CompressedTensorsDequantizer(Converter):
             names = self._compressor(scheme).compression_param_names(scheme)
             if "Linear" in scheme.targets or any(match_name(module_name, t) for t in scheme.targets):
                 if param_name == names[0]:
-                    return {f"{module_name}.{p}" for p in names[1:]}
+                    return {f"{module_name}.{p}" for p in self._param_names(scheme, module_name, self._in_checkpoint)[1:]}
                 return set()
         return set()

@@ -37,6 +37,12 @@ def mxfp4_preset_args(activations: bool):
     return _preset(**mx), (_preset(dynamic=True, observer=None, **mx) if activations else None)
 
 
+def mxfp8_preset_args():
+    """(weights, input_activations) of the reference's MXFP8 preset (quant_scheme.py:253-274)"""
+    mx = dict(strategy="group", group_size=32, scale_dtype="torch.uint8")
+    return _preset(**mx), _preset(dynamic=True, observer=None, **mx)
+
+
 class _DenseQuantizer(Converter):
     """The body of every dense-checkpoint quantizer: each targeted 2-D bf16 / fp16 `weight` of a shard is replaced by its entries under the scheme, in the
     input's order; every other tensor passes through as the same object.
@@ -245,9 +251,8 @@ class MXFP8Quantizer(_DenseQuantizer):
     format = "mxfp8-quantized"
     entry_of = {"dst": "weight", "zp_packed": "weight_scale"}  # the stored scale is the E8M0 code output
 
-    def _preset_args(self):  # the reference's MXFP8 (quant_scheme.py:253-274)
-        mx = dict(strategy="group", group_size=32, scale_dtype="torch.uint8")
-        return _preset(**mx), _preset(dynamic=True, observer=None, **mx)
+    def _preset_args(self):
+        return mxfp8_preset_args()
 
     def _scheme(self):
         mx = dict(num_bits=8, type="float", strategy="group", symmetric=True, group_size=32, scale_dtype=torch.uint8, zp_dtype=torch.uint8)

@@ -831,6 +831,46 @@ typedef struct ct_fp8block_mx_item {
 int64_t ct_fp8block_mxfp4_plan(ct_fp8block_mx_item* items_host, int n);
 int ct_fp8block_mxfp4_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
 
+/* FP8 block-quantized weights straight to mxfp8-quantized for a TABLE of modules in ONE launch: the bytes of ct_fp8block_dequant_batch (odt = xdt)
+ * followed by the one-pass MXFP8 table (ct_rtn_quant_group8_batch, kind 4), without the dense weight in between.  Per MX group (32 consecutive
+ * elements of a row): d[i] as above, s = the MXFP8 scale of max |d|, e8m0 = its stored exponent byte (code_table: the 65536-entry table
+ * ct_mx_scale_compress reads, of the dense dtype, consulted for a non-finite scale), codes = float8_e4m3fn of d / s.
+ * The row is ct_fp8block_mx_item with `packed` = the float8 codes (rows, cols); the plan admits what ct_fp8block_mxfp4_plan admits (cols % 32 == 0,
+ * block_w % 32 == 0, 16-byte aligned w and codes, the scale shapes and dtypes of ct_fp8block_dequant_plan).  A workgroup owns
+ * CT_FP8BLOCK_MXFP8_GROUPS_PER_BLOCK consecutive groups of one item. */
+#define CT_FP8BLOCK_MXFP8_GROUPS_PER_BLOCK 512
+int64_t ct_fp8block_mxfp8_plan(ct_fp8block_mx_item* items_host, int n);
+int ct_fp8block_mxfp8_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t total_blocks, int xdt, const uint8_t* code_table, ct_stream_t stream);
+
+/* FP8 block-quantized weights straight to nvfp4-pack-quantized for a TABLE of modules in TWO launches over the same planned rows: the bytes of
+ * ct_fp8block_dequant_batch (odt = xdt) followed by ct_rtn_nvfp4_amax_batch and ct_rtn_nvfp4_quant_pack_batch, without the dense weight in between.
+ * ct_fp8block_nvfp4_amax_batch folds max |d| of every item into its `key` (one 32-bit word the caller has ZEROED on the stream);
+ * ct_fp8block_nvfp4_batch derives the item's global scale from the key (generate_gparam), stores it in `global_scale` and writes, per group of 16
+ * consecutive elements of a row, the float8_e4m3fn scale byte and the E2M1 nibbles (low nibble first).
+ * packed is uint8 (rows, cols / 2), scale_f8 float8_e4m3fn (rows, cols / 16), global_scale float32 (1,).  The plan admits an item with cols % 16 == 0,
+ * block_w % 16 == 0, 16-byte aligned w and packed, 4-byte aligned key and global_scale, and the scale shapes and dtypes of
+ * ct_fp8block_dequant_plan.  A workgroup owns CT_FP8BLOCK_NV_GROUPS_PER_BLOCK consecutive groups of one item. */
+#define CT_FP8BLOCK_NV_GROUPS_PER_BLOCK 1024
+typedef struct ct_fp8block_nv_item {
+    const uint8_t* w;
+    const void* scale;
+    uint8_t* packed;
+    uint8_t* scale_f8;
+    uint32_t* key;
+    float* global_scale;
+    int64_t rows, cols, block_h, block_w;
+    int64_t scale_shape[2];    /* as found; the plan checks it */
+    int32_t sdt;
+    int32_t reserved;          /* derived: 0 */
+    int64_t scale_stride[2];   /* derived: in elements, 0 along a broadcast dimension */
+    int64_t units_per_row;     /* derived: cols / 16, the groups of a row */
+    int64_t units;             /* derived: rows * units_per_row */
+    int64_t first_block;       /* derived */
+} ct_fp8block_nv_item;         /* 18 64-bit words */
+int64_t ct_fp8block_nvfp4_plan(ct_fp8block_nv_item* items_host, int n);
+int ct_fp8block_nvfp4_amax_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
+int ct_fp8block_nvfp4_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
+
 /* sparse-bitmask decompress: out = zeros; out[mask] = values.  row_offsets may be NULL only if
  * fixed_row_nnz >= 0 (every row holds exactly that many values: the 2:4 codec).  16-bit payloads with
  * cols % 32 == 0 and 32-bit payloads with cols % 16 == 0 (as pairs of halves) take the LDS-window
