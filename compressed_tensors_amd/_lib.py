@@ -153,6 +153,8 @@ _PROTOTYPES = {
     "ct_fp8block_nvfp4_plan": ([_P, _I], _L),
     "ct_fp8block_nvfp4_amax_batch": ([_P, _I, _L, _I, _S], _I),
     "ct_fp8block_nvfp4_batch": ([_P, _I, _L, _I, _S], _I),
+    "ct_nvfp4_mxfp4_plan": ([_P, _I], _L),
+    "ct_nvfp4_mxfp4_batch": ([_P, _I, _L, _S], _I),
     "ct_bitmask_row_popcount": ([_P, _L, _L, _P, _S], _I),
     "ct_sparse24_compress": ([_P, _I, _L, _L, _P, _P, _S], _I),
     "ct_sparse24_mask": ([_P, _I, _L, _P, _S], _I),
@@ -225,9 +227,16 @@ class Fp8BlockNvItem(ctypes.Structure):
                 ("units_per_row", _L), ("units", _L), ("first_block", _L)]
 
 
+class Nvfp4MxItem(ctypes.Structure):
+    """struct ct_nvfp4_mx_item of include/ct_hip.h (a row of ct_nvfp4_mxfp4_batch's table)"""
+    _fields_ = [("packed_in", _P), ("scale_f8", _P), ("global_scale", _P), ("packed_out", _P), ("e8m0", _P), ("rows", _L), ("cols", _L),
+                ("units", _L), ("first_block", _L)]
+
+
 FP8BLOCK_MX_GROUPS_PER_BLOCK = 512  # CT_FP8BLOCK_MX_GROUPS_PER_BLOCK of include/ct_hip.h
 FP8BLOCK_MXFP8_GROUPS_PER_BLOCK = 512  # CT_FP8BLOCK_MXFP8_GROUPS_PER_BLOCK
 FP8BLOCK_NV_GROUPS_PER_BLOCK = 1024  # CT_FP8BLOCK_NV_GROUPS_PER_BLOCK
+NVFP4_MX_GROUPS_PER_BLOCK = 1024  # CT_NVFP4_MX_GROUPS_PER_BLOCK
 
 
 class AttnTensor(ctypes.Structure):

@@ -145,6 +145,7 @@ __all__ = [
     "fp8block_to_mxfp4",
     "fp8block_to_mxfp8",
     "fp8block_to_nvfp4",
+    "nvfp4_to_mxfp4",
 ]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
@@ -1955,6 +1956,16 @@ def fp8block_to_nvfp4(weight: torch.Tensor, weight_scale_inv: torch.Tensor, *, w
     from .entrypoints.convert import fp8block_transcode as ft
 
     return ft.transcode_one(ft.NVFP4, "fp8block_to_nvfp4", weight, weight_scale_inv, weight_block_size, dtype)
+
+
+def nvfp4_to_mxfp4(weight_packed: torch.Tensor, weight_scale: torch.Tensor, weight_global_scale: torch.Tensor):
+    """An NVFP4 weight (nibbles uint8 (R, C / 2), float8_e4m3fn scales (R, C / 16), one global scale) straight to MXFP4: (packed uint8 (R, C / 2),
+    E8M0 codes uint8 (R, C / 32)), byte for byte `rtn_mxfp4_quantize_and_pack` of the bfloat16 weight the NVFP4 decompress yields, which is never
+    materialised (`ct_nvfp4_mxfp4_batch`; a global scale that is not float32 or a misaligned device tensor takes the two launches).
+    Host tensors in, host tensors out; device tensors stay on their device."""
+    from .entrypoints.convert import nvfp4_mxfp4 as nm
+
+    return nm.transcode_one(weight_packed, weight_scale, weight_global_scale)
 
 
 def rtn_nvfp4_quantize_and_pack(x: torch.Tensor, global_scale: Optional[torch.Tensor] = None, *, return_scale: bool = False):

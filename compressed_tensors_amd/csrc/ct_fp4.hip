@@ -285,12 +285,10 @@ __global__ __launch_bounds__(kBlock) void fp4_quant_pack_batch_kernel(const ct_w
 // 127 + that, as uint8, is 127 (tests/test_gpu_nonfinite_rtn.py holds it against the table ct_mx_scale_compress reads)
 constexpr uint32_t kE8M0OfInf = 127u;
 
+// the arithmetic of group l on its 32 dense values in registers (r: the four 16-byte words of the group as the weight holds them); rtn_mxfp4_lane
+// loads them, nvfp4_mxfp4_kernel makes them
 template <int XDT>
-__device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0, void* __restrict__ scale_out,
-                                               int64_t l) {
-    u32x4 r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = in[l * 4 + i];
+__device__ __forceinline__ void rtn_mxfp4_group(const u32x4 (&r)[4], u32x4* __restrict__ out, uint8_t* __restrict__ e8m0, void* __restrict__ scale_out, int64_t l) {
     uint32_t acc = 0;  // max |x| on the raw bit pairs (ct_minmax.h): the MX schemes are symmetric
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc = absmax_acc(absmax_acc(absmax_acc(absmax_acc(acc, r[i].x), r[i].y), r[i].z), r[i].w);
@@ -309,6 +307,15 @@ __device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32
         w[i] = fp4_quant_unit<XDT, false>(ws, s, 1.0f, true);
     }
     stream_store16(out + l, u32x4{w[0], w[1], w[2], w[3]});
+}
+
+template <int XDT>
+__device__ __forceinline__ void rtn_mxfp4_lane(const u32x4* __restrict__ in, u32x4* __restrict__ out, uint8_t* __restrict__ e8m0, void* __restrict__ scale_out,
+                                               int64_t l) {
+    u32x4 r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = in[l * 4 + i];
+    rtn_mxfp4_group<XDT>(r, out, e8m0, scale_out, l);
 }
 
 template <int XDT>
@@ -815,6 +822,64 @@ __global__ __launch_bounds__(kBlock) void fp4_unpack_dequant_batch_kernel(const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// NVFP4 -> MXFP4 in ONE pass over a table (ct_nvfp4_mxfp4_batch): the bfloat16 element fp4_unpack_dequant_batch_kernel<CT_BF16, true> stores — the E2M1
+// value times the workgroup's s_eff entry of the scale byte, rounded as store8 rounds it — made in registers, then rtn_mxfp4_group on those bits: byte
+// for byte the two launches, 0.5 + 1/16 B in and 0.5 + 1/32 B out per element instead of (0.5 + 1/16 + 2) + (2 + 0.5 + 1/32).
+// Work unit: one MX group = two NVFP4 groups of one row (cols % 32 == 0, so group g is the elements 32 g .. 32 g + 31 of the flat tensor: 16 bytes of
+// nibbles at 16 g, two scale bytes at 2 g).  ONE lane owns a group: one 16-byte load and one 2-byte load, one 16-byte non-temporal store and one byte
+// store, all contiguous across a wave, nothing crosses lanes.  Lane t takes the groups wg_g0 + t + 256 k, k = 0..3, all loads before the arithmetic as
+// in fp8b_mx_groups; the item's last workgroup goes step by step.  A workgroup belongs to one item, so its s_eff table is that item's: one IEEE
+// division per thread and one barrier, which every lane reaches before it may leave.
+constexpr int kNvMxSteps = 4;  // groups per lane
+constexpr int64_t kNvMxGroupsPerBlock = int64_t(kBlock) * kNvMxSteps;
+static_assert(kNvMxGroupsPerBlock == CT_NVFP4_MX_GROUPS_PER_BLOCK, "include/ct_hip.h states the workgroup's share");
+
+// group g: q = its 32 nibbles, sb = its two scale bytes (the low one over the first 16 codes)
+__device__ __forceinline__ void nv_mx_group(const ct_nvfp4_mx_item& it, const float* s_eff, int64_t g, const u32x4 q, uint32_t sb) {
+    const uint32_t words[4] = {q.x, q.y, q.z, q.w};
+    const float s[2] = {s_eff[sb & 0xffu], s_eff[(sb >> 8) & 0xffu]};
+    u32x4 r[4];  // the 32 dense values, as the decompress would have stored them
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float v[8];
+        fp4_word_values(words[i], v);
+        uint32_t d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] = fp8b_mx_pair<CT_BF16>(fp8b_mul(v[2 * j], s[i >> 1]), fp8b_mul(v[2 * j + 1], s[i >> 1]));
+        r[i] = u32x4{d[0], d[1], d[2], d[3]};
+    }
+    rtn_mxfp4_group<CT_BF16>(r, reinterpret_cast<u32x4*>(it.packed_out), it.e8m0, nullptr, g);
+}
+
+__global__ __launch_bounds__(kBlock) void nvfp4_mxfp4_kernel(const ct_nvfp4_mx_item* __restrict__ items, int n) {
+    __shared__ float s_eff[256];
+    static_assert(kBlock == 256, "one table entry per thread");
+    const ct_nvfp4_mx_item it = fp8b_find(items, n, (int64_t)blockIdx.x);
+    s_eff[threadIdx.x] = __builtin_amdgcn_cvt_f32_fp8((int)threadIdx.x, 0) / fp8b_global<float>(it.global_scale)[0];
+    __syncthreads();
+    const int64_t units = it.units;
+    const int64_t wg_g0 = ((int64_t)blockIdx.x - it.first_block) * kNvMxGroupsPerBlock, g0 = wg_g0 + threadIdx.x;
+    const auto src = fp8b_global<u32x4>(it.packed_in);
+    const auto scale = fp8b_global<uint16_t>(it.scale_f8);
+    const auto group = [&](int k) { return g0 + (int64_t)kBlock * k; };
+    if (wg_g0 + kNvMxGroupsPerBlock <= units) {
+        // every step of every lane exists: the four 16-byte code loads and the four scale loads in flight, with no condition the compiler could sink them into
+        u32x4 q[kNvMxSteps];
+        uint32_t sb[kNvMxSteps];
+#pragma unroll
+        for (int k = 0; k < kNvMxSteps; ++k) {
+            q[k] = src[group(k)];
+            sb[k] = scale[group(k)];
+        }
+#pragma unroll
+        for (int k = 0; k < kNvMxSteps; ++k) nv_mx_group(it, s_eff, group(k), q[k], sb[k]);
+    } else {
+        // the item's last workgroup
+        for (int k = 0; k < kNvMxSteps && group(k) < units; ++k) nv_mx_group(it, s_eff, group(k), src[group(k)], scale[group(k)]);
+    }
+}
+
 // the MX scale tensors by themselves (mx_utils.py:18-44; the MXFP8 codec and upstream's helpers call them): one launch each instead of four tensor ops
 __global__ __launch_bounds__(kBlock) void mx_scale_compress_kernel(const uint16_t* __restrict__ scale_bits, int64_t n, const uint8_t* __restrict__ table,
                                                                    uint8_t* __restrict__ out) {
@@ -1210,6 +1275,51 @@ int ct_fp8block_mxfp4_batch(const ct_fp8block_mx_item* items_dev, int n, int64_t
     CT_REQUIRE(items_dev != nullptr, "ct_fp8block_mxfp4_batch: table is NULL");
     for_dt16(xdt, [&](auto DT) { hipLaunchKernelGGL((fp8block_mxfp4_kernel<DT()>), dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n); });
     CT_LAUNCH_CHECK("ct_fp8block_mxfp4_batch");
+}
+
+static int64_t nv_mx_plan_item(ct_nvfp4_mx_item& it, int i, int64_t first_block) {
+    constexpr int64_t kDimMax = int64_t(1) << 31;  // as the other transcoding plans
+    const char* const name = "ct_nvfp4_mxfp4_plan";
+    if (!(it.packed_in && it.scale_f8 && it.global_scale && it.packed_out && it.e8m0)) {
+        set_error("%s: item %d has a NULL pointer", name, i);
+        return -1;
+    }
+    if (!(it.rows > 0 && it.cols > 0 && it.rows < kDimMax && it.cols < kDimMax)) {
+        set_error("%s: item %d has shape (%lld, %lld) (need positive sizes below 2^31)", name, i, (long long)it.rows, (long long)it.cols);
+        return -1;
+    }
+    if (it.cols % 32 != 0) {
+        set_error("%s: item %d: columns (%lld) must be a multiple of the MX group size 32", name, i, (long long)it.cols);
+        return -1;
+    }
+    if (!aligned16(it.packed_in)) {
+        set_error("%s: item %d: the NVFP4 weight_packed is not 16-byte aligned", name, i);
+        return -1;
+    }
+    if (!aligned16(it.packed_out)) {
+        set_error("%s: item %d: the MXFP4 weight_packed is not 16-byte aligned", name, i);
+        return -1;
+    }
+    if (!aligned_to<2>(it.scale_f8)) {
+        set_error("%s: item %d: the NVFP4 weight_scale is not 2-byte aligned", name, i);
+        return -1;
+    }
+    if (!aligned_to<4>(it.global_scale)) {
+        set_error("%s: item %d: weight_global_scale is not 4-byte aligned", name, i);
+        return -1;
+    }
+    it.units = it.rows * (it.cols / 32);
+    it.first_block = first_block;
+    return cdiv64(it.units, kNvMxGroupsPerBlock);
+}
+
+int64_t ct_nvfp4_mxfp4_plan(ct_nvfp4_mx_item* items, int n) { return plan_table("ct_nvfp4_mxfp4_plan", items, n, nv_mx_plan_item); }
+
+int ct_nvfp4_mxfp4_batch(const ct_nvfp4_mx_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream) {
+    CT_BATCH_ARGS(n, total_blocks);
+    CT_REQUIRE(items_dev != nullptr, "ct_nvfp4_mxfp4_batch: table is NULL");
+    hipLaunchKernelGGL(nvfp4_mxfp4_kernel, dim3((unsigned)total_blocks), dim3(kBlock), 0, as_stream(stream), items_dev, n);
+    CT_LAUNCH_CHECK("ct_nvfp4_mxfp4_batch");
 }
 
 static int64_t fp8b_nv_plan_item(ct_fp8block_nv_item& it, int i, int64_t first_block) {

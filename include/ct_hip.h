@@ -871,6 +871,30 @@ int64_t ct_fp8block_nvfp4_plan(ct_fp8block_nv_item* items_host, int n);
 int ct_fp8block_nvfp4_amax_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
 int ct_fp8block_nvfp4_batch(const ct_fp8block_nv_item* items_dev, int n, int64_t total_blocks, int xdt, ct_stream_t stream);
 
+/* nvfp4-pack-quantized weights straight to mxfp4-pack-quantized for a TABLE of modules in ONE launch: the bytes of ct_fp4_unpack_dequant_batch
+ * (group 16, odt = CT_BF16: the dtype the NVFP4 decompress always yields) followed by ct_rtn_mxfp4_quant_pack_batch, without the dense weight in
+ * between.  Per MX group (32 consecutive elements of a row, two NVFP4 groups):
+ *   d[i] = rnd_bf16( E2M1(packed_in nibble i) * fl32(f32(scale_f8 of i's group of 16) / global_scale[0]) ),  s = the MX scale of max |d|,
+ *   e8m0 = the stored exponent byte of s,  packed_out = the E2M1 nibbles of d / s (low nibble first).
+ * packed_in is uint8 (rows, cols / 2), scale_f8 float8_e4m3fn (rows, cols / 16), global_scale float32 (one element), packed_out uint8
+ * (rows, cols / 2), e8m0 uint8 (rows, cols / 32), all contiguous.  The plan admits an item with positive sizes below 2^31, cols % 32 == 0, 16-byte
+ * aligned packed_in and packed_out, a 2-byte aligned scale_f8 and a 4-byte aligned global_scale; anything else returns -1 with ct_last_error naming
+ * the item.  A workgroup owns CT_NVFP4_MX_GROUPS_PER_BLOCK consecutive groups of one item and reads that item's global scale alone.  Protocol as the
+ * other batches. */
+#define CT_NVFP4_MX_GROUPS_PER_BLOCK 1024
+typedef struct ct_nvfp4_mx_item {
+    const uint8_t* packed_in;
+    const uint8_t* scale_f8;
+    const float* global_scale;
+    uint8_t* packed_out;
+    uint8_t* e8m0;
+    int64_t rows, cols;
+    int64_t units;             /* derived: rows * cols / 32, the MX groups */
+    int64_t first_block;       /* derived */
+} ct_nvfp4_mx_item;            /* 9 64-bit words */
+int64_t ct_nvfp4_mxfp4_plan(ct_nvfp4_mx_item* items_host, int n);
+int ct_nvfp4_mxfp4_batch(const ct_nvfp4_mx_item* items_dev, int n, int64_t total_blocks, ct_stream_t stream);
+
 /* sparse-bitmask decompress: out = zeros; out[mask] = values.  row_offsets may be NULL only if
  * fixed_row_nnz >= 0 (every row holds exactly that many values: the 2:4 codec).  16-bit payloads with
  * cols % 32 == 0 and 32-bit payloads with cols % 16 == 0 (as pairs of halves) take the LDS-window
