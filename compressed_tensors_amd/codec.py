@@ -32,6 +32,7 @@ __all__ = [
     "minmax_qparams_float",
     "dynamic_qdq",
     "hadamard_dynamic_qdq",
+    "hadamard_k_dynamic_qdq",
     "generate_gparam",
     "HadamardPlan",
     "plan_hadamard",
@@ -1842,6 +1843,32 @@ def hadamard_dynamic_qdq(x: torch.Tensor, size: int, *, kind: str, seg_len: int,
     gs = _gs_arg(global_scale, dev)
     call("ct_hadamard_dynamic_qdq", ptr(x), DT[x.dtype], x.numel(), int(size), int(seg_len), DYNAMIC_KINDS[kind], int(num_bits),
          int(bool(symmetric)), ptr(gs), ptr(rotated), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
+    return out, scale, zp, rotated
+
+
+def hadamard_k_dynamic_qdq(x: torch.Tensor, n: int, had_k: torch.Tensor, signs: Optional[torch.Tensor] = None, *, kind: str, seg_len: int,
+                           num_bits: int = 8, symmetric: bool = True, global_scale: Optional[torch.Tensor] = None, scale_shape=None,
+                           scale_dtype=None, zp_dtype=None, want_out: bool = True, want_rotated: bool = False):
+    """`hadamard_k_transform(x, n, had_k, signs)` (last dimension, float32 accumulation, the plain form) followed by `dynamic_qdq`
+    over segments of `seg_len` elements of the rotated tensor, in ONE launch (ct_hadamard_k_dynamic_qdq, csrc/ct_rotated_k.hip): the
+    rotated block is quantized while it sits in LDS and goes to memory only if `want_rotated` asks for it.  Returns (out or None,
+    scale or None, zero_point or None, rotated or None), bit for bit what the two calls return; the library answers
+    CT_ERR_UNSUPPORTED (NotImplementedError) for a combination it does not fuse — quantization.dynamic.plan_rotated_k_dynamic is
+    the rule."""
+    _check_float(x, "activation")
+    if not x.is_contiguous():
+        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    k = 1 if had_k is None else int(had_k.shape[0])
+    out, _ = _rotation_launch(x, had_k, k, signs, int(n))  # the tables' checks of hadamard_k_transform, in its order
+    dev = x.device
+    out = out if want_out else None
+    rotated = torch.empty_like(x) if want_rotated else None
+    scale = torch.empty(scale_shape, dtype=scale_dtype, device=dev) if scale_dtype is not None else None
+    zp = torch.empty(scale_shape, dtype=zp_dtype, device=dev) if zp_dtype is not None else None
+    zdt = DT[zp_dtype] if zp_dtype is not None else -1
+    gs = _gs_arg(global_scale, dev)
+    call("ct_hadamard_k_dynamic_qdq", ptr(x), DT[x.dtype], x.numel(), int(n), k, ptr(had_k), ptr(signs), int(seg_len), DYNAMIC_KINDS[kind],
+         int(num_bits), int(bool(symmetric)), ptr(gs), ptr(rotated), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
     return out, scale, zp, rotated
 
 

@@ -10,6 +10,8 @@ own ValueError where it raises one.
 `plan_rotated_dynamic` / `rotated_fake_quantize` / `forward_rotate_quantize` are the same forward behind an online Hadamard
 rotation (QuaRot, SpinQuant, a `transform_config` with `location: input`): where the plan fuses, the rotation and the QDQ are
 ONE launch of csrc/ct_rotated.hip; where it does not, they are the two existing calls — the same bits either way.
+`plan_rotated_k_dynamic` / `random_rotated_fake_quantize` are that pair for the `random-hadamard` rotation of size K * 2^m with
+K > 1 (R4 in front of down_proj): one launch of csrc/ct_rotated_k.hip where the plan fuses.
 """
 import math
 import weakref
@@ -22,7 +24,8 @@ from .forward import fake_quantize
 from .quant_args import enum_value
 
 __all__ = ["compute_dynamic_scales_and_zp", "forward_quantize", "plan_dynamic", "DynamicPlan", "plan_rotated_dynamic", "RotatedPlan",
-           "rotated_fake_quantize", "forward_rotate_quantize", "MEASURED_FASTER", "ALL_FORMS", "remember_prequantized", "take_prequantized"]
+           "rotated_fake_quantize", "forward_rotate_quantize", "MEASURED_FASTER", "ALL_FORMS", "remember_prequantized", "take_prequantized",
+           "plan_rotated_k_dynamic", "RotatedKPlan", "random_rotated_fake_quantize", "ROTATED_K_ALL_FORMS", "ROTATED_K_MEASURED_FASTER"]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _F8 = torch.float8_e4m3fn
@@ -299,3 +302,89 @@ def forward_rotate_quantize(module: torch.nn.Module, value: torch.Tensor, base_n
     scale = getattr(module, f"{base_name}_scale")
     zero_point = getattr(module, f"{base_name}_zero_point", None)
     return fake_quantize(x=codec.hadamard_transform(value, size), scale=scale, zero_point=zero_point, args=args, g_idx=g_idx, global_scale=global_scale)
+
+
+# ---- the same forward behind a random-hadamard rotation of size K * 2^m, K > 1 (csrc/ct_rotated_k.hip) ------------------------------
+class RotatedKPlan:
+    """what `random_rotated_fake_quantize` launches for one call: `fused` (one launch of ct_hadamard_k_dynamic_qdq) in `form`
+      "mfma_group"  segments of 8 * 2^j <= 512 elements that divide the rotation block: reduced inside a wave on the block in LDS
+      "mfma_row"    the rotation block IS the segment (a token row, M >= 32): min / max finished across the waves
+    or not fused (`form` None, `reason` says why): the two existing calls.  `key` names the measurement that speaks for the shape
+    (form and accumulator tiles, e.g. "mfma_row_tt2") wherever the kernel computes it, dispatched or not; None where it does not.
+    `hadamard` / `dynamic` are the parents' plans."""
+
+    __slots__ = ("fused", "form", "key", "reason", "hadamard", "dynamic")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def launches(self) -> int:
+        return 1 if self.fused else (2 if self.hadamard.form == "valu" else 1) + self.dynamic.launches()
+
+
+ROTATED_K_ALL_FORMS = frozenset(f"{f}_tt{tt}" for f in ("mfma_group", "mfma_row") for tt in (1, 2, 4))
+# The keys the plan dispatches to the one launch: those `tools/rotated_k_bench.py` has MEASURED faster than the two launches by more
+# than the spread between its runs (profiles/rotated_k_bench.jsonl, DESIGN 5.31).  A key that is not listed — not measured, or
+# measured and not faster — is declined: random_rotated_fake_quantize is then the two existing calls.
+ROTATED_K_MEASURED_FASTER = frozenset({"mfma_row_tt4"})  # 0.95-0.97 of the two launches; every other key measured 1.13-1.48 x SLOWER
+
+
+def plan_rotated_k_dynamic(shape, dtype: torch.dtype, size: int, k: int, args, global_scale: Optional[torch.Tensor] = None) -> RotatedKPlan:
+    """Host plan of `dynamic_fake_quantize(hadamard_k_transform(x, size, had_k, signs), args, global_scale)` for an activation of
+    `shape` / `dtype` and a k x k mix: plan_hadamard_k (last dimension, float32, plain form) and plan_dynamic composed — their
+    ValueErrors and NotImplementedErrors come through unchanged — the rule of csrc/ct_rotated_k.hip for what one launch computes,
+    and ROTATED_K_MEASURED_FASTER for which of those keys are dispatched to it.  No tensor is touched."""
+    hp = codec.plan_hadamard_k(shape, dtype, size, k, -1, torch.float32)
+    dp = plan_dynamic(shape, dtype, args, global_scale)
+    n, m, L = hp.size, hp.m, dp.seg_len
+    units = L // 8
+    in_wave = L % 8 == 0 and units <= 64 and units & (units - 1) == 0  # ct_dynamic_qdq's in-wave segments
+    form = reason = None
+    if hp.k == 1:
+        reason = "k == 1 (signs and the butterfly) has no fused launch"
+    elif dtype is torch.float32:
+        reason = "float32 activations take the vector form of the mix"
+    elif hp.form != "mfma":
+        reason = f"runs of {m} elements take the vector form of the mix"
+    elif dp.launches() == 2:
+        reason = f"one segment of {L} elements is the tensor form: its reduction is global"
+    elif in_wave and n % L == 0:
+        form = "mfma_group"
+    elif L == n:
+        if m >= 32:
+            form = "mfma_row"
+        else:
+            reason = f"a token row of {n} elements shares its workgroup with {32 // m - 1} more blocks"
+    elif L % n == 0:
+        reason = f"a token row of {L} elements is {L // n} rotation blocks of {n}"
+    else:
+        reason = f"a segment of {L} elements over rotation blocks of {n} is not fused"
+    key = None if form is None else f"{form}_tt{max(m, 32) // 32}"
+    if key is not None and key not in ROTATED_K_MEASURED_FASTER:
+        form, reason = None, f"the {key} form is not measured faster than the two launches (ROTATED_K_MEASURED_FASTER)"
+    return RotatedKPlan(fused=form is not None, form=form, key=key, reason=reason, hadamard=hp, dynamic=dp)
+
+
+def random_rotated_fake_quantize(value: torch.Tensor, size: int, had_k: Optional[torch.Tensor], signs: Optional[torch.Tensor], args,
+                                 global_scale: Optional[torch.Tensor] = None, *, return_qparams: bool = False, return_rotated: bool = False,
+                                 fused: Optional[bool] = None):
+    """dynamic_fake_quantize(hadamard_k_transform(value, size, had_k, signs), args, global_scale, ...).  `fused=None` follows the
+    plan: one launch where it fuses, the two existing calls where it does not; `fused=True` asks for the one launch wherever the
+    kernel computes the shape, measured faster or not; `fused=False` is the composition.  The same bits in all three.  Returns out,
+    or (out, scale, zero_point) with return_qparams, with the rotated tensor appended under return_rotated."""
+    k = 1 if had_k is None else int(had_k.shape[0])
+    plan = plan_rotated_k_dynamic(value.shape, value.dtype, size, k, args, global_scale)
+    dp = plan.dynamic
+    if plan.fused if fused is None else (bool(fused) and plan.key is not None):
+        out, scale, zp, rotated = codec.hadamard_k_dynamic_qdq(
+            value, size, had_k, signs, kind=dp.kind, seg_len=dp.seg_len, num_bits=dp.num_bits, symmetric=dp.symmetric, global_scale=global_scale,
+            scale_shape=dp.scale_shape, scale_dtype=dp.scale_dtype if return_qparams else None, zp_dtype=dp.zp_dtype if return_qparams else None,
+            want_out=True, want_rotated=return_rotated)
+    else:
+        rotated = codec.hadamard_k_transform(value, size, had_k, signs)
+        out, scale, zp = _run(rotated, dp, global_scale, want_out=True, want_qparams=return_qparams)
+    res = (out, scale, zp) if return_qparams else (out,)
+    if return_rotated:
+        res += (rotated,)
+    return res if len(res) > 1 else out

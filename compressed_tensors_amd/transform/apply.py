@@ -12,7 +12,7 @@ from .config import TRANSFORM_CONFIG_NAME, TransformConfig, TransformLocation
 from .hadamard import HadamardTransform, get_transform_size
 from .random_hadamard import RandomHadamardTransform, factor_hadamard_weight
 
-__all__ = ["apply_transform_config", "fuse_input_quantization", "fuse_attention_quantization", "match_named_modules"]
+__all__ = ["apply_transform_config", "fuse_input_quantization", "fuse_random_input_quantization", "fuse_attention_quantization", "match_named_modules"]
 
 
 def _match_class(module: torch.nn.Module, target: str) -> bool:
@@ -111,6 +111,73 @@ class InputRotation:
         out = dynamic.rotated_fake_quantize(value, self.transform.size, args, global_scale)
         dynamic.remember_prequantized(module, out)
         return out
+
+
+_RANDOM_INPUT_ROTATIONS = "_ct_random_input_rotations"  # module attribute: the RandomInputRotation pre-hooks apply_transform_config registered
+
+
+class RandomInputRotation:
+    """the forward pre-hook of an `input` RandomHadamardTransform: inputs[0] rotated.  With `fuse_quantization` set
+    (fuse_random_input_quantization) it is InputRotation for the K * 2^m rotation: under upstream's quantized_forward predicate,
+    evaluated per call, a call whose plan (dynamic.plan_rotated_k_dynamic) fuses returns the rotated AND dynamically quantized
+    input from one launch (csrc/ct_rotated_k.hip) and hands it to forward_quantize through remember_prequantized; every other call
+    rotates only.  The precondition of the opt-in is InputRotation's."""
+
+    def __init__(self, transform: RandomHadamardTransform):
+        self.transform = transform
+        self.fuse_quantization = False
+
+    def __call__(self, module, inputs):
+        value = inputs[0]
+        if self.fuse_quantization:
+            out = self._rotate_and_quantize(module, value)
+            if out is not None:
+                return out
+        return self.transform(value)
+
+    def fusable(self) -> bool:
+        t = self.transform
+        return t.perm is None and not t.transposed and t.precision is torch.float32 and t.dim == -1
+
+    def _rotate_and_quantize(self, module, value):
+        from ..quantization import dynamic
+
+        scheme = getattr(module, "quantization_scheme", None)
+        # quantized_forward's own predicate (quantization/lifecycle/forward.py:265-276)
+        if not getattr(module, "quantization_enabled", True) or scheme is None or getattr(module, "quantization_status", None) is None:
+            return None
+        args = getattr(scheme, "input_activations", None)
+        if args is None or not _dynamic_args(args, module) or not self.fusable():
+            return None
+        t = self.transform
+        value = value.contiguous()
+        global_scale = getattr(module, "input_global_scale", None)
+        try:
+            if not dynamic.plan_rotated_k_dynamic(value.shape, value.dtype, t.size, t.k, args, global_scale).fused:
+                return None
+        except (NotImplementedError, ValueError):
+            return None  # the rotation alone raises what it raises
+        if value.data_ptr() % 16 or t.signs.data_ptr() % 8 or t.signs.device != value.device:
+            return None
+        out = dynamic.random_rotated_fake_quantize(value, t.size, t.had_k, t.signs, args, global_scale)
+        dynamic.remember_prequantized(module, out)
+        return out
+
+
+def fuse_random_input_quantization(model: torch.nn.Module) -> list:
+    """Opt-in, the sibling of fuse_input_quantization for the `random-hadamard` type: every module whose ONE `input`
+    RandomHadamardTransform — not permuted, not transposed, float32 precision — stands in front of dynamic `input_activations` of a
+    kind the kernels know gets the fused pre-hook (RandomInputRotation).  Returns the names of the modules it fused.  The model
+    computes the same bits, one launch per fused module input instead of two; calls whose plan does not fuse rotate only."""
+    fused = []
+    for name, module in model.named_modules():
+        hooks = module.__dict__.get(_RANDOM_INPUT_ROTATIONS, ())
+        args = getattr(getattr(module, "quantization_scheme", None), "input_activations", None)
+        if len(hooks) != 1 or module.__dict__.get(_INPUT_ROTATIONS) or args is None or not _dynamic_args(args, module) or not hooks[0].fusable():
+            continue  # several rotations: only the last one could share the QDQ's launch, and the hooks do not know their order
+        hooks[0].fuse_quantization = True
+        fused.append(name)
+    return fused
 
 
 def _dynamic_args(args, module) -> bool:
@@ -330,8 +397,8 @@ def _apply_to_module(name, scheme, module, args, random_weights=None, model=None
             hook = InputRotation(transform)
             module.__dict__.setdefault(_INPUT_ROTATIONS, []).append(hook)
         else:
-            def hook(_, inputs, transform=transform):
-                return transform(inputs[0])
+            hook = RandomInputRotation(transform)
+            module.__dict__.setdefault(_RANDOM_INPUT_ROTATIONS, []).append(hook)
         module.register_forward_pre_hook(hook, prepend=True)
     elif location == TransformLocation.OUTPUT:
         module.register_module(transform_name, transform)

@@ -85,7 +85,9 @@ def transform_transposed(location, module_type, inverse: bool) -> bool:
 class RandomHadamardTransform(_PermutedMixin, torch.nn.Module):
     """value -> value @ W / sqrt(n) (or W.T, per location, module type and `args.inverse`) for a factored random-hadamard weight.
     Fused (offline) locations accumulate in float64, online ones in `scheme.precision`, as HadamardTransform does.  Not a
-    HadamardTransform: fuse_input_quantization, which fuses the Sylvester rotation into the QDQ launch, leaves it alone.
+    HadamardTransform: fuse_input_quantization, which fuses the Sylvester rotation into the QDQ launch, leaves it alone;
+    fuse_random_input_quantization is the opt-in that runs an `input` rotation with K > 1 in the launch of the dynamic QDQ
+    behind it (csrc/ct_rotated_k.hip).
     `perm` (randomize=True upstream): the weight W[perm][:, perm]."""
 
     def __init__(self, factors: HadamardFactors, scheme, args, module_type=torch.nn.Linear, perm=None):

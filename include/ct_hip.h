@@ -450,6 +450,20 @@ int ct_hadamard_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, in
                             const float* global_scale, void* rotated_out, void* out, void* scale_out, void* zp_out, int zdt,
                             ct_stream_t stream);
 
+/* The same behind the random-hadamard rotation of ct_hadamard_k_rows (plain form, float32 accumulation) with k > 1, one launch:
+ * r = round_to_xdt((had_k (x) H_M)(signs . x) / sqrt(n)) over runs of n = k * M elements — the mix on the matrix cores, the
+ * butterfly on the accumulators — then ct_dynamic_qdq's observer / calculate_qparams / fake_quantize over runs of seg_len
+ * elements of r, on the rounded block while it sits in LDS.  had_k / signs as in ct_hadamard_k_rows; every other argument as in
+ * ct_hadamard_dynamic_qdq.  Output, scale and zero point are the bits ct_hadamard_k_rows followed by ct_dynamic_qdq produce.
+ * Fused: 16-bit x, 8 <= M <= 128, and seg_len = 8 * 2^j <= 512 dividing n (reduced inside a wave) or seg_len == n with M >= 32
+ * (a token row that is one rotation block, finished across the waves).  Asynchronous on `stream`; allocates nothing, keeps no
+ * state.  CT_ERR_UNSUPPORTED for everything else: k == 1, float32 x, M < 8 or M > 128, k > 256, n > 32768, seg_len == n with
+ * M < 32, any other seg_len (it does not divide n, or a row of several blocks), one segment (the tensor form), a staged row
+ * beyond 64 KiB of LDS, tensors that are not 16-byte aligned, signs that are not 8-byte aligned. */
+int ct_hadamard_k_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, int64_t k, const int8_t* had_k, const int8_t* signs,
+                              int64_t seg_len, int kind, int bits, int symmetric, const float* global_scale, void* rotated_out,
+                              void* out, void* scale_out, void* zp_out, int zdt, ct_stream_t stream);
+
 /* Static quantize / dequantize / fake_quantize of the query, key and value states of an attention module
  * (modeling/attention.py, modeling/kvcache.py -> forward_quantize -> forward_helpers.py:180-215, 525-572): one or two 4-D
  * tensors (B, H, S, D) read and written IN PLACE through their strides.  The last dimension has stride 1; the b / h / s
