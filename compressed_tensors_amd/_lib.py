@@ -124,6 +124,7 @@ _PROTOTYPES = {
     "ct_hadamard_perm_cols": ([_P, _P, _P, _I, _L, _L, _L, _I, _P, _P, _P, _I, _S], _I),
     "ct_hadamard_dynamic_qdq": ([_P, _I, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_hadamard_k_dynamic_qdq": ([_P, _I, _L, _L, _L, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
+    "ct_hadamard_signed_dynamic_qdq": ([_P, _I, _L, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _S], _I),
     "ct_attn_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_rot_qdq": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),
     "ct_attn_observe": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _S], _I),

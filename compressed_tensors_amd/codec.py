@@ -33,6 +33,7 @@ __all__ = [
     "dynamic_qdq",
     "hadamard_dynamic_qdq",
     "hadamard_k_dynamic_qdq",
+    "hadamard_signed_dynamic_qdq",
     "generate_gparam",
     "HadamardPlan",
     "plan_hadamard",
@@ -1869,6 +1870,33 @@ def hadamard_k_dynamic_qdq(x: torch.Tensor, n: int, had_k: torch.Tensor, signs: 
     gs = _gs_arg(global_scale, dev)
     call("ct_hadamard_k_dynamic_qdq", ptr(x), DT[x.dtype], x.numel(), int(n), k, ptr(had_k), ptr(signs), int(seg_len), DYNAMIC_KINDS[kind],
          int(num_bits), int(bool(symmetric)), ptr(gs), ptr(rotated), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
+    return out, scale, zp, rotated
+
+
+def hadamard_signed_dynamic_qdq(x: torch.Tensor, n: int, signs: torch.Tensor, *, kind: str, seg_len: int, num_bits: int = 8, symmetric: bool = True,
+                                global_scale: Optional[torch.Tensor] = None, scale_shape=None, scale_dtype=None, zp_dtype=None,
+                                want_out: bool = True, want_rotated: bool = False):
+    """`hadamard_k_transform(x, n, None, signs)` (k == 1: signs and the butterfly; last dimension, float32 accumulation, the plain
+    form) followed by `dynamic_qdq` over segments of `seg_len` elements of the rotated tensor, in ONE launch
+    (ct_hadamard_signed_dynamic_qdq, csrc/ct_rotated_signed.hip): a workgroup reads the signs once and flips the sign bit of the
+    16-bit input at its load.  Returns (out or None, scale or None, zero_point or None, rotated or None), bit for bit what the two
+    calls return; the library answers CT_ERR_UNSUPPORTED (NotImplementedError) for a combination it does not fuse —
+    quantization.dynamic.plan_rotated_dynamic(signed=True) is the rule."""
+    _check_float(x, "activation")
+    if not x.is_contiguous():
+        raise NotImplementedError("the hadamard kernels take contiguous tensors")
+    if signs is None:
+        raise ValueError("signs must be a contiguous int8 tensor of +-1; hadamard_dynamic_qdq is the rotation without")
+    out, _ = _rotation_launch(x, None, 1, signs, int(n))  # the tables' checks of hadamard_k_transform, in its order
+    dev = x.device
+    out = out if want_out else None
+    rotated = torch.empty_like(x) if want_rotated else None
+    scale = torch.empty(scale_shape, dtype=scale_dtype, device=dev) if scale_dtype is not None else None
+    zp = torch.empty(scale_shape, dtype=zp_dtype, device=dev) if zp_dtype is not None else None
+    zdt = DT[zp_dtype] if zp_dtype is not None else -1
+    gs = _gs_arg(global_scale, dev)
+    call("ct_hadamard_signed_dynamic_qdq", ptr(x), DT[x.dtype], x.numel(), int(n), ptr(signs), int(seg_len), DYNAMIC_KINDS[kind], int(num_bits),
+         int(bool(symmetric)), ptr(gs), ptr(rotated), ptr(out), ptr(scale), ptr(zp), zdt, stream_of(x))
     return out, scale, zp, rotated
 
 

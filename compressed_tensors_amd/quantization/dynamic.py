@@ -11,7 +11,9 @@ own ValueError where it raises one.
 rotation (QuaRot, SpinQuant, a `transform_config` with `location: input`): where the plan fuses, the rotation and the QDQ are
 ONE launch of csrc/ct_rotated.hip; where it does not, they are the two existing calls — the same bits either way.
 `plan_rotated_k_dynamic` / `random_rotated_fake_quantize` are that pair for the `random-hadamard` rotation of size K * 2^m with
-K > 1 (R4 in front of down_proj): one launch of csrc/ct_rotated_k.hip where the plan fuses.
+K > 1 (R4 in front of down_proj): one launch of csrc/ct_rotated_k.hip where the plan fuses.  The `random-hadamard` rotation whose
+size is a power of two (K = 1: signs and the butterfly) is `rotated_fake_quantize(signs=)` / `plan_rotated_dynamic(signed=True)`:
+one launch of csrc/ct_rotated_signed.hip.
 """
 import math
 import weakref
@@ -25,7 +27,8 @@ from .quant_args import enum_value
 
 __all__ = ["compute_dynamic_scales_and_zp", "forward_quantize", "plan_dynamic", "DynamicPlan", "plan_rotated_dynamic", "RotatedPlan",
            "rotated_fake_quantize", "forward_rotate_quantize", "MEASURED_FASTER", "ALL_FORMS", "remember_prequantized", "take_prequantized",
-           "plan_rotated_k_dynamic", "RotatedKPlan", "random_rotated_fake_quantize", "ROTATED_K_ALL_FORMS", "ROTATED_K_MEASURED_FASTER"]
+           "plan_rotated_k_dynamic", "RotatedKPlan", "random_rotated_fake_quantize", "ROTATED_K_ALL_FORMS", "ROTATED_K_MEASURED_FASTER",
+           "ROTATED_SIGNED_MEASURED_FASTER"]
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 _F8 = torch.float8_e4m3fn
@@ -196,15 +199,17 @@ def take_prequantized(module: torch.nn.Module, value: torch.Tensor, base_name: s
 
 
 class RotatedPlan:
-    """what `rotated_fake_quantize` launches for one call: `fused` (one launch of ct_hadamard_dynamic_qdq) in `form`
+    """what `rotated_fake_quantize` launches for one call: `fused` (one launch of ct_hadamard_dynamic_qdq, or of
+    ct_hadamard_signed_dynamic_qdq for a signed plan) in `form`
       "in_wave"    n <= 512, segments of 8 * 2^k <= 512 elements: butterfly, reduction and QDQ inside a wave
       "block"      n = 1024 .. 8192, one workgroup per rotation block, such segments reduced inside the wave
       "block_row"  n = 1024 .. 8192 and the block IS the segment (a token row): min / max finished across the waves
       "head_row"   n <= 512 dividing a longer segment (a token row of head-dim blocks, up to 32768 elements)
     or not fused (`form` None, `reason` says why — a shape the kernels do not fuse, or a form outside MEASURED_FASTER): the two
-    existing calls.  `hadamard` / `dynamic` are the parents' plans."""
+    existing calls.  `key` names the measurement that speaks for the shape (`_measure_key`) wherever the kernel computes it,
+    dispatched or not; None where it does not.  `hadamard` / `dynamic` are the parents' plans."""
 
-    __slots__ = ("fused", "form", "reason", "hadamard", "dynamic")
+    __slots__ = ("fused", "form", "key", "reason", "hadamard", "dynamic")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -224,20 +229,37 @@ ALL_FORMS = frozenset({"in_wave", "head_row"} | {f"{f}_{n}" for f in ("block", "
 # more than the spread between its runs (profiles/rotated_bench.jsonl).  A form that is not listed — not measured
 # yet, or measured and not faster — is declined: rotated_fake_quantize is then the two existing calls.
 MEASURED_FASTER = frozenset({"head_row", "block_1024", "block_2048", "block_4096", "block_row_1024", "block_row_2048", "block_row_4096", "block_row_8192"})
+# The same rule for the signed rotation (csrc/ct_rotated_signed.hip, the keys of ALL_FORMS): filled only from a GPU run of
+# `tools/rotated_signed_bench.py` (profiles/rotated_signed_bench.jsonl).  Not measured yet: nothing is dispatched.
+ROTATED_SIGNED_MEASURED_FASTER = frozenset()
 
 
-def plan_rotated_dynamic(shape, dtype: torch.dtype, size: int, args, global_scale: Optional[torch.Tensor] = None) -> RotatedPlan:
+def plan_rotated_dynamic(shape, dtype: torch.dtype, size: int, args, global_scale: Optional[torch.Tensor] = None, *, signed: bool = False) -> RotatedPlan:
     """Host plan of `dynamic_fake_quantize(hadamard_transform(x, size), args, global_scale)` for an activation of `shape` /
     `dtype`: plan_hadamard (last dimension, float32) and plan_dynamic composed — their ValueErrors and NotImplementedErrors come
     through unchanged — the rule of csrc/ct_rotated.hip for what one launch computes, and MEASURED_FASTER for which of those forms
-    are dispatched to it.  No tensor is touched."""
-    hp = codec.plan_hadamard(shape, dtype, size, -1, torch.float32)
+    are dispatched to it.  `signed`: the plan of `dynamic_fake_quantize(hadamard_k_transform(x, size, None, signs), ...)` instead —
+    plan_hadamard_k with k = 1 behind a ValueError for a size that is not a power of two, the rule of csrc/ct_rotated_signed.hip
+    (16-bit activations, 8 <= size) and ROTATED_SIGNED_MEASURED_FASTER.  No tensor is touched."""
+    if signed:
+        if int(size) <= 0 or int(size) & (int(size) - 1):
+            raise ValueError(f"hadamard size {size} is not a power of two: the signed butterfly is the k == 1 rotation")
+        hp = codec.plan_hadamard_k(shape, dtype, size, 1, -1, torch.float32)
+    else:
+        hp = codec.plan_hadamard(shape, dtype, size, -1, torch.float32)
     dp = plan_dynamic(shape, dtype, args, global_scale)
     n, L = hp.size, dp.seg_len
     units = L // 8
     in_wave = L % 8 == 0 and units <= 64 and units & (units - 1) == 0  # ct_dynamic_qdq's in-wave segments
+    measured = ROTATED_SIGNED_MEASURED_FASTER if signed else MEASURED_FASTER
     form = reason = None
-    if dp.launches() == 2:
+    if signed and dtype is torch.float32:
+        reason = "float32 activations take the two launches: the fused sign is a flip of a 16-bit word"
+    elif signed and n < 8:
+        reason = f"blocks of {n} elements are not whole 16-byte units"
+    elif signed and n > codec.ROTATED_MAX_BLOCK:
+        reason = f"hadamard size {n} exceeds the fused maximum {codec.ROTATED_MAX_BLOCK}"
+    elif dp.launches() == 2:
         reason = f"one segment of {L} elements is the tensor form: its reduction is global"
     elif n <= 512 and in_wave:
         form = "in_wave"
@@ -256,29 +278,35 @@ def plan_rotated_dynamic(shape, dtype: torch.dtype, size: int, args, global_scal
         form = "block_row"
     else:
         reason = f"a segment of {L} elements over workgroup-sized blocks of {n} is not fused"
-    if form is not None and _measure_key(form, n) not in MEASURED_FASTER:
-        form, reason = None, f"the {_measure_key(form, n)} form is not measured faster than the two launches (MEASURED_FASTER)"
-    return RotatedPlan(fused=form is not None, form=form, reason=reason, hadamard=hp, dynamic=dp)
+    key = None if form is None else _measure_key(form, n)
+    if key is not None and key not in measured:
+        form, reason = None, f"the {key} form is not measured faster than the two launches ({'ROTATED_SIGNED_' * signed}MEASURED_FASTER)"
+    return RotatedPlan(fused=form is not None, form=form, key=key, reason=reason, hadamard=hp, dynamic=dp)
 
 
-def _run_rotated(value, size, plan: RotatedPlan, global_scale, want_qparams: bool, want_rotated: bool):
+def _run_rotated(value, size, plan: RotatedPlan, global_scale, want_qparams: bool, want_rotated: bool, signs=None):
     dp = plan.dynamic
-    return codec.hadamard_dynamic_qdq(value, size, kind=dp.kind, seg_len=dp.seg_len, num_bits=dp.num_bits, symmetric=dp.symmetric,
-                                      global_scale=global_scale, scale_shape=dp.scale_shape,
-                                      scale_dtype=dp.scale_dtype if want_qparams else None, zp_dtype=dp.zp_dtype if want_qparams else None,
-                                      want_out=True, want_rotated=want_rotated)
+    kw = dict(kind=dp.kind, seg_len=dp.seg_len, num_bits=dp.num_bits, symmetric=dp.symmetric, global_scale=global_scale, scale_shape=dp.scale_shape,
+              scale_dtype=dp.scale_dtype if want_qparams else None, zp_dtype=dp.zp_dtype if want_qparams else None, want_out=True, want_rotated=want_rotated)
+    if signs is not None:
+        return codec.hadamard_signed_dynamic_qdq(value, size, signs, **kw)
+    return codec.hadamard_dynamic_qdq(value, size, **kw)
 
 
 def rotated_fake_quantize(value: torch.Tensor, size: int, args, global_scale: Optional[torch.Tensor] = None, *,
-                          return_qparams: bool = False, return_rotated: bool = False):
+                          return_qparams: bool = False, return_rotated: bool = False, signs: Optional[torch.Tensor] = None,
+                          fused: Optional[bool] = None):
     """dynamic_fake_quantize(hadamard_transform(value, size), args, global_scale, ...): one launch where the plan fuses, the two
-    existing calls where it does not — the same bits either way.  Returns out, or (out, scale, zero_point) with return_qparams,
-    with the rotated tensor appended under return_rotated."""
-    plan = plan_rotated_dynamic(value.shape, value.dtype, size, args, global_scale)
-    if plan.fused:
-        out, scale, zp, rotated = _run_rotated(value, size, plan, global_scale, return_qparams, return_rotated)
+    existing calls where it does not — the same bits either way.  `signs` (int8 (size,) of +-1 on value's device): the rotation
+    is hadamard_k_transform(value, size, None, signs), the `random-hadamard` rotation whose size is a power of two, and the plan
+    the signed one.  `fused=None` follows the plan; `fused=True` asks for the one launch wherever the kernel computes the shape,
+    measured faster or not; `fused=False` is the composition.  Returns out, or (out, scale, zero_point) with return_qparams, with
+    the rotated tensor appended under return_rotated."""
+    plan = plan_rotated_dynamic(value.shape, value.dtype, size, args, global_scale, signed=signs is not None)
+    if plan.fused if fused is None else (bool(fused) and plan.key is not None):
+        out, scale, zp, rotated = _run_rotated(value, size, plan, global_scale, return_qparams, return_rotated, signs)
     else:
-        rotated = codec.hadamard_transform(value, size)
+        rotated = codec.hadamard_transform(value, size) if signs is None else codec.hadamard_k_transform(value, size, None, signs)
         out, scale, zp = _run(rotated, plan.dynamic, global_scale, want_out=True, want_qparams=return_qparams)
     res = (out, scale, zp) if return_qparams else (out,)
     if return_rotated:

@@ -464,6 +464,19 @@ int ct_hadamard_k_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, 
                               int64_t seg_len, int kind, int bits, int symmetric, const float* global_scale, void* rotated_out,
                               void* out, void* scale_out, void* zp_out, int zdt, ct_stream_t stream);
 
+/* The same behind the random-hadamard rotation whose size is a power of two (k == 1 of ct_hadamard_k_rows, plain form, float32
+ * accumulation), one launch: r = round_to_xdt(FWHT_n(signs . x) / sqrt(n)) over runs of n elements, then ct_dynamic_qdq's observer /
+ * calculate_qparams / fake_quantize over runs of seg_len elements of r.  signs: int8 (n) of +-1 on the device, 8-byte aligned, read
+ * once per workgroup and applied as a flip of the sign bit of the 16-bit input; every other argument as in
+ * ct_hadamard_dynamic_qdq.  Output, scale and zero point are the bits ct_hadamard_k_rows followed by ct_dynamic_qdq produce.
+ * Fused: the shapes of ct_hadamard_dynamic_qdq for bfloat16 / float16 x and 8 <= n <= 8192.  Asynchronous on `stream`; allocates
+ * nothing, keeps no state.  CT_ERR_INVALID_ARG for an n that is not a power of two; CT_ERR_UNSUPPORTED for float32 x, n > 8192,
+ * one segment (the tensor form), segments that are not whole 16-byte units of whole blocks, 1024 <= n < seg_len, rows over 32768
+ * elements, tensors that are not 16-byte aligned. */
+int ct_hadamard_signed_dynamic_qdq(const void* x, int xdt, int64_t numel, int64_t n, const int8_t* signs, int64_t seg_len, int kind,
+                                   int bits, int symmetric, const float* global_scale, void* rotated_out, void* out, void* scale_out,
+                                   void* zp_out, int zdt, ct_stream_t stream);
+
 /* Static quantize / dequantize / fake_quantize of the query, key and value states of an attention module
  * (modeling/attention.py, modeling/kvcache.py -> forward_quantize -> forward_helpers.py:180-215, 525-572): one or two 4-D
  * tensors (B, H, S, D) read and written IN PLACE through their strides.  The last dimension has stride 1; the b / h / s
